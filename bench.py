@@ -30,6 +30,11 @@ concurrent real-time streams the job sustains.  Extra keys: `served` (continuous
 the same chunks, the same per-call results, every stream gets its next chunk as soon as its previous reply has been
 delivered), `resident_no_readback`, `long_context` (T ~ 1000 and T ~ 4500 encoder frames), `roofline`,
 `cpu_baseline`, `single_stream`, `whole_step`.
+
+`--dump-outputs DIR` (rank 0): after the timed steps, DIR/<name>.npy holds what a caller of the timed path received for
+the LAST timed chunk step, chunk preroll + warmup + steps - 1 of every stream: the arrays of sc_get_hyps_batch (best
+hypothesis; integers as float32, scores float64).  Inputs are seeded, and a reply depends on its stream's audio alone, so
+two runs or two builds with the same arguments can be compared file by file.
 """
 import argparse
 import ctypes as C
@@ -55,6 +60,7 @@ PEAK_HBM_GBS = 8000.0          # same guide: HBM3E ~8 TB/s
 # algorithmic work of one stream-hop (10 240 samples of one stream)
 GFLOP_ENCODER_SIDE_PER_HOP = 3.83
 GFLOP_PER_DECODE_STEP = 0.437  # at beam 10
+DUMP_CAP_BYTES = 64 << 20      # --dump-outputs: at most this much in all (a fixed, seeded sample of streams beyond)
 
 
 def capacities(n_steps_total):
@@ -167,7 +173,8 @@ def strict_window(sb, audio, k0, steps, dist=None, before_timing=None):
     return elapsed, (n_dec_steps(sb) - steps0) / float(sb.S) / max(steps, 1), last, extra
 
 
-def serve(sb, a3, nxt, steps, group, dist=None, boundary=True, before_timing=None, at_target=None, depth=1, exact=False):
+def serve(sb, a3, nxt, steps, group, dist=None, boundary=True, before_timing=None, at_target=None, depth=1, exact=False,
+          capture=None):
     """CONTINUOUS batching, closed loop: every stream is served on its own - sc_submit its chunk, sc_poll until replies
     are ready, read the best hypothesis of the streams that answered (sc_get_hyps_batch), submit THEIR next chunks
     (stream i continues at chunk nxt[i] of a3 [S][chunks][CHUNK]).  boundary: host PCM in (pinned staging, one H2D
@@ -177,10 +184,12 @@ def serve(sb, a3, nxt, steps, group, dist=None, boundary=True, before_timing=Non
     flight then is drained untimed.  depth > 1 (sc_streams_set_queue_depth): every stream keeps `depth` chunks with the
     engine - its next chunk is submitted while the previous one is still decoding (a host that has the audio already).
     exact: EVERY stream gets exactly `steps` chunks (a stream that has had its share is not fed again): the same S x steps
-    replies, every stream with the same weight - the tail runs at thinning buckets like any real end of a batch of calls."""
+    replies, every stream with the same weight - the tail runs at thinning buckets like any real end of a batch of calls.
+    capture (a ReplyCapture, boundary only): keeps the replies to its chunk as they are read."""
     S = sb.S
     end = a3.shape[1]
     k_start = nxt.copy()
+    answered = nxt.copy()             # the chunk each stream's next reply answers (replies come in order)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -209,7 +218,10 @@ def serve(sb, a3, nxt, steps, group, dist=None, boundary=True, before_timing=Non
         assert (st >= 0).all()
         n_polls += 1
         if boundary:
-            sb.hypotheses_arrays(done, nbest=1)
+            hyps = sb.hypotheses_arrays(done, nbest=1)
+            if capture is not None:
+                capture.take(done, answered[done], hyps)
+                answered[done] += 1
         n_replies += len(done)
         if n_replies >= target:
             if res is None:
@@ -238,6 +250,82 @@ def state_of(sb):
     T = [st.T_enc for st in sb.st]
     return {"encoder_frames_T": [min(T), max(T)], "tokens_L": [int(a["lens"].min()), int(a["lens"].max())],
             "process_idx": [min(st.process_idx for st in sb.st), max(st.process_idx for st in sb.st)]}
+
+
+class ReplyCapture:
+    """--dump-outputs: the reply of every stream to chunk `k` (the last timed chunk step) as its caller reads it -
+    hypotheses_arrays(nbest=1), row by row.  In continuous mode a stream's progress in the window depends on timing; a
+    reply does not (bit-identical in any batch and either mode: tests/test_gpu_baseline_size.py), so keying the
+    capture by chunk makes it the same from run to run."""
+
+    def __init__(self, n_streams, k):
+        self.k = k
+        self.rows = [None] * n_streams
+
+    def take(self, streams, chunks, hyps):
+        """hyps = hypotheses_arrays(streams) read after the replies of `streams` to chunks `chunks`"""
+        for i in np.nonzero(chunks == self.k)[0]:
+            self.rows[int(streams[i])] = {key: v[i] for key, v in hyps.items()}
+
+    def missing(self):
+        return np.array([s for s, r in enumerate(self.rows) if r is None], dtype=np.int32)
+
+
+def serve_rest(sb, a3, nxt, group, capture):
+    """untimed, after the timed window: streams the closed loop has not brought to chunk capture.k yet are served on
+    (the same host-boundary path, one chunk per stream at a time) until each has answered it"""
+    answered = nxt.copy()
+
+    def submit(streams):
+        streams = streams[nxt[streams] <= capture.k]
+        if len(streams):
+            sb.submit_block(streams, a3[streams, nxt[streams]])
+            nxt[streams] += 1
+
+    submit(np.arange(sb.S, dtype=np.int32))
+    while sb.outstanding:
+        done, st = sb.poll_ids(min(group, sb.outstanding))
+        assert (st >= 0).all()
+        capture.take(done, answered[done], sb.hypotheses_arrays(done, nbest=1))
+        answered[done] += 1
+        submit(done)
+    torch.cuda.synchronize()
+
+
+def write_outputs(path, rows, cap_bytes=DUMP_CAP_BYTES, seed=0):
+    """rows[s] = {name: array} of stream s -> path/<name>.npy with one leading row per stream (ids / xpos cut at the
+    longest hypothesis, zero beyond each one's length), integers as float32, floats as float64; stream.npy = which
+    streams the rows are.  Beyond cap_bytes a fixed, seeded sample of the streams is written.  Returns the file names."""
+    lm = max(1, max(int(r["lens"].max()) for r in rows))
+    out = {}
+    for name in rows[0]:
+        vals = []
+        for r in rows:
+            v = r[name]
+            if name in ("ids", "xpos"):
+                w = np.zeros(v.shape[:-1] + (lm,), v.dtype)
+                n = min(lm, v.shape[-1])
+                w[..., :n] = v[..., :n]
+                w[np.arange(lm) >= r["lens"][..., None]] = 0
+                v = w
+            vals.append(v)
+        a = np.stack(vals)
+        if np.issubdtype(a.dtype, np.integer):
+            assert np.abs(a).max(initial=0) < 1 << 24, name      # exact in float32
+            a = a.astype(np.float32)
+        else:
+            a = a.astype(np.float64)
+        out[name] = a
+    keep = np.arange(len(rows))
+    per_stream = sum(a[0].nbytes for a in out.values()) + 4
+    if per_stream * len(rows) > cap_bytes:
+        keep = np.sort(np.random.default_rng(seed).choice(len(rows), max(1, cap_bytes // per_stream), replace=False))
+    out = {name: a[keep] for name, a in out.items()}
+    out["stream"] = keep.astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
+    return sorted(f"{name}.npy" for name in out)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -348,8 +436,9 @@ def cpu_baseline(k0, budget_s=10.0, beam=10, bbd=False, max_steps=20):
 
 
 def measure(w, audio, streams, beam, bbd, preroll, warmup, steps, group, mode, total, dist=None, boundary=True, kv_dtype=None,
-            depth=1, exact=False):
-    """one fresh batch: pre-roll (lock-step, resident audio, untimed), warm-up in the timed mode, then the timed leg"""
+            depth=1, exact=False, capture=None):
+    """one fresh batch: pre-roll (lock-step, resident audio, untimed), warm-up in the timed mode, then the timed leg.
+    capture: a ReplyCapture of a chunk >= preroll + warmup, fed with the replies of the warm-up and the timed leg."""
     sb = build_native(w, streams, beam, bbd, total, kv_dtype=kv_dtype)
     if depth > 1:
         sb.set_queue_depth(depth)
@@ -358,15 +447,17 @@ def measure(w, audio, streams, beam, bbd, preroll, warmup, steps, group, mode, t
     a3 = audio.reshape(streams, -1, CHUNK)
     if mode == "strict":
         run_host(sb, step_blocks(audio, preroll, k0), np.arange(streams, dtype=np.int32))
-        e, dsh, _, extra = strict_window(sb, audio, k0, steps, dist)
+        e, dsh, last, extra = strict_window(sb, audio, k0, steps, dist)
+        if capture is not None:
+            capture.take(np.arange(streams), np.full(streams, k0 + steps - 1), last)
         out = dict(extra, elapsed=e, dec_steps_per_hop=dsh)
     else:
         nxt = np.full(streams, preroll, np.int64)
         if not boundary:
             preload_audio(sb, audio, a3.shape[1])
         if warmup > 0:
-            serve(sb, a3, nxt, warmup, group, boundary=boundary, depth=depth)
-        out = serve(sb, a3, nxt, steps, group, dist, boundary=boundary, depth=depth, exact=exact)
+            serve(sb, a3, nxt, warmup, group, boundary=boundary, depth=depth, capture=capture)
+        out = serve(sb, a3, nxt, steps, group, dist, boundary=boundary, depth=depth, exact=exact, capture=capture)
         out["next_chunk"] = nxt
     out["value"] = streams * steps * CHUNK / 16000.0 / out["elapsed"]
     return sb, out
@@ -564,7 +655,14 @@ def main():
                          "with fp16 MFMA inputs, fp32 accumulation (opt-in, BASELINE configs[4]; never the headline).  "
                          "split16: the feed-forward kernels evaluate their fp32 product sums on the fp16 matrix pipe from "
                          "fp16 hi + lo splits of both operands (three MFMAs per sum, fp32-grade results: sc_ffn_ln_s)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the timed path returned for its last chunk step (chunk preroll + "
+                         "warmup + steps - 1 of every stream: best hypothesis ids / xpos / lens / n_hyps / scores as its caller "
+                         "reads them) to DIR/<name>.npy; a stream the closed loop has not brought that far when the clock stops "
+                         "is served on, untimed, until it has answered that chunk")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
     if os.environ.get("SC_BENCH_CPUS"):      # a rank started by launch_ranks: its own slice of the host cores
@@ -622,8 +720,9 @@ def main():
     w = make_weights(device)
     audio = make_audio(S, total_steps, stream_offset=rank * S)
     a3 = audio.reshape(S, -1, CHUNK)
+    capture = ReplyCapture(S, k0 + args.steps - 1) if args.dump_outputs and rank == 0 else None
     sb, head = measure(w, audio, S, args.beam, bool(args.bbd), args.preroll, args.warmup, args.steps, group, args.mode,
-                       total_steps, dist, depth=args.queue_depth)
+                       total_steps, dist, depth=args.queue_depth, capture=capture)
     lib = sb.lib
     elapsed, dec_steps_per_hop = head["elapsed"], head["dec_steps_per_hop"]
     state = state_of(sb)
@@ -654,7 +753,8 @@ def main():
                 lib.sc_marker(1, sb.hip_stream)     # (the device is idle here: serve() synchronises before it calls back)
                 rows_at_target.append(counters)
 
-            serve(sb, a3, head["next_chunk"], args.roofline_steps, group, at_target=stop_timing, depth=args.queue_depth)
+            serve(sb, a3, head["next_chunk"], args.roofline_steps, group, at_target=stop_timing, depth=args.queue_depth,
+                  capture=capture)
         torch.cuda.synchronize()
         lib.sc_prof_enable(0)
         if args.mode == "strict":
@@ -680,6 +780,14 @@ def main():
         xattn_flops = {7: fa * rows["cross_rows"][0], 11: fa * rows["cross_rows"][1],
                        6: fa * rows["self_positions"][0], 10: fa * rows["self_positions"][1],
                        12: fa * (rows["cross_rows"][2] + rows["self_positions"][2])}
+
+    dumped = None
+    if capture is not None:
+        if len(capture.missing()):
+            serve_rest(sb, a3, head["next_chunk"], group, capture)
+        assert not len(capture.missing()), capture.missing()
+        files = write_outputs(args.dump_outputs, capture.rows)
+        dumped = {"dir": args.dump_outputs, "chunk": capture.k, "files": files}
 
     if dist is not None:
         t = torch.tensor([elapsed], device=coll_device, dtype=torch.float64)
@@ -1063,6 +1171,8 @@ def main():
         "kv_cache_fp16": kv16, "fp16_mode": fp16_mode, "ffn_split16": split16, "bbd_on": bbd_on, "queue_depth_2": queued, "l_like_dims": l_like, "long_context": long_ctx,
         "legs": args.legs,
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if args.mode == "continuous":
         out["continuous"] = {k: head[k] for k in ("iterations_per_step", "polls_per_step", "chunks_per_stream_min_max")}
         out["continuous"]["poll_min_done"] = group
