@@ -173,7 +173,7 @@ const char *sc_last_error(void);
 /* ABI revision of this header: bumped whenever a struct layout or a signature changes incompatibly.  sc_version()
  * returns the revision the LIBRARY was built with; a host compares the two before it passes any struct
  * (speechcatcher_amd/_abi.py does at load time, the C hosts in tests/ at start-up). */
-#define SC_ABI_VERSION 6
+#define SC_ABI_VERSION 7
 int sc_version(void);
 
 /* hipGraph capture / replay of any sequence of the launches below on a
@@ -355,6 +355,37 @@ int sc_copy_rows(const float *src, const int32_t *src_rows, float *dst, const in
 
 /* in-place log_softmax of selected rows (scorers.py:133-134, first block only) */
 int sc_log_softmax_rows(float *x, const int32_t *rows, int n, int V, void *stream);
+
+/* ---- CTC forced alignment (align.hip) -------------------------------------
+ * Viterbi alignment of a label sequence y[0..L) against T rows of a CTC emission table (the 2L+1 states blank, y0,
+ * blank, y1, ..., blank; a path starts in state 0 or 1 and ends in state 2L or 2L-1).  For a state s >= 1:
+ *   delta[t][s] = max(delta[t-1][s], delta[t-1][s-1], delta[t-1][s-2] if s is a label state and y != the previous
+ *   label) + e[t][label(s)]
+ * with the candidates compared in the order s, s-1, s-2, a later one taking over only if strictly greater (the final
+ * state: 2L only if strictly greater than 2L-1).  The adds are fp32 in frame order, on the stored values of the table
+ * (the path does not change when a row is shifted by a constant).  Per token: its frames [start, end) and logp_mean, the
+ * mean over those frames of e[t][y] - logsumexp_v e[t][v].  The table is only read. */
+#define SC_ALIGN_OK 0
+#define SC_ALIGN_INFEASIBLE 1 /* T < L + number of adjacent repeats in y */
+#define SC_ALIGN_NONFINITE 2  /* a row of the table holds a non-finite value */
+#define SC_ALIGN_BAD_INPUT 3  /* a label outside [0, V) or equal to blank, a blank outside [0, V), L > SC_ALIGN_MAX_L */
+#define SC_ALIGN_MAX_L 1023
+typedef struct sc_ctc_align_job {
+  const float *emis;       /* row t of the table at emis + t * stride, V floats (device) */
+  const int32_t *labels;   /* [L] (device) */
+  void *ws;                /* sc_ctc_align_ws_bytes(T) bytes of device workspace, 256-byte aligned */
+  int32_t *start;          /* [L] first frame of each token (device; -1 unless status is SC_ALIGN_OK) */
+  int32_t *end;            /* [L] one past its last frame */
+  float *logp_mean;        /* [L] */
+  float *path_score;       /* [1] sum of the emissions along the path (-inf unless SC_ALIGN_OK) */
+  int32_t *status;         /* [1] SC_ALIGN_* */
+  int64_t stride;          /* floats between two rows */
+  int32_t T, L, V, blank;
+} sc_ctc_align_job;
+size_t sc_ctc_align_ws_bytes(int T);
+/* jobs: device table of n_jobs entries; max_T / max_L bound their T and L (max_L <= SC_ALIGN_MAX_L).  Two launches on
+ * `stream`: per-row logsumexp, then one wave per job. */
+int sc_ctc_align(const sc_ctc_align_job *jobs, int n_jobs, int max_T, int max_L, void *stream);
 
 /* ---- frontend ------------------------------------------------------------ */
 
@@ -611,6 +642,17 @@ int sc_get_hyps(sc_streams *streams, int stream, int nbest, int max_len, int32_t
  * lens / scores / score_dec / score_ctc [n][nbest], n_hyps [n]; any output but n_hyps may be NULL. */
 int sc_get_hyps_batch(sc_streams *streams, const int *stream_ids, int n, int nbest, int max_len, int32_t *ids,
                       int32_t *xpos, int *lens, int *n_hyps, double *scores, double *score_dec, double *score_ctc);
+/* CTC forced alignment of the hypotheses sc_get_hyps_batch would return (same rules: the snapshot with a queue depth
+ * > 1, an error for a stream inside a decode block), best first, against the stream's own CTC rows: the T frames of
+ * the decode block the hypotheses come from.  Labels: yseq without <sos> and without a trailing <eos>.  Outputs
+ * start / end / logp_mean [n][nbest][max_len], path_score / status [n][nbest] (SC_ALIGN_*), n_hyps [n]; any output
+ * but n_hyps may be NULL.  Runs on the read-back stream; decoding is not affected.  The backpointer workspace is
+ * allocated on the first call and grows with the requests. */
+int sc_align_hyps(sc_streams *streams, const int *stream_ids, int n, int nbest, int max_len, int32_t *start,
+                  int32_t *end, float *logp_mean, double *path_score, int *status, int *n_hyps);
+/* ... of a caller-given transcript ids[0..L) against the same frames of one stream */
+int sc_align_tokens(sc_streams *streams, int stream, const int32_t *ids, int L, int32_t *start, int32_t *end,
+                    float *logp_mean, double *path_score, int *status);
 /* Speech2TextStreaming.reset (speech2text_streaming.py:252-263); not while the stream has a chunk outstanding */
 int sc_reset(sc_streams *streams, int stream);
 int sc_stream_info(const sc_streams *streams, int stream, sc_stream_info_t *out);
@@ -651,6 +693,9 @@ float *sc_streams_pcm(sc_streams *streams, long *capacity);
 int sc_streams_write_pcm(sc_streams *streams, int stream, long offset, const float *host, long n);
 long sc_streams_read_pcm_buffer(sc_streams *streams, int stream, float *host, long max_n);
 int sc_streams_read_enc(sc_streams *streams, int stream, float *host, int max_frames);
+/* test aid: the CTC rows [0, min(T, max_rows)) of a stream's table as sc_align_hyps sees them (T: the frames of the
+ * reported hypotheses' decode block) -> host [rows][vocab]; returns the number of rows */
+int sc_streams_read_ctc(sc_streams *streams, int stream, float *host, int max_rows);
 
 #ifdef __cplusplus
 }

@@ -32,8 +32,10 @@ def read_wav_16k_mono(path):
     return np.frombuffer(buf, dtype="<i2"), rate
 
 
-def recognize_file(speech2text, media_path, output_file="", quiet=True, progress=True, num_slots=1, chunk_length=8192):
-    """speechcatcher.py:358-400: recording -> text + paragraphs JSON next to the input."""
+def recognize_file(speech2text, media_path, output_file="", quiet=True, progress=True, num_slots=1, chunk_length=8192,
+                   token_alignment=False):
+    """speechcatcher.py:358-400: recording -> text + paragraphs JSON next to the input.  ``token_alignment``: the
+    paragraphs also get token_start / token_end (seconds) and token_conf from a CTC forced alignment of each segment."""
     from .config import SearchConfig
     from .native import NativeStreamBatch
     from .segmenter import recognize_recording
@@ -49,7 +51,7 @@ def recognize_file(speech2text, media_path, output_file="", quiet=True, progress
                               max_chunk_samples=max(chunk_length, 32768), engine=speech2text.batch.engine)
     # finalize_all only with the very last chunk of the recording, like the reference CLI (speechcatcher.py:586)
     text, info = recognize_recording(batch, raw, rate, chunk_length=chunk_length, token_list=speech2text.token_list,
-                                     reference_finalize=True)
+                                     reference_finalize=True, token_alignment=token_alignment)
     out_txt, out_json = (output_file or media_path) + ".txt", (output_file or media_path) + ".json"
     with open(out_txt, "w") as f:
         f.write(text)
@@ -62,7 +64,7 @@ def recognize_file(speech2text, media_path, output_file="", quiet=True, progress
     return complete
 
 
-def main(argv=None):
+def make_parser():
     p = argparse.ArgumentParser(prog="python -m speechcatcher_amd",
                                 description="Decode speech with speechcatcher models on an MI355X (native decoder path).")
     p.add_argument("-l", "--live-transcription", dest="live", action="store_true",
@@ -86,7 +88,15 @@ def main(argv=None):
                    help="raw audio samples per streaming call (default 8192)")
     p.add_argument("--log-level", dest="log_level", default="ERROR", choices=["DEBUG", "INFO", "WARNING", "ERROR", "CRITICAL"])
     p.add_argument("--show-ffmpeg-output", dest="show_ffmpeg_output", action="store_true", help="(unused: no ffmpeg step)")
+    p.add_argument("--token-alignment", dest="token_alignment", action="store_true",
+                   help="add token_start / token_end / token_conf to the .json: token times at 40 ms resolution and a per-token "
+                        "confidence from a CTC forced alignment on the GPU (token_timestamps stay as they are)")
     p.add_argument("inputfile", nargs="?", default="", help="input recording (16 kHz mono 16-bit WAV)")
+    return p
+
+
+def main(argv=None):
+    p = make_parser()
     args = p.parse_args(argv)
     logging.basicConfig(level=getattr(logging, args.log_level))
     if args.decoder != "native":
@@ -104,7 +114,8 @@ def main(argv=None):
                              cache_dir=args.cache_dir, decoder_impl=args.decoder, fp16=args.fp16,
                              use_bbd=not args.disable_bbd)
     recognize_file(speech2text, args.inputfile, quiet=args.quiet or not args.no_progress, progress=not args.no_progress,
-                   num_slots=1 if args.num_processes < 1 else args.num_processes, chunk_length=args.chunk_length)
+                   num_slots=1 if args.num_processes < 1 else args.num_processes, chunk_length=args.chunk_length,
+                   token_alignment=args.token_alignment)
     return 0
 
 

@@ -73,6 +73,17 @@ class StreamOptions(C.Structure):
                 ("kv_pool_rows", C.c_int32)]
 
 
+class AlignJob(C.Structure):
+    """sc_ctc_align_job (include/scasr.h): one CTC forced alignment of sc_ctc_align"""
+    _fields_ = ([(n, vp) for n in ("emis", "labels", "ws", "start", "end", "logp_mean", "path_score", "status")]
+                + [("stride", C.c_int64)] + [(n, C.c_int32) for n in ("T", "L", "V", "blank")])
+
+
+# SC_ALIGN_* of include/scasr.h
+ALIGN_OK, ALIGN_INFEASIBLE, ALIGN_NONFINITE, ALIGN_BAD_INPUT = 0, 1, 2, 3
+ALIGN_MAX_L = 1023
+
+
 class StreamInfo(C.Structure):
     _fields_ = ([(n, C.c_int32) for n in ("enc_frames", "processed_block", "process_idx", "n_hyp", "hyp_len",
                                            "pcm_buffered", "frontend_started")] + [("decode_steps", C.c_int64)])
@@ -195,13 +206,20 @@ _SIGS = {
     "sc_streams_write_pcm": (C.c_int, [vp, C.c_int, C.c_long, vp, C.c_long]),
     "sc_streams_read_pcm_buffer": (C.c_long, [vp, C.c_int, vp, C.c_long]),
     "sc_streams_read_enc": (C.c_int, [vp, C.c_int, vp, C.c_int]),
+    # CTC forced alignment (align.hip, streams.hip)
+    "sc_ctc_align_ws_bytes": (C.c_size_t, [C.c_int]),
+    "sc_ctc_align": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp]),
+    "sc_align_hyps": (C.c_int, [vp, c_int_p, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_float_p, c_double_p,
+                                c_int_p, c_int_p]),
+    "sc_align_tokens": (C.c_int, [vp, C.c_int, c_int_p, C.c_int, c_int_p, c_int_p, c_float_p, c_double_p, c_int_p]),
+    "sc_streams_read_ctc": (C.c_int, [vp, C.c_int, vp, C.c_int]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())
 
 # revision of include/scasr.h these ctypes mirrors were written against (SC_ABI_VERSION): a library built from another
 # revision would be handed mis-laid-out structs
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 _lib = None
 

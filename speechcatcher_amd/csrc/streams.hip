@@ -116,6 +116,7 @@ struct St {
   // emitted them); after a strict reset() T_proj restarts at the stale table's extent (scorers.py:342-350)
   int T_proj = 0, T_projkv = 0;
   long n_steps_total = 0;
+  int T_hyp = 0;   // frames [0, T_hyp) of the decode block the live hypotheses come from (sc_align_hyps)
 };
 
 // a decode block of the schedule (beam_search.py:590-634): the T frames [0, T) it presents to the scorers, whether
@@ -149,6 +150,7 @@ struct Snap {
   bool valid = false, reported = false;
   long seq = 0;
   int L = 1, nhyp = 0;
+  int T = 0;   // St::T_hyp of the copied hypotheses
 };
 
 template <typename T>
@@ -264,6 +266,9 @@ struct sc_streams {
   // ---- batched hypothesis read-back (sc_get_hyps_batch): pack kernel -> one D2H into pinned memory -------------------
   int32_t *pack_dev = nullptr, *pack_host = nullptr, *pjobs_host = nullptr, *pjobs_dev = nullptr;
   size_t pack_cap = 0;            // int32 elements
+  // ---- CTC forced alignment (sc_align_hyps / sc_align_tokens): job table, labels, outputs, workspaces -----------------
+  char *al_dev = nullptr;         // allocated on the first call, grown geometrically
+  size_t al_cap = 0;
   // ---- tick engine -----------------------------------------------------------------------------------------------------
   std::vector<St> st;
   std::vector<Run> run;
@@ -324,6 +329,7 @@ struct sc_streams {
     for (void *p : owned_host) (void)hipHostFree(p);
     if (stream_rb) (void)hipStreamDestroy(stream_rb);
     if (stream) (void)hipStreamDestroy(stream);
+    if (al_dev) (void)hipFree(al_dev);
   }
 
   template <typename T>
@@ -984,6 +990,7 @@ void finish_block(sc_streams *b, int s) {
   if (rw) { r.pidx -= 1; r.pvalid = false; }
   St &x = b->st[s];
   x.cur = r.cur; x.L = r.L; x.nhyp = r.nhyp; x.has_ctc = r.has;
+  x.T_hyp = r.T;
   x.process_idx = r.pidx; x.prev_valid = r.pvalid;
   x.output_index = r.out;
   x.n_steps_total += r.nsteps;
@@ -1043,6 +1050,7 @@ int snapshot_completed(sc_streams *b) {
     sn.reported = false;
     sn.seq = j.seq;
     sn.L = x.L;
+    sn.T = x.T_hyp;
     sn.nhyp = j.started ? x.nhyp : 0;
     if (sn.nhyp > 0) {
       a.s[a.n] = s; a.cur[a.n] = x.cur; a.L[a.n] = x.L; a.nhyp[a.n] = x.nhyp;
@@ -2312,6 +2320,170 @@ extern "C" int sc_get_hyps_batch(sc_streams *b, const int *stream_ids, int n, in
   SC_API_END
 }
 
+// ---- CTC forced alignment ------------------------------------------------------------------------------------------
+// One sc_ctc_align launch pair on the read-back stream for a list of (stream, frames, labels) requests; outputs back to
+// the host.  The device area holds [job table][labels][outputs: start, end | logp_mean | path_score, status][workspaces].
+struct AlignReq { int s, T; std::vector<int32_t> y; };
+struct AlignOut { std::vector<int32_t> start, end; std::vector<float> lp; float score; int32_t status; };
+
+static size_t al_round(size_t x) { return (x + 255) & ~(size_t)255; }
+
+static int run_align(sc_streams *b, const std::vector<AlignReq> &reqs, bool after_snap, std::vector<AlignOut> &out) {
+  const int n = (int)reqs.size();
+  out.assign(n, AlignOut());
+  if (n == 0) return SC_OK;
+  int max_T = 0, max_L = 0;
+  size_t n_lab = 0;
+  for (const AlignReq &r : reqs) {
+    max_T = std::max(max_T, r.T);
+    max_L = std::max(max_L, (int)r.y.size());
+    n_lab += r.y.size();
+  }
+  SC_CHECK_ARG(max_L <= SC_ALIGN_MAX_L, "a label sequence is longer than SC_ALIGN_MAX_L");
+  const size_t o_lab = al_round((size_t)n * sizeof(sc_ctc_align_job));
+  const size_t o_out = o_lab + al_round(n_lab * 4);
+  const size_t n_outw = 3 * n_lab + 2 * (size_t)n;   // start, end, logp_mean per label; path_score, status per job
+  size_t o_ws = o_out + al_round(n_outw * 4), total = o_ws;
+  for (const AlignReq &r : reqs) total += al_round(sc_ctc_align_ws_bytes(r.T));
+  if (total > b->al_cap) {
+    const size_t cap = std::max(total, 2 * b->al_cap);   // geometric: few reallocations (a hipFree may stall the device)
+    if (b->al_dev) {
+      HIP_TRY(hipStreamSynchronize(b->stream_rb));
+      HIP_TRY(hipFree(b->al_dev));
+      b->al_dev = nullptr;
+      b->al_cap = 0;
+    }
+    HIP_TRY(hipMalloc((void **)&b->al_dev, cap));
+    b->al_cap = cap;
+  }
+  char *D = b->al_dev;
+  std::vector<char> host(o_out, 0);
+  sc_ctc_align_job *J = (sc_ctc_align_job *)host.data();
+  int32_t *lab = (int32_t *)(host.data() + o_lab);
+  int32_t *od = (int32_t *)(D + o_out);
+  const int V = b->cfg.vocab_size;
+  size_t li = 0, wo = o_ws;
+  for (int k = 0; k < n; ++k) {
+    const AlignReq &r = reqs[k];
+    const int L = (int)r.y.size();
+    if (L) memcpy(lab + li, r.y.data(), (size_t)L * 4);
+    sc_ctc_align_job &j = J[k];
+    j.emis = b->sb.ctcx + (size_t)r.s * b->TCAP * V;
+    j.labels = (const int32_t *)(D + o_lab) + li;
+    j.ws = D + wo;
+    j.start = od + 3 * li;
+    j.end = od + 3 * li + L;
+    j.logp_mean = (float *)(od + 3 * li + 2 * L);
+    j.path_score = (float *)(od + 3 * n_lab + 2 * k);
+    j.status = od + 3 * n_lab + 2 * k + 1;
+    j.stride = V;
+    j.T = r.T; j.L = L; j.V = V; j.blank = b->cfg.blank_id;
+    li += L;
+    wo += al_round(sc_ctc_align_ws_bytes(r.T));
+  }
+  HIP_TRY(hipMemcpyAsync(D, host.data(), o_out, hipMemcpyHostToDevice, b->stream_rb));
+  if (after_snap) HIP_TRY(hipStreamWaitEvent(b->stream_rb, b->ev_snap, 0));
+  RC_TRY(sc_ctc_align((const sc_ctc_align_job *)D, n, max_T, max_L, b->stream_rb));
+  std::vector<int32_t> res(n_outw);
+  HIP_TRY(hipMemcpyAsync(res.data(), D + o_out, n_outw * 4, hipMemcpyDeviceToHost, b->stream_rb));
+  HIP_TRY(hipStreamSynchronize(b->stream_rb));
+  li = 0;
+  for (int k = 0; k < n; ++k) {
+    const int L = (int)reqs[k].y.size();
+    AlignOut &o = out[k];
+    o.start.assign(res.begin() + 3 * li, res.begin() + 3 * li + L);
+    o.end.assign(res.begin() + 3 * li + L, res.begin() + 3 * li + 2 * L);
+    o.lp.resize(L);
+    if (L) memcpy(o.lp.data(), res.data() + 3 * li + 2 * L, (size_t)L * 4);
+    memcpy(&o.score, res.data() + 3 * n_lab + 2 * k, 4);
+    o.status = res[3 * n_lab + 2 * k + 1];
+    li += L;
+  }
+  return SC_OK;
+}
+
+// frames of the hypotheses sc_get_hyps_batch reports for stream s (the snapshot's with a queue depth > 1)
+static int hyp_frames(const sc_streams *b, int s, int *T, bool *snap) {
+  const Snap &sn = b->snap[s];
+  *snap = sn.valid;
+  if (sn.valid) {
+    *T = sn.T;
+    return SC_OK;
+  }
+  SC_CHECK_ARG(!b->run[s].inblk && b->bq[s].empty(), "stream is inside a decode block (its chunk has not been reported yet)");
+  *T = b->st[s].T_hyp;
+  return SC_OK;
+}
+
+extern "C" int sc_align_hyps(sc_streams *b, const int *stream_ids, int n, int nbest, int max_len, int32_t *start,
+                             int32_t *end, float *logp_mean, double *path_score, int *status, int *n_hyps) {
+  SC_CHECK_ARG(b && stream_ids && n_hyps && n >= 0 && nbest >= 0 && max_len >= 0, "bad arguments");
+  SC_API_BEGIN
+  HIP_TRY(hipSetDevice(b->eng->device));
+  if (n == 0 || nbest == 0) {
+    for (int i = 0; i < n; ++i) n_hyps[i] = 0;
+    return SC_OK;
+  }
+  const int LC = b->LCAP;
+  std::vector<int32_t> ids((size_t)n * nbest * LC);
+  std::vector<int> lens((size_t)n * nbest);
+  RC_TRY(sc_get_hyps_batch(b, stream_ids, n, nbest, LC, ids.data(), nullptr, lens.data(), n_hyps, nullptr, nullptr, nullptr));
+  std::vector<AlignReq> reqs;
+  bool any_snap = false;
+  for (int i = 0; i < n; ++i) {
+    int T = 0;
+    bool snap = false;
+    RC_TRY(hyp_frames(b, stream_ids[i], &T, &snap));
+    any_snap |= snap && n_hyps[i] > 0;
+    for (int h = 0; h < n_hyps[i]; ++h) {
+      const size_t o = (size_t)i * nbest + h;
+      const int32_t *y = ids.data() + o * LC;
+      int a = 1, e = lens[o];                                  // without <sos> ...
+      if (e > a && y[e - 1] == b->cfg.eos_id) --e;             // ... and without a trailing <eos>
+      AlignReq r{stream_ids[i], T, std::vector<int32_t>(y + a, y + std::max(a, e))};
+      SC_CHECK_ARG((int)r.y.size() <= max_len || (!start && !end && !logp_mean), "max_len is smaller than the hypotheses");
+      reqs.push_back(std::move(r));
+    }
+  }
+  std::vector<AlignOut> out;
+  RC_TRY(run_align(b, reqs, any_snap, out));
+  int k = 0;
+  for (int i = 0; i < n; ++i)
+    for (int h = 0; h < n_hyps[i]; ++h, ++k) {
+      const size_t o = (size_t)i * nbest + h;
+      const AlignOut &a = out[k];
+      const size_t L = a.start.size();
+      if (start) memcpy(start + o * max_len, a.start.data(), L * 4);
+      if (end) memcpy(end + o * max_len, a.end.data(), L * 4);
+      if (logp_mean) memcpy(logp_mean + o * max_len, a.lp.data(), L * 4);
+      if (path_score) path_score[o] = a.score;
+      if (status) status[o] = a.status;
+    }
+  return SC_OK;
+  SC_API_END
+}
+
+extern "C" int sc_align_tokens(sc_streams *b, int stream, const int32_t *ids, int L, int32_t *start, int32_t *end,
+                               float *logp_mean, double *path_score, int *status) {
+  SC_CHECK_ARG(b && stream >= 0 && stream < b->S && L >= 0 && (L == 0 || ids), "bad arguments");
+  SC_API_BEGIN
+  HIP_TRY(hipSetDevice(b->eng->device));
+  int T = 0;
+  bool snap = false;
+  RC_TRY(hyp_frames(b, stream, &T, &snap));
+  std::vector<AlignReq> reqs{AlignReq{stream, T, std::vector<int32_t>(ids, ids + L)}};
+  std::vector<AlignOut> out;
+  RC_TRY(run_align(b, reqs, snap, out));
+  const AlignOut &a = out[0];
+  if (start) memcpy(start, a.start.data(), (size_t)L * 4);
+  if (end) memcpy(end, a.end.data(), (size_t)L * 4);
+  if (logp_mean) memcpy(logp_mean, a.lp.data(), (size_t)L * 4);
+  if (path_score) *path_score = a.score;
+  if (status) *status = a.status;
+  return SC_OK;
+  SC_API_END
+}
+
 // host <-> device copies of a stream's PCM ring and encoder output (tests, bench preload, the drop-in class's
 // frontend_states / encoder_buffer views)
 extern "C" int sc_streams_write_pcm(sc_streams *b, int stream, long offset, const float *host, long n) {
@@ -2346,6 +2518,24 @@ extern "C" int sc_streams_read_enc(sc_streams *b, int stream, float *host, int m
                 hipMemcpyDeviceToHost) != hipSuccess)
     return SC_ERR_LAUNCH;
   return T;
+}
+
+extern "C" int sc_streams_read_ctc(sc_streams *b, int stream, float *host, int max_rows) {
+  SC_CHECK_ARG(b && stream >= 0 && stream < b->S && max_rows >= 0, "bad arguments");
+  SC_API_BEGIN
+  HIP_TRY(hipSetDevice(b->eng->device));
+  int T = 0;
+  bool snap = false;
+  RC_TRY(hyp_frames(b, stream, &T, &snap));
+  T = std::min(T, max_rows);
+  const size_t V = (size_t)b->cfg.vocab_size;
+  if (host && T > 0) {
+    HIP_TRY(hipMemcpyAsync(host, b->sb.ctcx + (size_t)stream * b->TCAP * V, (size_t)T * V * sizeof(float),
+                           hipMemcpyDeviceToHost, b->stream_rb));
+    HIP_TRY(hipStreamSynchronize(b->stream_rb));
+  }
+  return T;
+  SC_API_END
 }
 
 extern "C" int sc_stream_info(const sc_streams *b, int stream, sc_stream_info_t *out) {

@@ -219,6 +219,39 @@ class HipBackend:
             self._enc_graphs[key] = g = out
         self._chk(self.lib.sc_graph_launch(g, st), "sc_graph_launch")
 
+    def ctc_align(self, jobs):
+        """Batched CTC forced alignment (sc_ctc_align), one launch pair for all jobs.  jobs: list of
+        (emis [T, V] fp32 tensor, a row-major view: rows may be strided; labels int32 tensor [L]; blank).
+        Returns (start [n, Lmax], end [n, Lmax], logp_mean [n, Lmax], path_score [n] fp32, status [n]) as numpy arrays;
+        entries past a job's L are undefined."""
+        import numpy as np
+        n = len(jobs)
+        Lmax = max([1] + [int(j[1].numel()) for j in jobs])
+        Tmax = max([0] + [int(j[0].shape[0]) for j in jobs])
+        dev = self.device
+        out_i = torch.full((n, 2, Lmax), -7, dtype=torch.int32, device=dev)
+        out_f = torch.zeros((n, Lmax), dtype=torch.float32, device=dev)
+        ps = torch.zeros(n, dtype=torch.float32, device=dev)
+        stt = torch.full((n,), -7, dtype=torch.int32, device=dev)
+        ws_sizes = [(int(self.lib.sc_ctc_align_ws_bytes(int(j[0].shape[0]))) + 255) // 256 * 256 for j in jobs]
+        ws = torch.empty(max(1, sum(ws_sizes)), dtype=torch.uint8, device=dev)
+        tab = (_abi.AlignJob * max(1, n))()
+        off = 0
+        for k, (emis, labels, blank) in enumerate(jobs):
+            assert emis.dtype == torch.float32 and emis.dim() == 2 and emis.stride(1) == 1
+            assert labels.dtype == torch.int32 and labels.is_contiguous()
+            j = tab[k]
+            j.emis, j.labels, j.ws = emis.data_ptr(), labels.data_ptr() if labels.numel() else None, ws.data_ptr() + off
+            j.start, j.end = out_i[k, 0].data_ptr(), out_i[k, 1].data_ptr()
+            j.logp_mean, j.path_score, j.status = out_f[k].data_ptr(), ps[k].data_ptr(), stt[k].data_ptr()
+            j.stride, j.T, j.L, j.V, j.blank = emis.stride(0), emis.shape[0], labels.numel(), emis.shape[1], int(blank)
+            off += ws_sizes[k]
+        tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+        self._chk(self.lib.sc_ctc_align(tab_dev.data_ptr(), n, Tmax, Lmax if n else 0, self._stream()), "sc_ctc_align")
+        torch.cuda.synchronize(dev)
+        oi = out_i.cpu().numpy()
+        return oi[:, 0], oi[:, 1], out_f.cpu().numpy(), ps.cpu().numpy().astype(np.float32), stt.cpu().numpy()
+
     # ------------------------------------------------------------------
     def search_struct(self, sb):
         cached = getattr(sb, "_sc_search_struct", None)

@@ -312,6 +312,51 @@ class NativeStreamBatch:
                    "sc_get_hyps_batch")
         return {"ids": ids, "xpos": xp, "lens": lens, "n_hyps": nh, "score": sc, "score_dec": sd, "score_ctc": scc}
 
+    def align(self, streams: Sequence[int], nbest: Optional[int] = None):
+        """CTC forced alignment of the hypotheses hypotheses_arrays reports, best first (sc_align_hyps), against the
+        stream's CTC rows of the decode block they come from.  Labels: yseq without <sos> and a trailing <eos>.
+        numpy arrays start / end (exclusive) [n, nbest, Lmax] in encoder frames, logp_mean [n, nbest, Lmax],
+        path_score / status [n, nbest] (status: _abi.ALIGN_*), n_hyps [n]; entries past a hypothesis' label count
+        are undefined (labels = lens - 1, or - 2 when the hypothesis ends with <eos>)."""
+        nb = self.W if nbest is None else int(nbest)
+        sid = np.ascontiguousarray(streams, dtype=np.int32)
+        n = len(sid)
+        lmax = self.LCAP
+        start = np.zeros((n, nb, lmax), np.int32)
+        end = np.zeros((n, nb, lmax), np.int32)
+        lp = np.zeros((n, nb, lmax), np.float32)
+        ps = np.zeros((n, nb))
+        st = np.zeros((n, nb), np.int32)
+        nh = np.zeros(n, np.int32)
+        ip = _abi.c_int_p
+        _abi.check(self.lib.sc_align_hyps(self.handle, sid.ctypes.data_as(ip), n, nb, lmax, start.ctypes.data_as(ip),
+                                          end.ctypes.data_as(ip), lp.ctypes.data_as(_abi.c_float_p),
+                                          ps.ctypes.data_as(_abi.c_double_p), st.ctypes.data_as(ip),
+                                          nh.ctypes.data_as(ip)), "sc_align_hyps")
+        return {"start": start, "end": end, "logp_mean": lp, "path_score": ps, "status": st, "n_hyps": nh}
+
+    def align_tokens(self, s: int, ids: Sequence[int]):
+        """CTC forced alignment of a given transcript (token ids, no <sos> / <eos>) against the frames of stream s's
+        reported hypotheses (sc_align_tokens): {"start", "end", "logp_mean": [L] arrays, "path_score", "status"}."""
+        y = np.ascontiguousarray(ids, dtype=np.int32)
+        L = y.shape[0]
+        start, end = np.zeros(max(L, 1), np.int32), np.zeros(max(L, 1), np.int32)
+        lp = np.zeros(max(L, 1), np.float32)
+        ps, st = C.c_double(0.0), C.c_int32(0)
+        ip = _abi.c_int_p
+        _abi.check(self.lib.sc_align_tokens(self.handle, int(s), y.ctypes.data_as(ip), L, start.ctypes.data_as(ip),
+                                            end.ctypes.data_as(ip), lp.ctypes.data_as(_abi.c_float_p), C.byref(ps),
+                                            C.byref(st)), "sc_align_tokens")
+        return {"start": start[:L], "end": end[:L], "logp_mean": lp[:L], "path_score": ps.value, "status": st.value}
+
+    def read_ctc(self, s: int) -> np.ndarray:
+        """Test aid: the CTC rows sc_align_hyps / align_tokens align stream s against -> [T, vocab] (sc_streams_read_ctc)."""
+        a = np.zeros((self.TCAP, self.cfg.vocab_size), np.float32)
+        T = self.lib.sc_streams_read_ctc(self.handle, int(s), a.ctypes.data, self.TCAP)
+        if T < 0:
+            _abi.check(T, "sc_streams_read_ctc")
+        return a[:T].copy()
+
     def hypotheses_batch(self, streams: Sequence[int], nbest: Optional[int] = None):
         """{stream: [hypothesis dicts, best first]} for the listed streams, one device round trip for all."""
         a = self.hypotheses_arrays(streams, nbest)

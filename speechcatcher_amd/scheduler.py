@@ -19,7 +19,8 @@ from typing import Deque, Dict, List, Optional, Tuple
 import numpy as np
 
 from .engine import StreamBatch
-from .speech2text_streaming import hyps_to_results
+from .align import FeatureClock
+from .speech2text_streaming import hyps_to_results, result_token_alignment
 
 EOS_ID = 1023   # hard-coded in the reference's result assembly (speech2text_streaming.py:474,500: SURVEY A4)
 
@@ -29,10 +30,16 @@ class ServerBusy(RuntimeError):
     speechcatcher_server.py:365-368)."""
 
 
+class AlignedResults(list):
+    """the results of a final reply (a list, like every reply) and ``alignment``: result_token_alignment of its first
+    result (None when it has none) - StreamScheduler(align_final=True)"""
+    alignment: Optional[dict] = None
+
+
 class StreamScheduler:
     def __init__(self, batch: StreamBatch, token_list: Optional[List[str]] = None,
                  result_format: str = "native", reset_after_final: bool = True, reset_on_open: bool = True,
-                 queue_depth: int = 1):
+                 queue_depth: int = 1, align_final: bool = False):
         """``queue_depth`` > 1 (C++ engine, ``pump``): up to that many queued chunks of a session are handed to the engine
         at a time (sc_streams_set_queue_depth) - for sessions whose audio is already there (files): the encoder stage of
         the next chunk runs beside the decoding of the current one.  Replies and their order per session do not change.
@@ -41,7 +48,13 @@ class StreamScheduler:
         session start from a reset stream - what the reference CLI does (speechcatcher.py:618-619).  The
         reference SERVER does neither (speechcatcher_server.py:270,364-397: no reset after is_final=True, models
         go back to the pool as they are); ``ServerLoop(strict_reference=True)`` switches both off to reproduce
-        that.  What reset() itself leaves behind is the batch's ``strict_reference`` (StreamBatch.reset)."""
+        that.  What reset() itself leaves behind is the batch's ``strict_reference`` (StreamBatch.reset).
+
+        ``align_final`` (C++ engine): every final reply is an ``AlignedResults`` whose ``alignment`` holds the token times and
+        confidences of its first result (CTC forced alignment, NativeStreamBatch.align), taken before the stream is reset."""
+        self.align_final = align_final
+        self._clock: Dict[int, FeatureClock] = {}             # align_final: per session, the calls since its last reset
+        self._fed: Dict[int, Deque[Tuple[int, bool]]] = {}   # ... and its fed chunks not reported yet (length, final)
         self.reset_after_final, self.reset_on_open = reset_after_final, reset_on_open
         self.batch = batch
         self.token_list = token_list
@@ -72,6 +85,8 @@ class StreamScheduler:
         self._next_sid += 1
         self._slot_of[sid] = slot
         self._queue[sid] = deque()
+        self._clock.pop(sid, None)
+        self._fed.pop(sid, None)
         return sid
 
     def close(self, sid: int):
@@ -82,6 +97,8 @@ class StreamScheduler:
         self._stash.pop(sid, None)
         slot = self._slot_of.pop(sid)
         self._queue.pop(sid)
+        self._clock.pop(sid, None)
+        self._fed.pop(sid, None)
         if self.reset_on_open:
             self.batch.reset(slot)
         self._free.append(slot)
@@ -94,6 +111,8 @@ class StreamScheduler:
     def feed(self, sid: int, pcm: np.ndarray, is_final: bool = False, finalize_all: bool = False):
         """Queue one chunk of a session (float PCM in +-1, like the reference API)."""
         self._queue[sid].append((np.asarray(pcm, dtype=np.float32), bool(is_final), bool(finalize_all)))
+        if self.align_final:
+            self._fed.setdefault(sid, deque()).append((int(np.shape(pcm)[0]), bool(is_final)))
 
     def pending(self) -> int:
         return sum(1 for sid, q in self._queue.items() if q or sid in self._in_flight or sid in self._stash)
@@ -126,8 +145,13 @@ class StreamScheduler:
             else:
                 hyps = {slot: self.batch.hypotheses(slot) for slot in want}
         for sid, (slot, fin, fa) in meta.items():
+            if self.align_final:              # the stream's clock advances by the reported chunk
+                n, f = self._fed[sid].popleft()
+                cfg = self.batch.cfg
+                self._clock.setdefault(sid, FeatureClock(cfg.win_length, cfg.hop_length)).call(n, f)
             if isinstance(has[slot], Exception):
                 out[sid] = has[slot]          # the engine has reset the stream
+                self._clock.pop(sid, None)
                 continue
             if not has[slot]:
                 out[sid] = []
@@ -135,8 +159,24 @@ class StreamScheduler:
                 out[sid] = hyps_to_results(_select_hyps(arrays, row[slot], fin, fa), fin, fa, self.token_list, self.result_format)
             else:
                 out[sid] = hyps_to_results(hyps[slot], fin, fa, self.token_list, self.result_format)
+            if fin and self.align_final and not isinstance(out[sid], Exception):
+                out[sid] = self._aligned(out[sid], arrays, row[slot] if arrays is not None and has[slot] is True else None,
+                                         slot, fin, fa, self._clock.get(sid))
             if fin and self.reset_after_final:
                 self.batch.reset(slot)
+                self._clock.pop(sid, None)
+        return out
+
+    def _aligned(self, res: list, arrays, i, slot: int, fin: bool, fa: bool, clock) -> "AlignedResults":
+        out = AlignedResults(res)
+        if not res or arrays is None:
+            return out
+        # the hypothesis behind res[0]: the first one _select_hyps keeps
+        j = next(j for j in range(int(arrays["n_hyps"][i]))
+                 if (fin and fa) or int(arrays["ids"][i, j, int(arrays["lens"][i, j]) - 1]) == EOS_ID)
+        al = self.batch.align([slot], j + 1)
+        L = int(arrays["lens"][i, j])
+        out.alignment = result_token_alignment(arrays["ids"][i, j, :L].tolist(), fin, al, 0, j, self.batch.cfg, clock)
         return out
 
     def step(self) -> Dict[int, list]:
@@ -233,18 +273,20 @@ def _select_hyps(a: dict, i: int, is_final: bool, finalize_all: bool) -> List[di
 def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tuple[int, int]],
                        chunk_length: int = 8192, token_list: Optional[List[str]] = None,
                        frames_per_second: float = 24.0, finalize_all_last_only: bool = False,
-                       queue_depth: int = 1) -> List[dict]:
+                       queue_depth: int = 1, token_alignment: bool = False) -> List[dict]:
     """Decode the (start, end) sample ranges of one recording as PARALLEL streams
     of one batch instead of the reference's process pool over segments
     (speechcatcher/speechcatcher.py:474-497, chunk loop :574-592; SURVEY 8(f)
     rank 2).  Every segment is fed in ``chunk_length`` pieces, the last one with
     is_final=finalize_all=True.  Token timestamps follow the reference's
     convention: encoder-frame position / 24.0 s + segment start
-    (speechcatcher.py:48,509-536)."""
+    (speechcatcher.py:48,509-536).  ``token_alignment`` (C++ engine): every segment also gets ``token_start`` /
+    ``token_end`` / ``token_conf`` per token, from a CTC forced alignment of its result (seconds of the recording; None
+    for a token without one)."""
     # queue_depth > 1 (C++ engine): that many chunks of a segment at the engine - the audio is all there.  Measured: worth
     # +6..12 % when the search is decode-heavy (no block-boundary detection, <= 32 segments), nothing to -8 % with
     # detection on (the CLI's default), hence off by default (DESIGN section 4)
-    sch = StreamScheduler(batch, token_list, result_format="espnet", queue_depth=queue_depth)
+    sch = StreamScheduler(batch, token_list, result_format="espnet", queue_depth=queue_depth, align_final=token_alignment)
     out: List[Optional[dict]] = [None] * len(segments)
     todo = list(enumerate(segments))
     sid_to_seg: Dict[int, int] = {}
@@ -277,5 +319,13 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
                 else:
                     out[idx] = {"text": "", "tokens": [], "token_ids": [], "token_timestamps": [],
                                 "score": 0.0, "start": start_s}
+                if token_alignment:
+                    al = getattr(res, "alignment", None) if res else None
+                    n = len(out[idx]["tokens"])
+                    if al is None:
+                        al = {"start_s": [None] * n, "end_s": [None] * n, "conf": [None] * n}
+                    out[idx]["token_start"] = [None if a is None else start_s + a for a in al["start_s"]]
+                    out[idx]["token_end"] = [None if b is None else start_s + b for b in al["end_s"]]
+                    out[idx]["token_conf"] = list(al["conf"])
                 sch.close(sid)
     return out  # type: ignore[return-value]

@@ -188,6 +188,9 @@ def interpolate_repeating_positions(positions: List[float]) -> List[float]:
     return out[1:]
 
 
+ALIGNMENT_KEYS = ("token_start", "token_end", "token_conf")   # --token-alignment (recognize_segments)
+
+
 def merge_paragraphs(segments: List[dict]) -> Tuple[str, List[dict]]:
     """speechcatcher.py:516-572: a segment starts a new paragraph (first letter capitalised)
     only if the previous segment's text ended a sentence; otherwise its text, tokens and
@@ -208,12 +211,15 @@ def merge_paragraphs(segments: List[dict]) -> Tuple[str, List[dict]]:
             last["text"] += " " + seg["text"]
             last["tokens"] = list(last["tokens"]) + list(seg["tokens"])
             last["token_timestamps"] = list(last["token_timestamps"]) + list(seg["token_timestamps"])
+            for key in ALIGNMENT_KEYS:
+                if key in last:
+                    last[key] = list(last[key]) + list(seg[key])
     return "\n\n".join(merged) + "\n", info
 
 
 def recognize_recording_segments(batch, raw_speech_data: np.ndarray, rate: int = 16000, chunk_length: int = 8192,
                                  token_list: Optional[List[str]] = None, reference_finalize: bool = False,
-                                 average_segment_length: float = 60.0):
+                                 average_segment_length: float = 60.0, token_alignment: bool = False):
     """The segment loop of ``recognize`` (speechcatcher.py:414-497): int16 recording -> chunk-aligned sample
     ranges and the raw per-segment results of ``recognize_segments`` (before paragraph merging)."""
     assert rate == 16000
@@ -222,21 +228,23 @@ def recognize_recording_segments(batch, raw_speech_data: np.ndarray, rate: int =
                 if len(speech) > 60.0 * rate else [])
     ranges = plan_segments(len(speech), rate, segments, chunk_length)
     res = recognize_segments(batch, speech, ranges, chunk_length=chunk_length, token_list=token_list,
-                             finalize_all_last_only=reference_finalize)
+                             finalize_all_last_only=reference_finalize, token_alignment=token_alignment)
     return ranges, res
 
 
 def recognize_recording(batch, raw_speech_data: np.ndarray, rate: int = 16000, chunk_length: int = 8192,
                         token_list: Optional[List[str]] = None, reference_finalize: bool = False,
-                        average_segment_length: float = 60.0) -> Tuple[str, List[dict]]:
+                        average_segment_length: float = 60.0, token_alignment: bool = False) -> Tuple[str, List[dict]]:
     """int16 recording -> (text, per-paragraph info).  Native-decoder input scaling
     /32768 in fp32 (speechcatcher.py:421); recordings over a minute are segmented;
     the segments run as parallel streams of ``batch`` (one slot = the reference CLI with one worker:
     serial segments on one model); paragraphs are merged like the CLI does.
     ``reference_finalize``: pass finalize_all only with the last chunk of the recording, as the
-    reference CLI does."""
+    reference CLI does.  ``token_alignment``: the paragraphs also carry ``token_start`` / ``token_end`` /
+    ``token_conf`` (CTC forced alignment, next to ``token_timestamps``)."""
     ranges, res = recognize_recording_segments(batch, raw_speech_data, rate, chunk_length, token_list,
-                                               reference_finalize, average_segment_length)
+                                               reference_finalize, average_segment_length, token_alignment)
     segs = [{"start": lo / rate, "end": hi / rate, "text": r["text"], "tokens": r["tokens"],
-             "token_timestamps": r["token_timestamps"]} for (lo, hi), r in zip(ranges, res)]
+             "token_timestamps": r["token_timestamps"], **{k: r[k] for k in ALIGNMENT_KEYS if k in r}}
+            for (lo, hi), r in zip(ranges, res)]
     return merge_paragraphs(segs)

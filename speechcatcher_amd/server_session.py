@@ -30,6 +30,7 @@ from typing import Deque, Dict, List, Optional, Union
 
 import numpy as np
 
+from .align import merge_words
 from .scheduler import ServerBusy, StreamScheduler
 
 Message = Union[str, bytes, np.ndarray]
@@ -82,6 +83,17 @@ def vosk_result(tokens: List[str], token_pos: Optional[List[int]] = None) -> dic
     return {"result": words, "text": text.replace("▁", " ").strip()}
 
 
+def vosk_result_aligned(tokens: List[str], alignment: dict) -> dict:
+    """Final result with CTC forced-alignment times (ServerLoop(vosk_alignment=True)): one entry per WORD -
+    SentencePiece tokens merged at "▁" - with the aligned start / end of its tokens (seconds of the stream) and
+    conf = the product of their confidences; tokens without an alignment are left out of the words."""
+    keep = [k for k in range(len(tokens)) if alignment["start_s"][k] is not None]
+    words = merge_words([tokens[k] for k in keep], [alignment["start_s"][k] for k in keep],
+                        [alignment["end_s"][k] for k in keep], [alignment["conf"][k] for k in keep])
+    return {"result": [{"conf": w["conf"], "start": w["start"], "end": w["end"], "word": w["word"]} for w in words],
+            "text": "".join(tokens).replace("▁", " ").strip()}
+
+
 def scale_server_pcm(data: np.ndarray) -> np.ndarray:
     """int16 -> the float values the reference server feeds its model:
     ``astype(float16) / 32767.0`` (rounded to float16), then fp32."""
@@ -104,14 +116,17 @@ class ServerLoop:
 
     def __init__(self, scheduler: StreamScheduler, vosk_output_format: bool = False,
                  finalize_update_iters: int = 6, max_partial_iters: int = 42, strict_reference: bool = False,
-                 continuous: Optional[bool] = None, min_replies: int = 1):
+                 continuous: Optional[bool] = None, min_replies: int = 1, vosk_alignment: bool = False):
         """``strict_reference``: no stream reset after a finalised utterance nor between clients, exactly like
         ``recognize_ws`` / ``process_audio_chunk`` (speechcatcher_server.py:270,359-397); the default resets.
         ``continuous`` (default: on whenever the batch has the C++ engine's submit / poll - round 4; False forces one
         batched lock-step call per step): a step hands the engine the chunks of the sessions that are ready and returns as soon as
         ``min_replies`` replies are (``StreamScheduler.pump``): every client is answered when ITS chunk is decoded
         and may send the next one at once, instead of all clients waiting for the slowest stream of a batch -
-        the reference's per-client handler loop (:359-397), same calls and replies per session."""
+        the reference's per-client handler loop (:359-397), same calls and replies per session.
+        ``vosk_alignment`` (C++ engine, Vosk format): final results carry WORDS with times and confidences from a CTC
+        forced alignment (vosk_result_aligned) instead of one entry per token at its block's frame with conf 1.0; a result
+        whose hypothesis cannot be aligned (more tokens than its block has frames) keeps those default entries."""
         assert scheduler.result_format == "espnet", "sessions need token positions: result_format='espnet'"
         if strict_reference:
             scheduler.reset_after_final = scheduler.reset_on_open = False
@@ -120,6 +135,9 @@ class ServerLoop:
             continuous = hasattr(scheduler.batch, "submit")
         self.continuous, self.min_replies = continuous, min_replies
         self.vosk = vosk_output_format
+        self.vosk_alignment = vosk_alignment and vosk_output_format
+        if self.vosk_alignment:
+            scheduler.align_final = True
         self.fui, self.mpi = finalize_update_iters, max_partial_iters
         self.sessions: Dict[int, _Session] = {}
 
@@ -214,6 +232,9 @@ class ServerLoop:
                 if text[-1] not in ".!?":
                     text += "."
                 text += "\n"
+            al = getattr(results, "alignment", None)
+            if ses.vosk and self.vosk_alignment and al is not None and any(a is not None for a in al["start_s"]):
+                return vosk_result_aligned(tokens, al)
             return vosk_result(tokens, pos) if ses.vosk else text
         ses.endpointer.observe(len(text))
         return vosk_partial(text) if ses.vosk else text
@@ -276,4 +297,5 @@ class StepPacer:
         return replies
 
 
-__all__ = ["Endpointer", "ServerLoop", "StepPacer", "ServerBusy", "vosk_partial", "vosk_result", "scale_server_pcm"]
+__all__ = ["Endpointer", "ServerLoop", "StepPacer", "ServerBusy", "vosk_partial", "vosk_result", "vosk_result_aligned",
+           "scale_server_pcm"]

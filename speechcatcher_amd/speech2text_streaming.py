@@ -180,6 +180,7 @@ class _BeamSearchView:
 
     def reset(self):
         self._o.batch.reset(self._o.stream)
+        self._o._clock = None
 
 
 class _BeamStateView:
@@ -224,6 +225,30 @@ def hyps_to_results(hyps, is_final, finalize_all, token_list, fmt="native"):
             # native 3-tuples carry 0-dim torch.LongTensors, not ints (speech2text_streaming.py:498,518,537)
             res.append((text, toks, [torch.tensor(t, dtype=torch.long) for t in ids]))
     return res
+
+
+def result_token_alignment(ys, is_final, al, i, j, cfg, clock=None) -> dict:
+    """the tokens hyps_to_results returns for hypothesis yseq `ys` (same selection and id filtering), with their
+    alignment: row (i, j) of NativeStreamBatch.align.  {"token_ids", "start_s", "end_s", "conf"}: seconds of the stream
+    (speechcatcher_amd.align), conf = exp(mean CTC log-posterior over the token's frames).  None for a token without a
+    label state of the alignment (a trailing <eos> when the model's eos is not 1023 - A4) and for every token when the
+    hypothesis could not be aligned.  ``clock``: the stream's align.FeatureClock (a stream fed as audio); without one
+    the feature frames are taken as continuous."""
+    from .align import cfg_frames_to_seconds
+    ids = ys[1:] if is_final else ys[1:min(1, len(ys))]
+    if ids and ids[-1] == 1023:
+        ids = ids[:-1]
+    n_lab = len(ys) - 1 - (1 if ys[-1] == cfg.eos_id else 0)    # labels of the alignment: yseq without <sos> / <eos>
+    keep = [k for k, t in enumerate(ids) if t not in (0, 1, 1023)]
+    ok = int(al["status"][i, j]) == _abi.ALIGN_OK
+    lab = [k for k in keep if ok and k < n_lab]
+    st, en = [int(al["start"][i, j, k]) for k in lab], [int(al["end"][i, j, k]) for k in lab]
+    a, b = (clock.seconds(st, en, cfg.subsample, cfg.sample_rate) if clock is not None
+            else cfg_frames_to_seconds(cfg, st, en))
+    t_a, t_b = dict(zip(lab, a)), dict(zip(lab, b))
+    return {"token_ids": [int(ids[k]) for k in keep], "start_s": [t_a.get(k) for k in keep],
+            "end_s": [t_b.get(k) for k in keep],
+            "conf": [float(np.exp(al["logp_mean"][i, j, k])) if k in t_a else None for k in keep]}
 
 
 class Speech2TextStreaming:
@@ -287,6 +312,7 @@ class Speech2TextStreaming:
     # ------------------------------------------------------------------
     def reset(self):
         self.batch.reset(self.stream)
+        self._clock = None
         self.beam_state = None
         self.processed_frames = 0
 
@@ -303,6 +329,10 @@ class Speech2TextStreaming:
         speech = np.asarray(speech, dtype=np.float32)
         if speech.ndim == 1:
             out = self.batch.push([(self.stream, speech, is_final)])
+            if getattr(self, "_clock", None) is None:
+                from .align import FeatureClock
+                self._clock = FeatureClock(self.cfg.win_length, self.cfg.hop_length)
+            self._clock.call(speech.shape[0], is_final)   # feature frame -> sample, for token_alignment
             if not out[self.stream]:
                 return []
         elif speech.ndim == 2:
@@ -314,7 +344,27 @@ class Speech2TextStreaming:
             self.batch.push_features([(self.stream, torch.from_numpy(np.ascontiguousarray(speech[0])), is_final)])
         hyps = self.batch.hypotheses(self.stream)
         self.beam_state = _BeamStateView(hyps)
+        self._last_call = (is_final, finalize_all)
         return hyps_to_results(hyps, is_final, finalize_all, self.token_list, self.result_format)
+
+    def token_alignment(self, nbest: Optional[int] = None):
+        """CTC forced alignment of the hypotheses behind the last call's results (NativeStreamBatch.align, against the
+        stream's CTC rows of the decode block they come from): one entry per result, in the same order and with the
+        same token filtering as hyps_to_results - {"token_ids", "start_s", "end_s", "conf"}, times in seconds of the
+        stream (speechcatcher_amd.align), conf = exp(mean CTC log-posterior over the token's frames); None where a token
+        has no alignment (result_token_alignment)."""
+        last = getattr(self, "_last_call", None)
+        hyps = self.beam_state.hypotheses if last is not None else []
+        if not hyps:
+            return []
+        is_final, finalize_all = last
+        al = self.batch.align([self.stream], nbest if nbest is not None else len(hyps))
+        out = []
+        for j, h in enumerate(hyps[:int(al["n_hyps"][0])]):
+            if (not is_final or not finalize_all) and h["yseq"][-1] != 1023:   # hyps_to_results' selection (A4)
+                continue
+            out.append(result_token_alignment(h["yseq"], is_final, al, 0, j, self.cfg, getattr(self, "_clock", None)))
+        return out
 
     def recognize(self, speech):
         self.reset()
