@@ -330,10 +330,11 @@ int sc_set_stream_workspace(void *stream, void *ptr, size_t bytes);
  * 3055 / 3035 audio-s/s; strict lock-step, where the medium buckets count (tools/ab_hpw_strict.sh, 96 / 320 / 480 / 640 /
  * 960 / never): 2038 / 2137 / 2159 / 2126 / 2195 / 2151 - four heads from half of a 128-stream batch on */
 #define SC_HPW_MIN_ROWS 640
-/* (round 6) ... and from SC_STREAM_MIN_ROWS rows on in the STREAM-RESIDENT form (decoder_stream.hip: one 1024-thread workgroup per
- * stream runs both attentions of a layer for all heads, two launches per layer): a full 128-stream bucket then holds 128 of the
- * 256 compute units and the encoder groups run beside the decode chain instead of between its kernels.  Same bits as the
- * other two forms (canonical summation, common.h).  SC_STREAM_FFN_CUS: compute units its feed-forward launch is sized for. */
+/* (round 6) ... and from SC_STREAM_MIN_ROWS rows on in the STREAM-RESIDENT form (decoder_stream.hip: one 512-thread workgroup of
+ * 8 waves per stream runs both attentions of a layer for all heads, two launches per layer): buckets of more than 128 streams
+ * at beam 10, of at least 257 at beam 5.  A stream then holds one compute unit instead of two, and the encoder groups run beside
+ * the decode chain instead of between its kernels.  Same bits as the other two forms (canonical summation, common.h).
+ * SC_STREAM_FFN_CUS: compute units its feed-forward launch is sized for. */
 #define SC_STREAM_MIN_ROWS 1281
 #define SC_STREAM_FFN_CUS 256
 int sc_prof_collect_kinds(double *ms, double *flops, double *bytes, long long *n, int nkinds);

@@ -13,13 +13,14 @@
 // transformer_decoder.py:231 (embedding).
 //
 // Why (docs/r06_findings.md): the three-launch form (decoder_layer.hip) puts a stream on TWO compute units
-// (four heads each) and a full 128-stream bucket on all 256 - and every one of those workgroups spends 3/4 of its time in
+// (four heads each), so 128 streams already fill all 256 - and every one of those workgroups spends 3/4 of its time in
 // latency chains (partial-sum fetches, weight bursts from L2, merges) during which its CU does nothing, while the encoder
 // side, whose kernels need whole CUs as well, waits its turn: wall = decode time + encoder time (29.5 % of the round-5
 // wall).  Here a stream owns ONE CU for the layer: the rows never leave the workgroup between the two attentions (no
 // partial products, no second prologue, no LayerNorm recomputed by a sibling), the matrix pipe of that CU is busy for
-// ~2/3 of the kernel instead of 1/5, and a full bucket leaves 128 CUs to the encoder groups, which then run BESIDE the
-// decode chain instead of between its kernels.
+// ~2/3 of the kernel instead of 1/5, and a bucket needs half as many CUs, so the encoder groups run BESIDE the decode
+// chain instead of between its kernels.  The form serves buckets of at least SC_STREAM_MIN_ROWS rows (scasr.h): more
+// than 128 streams at beam 10, at least 257 at beam 5.
 //
 // BITS: every sum is evaluated in the canonical order of common.h - the result of a stream is bit for bit what the
 // one-head and four-head workgroups of decoder_layer.hip produce (tests/test_gpu_ops.py lock-step, bit-reproducible
@@ -166,11 +167,7 @@ __device__ __forceinline__ void ds_load2(DsTiles &b, const float *kv, int t0, in
   const int n = lane & 15, kg = lane >> 4;
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-#ifdef SC_DS_PROBE_SAMEROWS   // timing probe only (tools/build_variant.sh): every tile = tile 0, i.e. a walk whose loads hit the L1
-    const int t = i * 0 * t0;
-#else
     const int t = t0 + 4 * i;
-#endif
     long ke;
     unsigned unused;
     rowfn(16 * t + n, ke, unused);

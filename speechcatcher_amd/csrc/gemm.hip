@@ -925,9 +925,6 @@ extern "C" int sc_gemm_ln(const float *A, const int32_t *a_rows, int lda, const 
 // partial round trip 2*D*4*F/128/CPW).
 // ===========================================================================
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-#ifndef SC_FFN_EARLY_B2
-#define SC_FFN_EARLY_B2 1
-#endif
 
 __device__ __forceinline__ f32x4 ffn_mfma8(f32x4 acc, const float4 &a0, const float4 &a1, const float4 &b0,
                                            const float4 &b1) {
@@ -1198,12 +1195,10 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(FfnArgs p) {
   for (int cc = 0; cc < p.cpw; ++cc) {
     const int chunk = grp * p.cpw + cc;
     const float bias = p.b1 ? p.b1[chunk * FC + wave * 16 + r] : 0.f;
-#if SC_FFN_EARLY_B2
     // GEMM 2's weight fragments of this chunk are requested BEFORE GEMM 1: they travel behind its MFMAs.  Requested
     // after it (round 1-3) only the short epilogue lay between the request and their first use, and both waves of a
     // SIMD reach that point together (barrier): the matrix pipe idled for an L2 round trip per chunk.
     load_b2(chunk);
-#endif
     // ---- GEMM 1: h[RT x 16] of this wave ----
     f32x4 acc1[RTT];
     f32x4 acc1c[WS ? RTT : 1];
@@ -1261,10 +1256,6 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(FfnArgs p) {
         a1 = n1;
       }
     }
-#if !SC_FFN_EARLY_B2
-    // GEMM 2 weights of this chunk: in flight during the epilogue
-    load_b2(chunk);
-#endif
     if (cc > 0) __syncthreads();  // previous chunk's GEMM 2 is done reading Hs
 #pragma unroll
     for (int rt = 0; rt < RTT; ++rt)

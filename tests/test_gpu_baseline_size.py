@@ -285,12 +285,16 @@ def test_stream_resident_layers_give_the_bits_of_the_head_parallel_forms(monkeyp
         sb = make_batch("XL", 1234, "meanstd", beam, False, backend="native", n_streams=S, **kw)
         _feed(sb, audio, n)
         o = sb.hypotheses_arrays(list(range(S)))
+        by_kernel = sb.take_xattn_rows_by_kernel()   # cross-attention rows read by [flash, head-parallel, stream-resident] launches
         sb.close()
+        # the stream-resident kernel ran exactly when it was asked for
+        assert (by_kernel[2] > 0) if form == "1" else (by_kernel[2] == 0), (form, split, by_kernel)
         return o
 
     a, b = run("1"), run("0")
     assert a["lens"][:, 0].min() >= (60 if n < 20 else 150), int(a["lens"][:, 0].min())
-    # ... and the four-head form with the head partials summed in a launch of their own (sc_dec_layer_reduce_ln, an A/B hook)
+    # ... and the four-head form with the head partials summed in a launch of their own (sc_dec_layer_reduce_ln, an A/B hook;
+    # no counter tells whether that launch ran)
     for other, what in ((b, "four heads per workgroup"), (run("0", "1"), "four heads per workgroup, partials summed once per row")):
         for key in ("n_hyps", "lens", "ids", "xpos"):
             assert np.array_equal(a[key], other[key]), (what, key)
