@@ -443,6 +443,10 @@ int sc_dec_self_attn(const sc_search *sb, int layer, void *stream);
 /* decoder cross-attention over the shared per-stream K/V (decoder_layer.py:106-115) */
 int sc_dec_cross_attn(const sc_search *sb, int layer, void *stream);
 int sc_decoder_layers(const sc_search *sb, void *stream);
+/* Largest vocabulary the search kernels serve: sc_fuse_topw's full-vocabulary path keeps 8 V + 8 nextpow2(V) bytes in
+ * LDS (128 KiB at V = 8192, of the 160 KiB of a CU; 8193 would need 192 KiB).  Larger vocabularies are refused when a
+ * batch is made (sc_streams_create; speechcatcher_amd.hip_backend.HipBackend.check_supported) and by both kernels. */
+#define SC_MAX_VOCAB 8192
 /* log_softmax + pre-beam top-K (transformer_decoder.py:249, beam_search.py:150-154) */
 int sc_logsoftmax_topk(const sc_search *sb, void *stream);
 /* CTCPrefixScoreTH.__call__ on the K candidates (ctc_prefix_score_full.py:88-291) */

@@ -82,6 +82,8 @@ class AlignJob(C.Structure):
 # SC_ALIGN_* of include/scasr.h
 ALIGN_OK, ALIGN_INFEASIBLE, ALIGN_NONFINITE, ALIGN_BAD_INPUT = 0, 1, 2, 3
 ALIGN_MAX_L = 1023
+# SC_MAX_VOCAB of include/scasr.h: largest vocabulary the search kernels serve (LDS of sc_fuse_topw's full path)
+MAX_VOCAB = 8192
 
 
 class StreamInfo(C.Structure):

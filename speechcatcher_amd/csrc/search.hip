@@ -572,14 +572,48 @@ __global__ __launch_bounds__(256) void logsoftmax_topk_sort_kernel(sc_search sb)
   for (int k = tid; k < sb.K; k += 256) sb.pre_ids[(long)row * sb.K + k] = sort_key_index(comp[k]);
 }
 
+// Dynamic LDS of the two full-vocabulary sorts (8 nextpow2(V) bytes of keys; fuse_topw also 8 V of scores).  Above
+// 64 KiB a launch needs the kernel's limit raised first: done once per (kernel, device) to the size SC_MAX_VOCAB needs.
+static size_t pow2_keys_bytes(int V) {
+  size_t np = 1;
+  while (np < (size_t)V) np <<= 1;
+  return np * sizeof(unsigned long long);
+}
+static size_t fuse_topw_lds(int V) { return 2 * (size_t)V * sizeof(float) + pow2_keys_bytes(V); }
+
+static int allow_large_lds(const void *fn, size_t need, size_t max_bytes, const char *what) {
+  if (need + 256 <= 64 * 1024) return SC_OK;   // (256: room for the kernels' static LDS)
+  static std::mutex mu;
+  static std::unordered_map<const void *, unsigned long long> done;   // kernel -> bit per device
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
+    sc_set_error("%s: no current HIP device", what);
+    return SC_ERR_LAUNCH;
+  }
+  std::lock_guard<std::mutex> lk(mu);
+  unsigned long long &bits = done[fn];
+  if (bits >> dev & 1ull) return SC_OK;
+  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_bytes);
+  if (e != hipSuccess) {
+    sc_set_error("%s: raising the dynamic LDS limit to %zu bytes failed: %s", what, max_bytes, hipGetErrorString(e));
+    return SC_ERR_LAUNCH;
+  }
+  bits |= 1ull << dev;
+  return SC_OK;
+}
+
 extern "C" int sc_logsoftmax_topk(const sc_search *sbp, void *stream) {
   SC_CHECK_ARG(sbp, "null");
-  int np = 1;
-  while (np < sbp->V) np <<= 1;
+  SC_CHECK_ARG(sbp->V > 0 && sbp->V <= SC_MAX_VOCAB, "vocabulary larger than SC_MAX_VOCAB (8192)");
   if (sbp->V <= 1024 && sbp->K <= 64)
     logsoftmax_topk_kernel<<<sbp->S * sbp->W, 256, 0, (hipStream_t)stream>>>(*sbp);
-  else
-    logsoftmax_topk_sort_kernel<<<sbp->S * sbp->W, 256, np * sizeof(unsigned long long), (hipStream_t)stream>>>(*sbp);
+  else {
+    const size_t lds = pow2_keys_bytes(sbp->V);
+    const int rc = allow_large_lds(reinterpret_cast<const void *>(&logsoftmax_topk_sort_kernel), lds,
+                                   pow2_keys_bytes(SC_MAX_VOCAB), "sc_logsoftmax_topk");
+    if (rc != SC_OK) return rc;
+    logsoftmax_topk_sort_kernel<<<sbp->S * sbp->W, 256, lds, (hipStream_t)stream>>>(*sbp);
+  }
   SC_CHECK_LAUNCH();
   return SC_OK;
 }
@@ -1041,9 +1075,11 @@ __global__ __launch_bounds__(256) void fuse_topw_kernel(sc_search sb) {
 
 extern "C" int sc_fuse_topw(const sc_search *sbp, void *stream) {
   SC_CHECK_ARG(sbp, "null");
-  int np = 1;
-  while (np < sbp->V) np <<= 1;
-  size_t smem = 2 * sbp->V * sizeof(float) + np * sizeof(unsigned long long);
+  SC_CHECK_ARG(sbp->V > 0 && sbp->V <= SC_MAX_VOCAB, "vocabulary larger than SC_MAX_VOCAB (8192)");
+  const size_t smem = fuse_topw_lds(sbp->V);
+  const int rc = allow_large_lds(reinterpret_cast<const void *>(&fuse_topw_kernel), smem, fuse_topw_lds(SC_MAX_VOCAB),
+                                 "sc_fuse_topw");
+  if (rc != SC_OK) return rc;
   fuse_topw_kernel<<<sbp->S * sbp->W, 256, smem, (hipStream_t)stream>>>(*sbp);
   SC_CHECK_LAUNCH();
   return SC_OK;

@@ -1723,6 +1723,8 @@ extern "C" int sc_streams_create(sc_engine *e, const sc_stream_options *o, sc_st
   const int dk = c.d_model / c.dec_heads;
   SC_CHECK_ARG(c.d_model % c.dec_heads == 0 && (dk == 16 || dk == 32 || (dk == 64 && o->beam_size <= 10)),
                "decoder head dim must be 16, 32 or 64 (64: beam <= 10)");
+  SC_CHECK_ARG(c.vocab_size > 1 && c.vocab_size <= SC_MAX_VOCAB,
+               "vocabulary larger than SC_MAX_VOCAB (8192): the LDS of the full-vocabulary top-k of sc_fuse_topw");
   HIP_TRY(hipSetDevice(e->device));
   sc_streams *b = new sc_streams;
   b->eng = e;

@@ -53,6 +53,10 @@ class HipBackend:
             raise _abi.ScasrError(f"beam size {beam_size} > 16 is not supported by the decoder attention kernels")
         if cfg.d_model % 32:
             raise _abi.ScasrError("d_model must be a multiple of 32 (sc_gemm K tiles)")
+        if not 1 < cfg.vocab_size <= _abi.MAX_VOCAB:
+            raise _abi.ScasrError(
+                f"vocabulary size {cfg.vocab_size} is not supported (at most {_abi.MAX_VOCAB}): the full-vocabulary "
+                "top-k of sc_fuse_topw keeps 8 V + 8 nextpow2(V) bytes in LDS (include/scasr.h: SC_MAX_VOCAB)")
 
     # ------------------------------------------------------------------
     def _stream(self):

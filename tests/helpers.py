@@ -1,4 +1,5 @@
 """Shared helpers for the parity tests (oracle side)."""
+import dataclasses
 import functools
 
 import numpy as np
@@ -8,7 +9,8 @@ from speechcatcher_amd import synth
 from speechcatcher_amd.config import L_LIKE, MICRO, TINY, XL
 from speechcatcher_amd.mel import melscale_fbanks_slaney
 
-CFGS = {"TINY": TINY, "XL": XL, "MICRO": MICRO, "L_LIKE": L_LIKE}
+# TINY_V1182: the tiny model at the vocabulary believed to be the XL checkpoint's (tests/golden/tiny_v1182_*)
+CFGS = {"TINY": TINY, "XL": XL, "MICRO": MICRO, "L_LIKE": L_LIKE, "TINY_V1182": dataclasses.replace(TINY, vocab_size=1182)}
 
 
 @functools.lru_cache(maxsize=4)

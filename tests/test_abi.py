@@ -155,3 +155,32 @@ def test_oracle_is_only_used_as_the_checker():
     # the product's only compute backend is the HIP library: no torch arithmetic fallback in the engine
     engine_src = (ROOT / "speechcatcher_amd" / "engine.py").read_text()
     assert "SpecBackend" not in engine_src
+
+
+def test_vocabulary_limit_is_checked_at_construction():
+    """SC_MAX_VOCAB (include/scasr.h): the full-vocabulary path of sc_fuse_topw keeps 8 V + 8 nextpow2(V) bytes in LDS -
+    128 KiB at V = 8192 fits the 160 KiB of a CU, V = 8193 would need 192 KiB.  HipBackend.check_supported refuses larger
+    vocabularies when a batch is made (StreamBatch calls it before it allocates anything); the C engine's
+    sc_streams_create has the same check (tests/test_gpu_native.py)."""
+    import dataclasses
+
+    from speechcatcher_amd import _abi
+    from speechcatcher_amd.config import TINY, SearchConfig
+    from speechcatcher_amd.engine import StreamBatch
+    from speechcatcher_amd.hip_backend import HipBackend
+    hdr = (ROOT / "include" / "scasr.h").read_text()
+    assert int(re.search(r"#define SC_MAX_VOCAB (\d+)", hdr).group(1)) == _abi.MAX_VOCAB == 8192
+    lds = lambda V: 8 * V + 8 * (1 << (V - 1).bit_length())   # noqa: E731
+    assert lds(_abi.MAX_VOCAB) <= 160 * 1024 < lds(_abi.MAX_VOCAB + 1)
+    for V in (37, 1024, 1182, 5000, _abi.MAX_VOCAB):
+        HipBackend.check_supported(None, dataclasses.replace(TINY, vocab_size=V), 10)
+    for V in (_abi.MAX_VOCAB + 1, 16384, 1):
+        with pytest.raises(_abi.ScasrError, match="vocabulary size"):
+            HipBackend.check_supported(None, dataclasses.replace(TINY, vocab_size=V), 10)
+
+    class _Weights:       # what StreamBatch reads before it checks the backend
+        cfg = dataclasses.replace(TINY, vocab_size=_abi.MAX_VOCAB + 1)
+        device = "cpu"
+
+    with pytest.raises(_abi.ScasrError, match="vocabulary size"):
+        StreamBatch(_Weights(), object.__new__(HipBackend), 1, SearchConfig(beam_size=10), max_frames=64, max_tokens=16)

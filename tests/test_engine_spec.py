@@ -3,6 +3,7 @@ torch per-kernel spec backend (oracle/kernel_spec.py), checked against the
 fixtures produced by the real reference.  CPU only: validates the buffering
 arithmetic, block schedule, beam bookkeeping (ancestor tables, ping-pong
 hypothesis buffers, rewind) and the kernel decomposition itself."""
+import dataclasses
 import json
 
 import numpy as np
@@ -15,7 +16,8 @@ from speechcatcher_amd.engine import EngineError, StreamBatch
 from speechcatcher_amd.weights import PackedWeights
 
 from speechcatcher_amd.config import L_LIKE, M_DEFAULTS  # noqa: E402
-CFGS = {"TINY": TINY, "XL": XL, "L_LIKE": L_LIKE, "M_DEFAULTS": M_DEFAULTS}
+CFGS = {"TINY": TINY, "XL": XL, "L_LIKE": L_LIKE, "M_DEFAULTS": M_DEFAULTS,
+        "TINY_V1182": dataclasses.replace(TINY, vocab_size=1182)}   # tests/golden/tiny_v1182_*
 
 
 def make_batch(cfg_name, seed, stats, beam, bbd, n_streams=1, backend=None, device="cpu", ffn_dtype="float32",
@@ -105,6 +107,13 @@ def test_engine_ctc_weight_fixtures(name):
     """Speech2TextStreaming(ctc_weight=...): 0.5, and 0.0 = no CTC scorer at all (beam_search.py:925).  The decoder-only
     tiny fixtures run into max_length = 500 (beam_search.py:701): the step loop's bound is part of the case."""
     run_case(name, max_tokens=520)
+
+
+@pytest.mark.parametrize("name", [f"tiny_v1182_c10240_b10_bbd{d}" for d in (0, 1)])
+def test_engine_vocabulary_1182(name):
+    """The engine on the spec backend at V = 1182 (tools/gen_golden.py --vocab): trajectories of the real reference."""
+    sb, js, _ = run_case(name)
+    assert sb.cfg.vocab_size == 1182 and sb.logp.shape[-1] == 1182
 
 
 def test_engine_other_stream_slot_and_float64_stats():

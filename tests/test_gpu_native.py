@@ -50,6 +50,82 @@ def test_ctc_weight_fixtures_on_the_gpu(name, engine):
         run_case(name, backend=HipBackend("cuda:0"), device="cuda:0", score_tol=1e-3, **kw)
 
 
+@pytest.mark.parametrize("engine", ["native", "python"])
+@pytest.mark.parametrize("name", [f"tiny_v1182_c10240_b10_bbd{d}" for d in (0, 1)])
+def test_vocabulary_1182_fixtures_on_the_gpu(name, engine):
+    """The real reference's trajectories of the tiny model at V = 1182 (tools/gen_golden.py --vocab) on both engines:
+    V % d != 0 takes the six-launch decoder layers with the generic output GEMM, V > 1024 the LDS sort of the pre-beam."""
+    from test_engine_spec import run_case
+    if engine == "native":
+        sb, _, _ = run_case(name, backend="native", score_tol=1e-3)
+        c = sb.take_attn_counters()
+        assert c["self_positions"][0] > 0 and c["self_positions"][1] == c["self_positions"][2] == 0, c
+    else:
+        from speechcatcher_amd.hip_backend import HipBackend
+        sb, _, _ = run_case(name, backend=HipBackend("cuda:0"), device="cuda:0", score_tol=1e-3)
+        assert sb.ph1 is None
+    assert sb.cfg.vocab_size == 1182
+
+
+def test_native_engine_at_vocabulary_1182_against_the_oracle():
+    """The C++ engine at V = 1182 (tiny dims): 3 streams of different audio in one batch, whole utterances, against the
+    oracle run on the same box - token ids exact, scores within 1e-3 - and the forced alignment of the reported
+    hypotheses (sc_align_hyps) against the float32 spec of tests/ctc_align_ref.py on the CTC rows it aligned against."""
+    import helpers
+    from oracle.ref_port import RefPortStreaming
+    from test_engine_spec import check_against_blocks, make_batch
+    from test_gpu_ctc_align import _check_stream
+    S, chunk = 3, 10240
+    lens = [16000 * 5 + 1234, 16000 * 4 + 77, 16000 * 6 + 3217]
+    audio = [synth.synth_audio(40 + i, n) for i, n in enumerate(lens)]
+    sb = make_batch("TINY_V1182", 1234, "meanstd", 10, False, n_streams=S, backend="native", max_frames=256,
+                    max_tokens=300, pcm_capacity=1 << 18)
+    model = helpers.oracle_model("TINY_V1182", 1234, "meanstd")
+    oras = [RefPortStreaming(model, beam_size=10, use_bbd=False) for _ in range(S)]
+    pos = 0
+    while pos < max(lens):
+        items = []
+        for i in range(S):
+            if pos < lens[i]:
+                end = min(pos + chunk, lens[i])
+                fin = end >= lens[i]
+                items.append((i, audio[i][pos:end], fin))
+                oras[i](audio[i][pos:end], is_final=fin, finalize_all=fin)
+        sb.push(items)
+        pos += chunk
+    c = sb.take_attn_counters()
+    assert c["self_positions"][0] > 0 and c["self_positions"][1] == c["self_positions"][2] == 0, c
+    for i, ora in enumerate(oras):
+        ref = ora.running_hyps
+        blk = {"yseq": [list(h.yseq) for h in ref], "xpos": [list(h.xpos) for h in ref],
+               "score": [h.score for h in ref], "score_dec": [h.scores.get("decoder", 0.0) for h in ref],
+               "score_ctc": [h.scores.get("ctc", 0.0) for h in ref], "process_idx": ora.process_idx}
+        check_against_blocks(sb, i, blk, 1e-3)
+        assert len(sb.hypotheses(i)[0]["yseq"]) > 5
+    assert any(max(h["yseq"]) > 1023 for i in range(S) for h in sb.hypotheses(i))   # ids past the old vocabulary
+    _check_stream(sb, 1)
+
+
+def test_native_streams_refuse_a_vocabulary_above_the_limit():
+    """sc_streams_create refuses V > SC_MAX_VOCAB (the full-vocabulary LDS of sc_fuse_topw) with an error before it
+    allocates or launches anything; V = SC_MAX_VOCAB itself is accepted (the kernels run there: tests/test_gpu_ops.py)."""
+    import dataclasses
+
+    import test_engine_spec
+    from speechcatcher_amd._abi import MAX_VOCAB
+    from speechcatcher_amd.config import TINY
+    from speechcatcher_amd.engine import EngineError
+    from test_engine_spec import make_batch
+    for V in (MAX_VOCAB, MAX_VOCAB + 1):
+        test_engine_spec.CFGS.setdefault(f"TINY_V{V}", dataclasses.replace(TINY, vocab_size=V))
+    kw = dict(backend="native", max_frames=64, max_tokens=32, pcm_capacity=1 << 14)
+    with pytest.raises(EngineError, match="SC_MAX_VOCAB"):
+        make_batch(f"TINY_V{MAX_VOCAB + 1}", 1234, "meanstd", 5, False, **kw)
+    sb = make_batch(f"TINY_V{MAX_VOCAB}", 1234, "meanstd", 5, False, **kw)
+    sb.push([(0, synth.synth_audio(5, 12000), True)])
+    assert len(sb.hypotheses(0)) > 0
+
+
 @pytest.mark.parametrize("name", ["tiny_c10240_b10_bbd0", "tiny_c8192_b10_bbd1", "xl_c10240_b10_bbd0"])
 def test_native_engine_with_the_t_parallel_ctc_scan(name, monkeypatch):
     """the same fixtures with the CTC prefix scan split over T from 32 frames on (default: 256): every block after

@@ -824,3 +824,502 @@ def test_ctc_prefix_scan_time_at_long_tables(hip):
     assert out["T4500_column_streaming_us"] < 800.0
     assert out["T4500_t_parallel_us"] < 150.0
     # (T = 450 with 250-token hypotheses has 201 frames to walk: below the 256-frame threshold, not split)
+
+
+# ---------------------------------------------------------------------------
+# The search kernels at vocabularies other than 1024: the product takes V from the checkpoint
+# (speech2text_streaming.py:62).  Crafted buffers, one launch, a plain reference written here (float64, or numpy
+# float32 where the kernel's own operations are exact fp32 ones) and the spec.  Every batch has an active stream with W
+# live hypotheses, an inactive one and one with fewer live hypotheses: the rows of the last two must keep a sentinel.
+# ---------------------------------------------------------------------------
+LOGZERO = -10000000000.0
+EPS32 = float(np.finfo(np.float32).eps)
+
+
+def _vocab_batches(hip, V, W=10, ctc_weight=0.3, S=3, max_frames=64, max_tokens=24):
+    """Spec (CPU) and GPU batches of the tiny model at vocabulary V: config TINY_V<V> of test_engine_spec.CFGS."""
+    import dataclasses
+
+    import test_engine_spec
+    from oracle.kernel_spec import SpecBackend
+    from speechcatcher_amd.config import TINY
+    from test_engine_spec import make_batch
+    name = f"TINY_V{V}"
+    test_engine_spec.CFGS.setdefault(name, dataclasses.replace(TINY, vocab_size=V))
+    kw = dict(n_streams=S, max_frames=max_frames, max_tokens=max_tokens, pcm_capacity=1 << 12, ctc_weight=ctc_weight)
+    sc = make_batch(name, 1234, "meanstd", W, False, backend=SpecBackend(), **kw)
+    sg = make_batch(name, 1234, "meanstd", W, False, backend=hip, device="cuda:0", **kw)
+    assert sc.cfg.vocab_size == V
+    return sc, sg
+
+
+def _set_ctrl(sc, sg, rows):
+    """rows: per stream [active, cur, final, T, L, nhyp, has, told]"""
+    t = torch.tensor(rows, dtype=torch.int32)
+    sc.ctrl.copy_(t)
+    sg.ctrl.copy_(t)
+
+
+def _mirror(sc, sg, *names):
+    for k in names:
+        getattr(sg, k).copy_(getattr(sc, k))
+
+
+def _rank_desc(key):
+    """indices of a 1-d array by descending value, ties towards the lowest index"""
+    key = np.asarray(key)
+    return np.lexsort((np.arange(key.shape[0]), -key))
+
+
+def _live_rows(sc, nh):
+    return [s * sc.W + h for s in range(sc.S) for h in range(nh[s])]
+
+
+TOPK_VOCABS = [37, 100, 1000, 1024, 1025, 1182, 1280, 2048, 4096, 8192]
+
+
+def test_topk_vocabularies_reach_the_supported_limit():
+    from speechcatcher_amd._abi import MAX_VOCAB
+    assert max(TOPK_VOCABS) == MAX_VOCAB      # the limit of include/scasr.h is launched from below (and refused above it)
+
+
+@pytest.mark.parametrize("V", TOPK_VOCABS)
+def test_logsoftmax_topk_vocabularies(hip, V):
+    """sc_logsoftmax_topk: V <= 1024 takes the register kernel, V > 1024 the LDS bitonic sort over nextpow2(V) keys.
+    Logits with common offsets of +-60 and planted exact ties (ranks K-3 .. K+2 and 1 .. 3 share one logit).
+    logp against the float64 log-softmax: |err| <= eps32 * (4 (|x - max| + |logp|) + V/256 + 64) - the rounding of
+    x - max, of the final subtraction and of the fp32 sum of V exponentials (V/256 terms per lane, then a tree).
+    pre_ids: exactly the ranking of fl32(w_dec * logp) (the kernel's own logp), ties to the lowest id; against the
+    float64 ranking and the spec's, a swap only between keys closer than 1e-6 and never at a planted tie."""
+    from oracle.kernel_spec import SpecBackend
+    W = 10
+    sc, sg = _vocab_batches(hip, V, W)
+    S, K = sc.S, sc.K
+    nh = [W, 0, W - 3]
+    _set_ctrl(sc, sg, [[1, 0, 0, 40, 3, W, 1, 0], [0, 0, 0, 40, 3, W, 1, 0], [1, 0, 0, 40, 3, W - 3, 1, 0]])
+    g = torch.Generator().manual_seed(V)
+    x = torch.randn(S * W, V, generator=g, dtype=torch.float64) * 3.0
+    x += torch.tensor([60.0 if r % 2 else -60.0 for r in range(S * W)], dtype=torch.float64)[:, None]
+    x = x.float()
+    planted = {}
+    for r in range(S * W):
+        order = _rank_desc(x[r].numpy())
+        tie_k = order[max(0, K - 3):min(V, K + 3)]
+        tie_top = order[1:4]
+        x[r, torch.from_numpy(tie_k)] = x[r, int(order[K - 1])].item()
+        x[r, torch.from_numpy(tie_top)] = x[r, int(order[1])].item()
+        planted[r] = set(tie_k.tolist()) | set(tie_top.tolist())
+    sc.logits.copy_(x)
+    sc.logp.fill_(7.0)
+    sc.pre_ids.fill_(-5)
+    _mirror(sc, sg, "logits", "logp", "pre_ids")
+    SpecBackend().logsoftmax_topk(sc)
+    hip.logsoftmax_topk(sg)
+    torch.cuda.synchronize()
+    lp, ids = sg.logp.cpu(), sg.pre_ids.cpu()
+    live = _live_rows(sc, nh)
+    dead = [r for r in range(S * W) if r not in live]
+    assert bool((lp[dead] == 7.0).all()) and bool((ids[dead] == -5).all())
+    wd32 = np.float32(sc.search.decoder_weight)
+    for r in live:
+        x64 = x[r].double()
+        lp64 = (x64 - torch.logsumexp(x64, 0)).numpy()
+        bound = EPS32 * (4.0 * ((x64 - x64.max()).abs().numpy() + np.abs(lp64)) + V / 256 + 64)
+        err = np.abs(lp[r].numpy().astype(np.float64) - lp64)
+        assert bool((err <= bound).all()), (r, float((err / bound).max()))
+        got = ids[r].numpy()
+        exact = _rank_desc(wd32 * lp[r].numpy())[:K]           # numpy float32 product: __fmul_rn
+        np.testing.assert_array_equal(got, exact, err_msg=f"row {r}")
+        key64 = float(wd32) * lp64
+        for other in (_rank_desc(key64)[:K], sc.pre_ids[r].numpy()):
+            for a, b in zip(got, other):
+                if a != b:
+                    assert a not in planted[r] and b not in planted[r], (r, a, b)
+                    assert abs(key64[a] - key64[b]) < 1e-6, (r, a, b, key64[a], key64[b])
+    np.testing.assert_allclose(lp[live].numpy(), sc.logp[live].numpy(), rtol=0, atol=2e-5 * 70)
+
+
+def _fuse_inputs(sc, V, K, W, case, g):
+    """logp rows (log-softmax of random logits), pre-beam ids (the top K of fl(w_dec logp)), psi / psi_eos / s_prev for
+    one fuse_topw case; returns the has flag per stream."""
+    S = sc.S
+    wd32 = np.float32(sc.search.decoder_weight)
+    x = torch.randn(S * W, V, generator=g, dtype=torch.float64) * 3.0
+    sc.logp.copy_(torch.log_softmax(x, -1).float())
+    eos, blank = sc.cfg.eos_id, sc.cfg.blank_id
+    for r in range(S * W):
+        ids = _rank_desc(wd32 * sc.logp[r].numpy())[:K].copy()
+        if case != "decoder_only":
+            if blank not in ids:
+                ids[5 % K] = blank
+            if case == "fast_eos_unlisted":
+                rest = [v for v in _rank_desc(wd32 * sc.logp[r].numpy())[K:] if v not in (eos, blank)]
+                ids = np.array([v if v != eos else rest[0] for v in ids])
+            elif eos not in ids:
+                ids[7 % K] = eos
+        assert len(set(ids.tolist())) == K
+        sc.pre_ids[r] = torch.from_numpy(ids.astype(np.int32))
+    s_prev = -20.0 + torch.randn(2, S, W, generator=g)
+    psi = s_prev[0].reshape(S * W, 1) - 3.0 * torch.rand(S * W, K, generator=g)
+    psi_eos = s_prev[0].reshape(S * W) - 3.0 * torch.rand(S * W, generator=g)
+    if case == "full_few_psi":             # fewer than W candidates keep a CTC score: the top W need the whole vocabulary
+        psi[:, W - 4 if W > 4 else 0:] = LOGZERO
+        psi_eos[:] = LOGZERO
+    if case == "full_dead_prefix":         # prefixes whose own CTC score is logzero: the bound wins (w_ctc * 0 = 0)
+        s_prev[:] = LOGZERO
+        psi[:] = LOGZERO
+        psi_eos[:] = LOGZERO
+    sc.ctc_s.copy_(s_prev)
+    sc.psi.copy_(psi)
+    sc.psi_eos.copy_(psi_eos)
+
+
+def _fuse_reference(lp, ids, psi, psi_eos, s_prev, wd, wc, W, eos, blank):
+    """fuse_topw in numpy float32, every operation rounded as the kernel's: ctc = psi (eos: psi_eos, blank and
+    non-candidates: logzero) - s_prev; combined = fl(fl(wd lp) + fl(wc ctc)); top W of the whole vocabulary.
+    Also returns whether the kernel's fast path (the <= K+1 tokens with a CTC score) would be exact: its W-th score
+    must beat w_ctc (logzero - s_prev), the best any other token can reach."""
+    f = np.float32
+    V = lp.shape[0]
+    ctc = np.full(V, f(LOGZERO), np.float32)
+    ctc[ids] = psi
+    ctc[eos] = psi_eos
+    ctc[blank] = f(LOGZERO)
+    cv = (ctc - f(s_prev)).astype(np.float32)
+    comb = (f(wd) * lp + f(wc) * cv).astype(np.float32)
+    order = _rank_desc(comb)[:W]
+    cands = set(ids.tolist()) | {eos}
+    ck = sorted(((comb[c] if c != blank else f(f(wd) * lp[c]) + f(f(wc) * f(f(LOGZERO) - f(s_prev))), -c) for c in cands),
+                reverse=True)
+    bound = f(f(wc) * f(f(LOGZERO) - f(s_prev)))
+    fast_ok = len(ck) >= W and ck[W - 1][0] > bound
+    return order, comb[order], cv[order], fast_ok
+
+
+@pytest.mark.parametrize("V", [100, 1024, 1182, 4096, 8192])
+@pytest.mark.parametrize("cw", [0.0, 0.3, 1.0])
+def test_fuse_topw_vocabularies(hip, V, cw):
+    """sc_fuse_topw (beam_search.py:113-185 fusion + the per-hypothesis top W) bit for bit against numpy float32:
+    eos among the pre-beam candidates and not, blank among them; the fast path (one wave sorts the <= K+1 tokens with a
+    CTC score) and the full-vocabulary path (LDS bitonic sort over nextpow2(V) keys, 8 V + 8 nextpow2(V) bytes), each
+    asserted by a predicate to be the one the case needs.  ctc_weight 0: no CTC scorer, the top W pre-beam ids."""
+    from oracle.kernel_spec import SpecBackend
+    W = 10
+    sc, sg = _vocab_batches(hip, V, W, ctc_weight=cw)
+    S, K = sc.S, sc.K
+    eos, blank = sc.cfg.eos_id, sc.cfg.blank_id
+    wd, wc = sc.search.decoder_weight, sc.search.ctc_weight
+    nh = [W, 0, W - 3]
+    _set_ctrl(sc, sg, [[1, 0, 0, 40, 3, W, 1, 0], [0, 0, 0, 40, 3, W, 1, 0], [1, 0, 0, 40, 3, W - 3, 0, 0]])
+    cases = ["decoder_only"] if cw == 0.0 else ["fast_eos_listed", "fast_eos_unlisted", "full_few_psi", "full_dead_prefix"]
+    g = torch.Generator().manual_seed(V + int(cw * 10))
+    paths = set()
+    for case in cases:
+        _fuse_inputs(sc, V, K, W, case, g)
+        sc.cand_tok.fill_(-7)
+        sc.cand_score.fill_(9.0)
+        sc.cand_ctc.fill_(9.0)
+        _mirror(sc, sg, "logp", "pre_ids", "psi", "psi_eos", "ctc_s", "cand_tok", "cand_score", "cand_ctc")
+        hip.fuse_topw(sg)
+        SpecBackend().fuse_topw(sc)
+        torch.cuda.synchronize()
+        tok, scr, ctc = sg.cand_tok.cpu(), sg.cand_score.cpu(), sg.cand_ctc.cpu()
+        live = _live_rows(sc, nh)
+        dead = [r for r in range(S * W) if r not in live]
+        assert bool((tok[dead] == -7).all()) and bool((scr[dead] == 9.0).all()) and bool((ctc[dead] == 9.0).all())
+        for r in live:
+            s, h = divmod(r, W)
+            lp = sc.logp[r].numpy()
+            if case == "decoder_only":
+                want_t = sc.pre_ids[r].numpy()[:W]
+                want_s = (np.float32(wd) * lp[want_t]).astype(np.float32)
+                want_c = np.zeros(W, np.float32)
+                assert list(want_t) == list(_rank_desc(np.float32(wd) * lp)[:W])
+            else:
+                has = int(sc.ctrl[s, 6])
+                s_prev = float(sc.ctc_s[0, s, h]) if has else 0.0
+                want_t, want_s, want_c, fast_ok = _fuse_reference(lp, sc.pre_ids[r].numpy(), sc.psi[r].numpy(),
+                                                                  sc.psi_eos[r].numpy(), s_prev, wd, wc, W, eos, blank)
+                assert fast_ok == case.startswith("fast"), (case, r)
+                paths.add("fast" if fast_ok else "full")
+                if case == "fast_eos_unlisted":
+                    assert eos not in sc.pre_ids[r].tolist()
+            np.testing.assert_array_equal(tok[r].numpy(), want_t, err_msg=f"{case} row {r}")
+            assert scr[r].numpy().tobytes() == want_s.tobytes(), (case, r)
+            assert ctc[r].numpy().tobytes() == want_c.tobytes(), (case, r)
+        assert torch.equal(tok, sc.cand_tok) and torch.equal(scr, sc.cand_score) and torch.equal(ctc, sc.cand_ctc), case
+    if cw > 0.0:
+        assert paths == {"fast", "full"}
+
+
+def _prune_reference(score, cand_score, nh, W):
+    """ranks of beam_prune: float64 totals, stable descending sort (hypothesis-major), the best W (beam_search.py:757)"""
+    cands = [(float(score[h]) + float(cand_score[h * W + j]), h, j) for h in range(nh) for j in range(W)]
+    return sorted(cands, key=lambda c: c[0], reverse=True)[:W]
+
+
+@pytest.mark.parametrize("W,nh", [(1, 1), (5, 1), (5, 2), (5, 5), (10, 1), (10, 7), (10, 10), (16, 1), (16, 13), (16, 16)])
+def test_beam_prune_ties_flags_and_pool_rows(hip, W, nh):
+    """sc_beam_prune at V = 1182 against a plain reference: totals on a 1/8 grid (exact float64 sums) with planted exact
+    ties across hypotheses at the first and the W-th place (stable, hypothesis-major order as Python's
+    sorted(..., reverse=True) of beam_search.py:757); score / sc_dec / sc_ctc exactly the float64 sums; yseq, xpos, sel,
+    anc, ctc_s exact; flags for eos at rank 0, all winners eos, eos later and a repeated token; the K|V pool rows of the
+    new tokens = the lowest rows no winner's history holds, in rank order - and with a pool one row too small: kvflags = 1
+    and every row handed out < kv_rows.  Rows past nhyp carry totals that would win if they were read."""
+    from oracle.kernel_spec import SpecBackend
+    V, L, T = 1182, 6, 40
+    sc, sg = _vocab_batches(hip, V, W, S=3, max_tokens=16)
+    S, K = sc.S, sc.K
+    eos, sos = sc.cfg.eos_id, sc.cfg.sos_id
+    nhs = [nh, 0, max(1, nh - 2)]
+    _set_ctrl(sc, sg, [[1, 0, 0, T, L, nhs[0], 1, 0], [0, 0, 0, T, L, W, 1, 0], [1, 0, 0, T, L, nhs[2], 1, 0]])
+    g = torch.Generator().manual_seed(100 * W + nh)
+    sc.score[0] = torch.randint(-160, 1, (S, W), generator=g).double() / 8.0
+    cs = torch.randint(-64, 1, (S * W, W), generator=g).float() / 8.0
+    for s in (0, 2):
+        n = nhs[s]
+        sc.score[0, s, n:] = 1e6
+        cs[s * W + n:(s + 1) * W] = 1e6
+        rk = _prune_reference(sc.score[0, s], cs[s * W:(s + 1) * W].reshape(-1), n, W)
+        # plant: a candidate of the LAST live hypothesis ties with the best total, another ties with the W-th
+        for (tot, h, j), jj in ((rk[0], W - 1), (rk[-1], 0)):
+            hb = n - 1 if h != n - 1 else 0
+            if hb == h:          # one live hypothesis: the tie is between two of its candidates
+                jj = W - 1 if j != W - 1 else 0
+                if jj == j:
+                    continue
+            cs[s * W + hb, jj] = float(tot - float(sc.score[0, s, hb]))
+    sc.cand_score.copy_(cs)
+    sc.cand_ctc.copy_(torch.randn(S * W, W, generator=g))
+    sc.logp.copy_(-torch.rand(S * W, V, generator=g) * 10.0)
+    sc.sc_dec[0] = torch.randn(S, W, generator=g).double() * 30
+    sc.sc_ctc[0] = torch.randn(S, W, generator=g).double() * 30
+    sc.psi.copy_(-torch.rand(S * W, K, generator=g) * 30)
+    sc.psi_eos.copy_(-torch.rand(S * W, generator=g) * 30)
+    sc.yseq[0] = torch.randint(1, 500, (S, W, sc.LCAP), generator=g).to(torch.int32)
+    sc.yseq[0, :, :, 0] = sos
+    sc.xpos[0] = torch.randint(0, T, (S, W, sc.LCAP), generator=g).to(torch.int32)
+    ranks = {s: _prune_reference(sc.score[0, s], sc.cand_score[s * W:(s + 1) * W].reshape(-1), nhs[s], W) for s in (0, 2)}
+    if W > 1:
+        tot0 = [c[0] for c in ranks[0]]
+        assert len(set(tot0)) < W, "no exact tie among the winners"
+    # ancestor table: the winners' distinct parents hold dense rows with a few holes (at most W-1), the other hypotheses
+    # copy the first winner's history
+    n_used = {}
+    for s in (0, 2):
+        par = sorted({h for _, h, _ in ranks[s]})
+        hc = min(W - 1, (L * len(par)) // 4)
+        rows = [i + min(i // 4, hc) for i in range(L * len(par))]
+        n_used[s] = (len(rows), hc)
+        for q, h in enumerate(par):
+            sc.anc[0, s, :L, h] = torch.tensor(rows[q * L:(q + 1) * L], dtype=torch.int32)
+        for h in range(W):
+            if h not in par:
+                sc.anc[0, s, :L, h] = sc.anc[0, s, :L, par[0]]
+    expect_flags = {"plain": 0, "eos_best": 7 if W == 1 else 3, "all_eos": 7, "repeat": 8, "eos_later": 1 if W > 1 else 0,
+                    "exhaust": 0}
+    spec = SpecBackend()
+    for case in expect_flags:
+        # tokens: never eos, never in a parent's history (ids 1..499) - unless the case plants one
+        tok = torch.stack([torch.randperm(V - 601, generator=g)[:W] + 600 for _ in range(S * W)]).to(torch.int32)
+        for s in (0, 2):
+            if case == "eos_best":
+                _, h, j = ranks[s][0]
+                tok[s * W + h, j] = eos
+            if case == "all_eos":
+                tok[s * W:(s + 1) * W] = eos
+            if case == "repeat":
+                _, h, j = ranks[s][-1]
+                tok[s * W + h, j] = int(sc.yseq[0, s, h, 2])
+            if case == "eos_later" and W > 1:
+                _, h, j = ranks[s][1]
+                tok[s * W + h, j] = eos
+        sc.cand_tok.copy_(tok)
+        for r in range(S * W):               # half of the candidates' tokens are pre-beam candidates (sel / ctc_s)
+            ids = torch.randperm(V, generator=g)[:K].to(torch.int32)
+            ids[torch.randperm(K, generator=g)[:W // 2]] = tok[r, :W // 2]
+            sc.pre_ids[r] = ids
+        for k in ("yseq", "xpos", "anc"):
+            getattr(sc, k)[1] = -3
+        sc.score[1] = -3.0
+        sc.sc_dec[1] = -3.0
+        sc.sc_ctc[1] = -3.0
+        sc.ctc_s[1] = -3.0
+        sc.sel.fill_(-3)
+        sc.flags.fill_(-3)
+        sc.kvflags.fill_(-3)
+        if case == "exhaust":                # stream 0's winners leave exactly W-1 free rows below kv_rows
+            sc.kv_rows = n_used[0][0] + W - 1
+        else:
+            sc.kv_rows = max(u + hc for u, hc in n_used.values()) + W + 7
+        assert sc.kv_rows >= W
+        hip.search_struct(sg).kv_rows = int(sc.kv_rows)
+        _mirror(sc, sg, "score", "sc_dec", "sc_ctc", "cand_score", "cand_tok", "cand_ctc", "logp", "pre_ids", "psi",
+                "psi_eos", "yseq", "xpos", "anc", "ctc_s", "sel", "flags", "kvflags")
+        hip.beam_prune(sg)
+        spec.beam_prune(sc)
+        torch.cuda.synchronize()
+        NR = int(sc.kv_rows)
+        for s in (0, 2):
+            any_e = best_e = rep = False
+            all_e = True
+            used = set()
+            for i, (tot, h, j) in enumerate(ranks[s]):
+                r = s * W + h
+                t = int(sc.cand_tok[r, j])
+                assert float(sg.score[1, s, i]) == tot, (case, s, i)
+                assert float(sg.sc_dec[1, s, i]) == float(sc.sc_dec[0, s, h]) + float(sc.logp[r, t])
+                assert float(sg.sc_ctc[1, s, i]) == float(sc.sc_ctc[0, s, h]) + float(sc.cand_ctc[r, j])
+                assert sg.yseq[1, s, i, :L + 1].cpu().tolist() == sc.yseq[0, s, h, :L].tolist() + [t]
+                assert sg.xpos[1, s, i, :L + 1].cpu().tolist() == sc.xpos[0, s, h, :L].tolist() + [T - 1]
+                assert sg.anc[1, s, :L, i].cpu().tolist() == sc.anc[0, s, :L, h].tolist()
+                ids = sc.pre_ids[r].tolist()
+                kk = ids.index(t) if t in ids else -1
+                want = LOGZERO if t == sc.cfg.blank_id else float(sc.psi_eos[r]) if t == eos else \
+                    float(sc.psi[r, kk]) if kk >= 0 else LOGZERO
+                assert float(sg.ctc_s[1, s, i]) == float(np.float32(want)), (case, s, i)
+                assert sg.sel[s, i].cpu().tolist() == [h, max(kk, 0)], (case, s, i)
+                any_e |= t == eos
+                all_e &= t == eos
+                best_e |= i == 0 and t == eos
+                rep |= t not in (sos, eos) and t in sc.yseq[0, s, h, 1:L].tolist()
+                used |= set(sc.anc[0, s, :L, h].tolist())
+            flags = (1 if any_e else 0) | (2 if best_e else 0) | (4 if all_e else 0) | (8 if rep else 0)
+            assert flags == expect_flags[case], (case, s, flags)
+            assert int(sg.flags[s]) == flags, (case, s, int(sg.flags[s]), flags)
+            free = [r for r in range(NR) if r not in used][:W]
+            short = len(free) < W
+            free += [NR - 1] * (W - len(free))
+            got = sg.anc[1, s, L, :W].cpu().tolist()
+            assert got == free, (case, s, got, free)
+            assert max(got) < NR and int(sg.kvflags[s]) == int(short), (case, s)
+            if case != "exhaust":
+                assert not short, (case, s)
+            elif s == 0:
+                assert short
+        # the inactive stream keeps every sentinel; everything matches the spec (which zeroes inactive streams' flags)
+        assert int(sg.flags[1]) == -3 and int(sg.kvflags[1]) == -3
+        assert bool((sg.yseq[1, 1].cpu() == -3).all()) and bool((sg.anc[1, 1].cpu() == -3).all())
+        assert bool((sg.score[1, 1].cpu() == -3.0).all()) and bool((sg.sel[1].cpu() == -3).all())
+        assert torch.equal(sg.flags.cpu()[[0, 2]], sc.flags[[0, 2]])
+        for k in ("yseq", "xpos", "anc", "sel", "kvflags", "score", "sc_dec", "sc_ctc", "ctc_s"):
+            assert torch.equal(getattr(sg, k).cpu(), getattr(sc, k)), (case, k)
+
+
+@pytest.mark.parametrize("V", [100, 1182, 1280])
+def test_ctc_extend_state_transposes_ragged_tiles(hip, V):
+    """sc_ctc_extend_state: the column-major copy of the new CTC rows (32 x 32 tiles: V and the frame range told..T-1 not
+    multiples of 32, tiles that start in front of told) is the exact transpose for frames told..T-1 and leaves every
+    other element alone; the blank extension of r^b matches the spec bit for bit (the same sequential fp32 sums)."""
+    from oracle.kernel_spec import SpecBackend
+    W = 10
+    sc, sg = _vocab_batches(hip, V, W, S=4, max_frames=128)
+    S, TC = sc.S, sc.TCAP
+    spans = [(37, 101), (0, 0), (0, 45), (64, 64)]      # stream 1 inactive, stream 3 has nothing new
+    _set_ctrl(sc, sg, [[1, 0, 0, 101, 4, W, 1, 37], [0, 0, 0, 90, 4, W, 1, 3], [1, 0, 0, 45, 1, 1, 0, 0],
+                       [1, 0, 0, 64, 4, W - 3, 1, 64]])
+    g = torch.Generator().manual_seed(V)
+    sc.ctcx.copy_(torch.randn(S * TC, V, generator=g) - 5.0)
+    sc.ctcxT.fill_(5.0)
+    sc.ctc_r.copy_(torch.randn(sc.ctc_r.shape, generator=g) - 30.0)
+    sc.ctc_rs.copy_(torch.randn(sc.ctc_rs.shape, generator=g) - 30.0)
+    _mirror(sc, sg, "ctcx", "ctcxT", "ctc_r", "ctc_rs")
+    hip.ctc_extend_state(sg)
+    SpecBackend().ctc_extend_state(sc)
+    torch.cuda.synchronize()
+    xt = sg.ctcxT.cpu().view(S, V, -1)
+    x = sc.ctcx.view(S, TC, V)
+    for s, (told, T) in enumerate(spans):
+        if T > told:
+            assert torch.equal(xt[s, :, told:T], x[s, told:T].t()), s
+        keep = torch.ones(xt.shape[-1], dtype=torch.bool)
+        keep[told:T] = False
+        assert bool((xt[s][:, keep] == 5.0).all()), s
+    assert torch.equal(xt, sc.ctcxT.view(S, V, -1))
+    assert torch.equal(sg.ctc_r.cpu(), sc.ctc_r) and torch.equal(sg.ctc_rs.cpu(), sc.ctc_rs)
+
+
+@pytest.mark.parametrize("V", [100, 1182, 5000])
+def test_log_softmax_rows_vocabularies(hip, V):
+    """sc_log_softmax_rows (the CTC table rows, N = V) against float64, rows through a row table; other rows untouched.
+    Bound as for the pre-beam kernel: eps32 * (4 (|x - max| + |logp|) + V/256 + 64)."""
+    g = torch.Generator().manual_seed(V)
+    x0 = (torch.randn(20, V, generator=g, dtype=torch.float64) * 4.0 + 40.0).float()
+    rows = torch.tensor([3, 7, 0, 19, 11], dtype=torch.int32)
+    xg = x0.cuda()
+    hip.log_softmax_rows(xg, rows.cuda(), rows.numel(), V)
+    torch.cuda.synchronize()
+    out = xg.cpu()
+    for r in range(20):
+        if r not in rows.tolist():
+            assert torch.equal(out[r], x0[r]), r
+            continue
+        x64 = x0[r].double()
+        lp64 = x64 - torch.logsumexp(x64, 0)
+        bound = EPS32 * (4.0 * ((x64 - x64.max()).abs() + lp64.abs()) + V / 256 + 64)
+        assert bool(((out[r].double() - lp64).abs() <= bound).all()), r
+
+
+def _lockstep_vocab(hip, cfg_name, beam, n_samples, chunk, n_calls=None, **kw):
+    """Lock-step run of one utterance (audio stream 0) on a model of test_engine_spec.CFGS"""
+    from lockstep import LockstepBackend
+    from test_engine_spec import make_batch
+    ls = LockstepBackend(hip, **kw)
+    caps = dict(max_frames=256, max_tokens=200, pcm_capacity=1 << 18)
+    sb_cpu = make_batch(cfg_name, 1234, "meanstd", beam, False, backend=ls, **caps)
+    sb_gpu = make_batch(cfg_name, 1234, "meanstd", beam, False, backend=hip, device="cuda:0", **caps)
+    ls.attach(sb_cpu, sb_gpu)
+    audio = synth.synth_audio(0, n_samples)
+    pos, k = 0, 0
+    while pos < len(audio) and (n_calls is None or k < n_calls):
+        end = min(pos + chunk, len(audio))
+        sb_cpu.push([(0, audio[pos:end], end >= len(audio))])
+        pos, k = end, k + 1
+    return ls, sb_cpu
+
+
+@pytest.mark.parametrize("V", [100, 1182])
+def test_every_kernel_lockstep_tiny_vocabularies(hip, V):
+    """The tiny model at V = 100 and 1182 (the XL checkpoint's believed vocabulary), whole utterance, beam 10: every kernel
+    against its spec (2e-4).  V % 32 != 0: ragged tiles of the ctc_lo GEMM, the CTC table transpose and log-softmax rows;
+    1182 > 1024: the LDS sort of the pre-beam; V % d != 0: the six-launch decoder layers with the generic output GEMM."""
+    import dataclasses
+
+    import test_engine_spec
+    from speechcatcher_amd.config import TINY
+    test_engine_spec.CFGS.setdefault(f"TINY_V{V}", dataclasses.replace(TINY, vocab_size=V))
+    ls, sb = _lockstep_vocab(hip, f"TINY_V{V}", 10, 16000 * 6 + 3217, 10240)
+    _dump(ls, f"lockstep_tiny_v{V}")
+    assert sb.ph1 is None
+    assert ls.calls.get("dec_self_attn", 0) > 0 and "dec_layer_self" not in ls.calls
+    assert set(ls.report) >= ALL_OPS
+    assert len(sb.hypotheses(0)[0]["yseq"]) > 5
+    assert not ls.failures, ls.failures[:10]
+    assert not ls.int_mismatch, ls.int_mismatch[:10]
+
+
+@pytest.mark.parametrize("V", [1182, 1280])
+def test_every_kernel_lockstep_xl_geometry_vocabularies(hip, monkeypatch, V):
+    """XL geometry (d = 256, 8 heads; 3 + 2 layers), 5 calls, 5e-4: V = 1182 (V % d != 0) takes the six-launch decoder
+    layers and the generic output GEMM; V = 1280 the head-parallel layer kernels with the lane-packed output layer at
+    N = 1280 - and, both above 1024, the LDS sort of the pre-beam."""
+    import test_engine_spec
+    from lockstep import LockstepBackend
+    from speechcatcher_amd.config import ModelConfig
+    name = f"XL_GEOM_V{V}"
+    test_engine_spec.CFGS[name] = ModelConfig(d_model=256, enc_heads=8, enc_layers=3, dec_heads=8, dec_layers=2, vocab_size=V)
+    fused = V % 256 == 0
+    monkeypatch.setenv("SC_DEC_STREAM", "0")
+    monkeypatch.setattr(LockstepBackend, "stream_layers", False)
+    monkeypatch.setattr(LockstepBackend, "fused_layers", True)
+    ls, sb = _lockstep_vocab(hip, name, 10, 16000 * 6 + 3217, 10240, n_calls=5, atol=5e-4, rtol=5e-4)
+    _dump(ls, f"lockstep_xl_geometry_v{V}")
+    assert (sb.ph1 is not None) == fused
+    if fused:
+        assert ls.calls.get("dec_layer_self", 0) > 0 and ls.calls.get("dec_output_logits", 0) > 0
+        assert "dec_self_attn" not in ls.calls
+    else:
+        assert ls.calls.get("dec_self_attn", 0) > 0 and "dec_layer_self" not in ls.calls
+    assert ls.calls.get("logsoftmax_topk", 0) > 0 and ls.calls.get("beam_prune", 0) > 0
+    assert not ls.failures, ls.failures[:10]
+    assert not ls.int_mismatch, ls.int_mismatch[:10]

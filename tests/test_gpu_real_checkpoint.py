@@ -35,12 +35,17 @@ def test_real_checkpoint_matches_the_oracle_port():
     _check_model_dir(model_dir)
 
 
-def test_the_same_check_on_a_synthetic_model_directory(tmp_path):
+@pytest.mark.parametrize("vocab", [1024, 1182])
+def test_the_same_check_on_a_synthetic_model_directory(tmp_path, vocab):
     """the code path of the conditional test above, on a model directory written with seeded weights in the ESPnet
-    layout (M_DEFAULTS dims: what a config.yaml without sizes builds) - so that the check itself is known to run"""
+    layout (M_DEFAULTS dims: what a config.yaml without sizes builds) - so that the check itself is known to run; also
+    at V = 1182, the vocabulary the XL checkpoint is believed to have (read from the checkpoint's shapes)"""
+    import dataclasses
+
     from speechcatcher_amd import synth
     from speechcatcher_amd.config import M_DEFAULTS
-    _check_model_dir(synth.write_model_dir(tmp_path / "m", M_DEFAULTS, seed=11, stats_kind="meanstd"))
+    cfg = M_DEFAULTS if vocab == 1024 else dataclasses.replace(M_DEFAULTS, vocab_size=vocab)
+    assert _check_model_dir(synth.write_model_dir(tmp_path / "m", cfg, seed=11, stats_kind="meanstd")) == vocab
 
 
 def _check_model_dir(model_dir):
@@ -76,3 +81,4 @@ def _check_model_dir(model_dir):
     steps = max(1, len(ref[0].yseq))
     assert max(abs(a["score"] - b.score) for a, b in zip(hyps, ref)) <= 1e-3 * steps
     assert res is not None
+    return cfg.vocab_size

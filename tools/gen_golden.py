@@ -354,8 +354,33 @@ def ctc_weights():
             print(name, "blocks", len(rec.blocks), "final", calls[-1]["results"][:1])
 
 
+def vocab_cases():
+    """The product takes the vocabulary size from the checkpoint (speech2text_streaming.py:62); the XL model's is
+    believed to be 1182, which is not a multiple of d_model, of 32 or of a power of two.  ``python tools/gen_golden.py
+    --vocab`` records the tiny trajectories at V = 1182 (model name TINY_V1182 in the tests' config tables), BBD off
+    and on, no tensors.  (The reference's result assembly hard-codes eos = 1023: at this vocabulary id
+    1023 is an ordinary token and the real eos (1181) is kept in the results - the engines mirror it.)"""
+    import dataclasses
+    OUT.mkdir(parents=True, exist_ok=True)
+    torch.manual_seed(0)
+    torch.set_num_threads(8)
+    tmp = Path(tempfile.mkdtemp(prefix="golden_"))
+    cfg = dataclasses.replace(TINY, vocab_size=1182)
+    mdir = synth.write_model_dir(tmp / "tiny_v1182", cfg, seed=1234, stats_kind="meanstd")
+    audio = synth.synth_audio(0, 16000 * 6 + 3217)
+    for bbd in (False, True):
+        name = f"tiny_v1182_c10240_b10_bbd{int(bbd)}"
+        s2t, rec, calls = run_stream(mdir, audio, 10240, 10, bbd)
+        meta = {"model": "TINY_V1182", "seed": 1234, "stats": "meanstd", "audio_stream": 0,
+                "n_samples": len(audio), "chunk": 10240, "beam": 10, "bbd": bbd}
+        save_case(name, meta, rec, calls, with_tensors=False)
+        print(name, "blocks", len(rec.blocks), "final", calls[-1]["results"][:1])
+
+
 if __name__ == "__main__":
-    if "--ctc-weights" in sys.argv[1:]:
+    if "--vocab" in sys.argv[1:]:
+        vocab_cases()
+    elif "--ctc-weights" in sys.argv[1:]:
         ctc_weights()
     elif "--xl-extra" in sys.argv[1:]:
         xl_extra()
