@@ -21,15 +21,18 @@ Weights: de_streaming_transformer_xl dimensions, seeded synthetic (no checkpoint
 noise.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full      (also the roofline leg and the other legs: --legs)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
         --master-addr 127.0.0.1 --master-port 29500 bench.py --gpus 8 ...
     python bench.py --gpus 8 ...        (no launcher: bench.py starts the 8 rank processes itself, rank i on GPU i)
 
 Prints ONE JSON line (rank 0).  value = whole-job audio-seconds processed per wall-clock second = number of
-concurrent real-time streams the job sustains.  Extra keys: `served` (continuous batching through sc_submit / sc_poll:
-the same chunks, the same per-call results, every stream gets its next chunk as soon as its previous reply has been
-delivered), `resident_no_readback`, `long_context` (T ~ 1000 and T ~ 4500 encoder frames), `roofline`,
-`cpu_baseline`, `single_stream`, `whole_step`.
+concurrent real-time streams the job sustains.  A plain run does only what `value` needs: it sets up, rolls the streams
+to the window, warms up, times the steps, writes --dump-outputs and prints the line (`whole_step` is worked out from the
+timed steps).  The keys of what takes runs of its own are null there and filled with `--full`: `roofline`,
+`cpu_baseline`, `single_stream`, the other mode, `exact_steps`, `chunk_sizes`, `one_eighth_of_host_cores`,
+`wider_batches`, `fp16_mode`, and with `--full --legs all` also `resident_no_readback`, `long_context` (T ~ 1000 and
+T ~ 4500 encoder frames) and the other precisions and configurations.
 
 `--dump-outputs DIR` (rank 0): after the timed steps, DIR/<name>.npy holds what a caller of the timed path received for
 the LAST timed chunk step, chunk preroll + warmup + steps - 1 of every stream: the arrays of sc_get_hyps_batch (best
@@ -415,7 +418,7 @@ def cpu_baseline(k0, budget_s=10.0, beam=10, bbd=False, max_steps=20):
         for threads, procs in ((8, 1), (1, 1), (1, min(16, ncpu))):
             threads = min(threads, ncpu)
             with ctx.Pool(procs) as pool:
-                # (the quoted leg gets the whole budget, the two side legs 60 % of it: the default command stays under 90 s)
+                # (the quoted leg gets the whole budget, the two side legs 60 % of it: a --full run stays under 90 s)
                 res = pool.map(cpu_baseline_worker, [(threads, budget_s if not legs else 0.6 * budget_s, k0, max_steps, path) for _ in range(procs)])
             rate = sum(n * hop_s / dt for n, dt in res)
             legs.append({"processes": procs, "threads_per_process": threads, "audio_s_per_s": round(rate, 4),
@@ -607,7 +610,7 @@ def launch_ranks(n):
     return rc
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -631,13 +634,17 @@ def main():
     ap.add_argument("--encoder-batch", type=int, default=0,
                     help="continuous mode: merged encoder groups are issued when they hold this many streams "
                          "(sc_streams_set_encoder_batch; 0 = the engine's default)")
-    ap.add_argument("--legs", choices=["core", "all", "none"], default="core",
-                    help="core (default, <= 90 s): the headline + its roofline, strict lock-step, exact-steps, the 25 600- and 8 192-sample "
-                         "call sizes, single stream, fp16 mode, 1/8 of the host cores, CPU baseline; all: also resident audio, fp16 K|V, "
-                         "split16, block-boundary detection on, queue depth 2, long context (T ~ 1000 / 4500); none: the headline only")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run the roofline leg and the other legs (--legs); without it a run sets up, warms "
+                         "up, times the steps, writes --dump-outputs and prints the line, whose extra legs are then null")
+    ap.add_argument("--legs", choices=["core", "all", "none"], default=None,
+                    help="with --full: core (default, <= 90 s): the headline + its roofline, strict lock-step, exact-steps, the 25 600- and "
+                         "8 192-sample call sizes, single stream, fp16 mode, 1/8 of the host cores, CPU baseline; all: also resident audio, "
+                         "fp16 K|V, split16, block-boundary detection on, queue depth 2, long context (T ~ 1000 / 4500); none: the "
+                         "headline + its roofline.  Without --full only none")
     ap.add_argument("--roofline-csv", default="",
-                    help="write the per-kernel table of the roofline leg (launches, avg us, algorithmic bytes / flops per launch) here; "
-                         "tools/prof_bench.sh joins it with the rocprofv3 passes of the SAME launches (sc_marker brackets the leg)")
+                    help="(--full) write the per-kernel table of the roofline leg (launches, avg us, algorithmic bytes / flops per launch) "
+                         "here; tools/prof_bench.sh joins it with the rocprofv3 passes of the SAME launches (sc_marker brackets the leg)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-single-stream", action="store_true")
     ap.add_argument("--no-other-mode", action="store_true", help="skip the leg of the mode that is not the headline")
@@ -646,7 +653,8 @@ def main():
     ap.add_argument("--poll-group", type=int, default=0,
                     help="continuous: sc_poll returns when at least this many replies are ready (0: streams / 8)")
     ap.add_argument("--roofline-steps", type=int, default=2,
-                    help="extra (untimed for `value`) steps with per-launch HIP-event timing of the hot kernels")
+                    help="(--full) extra (untimed for `value`) steps with per-launch HIP-event timing of the hot kernels.  Their "
+                         "chunks are part of the window in either case, so a plain run times the same batch as a --full run")
     ap.add_argument("--kv-dtype", choices=["float32", "float16"], default="float32",
                     help="float16: self-/cross-attention K|V caches stored in fp16, arithmetic fp32 (opt-in; results "
                          "differ from the fp32 reference within the tolerance stated in tests/test_gpu_native.py)")
@@ -660,9 +668,20 @@ def main():
                          "warmup + steps - 1 of every stream: best hypothesis ids / xpos / lens / n_hyps / scores as its caller "
                          "reads them) to DIR/<name>.npy; a stream the closed loop has not brought that far when the clock stops "
                          "is served on, untimed, until it has answered that chunk")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.legs is None:
+        args.legs = "core" if args.full else "none"
+    elif args.legs != "none" and not args.full:
+        ap.error(f"--legs {args.legs} needs --full")
+    if args.roofline_csv and not args.full:
+        ap.error("--roofline-csv needs --full (the roofline leg runs only there)")
+    return args
+
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
     if os.environ.get("SC_BENCH_CPUS"):      # a rank started by launch_ranks: its own slice of the host cores
@@ -716,6 +735,7 @@ def main():
     per_rank_elapsed = None
 
     k0 = args.preroll + args.warmup
+    # (the roofline leg's chunks belong to the window whether it runs or not: the batch's capacities follow from it)
     total_steps = k0 + args.steps + args.roofline_steps + SERVED_SPARE
     w = make_weights(device)
     audio = make_audio(S, total_steps, stream_offset=rank * S)
@@ -734,7 +754,7 @@ def main():
     ms, fl, by = (C.c_double * NK)(), (C.c_double * NK)(), (C.c_double * NK)()
     nn = (C.c_longlong * NK)()
     ev_over_ms, xattn_bytes, xattn_flops = 0.0, {}, {}
-    if args.roofline_steps > 0:
+    if args.full and args.roofline_steps > 0:
         sb.set_graphs(False)
         sb.take_attn_counters()
         torch.cuda.synchronize()
@@ -1169,7 +1189,7 @@ def main():
         "value_exact_steps": (exact or {}).get("value"),
         "exact_steps": exact, "chunk_sizes": chunk_legs, "one_eighth_of_host_cores": pinned, "wider_batches": wide,
         "kv_cache_fp16": kv16, "fp16_mode": fp16_mode, "ffn_split16": split16, "bbd_on": bbd_on, "queue_depth_2": queued, "l_like_dims": l_like, "long_context": long_ctx,
-        "legs": args.legs,
+        "legs": args.legs, "full": args.full,
     }
     if dumped is not None:
         out["dump_outputs"] = dumped

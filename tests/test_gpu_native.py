@@ -1002,28 +1002,33 @@ def test_bench_launches_its_own_ranks():
 
 def test_bench_dump_outputs_are_the_same_in_both_modes(tmp_path):
     """`bench.py --dump-outputs DIR`: the replies to the last timed chunk step.  The continuous closed loop (streams spread
-    over the window by timing; the roofline leg and the untimed catch-up feed the capture too) and strict lock-step (one
-    batched call per step) must write the same files, bit for bit, in float32 / float64 - and the line keeps `steps`
-    and `ms_per_step` of the timed window."""
+    over the window by timing; the untimed catch-up feeds the capture too, and with --full the roofline leg before it),
+    in a plain and in a --full run, and strict lock-step (one batched call per step) must write the same files, bit for
+    bit, in float32 / float64 - and the line keeps `steps` and `ms_per_step` of the timed window.  Only --full runs the
+    roofline leg."""
     import sys
     steps, warmup, preroll = 4, 2, 3
     got = {}
-    for mode in ("continuous", "strict"):
-        d = tmp_path / mode
+    for mode, full in (("continuous", False), ("continuous", True), ("strict", False)):
+        d = tmp_path / f"{mode}_{int(full)}"
         res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--streams", "8", "--steps", str(steps),
                               "--warmup", str(warmup), "--preroll", str(preroll), "--roofline-steps", "1", "--legs", "none",
-                              "--mode", mode, "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+                              "--mode", mode, "--dump-outputs", str(d)] + (["--full"] if full else []),
+                             capture_output=True, text=True, timeout=600)
         assert res.returncode == 0, res.stderr[-2000:]
         line = json.loads(res.stdout.strip().splitlines()[-1])
         assert line["steps"] == steps and line["ms_per_step"] > 0
+        assert line["full"] is full and (line["roofline"] is not None) is full
         assert line["dump_outputs"]["chunk"] == preroll + warmup + steps - 1
-        got[mode] = {f: np.load(d / f) for f in line["dump_outputs"]["files"]}
-        assert sum(a.nbytes for a in got[mode].values()) <= 64 << 20
-        assert all(a.dtype in (np.float32, np.float64) for a in got[mode].values())
-    a, b = got["continuous"], got["strict"]
-    assert sorted(a) == sorted(b) and {"ids.npy", "xpos.npy", "lens.npy", "score.npy"} <= set(a)
-    for f in a:
-        assert a[f].dtype == b[f].dtype and a[f].shape == b[f].shape and a[f].tobytes() == b[f].tobytes(), f
+        got[mode, full] = {f: np.load(d / f) for f in line["dump_outputs"]["files"]}
+        assert sum(a.nbytes for a in got[mode, full].values()) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) for a in got[mode, full].values())
+    a = got["continuous", False]
+    assert {"ids.npy", "xpos.npy", "lens.npy", "score.npy"} <= set(a)
+    for b in (got["continuous", True], got["strict", False]):
+        assert sorted(a) == sorted(b)
+        for f in a:
+            assert a[f].dtype == b[f].dtype and a[f].shape == b[f].shape and a[f].tobytes() == b[f].tobytes(), f
     assert a["ids.npy"].shape[0] == 8 and (a["lens.npy"] > 1).all() and (a["ids.npy"][:, 0, 0] == 1023).all()   # sos first
 
 

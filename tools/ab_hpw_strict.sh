@@ -1,7 +1,7 @@
 #!/bin/bash
 # strict lock-step (many small and medium compaction buckets) against the row threshold of the four-heads-per-workgroup
 # layer kernels (SC_HPW_MIN), and the single-stream leg
-B="python bench.py --mode strict --no-cpu-baseline --no-other-mode --no-resident --no-long-context --roofline-steps 0"
+B="python bench.py --full --mode strict --no-cpu-baseline --no-other-mode --no-resident --no-long-context --roofline-steps 0"
 export SC_TEST_HOOKS=1
 for m in 96 320 480 640 960 100000; do SC_HPW_MIN=$m $B > gpurun_out/r04_ab_strict_hpwmin$m.json 2> gpurun_out/r04_ab_strict_hpwmin$m.err; done
 python - <<'PY'

@@ -10,7 +10,7 @@
 #   bash tools/prof_bench.sh r03 split16 "--ffn-dtype split16"   -> gpurun_out/r03_bench_split16*
 TAG=${1:-r06}
 NAME=${2:-default}
-EXTRA=${3:-}
+EXTRA="--full ${3:-}"      # (the plain pass records every leg; the profiled passes need the roofline leg)
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 mkdir -p gpurun_out
