@@ -304,12 +304,12 @@ int sc_set_stream_workspace(void *stream, void *ptr, size_t bytes);
 
 /* Optional per-launch timing of sc_gemm with HIP events on the launch stream
  * (every `sample_every`-th launch; 0 disables).  sc_prof_collect synchronises
- * and returns, per kernel variant v (0 scalar, 1 = 32x128 tile, 2 = 128x128,
- * 3 = 64x64): summed milliseconds, summed algorithmic flops (2*M*N*K) and the
- * number of sampled launches (variant 1 = skinny register-direct kernel for M <= 64).  All three pointers are HOST arrays of 4. */
+ * and returns, per kernel variant v (0 scalar, 2 = 128x128 tile, 3 = 64x64;
+ * 1 stays empty): summed milliseconds, summed algorithmic flops (2*M*N*K) and the
+ * number of sampled launches.  All three pointers are HOST arrays of 4. */
 /* kernel kinds of the per-launch timing records */
 #define SC_PROF_GEMM_NAIVE 0
-#define SC_PROF_GEMM_SKINNY 1
+#define SC_PROF_GEMM_SKINNY 1 /* no kernel records this kind any more; the number stays, callers index the kinds by position */
 #define SC_PROF_GEMM_128 2
 #define SC_PROF_GEMM_64 3
 #define SC_PROF_PROJ_LN_PROJ 4
@@ -334,7 +334,7 @@ int sc_set_stream_workspace(void *stream, void *ptr, size_t bytes);
  * 8 waves per stream runs both attentions of a layer for all heads, two launches per layer): buckets of more than 128 streams
  * at beam 10, of at least 257 at beam 5.  A stream then holds one compute unit instead of two, and the encoder groups run beside
  * the decode chain instead of between its kernels.  Same bits as the other two forms (canonical summation, common.h).
- * SC_STREAM_FFN_CUS: compute units its feed-forward launch is sized for. */
+ * SC_STREAM_FFN_CUS: compute units its feed-forward launch is sized for (a constant of the build, like the thresholds). */
 #define SC_STREAM_MIN_ROWS 1281
 #define SC_STREAM_FFN_CUS 256
 int sc_prof_collect_kinds(double *ms, double *flops, double *bytes, long long *n, int nkinds);

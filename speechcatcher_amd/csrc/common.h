@@ -11,11 +11,17 @@
 
 void sc_set_error(const char *fmt, ...);
 
-// Test / measurement hooks.  The SC_* environment switches (kernel variants forced for parity tests, A/B runs and
-// tuning sweeps) are consulted ONLY when the process was started with SC_TEST_HOOKS=1 (tests/conftest.py and the
+// Test / measurement hooks.  The SC_* environment switches (kernel variants forced for parity tests and the sweeps of
+// tools/) are consulted ONLY when the process was started with SC_TEST_HOOKS=1 (tests/conftest.py and the
 // tools/ scripts set it); a production process never reads them, so nothing a server's environment contains can
-// change which kernels a captured graph holds.  gemm.hip.
+// change which kernels a captured graph holds.  A switch stays only while a file under tests/ or tools/ sets it
+// (tests/test_abi.py): the switch of a settled A/B goes, with the code only it reaches.  gemm.hip.
 const char *sc_hook(const char *name);
+
+// Raises the dynamic-LDS limit of kernel `fn` to max_bytes (the most any launch of it asks for) once per (kernel, device)
+// before a launch that needs `need` bytes; nothing to do while `need` fits the 64 KiB every kernel may have.  Not an
+// exported symbol.  gemm.hip.
+__attribute__((visibility("hidden"))) int allow_large_lds(const void *fn, size_t need, size_t max_bytes, const char *what);
 
 #define SC_CHECK_ARG(cond, msg)      \
   do {                               \
@@ -36,8 +42,19 @@ const char *sc_hook(const char *name);
 
 __host__ __device__ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-// HIP events around one kernel launch (enabled by sc_prof_enable; gemm.hip)
-struct ProfScope { bool on; hipEvent_t a, b; hipStream_t st; };
+// `int rc` in scope: run a launcher, hand its error up
+#define SC_TRY(call) do { rc = (call); if (rc != SC_OK) return rc; } while (0)
+
+// HIP events around one kernel launch (enabled by sc_prof_enable; gemm.hip).  A scope that is left open - the launcher
+// returned an error before sc_prof_end - has nothing to record and destroys its events.
+struct ProfScope {
+  bool on; hipEvent_t a, b; hipStream_t st;
+  ProfScope(bool on_, hipEvent_t a_, hipEvent_t b_, hipStream_t st_) : on(on_), a(a_), b(b_), st(st_) {}
+  ProfScope(const ProfScope &) = delete;
+  __attribute__((visibility("hidden"))) ~ProfScope() {   // (not an exported symbol)
+    if (on) { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
+  }
+};
 ProfScope sc_prof_begin(hipStream_t st);
 void sc_prof_end(ProfScope &p, int kind, double flops, double bytes);
 

@@ -37,7 +37,7 @@
 #define SC_STAMP_ON (p.dbg_stamp)
 #include "common.h"
 #include "attn.h"
-#include <mutex>
+#include <type_traits>
 
 #define CTRL(s, f) sb.ctrl[(s) * 8 + (f)]
 #define YSEQ(pp, s, h) (sb.yseq + (((long)(pp) * sb.S + (s)) * sb.W + (h)) * sb.LCAP)
@@ -726,23 +726,22 @@ int sc_dec_layer_hpw(const sc_search &sb) {
 }
 
 template <int D, int DK, int WM, bool SELF, int UNR, bool FIRST, bool KVH, int HPW, bool WH = false>
-static void launch_dec_layer_variant(const DecLayerArgs &p, int ns, hipStream_t st) {
+static int launch_dec_layer_variant(const DecLayerArgs &p, int ns, hipStream_t st) {
   const sc_search &sb = p.sb;
   // one or two streams: pad grid.x to 8 so that all H workgroups of a stream land on ONE XCD (linear id x + 8*y) and
   // share its L2 - single stream 5.41 -> 5.25 ms per hop; with more streams the padding concentrates the work on
   // fewer XCDs and costs 1 % at 128 streams, so larger buckets keep their natural spread
   const dim3 grid(ns <= 2 ? 8 : ns, sb.H / HPW);
   const size_t lds = (size_t)dl_lds_floats(D, DK, sb.W, WM, SELF, HPW) * sizeof(float);
-  // the attribute is set ONCE per instantiation, to the largest size any beam <= WM of it can ask for (it used to be
-  // the size of whichever beam width came first - a beam-5 engine followed by a beam-10 one in the same process), thread-safe
-  static std::once_flag attr_once;
-  std::call_once(attr_once, [&]() {
-    const size_t lds_max = (size_t)dl_lds_floats(D, DK, WM, WM, SELF, HPW) * sizeof(float);
-    if (lds_max > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&dec_layer_attn_kernel<D, DK, WM, SELF, UNR, FIRST, KVH, HPW, WH>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
-  });
+  // the limit is raised once per instantiation and device, to the largest size any beam <= WM of it can ask for (it
+  // used to be the size of whichever beam width came first - a beam-5 engine followed by a beam-10 one in the same process)
+  const size_t lds_max = (size_t)dl_lds_floats(D, DK, WM, WM, SELF, HPW) * sizeof(float);
+  const int rc = allow_large_lds(reinterpret_cast<const void *>(&dec_layer_attn_kernel<D, DK, WM, SELF, UNR, FIRST, KVH, HPW, WH>),
+                                 lds, lds_max, "dec_layer_attn_kernel");
+  if (rc != SC_OK) return rc;
   dec_layer_attn_kernel<D, DK, WM, SELF, UNR, FIRST, KVH, HPW, WH><<<grid, 256 * HPW, lds, st>>>(p);
+  SC_CHECK_LAUNCH();
+  return SC_OK;
 }
 
 template <int D, int DK, bool SELF, bool FIRST, bool KVH>
@@ -757,30 +756,23 @@ static int launch_dec_layer_kvh(const DecLayerArgs &p, hipStream_t st) {
   if constexpr (KVH) {
     if (sb.act_half & 1) {
       if constexpr (D == 256 && DK == 32) {
-        if (hpw == 4) { launch_dec_layer_variant<D, DK, 10, SELF, 2, FIRST, KVH, 4, true>(p, ns, st); SC_CHECK_LAUNCH(); return SC_OK; }
+        if (hpw == 4) return launch_dec_layer_variant<D, DK, 10, SELF, 2, FIRST, KVH, 4, true>(p, ns, st);
       }
-      if (sb.W <= 5) launch_dec_layer_variant<D, DK, 5, SELF, 4, FIRST, KVH, 1, true>(p, ns, st);
-      else if (sb.W <= 10) {
-        if (deep) launch_dec_layer_variant<D, DK, 10, SELF, 8, FIRST, KVH, 1, true>(p, ns, st);
-        else launch_dec_layer_variant<D, DK, 10, SELF, 2, FIRST, KVH, 1, true>(p, ns, st);
-      } else launch_dec_layer_variant<D, DK, 16, SELF, 2, FIRST, KVH, 1, true>(p, ns, st);
-      SC_CHECK_LAUNCH();
-      return SC_OK;
+      if (sb.W <= 5) return launch_dec_layer_variant<D, DK, 5, SELF, 4, FIRST, KVH, 1, true>(p, ns, st);
+      if (sb.W <= 10)
+        return deep ? launch_dec_layer_variant<D, DK, 10, SELF, 8, FIRST, KVH, 1, true>(p, ns, st)
+                    : launch_dec_layer_variant<D, DK, 10, SELF, 2, FIRST, KVH, 1, true>(p, ns, st);
+      return launch_dec_layer_variant<D, DK, 16, SELF, 2, FIRST, KVH, 1, true>(p, ns, st);
     }
   }
   if constexpr (D == 256 && DK == 32) {
-    if (hpw == 4) { launch_dec_layer_variant<D, DK, 10, SELF, 2, FIRST, KVH, 4>(p, ns, st); SC_CHECK_LAUNCH(); return SC_OK; }
+    if (hpw == 4) return launch_dec_layer_variant<D, DK, 10, SELF, 2, FIRST, KVH, 4>(p, ns, st);
   }
-  if (sb.W <= 5) {
-    launch_dec_layer_variant<D, DK, 5, SELF, 4, FIRST, KVH, 1>(p, ns, st);
-  } else if (sb.W <= 10) {
-    if (deep) launch_dec_layer_variant<D, DK, 10, SELF, 8, FIRST, KVH, 1>(p, ns, st);
-    else launch_dec_layer_variant<D, DK, 10, SELF, 2, FIRST, KVH, 1>(p, ns, st);
-  } else {
-    launch_dec_layer_variant<D, DK, 16, SELF, 2, FIRST, KVH, 1>(p, ns, st);
-  }
-  SC_CHECK_LAUNCH();
-  return SC_OK;
+  if (sb.W <= 5) return launch_dec_layer_variant<D, DK, 5, SELF, 4, FIRST, KVH, 1>(p, ns, st);
+  if (sb.W <= 10)
+    return deep ? launch_dec_layer_variant<D, DK, 10, SELF, 8, FIRST, KVH, 1>(p, ns, st)
+                : launch_dec_layer_variant<D, DK, 10, SELF, 2, FIRST, KVH, 1>(p, ns, st);
+  return launch_dec_layer_variant<D, DK, 16, SELF, 2, FIRST, KVH, 1>(p, ns, st);
 }
 
 template <int D, int DK, bool SELF, bool FIRST>
@@ -924,8 +916,8 @@ extern "C" int sc_dec_layer_reduce_ln(const sc_search *sbp, int layer, const flo
   ProfScope prof = sc_prof_begin(st);
   dec_head_reduce_ln_kernel<<<cdiv(M, 16), 256, 0, st>>>(sb.ph2, nph, nph == sb.H ? 4 : 1, w.bo2, xin, xout, xn_out, sb.rowmap, M, w.ln3_g,
                                                         w.ln3_b, sb.ln_eps);
-  SC_CHECK_LAUNCH();
   sc_prof_end(prof, SC_PROF_PROJ_LN_PROJ, 0.0, 4.0 * (double)M * sb.d * (3 + nph));
+  SC_CHECK_LAUNCH();
   return SC_OK;
 }
 

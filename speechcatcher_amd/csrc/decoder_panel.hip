@@ -243,11 +243,7 @@ extern "C" int sc_proj_ln_proj(const float *A, int lda, const float *W1q, const 
   SC_CHECK_ARG(XN || W2q, "nothing to produce after the LayerNorm");
   // rows per panel: the smallest that keeps the launch within one round of workgroups and
   // the weight re-streaming (every workgroup reads all of W) modest (tools/panel4_probe.py)
-  int rpp = M <= 1024 ? 4 : (M <= 2048 ? 8 : 16);   // <= 256 workgroups (measured sweep: one round is what matters)
-  if (const char *e = sc_hook("SC_PANEL_ROWS")) {
-    const int v = atoi(e);
-    if (v == 4 || v == 8 || v == 16) rpp = v;
-  }
+  const int rpp = M <= 1024 ? 4 : (M <= 2048 ? 8 : 16);   // <= 256 workgroups (measured sweep: one round is what matters)
   PanelArgs p{A, lda, W1q, b1, X, ldx, ln_g, ln_b, ln_eps, XN, ldn, W2q, b2, Q, ldq, rows, M};
   hipStream_t st = (hipStream_t)stream;
   ProfScope prof = sc_prof_begin(st);
@@ -450,11 +446,7 @@ int sc_launch_reduce_ln_proj(const float *part, int npart, int part_M, const flo
   SC_CHECK_ARG(Xin != Xout, "x_in and x_out must be different buffers");
   const int nblocks = N / D;
   // rows per panel: keep panels * column blocks within one round of workgroups
-  int rpp = (long)cdiv(M, 4) * nblocks <= 256 ? 4 : ((long)cdiv(M, 8) * nblocks <= 256 ? 8 : 16);
-  if (const char *e = sc_hook("SC_PANEL_ROWS")) {
-    const int v = atoi(e);
-    if (v == 4 || v == 8 || v == 16) rpp = v;
-  }
+  const int rpp = (long)cdiv(M, 4) * nblocks <= 256 ? 4 : ((long)cdiv(M, 8) * nblocks <= 256 ? 8 : 16);
   // half_mode (fp16 decoder mode, sc_search.act_half): bit 0 = Wq holds fp16 elements, bit 1 = the partial sums do
   // more than one round of workgroups even with 16-row panels (a full bucket's output layer: 80 panels x 4 column
   // blocks): two column blocks per workgroup - the panel's partial sums are reduced half as often and the launch is
@@ -538,7 +530,7 @@ extern "C" int sc_dec_output_logits(const sc_search *sbp, const float *xin, floa
   const int M = sb.rowmap ? sb.n_rows : sb.S * sb.W;
   const bool hm = (sb.act_half & 4) != 0 && sb.out_w_qh != nullptr;
   SC_CHECK_ARG(!(sb.act_half & 4) || hm, "fp16 output layer needs out_w_qh");
-  if (!hm && sb.d % 4 == 0 && sb.d <= 256 && sb.dq && sb.out_w && !sc_hook("SC_LOGITS_PANEL")) {
+  if (!hm && sb.d % 4 == 0 && sb.d <= 256 && sb.dq && sb.out_w) {
     // (round 5) reduce + after_norm once per row, then the output layer as one tiled GEMM over the bucket's rows - the
     // same two launches for every bucket size (the form must not depend on the row count: common.h)
     hipStream_t st = (hipStream_t)stream;

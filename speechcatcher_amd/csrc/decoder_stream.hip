@@ -31,7 +31,6 @@
 #define SC_STAMP_ON (p.dbg_stamp)
 #include "common.h"
 #include "attn.h"
-#include <mutex>
 #include <type_traits>
 
 #define CTRL(s, f) sb.ctrl[(s) * 8 + (f)]
@@ -695,22 +694,18 @@ extern "C" int sc_dec_layer_stream_supported(int d, int H, int W, int F) {
 int sc_dec_layer_stream_form(const sc_search &sb) {
   if (!sc_dec_layer_stream_supported(sb.d, sb.H, sb.W, sb.F) || sb.act_half || !sb.dq || !sb.ffn_part) return 0;
   if (!sb.layers || !sb.layers[0].wqkv_pp || !sb.layers[0].wq_pp || !sb.layers[0].wo_pp || !sb.layers[0].wo2_pp) return 0;
-  int min_rows = SC_STREAM_MIN_ROWS;
-  if (const char *e = sc_hook("SC_STREAM_MIN")) min_rows = atoi(e);
-  int on = (sb.rowmap ? sb.n_rows : sb.S * sb.W) >= min_rows;
+  int on = (sb.rowmap ? sb.n_rows : sb.S * sb.W) >= SC_STREAM_MIN_ROWS;
   if (const char *e = sc_hook("SC_DEC_STREAM")) on = atoi(e) != 0;
   return on;
 }
 
 template <bool FIRST, bool KVH>
-static void launch_stream_variant(const DecStreamArgs &p, int ns, hipStream_t st) {
-  const size_t lds = (size_t)dstream::LDS_FLOATS * sizeof(float);
-  static std::once_flag once;
-  std::call_once(once, [&]() {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&dec_layer_stream_kernel<FIRST, KVH>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  });
+static int launch_stream_variant(const DecStreamArgs &p, int ns, hipStream_t st) {
+  const size_t lds = (size_t)dstream::LDS_FLOATS * sizeof(float);   // (every launch asks for the same size)
+  const int rc = allow_large_lds(reinterpret_cast<const void *>(&dec_layer_stream_kernel<FIRST, KVH>), lds, lds, "dec_layer_stream_kernel");
+  if (rc != SC_OK) return rc;
   dec_layer_stream_kernel<FIRST, KVH><<<dim3(ns), dstream::NTH, lds, st>>>(p);
+  return SC_OK;
 }
 
 extern "C" int sc_dec_layer_stream(const sc_search *sbp, int layer, const float *xin, float *xout, float *xn_out,
@@ -729,18 +724,14 @@ extern "C" int sc_dec_layer_stream(const sc_search *sbp, int layer, const float 
   hipStream_t st = (hipStream_t)stream;
   const int ns = sb.rowmap ? sb.n_rows / sb.W : sb.S;
   ProfScope prof = sc_prof_begin(st);
-  if (sb.kv_half) {
-    if (layer == 0) launch_stream_variant<true, true>(p, ns, st);
-    else launch_stream_variant<false, true>(p, ns, st);
-  } else {
-    if (layer == 0) launch_stream_variant<true, false>(p, ns, st);
-    else launch_stream_variant<false, false>(p, ns, st);
-  }
-  SC_CHECK_LAUNCH();
+  const int rc = sb.kv_half ? (layer == 0 ? launch_stream_variant<true, true>(p, ns, st) : launch_stream_variant<false, true>(p, ns, st))
+                            : (layer == 0 ? launch_stream_variant<true, false>(p, ns, st) : launch_stream_variant<false, false>(p, ns, st));
+  if (rc != SC_OK) return rc;
   {   // MFMA part: Q|K|V + q projections and the two output projections of the bucket's rows; bytes without the K|V rows
       // (bench.py adds them: cross from T, self from the device counter): the four weight matrices once, x in, x and xn out
     const double M = sb.rowmap ? sb.n_rows : sb.S * sb.W;
     sc_prof_end(prof, SC_PROF_LAYER_STREAM, 12.0 * M * sb.d * sb.d, 4.0 * (6.0 * sb.d * sb.d + 3.0 * M * sb.d));
   }
+  SC_CHECK_LAUNCH();
   return SC_OK;
 }

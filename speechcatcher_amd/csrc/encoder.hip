@@ -682,20 +682,17 @@ extern "C" int sc_encoder_layers(const sc_enc_layer *L, int n_layers, float *x, 
   SC_CHECK_ARG(L && x && xn && qkv && att && ffh, "null pointer");
   const int M = nblk * R;
   if (M <= 0) return SC_OK;
-  const char *fe = sc_hook("SC_FFN_FUSED");      // =0: two GEMMs with the hidden activations in HBM
-  const bool ffn_fused = !(fe && atoi(fe) == 0) && sc_ffn_ln_supported(d, F) &&
-                         sc_workspace_bytes(stream) >= (size_t)(F / 128) * 80 * d * sizeof(float);
+  // (otherwise: two GEMMs with the hidden activations in HBM)
+  const bool ffn_fused = sc_ffn_ln_supported(d, F) && sc_workspace_bytes(stream) >= (size_t)(F / 128) * 80 * d * sizeof(float);
   // row-tile projections with the norms folded in (faster at every batch size: tools/rowtile_bench.py);
   // SC_ENC_ROWTILE=0: LayerNorm + GEMM launches instead (A/B switch)
   const char *re = sc_hook("SC_ENC_ROWTILE");
   const bool rowtile_ok = sc_rowtile_proj_supported(d, d) && !(re && atoi(re) == 0);
   int rc;
-#define SC_TRY(call) do { rc = (call); if (rc != SC_OK) return rc; } while (0)
   // the context hand-off behind every layer rides on the reduce of the fused feed-forward's split sums (one launch less
   // per layer) when all rows fit one slab of the split-sum workspace; its per-block table lives at the head of `ffh`,
-  // which the fused path does not use.  SC_ENC_HANDOFF=0: separate sc_ctx_handoff launches (A/B switch)
-  const char *he = sc_hook("SC_ENC_HANDOFF");
-  const bool fused_handoff = masked && ns > 0 && ffn_fused && !(he && atoi(he) == 0) && R > 1 &&
+  // which the fused path does not use.  Otherwise: separate sc_ctx_handoff launches
+  const bool fused_handoff = masked && ns > 0 && ffn_fused && R > 1 &&
                              sc_workspace_bytes(stream) >= (size_t)(F / 128) * M * d * sizeof(float) &&
                              (size_t)M * F >= (size_t)nblk * 4;
   int32_t *blkinfo = reinterpret_cast<int32_t *>(ffh);
@@ -755,6 +752,5 @@ extern "C" int sc_encoder_layers(const sc_enc_layer *L, int n_layers, float *x, 
     }
     if (masked && ns > 0) SC_TRY(sc_ctx_handoff(x, R, jobs, ns, past_ctx, li, d, stream));
   }
-#undef SC_TRY
   return SC_OK;
 }

@@ -293,107 +293,6 @@ __global__ __launch_bounds__(256) void gemm_mfma_kernel(GemmArgs g) {
   }
 }
 
-// ---------------------------------------------------------------------------
-// Skinny GEMM (M <= 64: one stream's decoder rows / one encoder block).  These
-// are weight-streaming, latency-bound problems: no LDS staging, no barriers in
-// the K loop.  Each lane loads its MFMA operands straight from global memory
-// as float4 (lane (i, half) reads k..k+3 of row i at column offset 4*half; the
-// 32x32x2 MFMA then pairs k with k+4, which is as good as any pairing), the 4
-// waves of a workgroup interleave 8-wide k groups, grid.y splits K further so
-// that >= ~256 workgroups stream the weight matrix concurrently.
-// ---------------------------------------------------------------------------
-template <int RT>
-__global__ __launch_bounds__(256) void gemm_skinny_kernel(GemmArgs g) {
-  __shared__ float red[4][RT][16][64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int i = lane & 31, half = lane >> 5;
-  const int n0 = blockIdx.x * 32;
-  const int mbase = blockIdx.z * (32 * RT);
-  const int kbeg = blockIdx.y * g.kslice;
-  const int kend = (kbeg + g.kslice < g.K) ? kbeg + g.kslice : g.K;
-  long abase[RT];
-  float amask[RT];
-#pragma unroll
-  for (int rt = 0; rt < RT; ++rt) {
-    int m = mbase + rt * 32 + i;
-    m = m < g.M ? m : g.M - 1;
-    int row = g.a_rows ? g.a_rows[m] : m;
-    amask[rt] = row < 0 ? 0.f : 1.f;
-    abase[rt] = (long)(row < 0 ? 0 : row) * g.lda + 4 * half;
-  }
-  const int n = n0 + i;
-  const float *__restrict__ wp = g.W + (long)(n < g.N ? n : g.N - 1) * g.K + 4 * half;
-  const float *__restrict__ ap = g.A;
-  f32x16 acc[RT];
-#pragma unroll
-  for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[rt][r] = 0.f;
-  // two 8-wide k groups per trip: 2*(1+RT) independent 16-byte loads in flight
-  auto step = [&](const float4 &b4, const float4 (&a4)[RT]) {
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-      acc[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[rt].x * amask[rt], b4.x, acc[rt], 0, 0, 0);
-      acc[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[rt].y * amask[rt], b4.y, acc[rt], 0, 0, 0);
-      acc[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[rt].z * amask[rt], b4.z, acc[rt], 0, 0, 0);
-      acc[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[rt].w * amask[rt], b4.w, acc[rt], 0, 0, 0);
-    }
-  };
-  // batches of NB 8-wide k groups: all NB*(1+RT) 16-byte loads are issued
-  // before the first MFMA, so a K = 256 slice costs ONE memory round trip.
-  constexpr int NB = 8;
-  int k = kbeg + wave * 8;
-  for (; k + 32 * (NB - 1) < kend; k += 32 * NB) {
-    float4 bq[NB], aq[NB][RT];
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-      const long ko = gemm_kofs(g, k + 32 * u);
-      bq[u] = *reinterpret_cast<const float4 *>(wp + k + 32 * u);
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) aq[u][rt] = *reinterpret_cast<const float4 *>(ap + abase[rt] + ko);
-    }
-#pragma unroll
-    for (int u = 0; u < NB; ++u) step(bq[u], aq[u]);
-  }
-  for (; k < kend; k += 32) {
-    const long ko0 = gemm_kofs(g, k);
-    const float4 b0 = *reinterpret_cast<const float4 *>(wp + k);
-    float4 a0[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) a0[rt] = *reinterpret_cast<const float4 *>(ap + abase[rt] + ko0);
-    step(b0, a0);
-  }
-#pragma unroll
-  for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) red[wave][rt][r][lane] = acc[rt][r];
-  __syncthreads();
-  // wave w finishes accumulator registers r = w, w+4, w+8, w+12 (fixed order)
-  const bool relu = g.flags & SC_GEMM_RELU, resid = g.flags & SC_GEMM_RESIDUAL;
-  const float bv = (g.bias && n < g.N && !g.part) ? g.bias[n] : 0.f;
-#pragma unroll
-  for (int rt = 0; rt < RT; ++rt) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int r = wave + 4 * q;
-      float v = ((red[0][rt][r][lane] + red[1][rt][r][lane]) + red[2][rt][r][lane]) + red[3][rt][r][lane];
-      const int m = mbase + rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-      if (m >= g.M || n >= g.N) continue;
-      if (g.part) {
-        g.part[((long)blockIdx.y * g.M + m) * g.N + n] = v;
-      } else {
-        const int crow = g.c_rows ? g.c_rows[m] : m;
-        if (crow < 0) continue;
-        float *p = g.C + (long)crow * g.ldc + n;
-        v += bv;
-        if (relu) v = fmaxf(v, 0.f);
-        if (resid) v = *p + v;
-        *p = v;
-      }
-    }
-  }
-}
-
 // out[c_rows[m], n] = epilogue(bias[n] + sum_z part[z][m][n]), z in fixed order
 __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(GemmArgs g, int ksplit) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -582,8 +481,6 @@ __global__ void gemm_naive_kernel(GemmArgs g) {
   *p = v;
 }
 
-static int g_force_naive = -1;
-
 // ---- optional per-launch timing with HIP events (bench.py roofline leg) ----
 struct ProfRec { hipEvent_t a, b; double flops, bytes; int variant; };
 static std::vector<ProfRec> g_recs;
@@ -592,15 +489,14 @@ static long long g_gemm_calls = 0;
 
 // shared by every launcher of the library (common.h): events around ONE kernel launch
 ProfScope sc_prof_begin(hipStream_t st) {
-  ProfScope p{false, nullptr, nullptr, st};
-  if (g_prof_every <= 0 || (g_gemm_calls++ % g_prof_every) != 0) return p;
+  if (g_prof_every <= 0 || (g_gemm_calls++ % g_prof_every) != 0) return ProfScope(false, nullptr, nullptr, st);
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;   // never record timing events into a stream capture
-  if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return p;
-  (void)hipEventCreate(&p.a);
-  (void)hipEventCreate(&p.b);
-  (void)hipEventRecord(p.a, st);
-  p.on = true;
-  return p;
+  if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return ProfScope(false, nullptr, nullptr, st);
+  hipEvent_t a = nullptr, b = nullptr;
+  (void)hipEventCreate(&a);
+  (void)hipEventCreate(&b);
+  (void)hipEventRecord(a, st);
+  return ProfScope(true, a, b, st);
 }
 void sc_prof_end(ProfScope &p, int kind, double flops, double bytes) {
   if (!p.on) return;
@@ -659,8 +555,6 @@ extern "C" int sc_prof_collect_kinds(double *ms, double *flops, double *bytes, l
   return SC_OK;
 }
 
-static int g_bk64 = 0;               // SC_GEMM_BK=64: 64-deep K tiles for the 64x64 kernel (A/B switch)
-static int g_skinny_max_m = 64;     // SC_SKINNY_MAX_M overrides (A-B tests: the LDS-tiled kernel wins for M > 64, docs/profiles_r1-r3/r01_gemm_skinny_ab.txt)
 // split-K workspaces: one per HIP stream (independent StreamBatches run
 // concurrently on their own streams), plus a default for unregistered streams
 struct Workspace { float *ptr; size_t bytes; };
@@ -676,6 +570,27 @@ const char *sc_hook(const char *name) {
     return e && atoi(e) != 0;
   }();
   return enabled ? getenv(name) : nullptr;
+}
+
+int allow_large_lds(const void *fn, size_t need, size_t max_bytes, const char *what) {
+  if (need + 256 <= 64 * 1024) return SC_OK;   // (256: room for the kernels' static LDS)
+  static std::mutex mu;
+  static std::unordered_map<const void *, unsigned long long> done;   // kernel -> bit per device
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
+    sc_set_error("%s: no current HIP device", what);
+    return SC_ERR_LAUNCH;
+  }
+  std::lock_guard<std::mutex> lk(mu);
+  unsigned long long &bits = done[fn];
+  if (bits >> dev & 1ull) return SC_OK;
+  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_bytes);
+  if (e != hipSuccess) {
+    sc_set_error("%s: raising the dynamic LDS limit to %zu bytes failed: %s", what, max_bytes, hipGetErrorString(e));
+    return SC_ERR_LAUNCH;
+  }
+  bits |= 1ull << dev;
+  return SC_OK;
 }
 
 extern "C" int sc_set_workspace(void *ptr, size_t bytes) {
@@ -709,43 +624,22 @@ extern "C" size_t sc_workspace_bytes(void *stream) {
 // K slices through *ksplit_out (0: the kernel wrote the final result itself).
 static int gemm_dispatch(GemmArgs &g, bool force_part, int *ksplit_out, int *variant_out, hipStream_t st) {
   const int M = g.M, N = g.N, K = g.K;
-  if (g_force_naive < 0) {
-    const char *e = sc_hook("SC_GEMM_NAIVE");
-    g_force_naive = (e && e[0] == '1') ? 1 : 0;
-    if (const char *m = sc_hook("SC_SKINNY_MAX_M")) g_skinny_max_m = atoi(m);
-    if (const char *m = sc_hook("SC_GEMM_BK")) g_bk64 = atoi(m) == 64;
-  }
   bool aligned = (K % 32 == 0) && (g.lda % 4 == 0) && (((uintptr_t)g.A & 15) == 0) &&
                  (((uintptr_t)g.W & 15) == 0) && (g.conv_f1 == 0 || g.lda % 32 == 0);
-  // variant: 0 scalar, 1 skinny register-direct (tools only), 2 = 128x128 tile, 3 = 64x64 tile
+  // variant: 0 scalar, 2 = 128x128 tile, 3 = 64x64 tile (the SC_PROF_GEMM_* kinds of scasr.h; 1 is not used)
   // CANONICAL SUMMATION ORDER (round 5, bit-reproducible serving): how the K dimension of a product is cut and in which
   // order its pieces are added is a function of (N, K) ALONE - never of M, which is the number of rows that happen to be
   // in flight (streams of an encoder group, frames of a chunk).  Every aligned problem takes the LDS-tiled kernel (k runs
   // in order inside a slice, both tile sizes issue the same v_mfma_f32_32x32x2_f32 chain per output element); K >= 2560
   // (the subsampling Linear: K = 19 * d) is cut into 8 slices that the reduce kernel adds as a tree (common.h), anything
-  // shorter is one chain.  The register-direct skinny kernel (round 1-4: M <= 64) interleaves k over its waves and is
-  // kept for A/B runs only (SC_SKINNY_MAX_M).
+  // shorter is one chain.
   int variant;
   const bool can_part_any = g_ws && (N % 4 == 0) && (g.ldc % 4 == 0) && (((uintptr_t)g.C & 15) == 0) &&
                             (!g.bias || (((uintptr_t)g.bias & 15) == 0)) &&
                             (size_t)M * N * sizeof(float) <= g_ws_bytes;
   int ksplit = 1;
-  const bool skinny_hook = sc_hook("SC_SKINNY_MAX_M") != nullptr;
-  if ((g.flags & SC_GEMM_NAIVE) || g_force_naive || !aligned) {
+  if ((g.flags & SC_GEMM_NAIVE) || !aligned) {
     variant = 0;
-  } else if (skinny_hook && (M <= 64 || (M <= g_skinny_max_m && (K <= 256 || can_part_any))) && M <= g_skinny_max_m) {
-    variant = 1;
-    if (can_part_any) {
-      if (M <= 64) {
-        const int ct = cdiv(N, 32);
-        ksplit = K / 64;
-        const int want = cdiv(256, ct);
-        if (ksplit > want) ksplit = want;
-      } else {
-        ksplit = K / 256;
-      }
-      if (ksplit < 1) ksplit = 1;
-    }
   } else {
     // tile size by a small cost model in cycles (wave quantisation dominates these small GEMMs): it changes which
     // workgroup computes an element, not how
@@ -779,9 +673,6 @@ static int gemm_dispatch(GemmArgs &g, bool force_part, int *ksplit_out, int *var
   if (variant == 0) {
     long total = (long)M * N;
     gemm_naive_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, st>>>(g);
-  } else if (variant == 1) {
-    if (M <= 32) gemm_skinny_kernel<1><<<dim3(cdiv(N, 32), ksplit, 1), 256, 0, st>>>(g);
-    else gemm_skinny_kernel<2><<<dim3(cdiv(N, 32), ksplit, cdiv(M, 64)), 256, 0, st>>>(g);
   } else if (variant == 2) {
     if (g.flags & SC_GEMM_SPLIT16)
       gemm_mfma_kernel<128, 128, 2, 2, 32, true><<<dim3(cdiv(N, 128), cdiv(M, 128), ksplit), 256, 0, st>>>(g);
@@ -790,10 +681,7 @@ static int gemm_dispatch(GemmArgs &g, bool force_part, int *ksplit_out, int *var
   } else if (g.flags & SC_GEMM_SPLIT16) {
     gemm_mfma_kernel<64, 64, 2, 2, 32, true><<<dim3(cdiv(N, 64), cdiv(M, 64), ksplit), 256, 0, st>>>(g);
   } else {
-    if (g_bk64 && g.kslice % 64 == 0 && K % 64 == 0 && (g.conv_f1 == 0 || g.lda % 64 == 0))
-      gemm_mfma_kernel<64, 64, 2, 2, 64><<<dim3(cdiv(N, 64), cdiv(M, 64), ksplit), 256, 0, st>>>(g);
-    else
-      gemm_mfma_kernel<64, 64, 2, 2><<<dim3(cdiv(N, 64), cdiv(M, 64), ksplit), 256, 0, st>>>(g);
+    gemm_mfma_kernel<64, 64, 2, 2><<<dim3(cdiv(N, 64), cdiv(M, 64), ksplit), 256, 0, st>>>(g);
   }
   *ksplit_out = part ? ksplit : 0;
   *variant_out = variant;
@@ -860,7 +748,7 @@ int sc_gemm_colblocks(const float *A, const int32_t *a_rows, int lda, const floa
   if (M == 0) return SC_OK;
   hipStream_t st = (hipStream_t)stream;
   resolve_workspace(stream);
-  if (sc_hook("SC_GEMM_NAIVE") || sc_hook("SC_SKINNY_MAX_M") || sc_hook("SC_KV_PER_LAYER")) return SC_ERR_ARG;   // A/B and test forms
+  if (sc_hook("SC_KV_PER_LAYER")) return SC_ERR_ARG;   // test form: one launch per layer
   ProfScope prof = sc_prof_begin(st);
   GemmArgs g{A, a_rows, lda, W, bias, C, c_rows, ldc, M, N, K, flags, 0, nullptr, K, ncb, cb_stride};
   int ksplit = 0, variant = 0;
@@ -1384,32 +1272,29 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(FfnArgs p) {
 SC_PHASE_GETTER(sc_phase_debug_ffn)
 
 template <int D, int RTT, bool PRO, int WH>
-static void launch_ffn_wh(const FfnArgs &p, int ngrp, hipStream_t st) {
+static int launch_ffn_wh(const FfnArgs &p, int ngrp, hipStream_t st) {
   constexpr int RT = 16 * RTT;
-  const size_t lds = ffn_lds_bytes(D, RT, PRO, WH);
-  static bool attr_done = false;
-  if (!attr_done && lds > 64 * 1024) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ffn_fused_kernel<D, RTT, PRO, WH>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_done = true;
-  }
+  const size_t lds = ffn_lds_bytes(D, RT, PRO, WH);   // (one size per instantiation)
+  const int rc = allow_large_lds(reinterpret_cast<const void *>(&ffn_fused_kernel<D, RTT, PRO, WH>), lds, lds, "ffn_fused_kernel");
+  if (rc != SC_OK) return rc;
   ffn_fused_kernel<D, RTT, PRO, WH><<<dim3(ngrp, cdiv(p.M, RT)), 512, lds, st>>>(p);
+  return SC_OK;
 }
 template <int D, int RTT, bool PRO = false>
-static void launch_ffn(const FfnArgs &p, int ngrp, hipStream_t st) {
-  if (p.w_form == 2) launch_ffn_wh<D, RTT, PRO, 2>(p, ngrp, st);
-  else if (p.w_form) launch_ffn_wh<D, RTT, PRO, 1>(p, ngrp, st);
-  else launch_ffn_wh<D, RTT, PRO, 0>(p, ngrp, st);
+static int launch_ffn(const FfnArgs &p, int ngrp, hipStream_t st) {
+  if (p.w_form == 2) return launch_ffn_wh<D, RTT, PRO, 2>(p, ngrp, st);
+  if (p.w_form) return launch_ffn_wh<D, RTT, PRO, 1>(p, ngrp, st);
+  return launch_ffn_wh<D, RTT, PRO, 0>(p, ngrp, st);
 }
 
 template <int D, bool PRO = false>
-static void launch_ffn_rtt(const FfnArgs &p, int rtt, int ngrp, hipStream_t st) {
+static int launch_ffn_rtt(const FfnArgs &p, int rtt, int ngrp, hipStream_t st) {
   switch (rtt) {
-    case 1: launch_ffn<D, 1, PRO>(p, ngrp, st); break;
-    case 2: launch_ffn<D, 2, PRO>(p, ngrp, st); break;
-    case 3: launch_ffn<D, 3, PRO>(p, ngrp, st); break;
-    case 4: launch_ffn<D, 4, PRO>(p, ngrp, st); break;
-    default: launch_ffn<D, 5, PRO>(p, ngrp, st); break;
+    case 1: return launch_ffn<D, 1, PRO>(p, ngrp, st);
+    case 2: return launch_ffn<D, 2, PRO>(p, ngrp, st);
+    case 3: return launch_ffn<D, 3, PRO>(p, ngrp, st);
+    case 4: return launch_ffn<D, 4, PRO>(p, ngrp, st);
+    default: return launch_ffn<D, 5, PRO>(p, ngrp, st);
   }
 }
 
@@ -1640,31 +1525,28 @@ __global__ __launch_bounds__(512) void rowtile_proj_kernel(RowProjArgs p) {
 }
 
 template <int D, int RTT, bool FULL, int WH>
-static void launch_rowtile_wh(const RowProjArgs &p, int ngrp, hipStream_t st) {
+static int launch_rowtile_wh(const RowProjArgs &p, int ngrp, hipStream_t st) {
   constexpr int RT = 16 * RTT;
   const size_t lds = (size_t)(RT * (D + 4) + RT * ((FULL ? D : 128) + 4)) * sizeof(float) + (WH == 1 ? (size_t)RT * (D + 8) * 2 : 0);
-  static bool attr_done = false;
-  if (!attr_done && lds > 64 * 1024) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&rowtile_proj_kernel<D, RTT, FULL, WH>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_done = true;
-  }
+  const int rc = allow_large_lds(reinterpret_cast<const void *>(&rowtile_proj_kernel<D, RTT, FULL, WH>), lds, lds, "rowtile_proj_kernel");
+  if (rc != SC_OK) return rc;
   rowtile_proj_kernel<D, RTT, FULL, WH><<<dim3(ngrp, cdiv(p.M, RT)), 512, lds, st>>>(p);
+  return SC_OK;
 }
 template <int D, int RTT, bool FULL>
-static void launch_rowtile(const RowProjArgs &p, int ngrp, hipStream_t st) {
-  if (p.w_form == 2) launch_rowtile_wh<D, RTT, FULL, 2>(p, ngrp, st);
-  else if (p.w_form) launch_rowtile_wh<D, RTT, FULL, 1>(p, ngrp, st);
-  else launch_rowtile_wh<D, RTT, FULL, 0>(p, ngrp, st);
+static int launch_rowtile(const RowProjArgs &p, int ngrp, hipStream_t st) {
+  if (p.w_form == 2) return launch_rowtile_wh<D, RTT, FULL, 2>(p, ngrp, st);
+  if (p.w_form) return launch_rowtile_wh<D, RTT, FULL, 1>(p, ngrp, st);
+  return launch_rowtile_wh<D, RTT, FULL, 0>(p, ngrp, st);
 }
 
 template <int D, bool FULL>
-static void launch_rowtile_rtt(const RowProjArgs &p, int rtt, int ngrp, hipStream_t st) {
+static int launch_rowtile_rtt(const RowProjArgs &p, int rtt, int ngrp, hipStream_t st) {
   switch (rtt) {
-    case 1: launch_rowtile<D, 1, FULL>(p, ngrp, st); break;
-    case 2: launch_rowtile<D, 2, FULL>(p, ngrp, st); break;
-    case 3: launch_rowtile<D, 3, FULL>(p, ngrp, st); break;
-    default: launch_rowtile<D, 4, FULL>(p, ngrp, st); break;
+    case 1: return launch_rowtile<D, 1, FULL>(p, ngrp, st);
+    case 2: return launch_rowtile<D, 2, FULL>(p, ngrp, st);
+    case 3: return launch_rowtile<D, 3, FULL>(p, ngrp, st);
+    default: return launch_rowtile<D, 4, FULL>(p, ngrp, st);
   }
 }
 
@@ -1711,13 +1593,9 @@ static int rowtile_run(const float *A, int lda, int M, int D, const float *ln_g,
   RowProjArgs p{A, lda, ln_g, ln_b, Wp, bias, R, C, ldc, g2, b2, LN2, eps, M, N, best_cpw, w_form};
   ProfScope prof = sc_prof_begin(st);
   const int ngrp = full ? 1 : nch / best_cpw;
-  if (D == 256) {
-    if (full) launch_rowtile_rtt<256, true>(p, best_rtt, ngrp, st);
-    else launch_rowtile_rtt<256, false>(p, best_rtt, ngrp, st);
-  } else {
-    if (full) launch_rowtile_rtt<128, true>(p, best_rtt, ngrp, st);
-    else launch_rowtile_rtt<128, false>(p, best_rtt, ngrp, st);
-  }
+  const int rc = D == 256 ? (full ? launch_rowtile_rtt<256, true>(p, best_rtt, ngrp, st) : launch_rowtile_rtt<256, false>(p, best_rtt, ngrp, st))
+                          : (full ? launch_rowtile_rtt<128, true>(p, best_rtt, ngrp, st) : launch_rowtile_rtt<128, false>(p, best_rtt, ngrp, st));
+  if (rc != SC_OK) return rc;
   sc_prof_end(prof, SC_PROF_ROWTILE_PROJ, 2.0 * (double)M * D * N,
               4.0 * ((double)M * (D + N) + (double)D * N / (w_form == 1 ? 2.0 : 1.0) + (full ? 2.0 * M * D : 0.0)));
   SC_CHECK_LAUNCH();
@@ -1815,8 +1693,8 @@ static int ffn_run(const float *XN, const int32_t *rows, int M, int D, int F, co
     const float *xn_base = rows ? XN : XN + (long)m_done * D;
     p.XN = xn_base;
     ProfScope prof = sc_prof_begin(st);
-    if (D == 256) launch_ffn_rtt<256>(p, best_rtt, ngrp, st);
-    else launch_ffn_rtt<128>(p, best_rtt, ngrp, st);
+    const int lrc = D == 256 ? launch_ffn_rtt<256>(p, best_rtt, ngrp, st) : launch_ffn_rtt<128>(p, best_rtt, ngrp, st);
+    if (lrc != SC_OK) return lrc;
     // algorithmic: 4*D*F flop per row; W1 + W2 once, x in, x out.  The split sums this decomposition
     // writes (ngrp x slab x D) and the reduce kernel re-reads are traffic, not algorithmic bytes
     sc_prof_end(prof, SC_PROF_FFN_FUSED, 4.0 * (double)slab * D * F,
@@ -1942,14 +1820,6 @@ extern "C" int sc_dec_layer_ffn(const sc_search *sbp, int layer, const float *xi
     }
   }
   SC_CHECK_ARG(best < 1e29, "max_part too small");
-  if (const char *f = sc_hook("SC_DEC_FFN_FORCE")) {   // A/B runs: "min_rows,rtt,cpw" for buckets of at least min_rows rows
-    int mr = 0, r = 0, c = 0;
-    if (sscanf(f, "%d,%d,%d", &mr, &r, &c) == 3 && M >= mr && r >= 1 && r <= ffn_rtt_max(D, wf) && c >= 1 && c <= 2 && nch % c == 0 &&
-        nch / c <= max_part) {
-      best_rtt = r;
-      best_cpw = c;
-    }
-  }
   const int ngrp = nch / best_cpw;
   const int nph = sb.H / sc_dec_layer_hpw(sb);   // partial products per row left by sc_dec_layer_cross (decoder_layer.hip)
   FfnArgs p{nullptr, rows, (const float *)w1x, w.b1, (const float *)w2x, ffn_part, M, F,
@@ -1957,8 +1827,8 @@ extern "C" int sc_dec_layer_ffn(const sc_search *sbp, int layer, const float *xi
             sc_phase_take(2), nph == sb.H ? 4 : 1};
   hipStream_t st = (hipStream_t)stream;
   ProfScope prof = sc_prof_begin(st);
-  if (D == 256) launch_ffn_rtt<256, true>(p, best_rtt, ngrp, st);
-  else launch_ffn_rtt<128, true>(p, best_rtt, ngrp, st);
+  const int rc = D == 256 ? launch_ffn_rtt<256, true>(p, best_rtt, ngrp, st) : launch_ffn_rtt<128, true>(p, best_rtt, ngrp, st);
+  if (rc != SC_OK) return rc;
   // algorithmic: 4*D*F flop per row; x + H head partials read, W1 + W2 read once, x and the partials written
   // algorithmic: 4*D*F flop per row; weights once + x in + x out - the head partials read and the
   // split sums written are TRAFFIC of this decomposition, not algorithmic bytes
@@ -1988,8 +1858,7 @@ extern "C" int sc_dec_layer_ffn_xn(const sc_search *sbp, int layer, const float 
   const void *w2x = wf == 2 ? w.w2_s : wf == 1 ? w.w2_h : (const void *)w.w2_p;
   // tile height and chunks per workgroup: the attention launches of this form hold ONE compute unit per stream and the encoder
   // groups run beside them, so the grid is sized for the compute units the decode chain has to itself (SC_STREAM_FFN_CUS)
-  int cus = SC_STREAM_FFN_CUS;
-  if (const char *e = sc_hook("SC_STREAM_FFN_CUS")) cus = atoi(e);
+  const int cus = SC_STREAM_FFN_CUS;
   int best_rtt = 5, best_cpw = nch;
   double best = 1e30;
   for (int cpw = 1; cpw <= 2; cpw *= 2) {   // (canonical summation order: one chunk or an aligned pair per workgroup)
@@ -2004,14 +1873,6 @@ extern "C" int sc_dec_layer_ffn_xn(const sc_search *sbp, int layer, const float 
     }
   }
   SC_CHECK_ARG(best < 1e29, "max_part too small");
-  if (const char *f = sc_hook("SC_DEC_FFN_FORCE")) {   // A/B runs: "min_rows,rtt,cpw"
-    int mr = 0, r = 0, c = 0;
-    if (sscanf(f, "%d,%d,%d", &mr, &r, &c) == 3 && M >= mr && r >= 1 && r <= ffn_rtt_max(D, wf) && c >= 1 && c <= 2 && nch % c == 0 &&
-        nch / c <= max_part) {
-      best_rtt = r;
-      best_cpw = c;
-    }
-  }
   const int ngrp = nch / best_cpw;
   FfnArgs p{xn, rows, (const float *)w1x, w.b1, (const float *)w2x, ffn_part, M, F, best_cpw};
   p.part_rows = sb.S * sb.W;
@@ -2019,8 +1880,8 @@ extern "C" int sc_dec_layer_ffn_xn(const sc_search *sbp, int layer, const float 
   p.dbg_stamp = sc_phase_take(3);
   hipStream_t st = (hipStream_t)stream;
   ProfScope prof = sc_prof_begin(st);
-  if (D == 256) launch_ffn_rtt<256, false>(p, best_rtt, ngrp, st);
-  else launch_ffn_rtt<128, false>(p, best_rtt, ngrp, st);
+  const int rc = D == 256 ? launch_ffn_rtt<256, false>(p, best_rtt, ngrp, st) : launch_ffn_rtt<128, false>(p, best_rtt, ngrp, st);
+  if (rc != SC_OK) return rc;
   sc_prof_end(prof, SC_PROF_FFN_PRO, 4.0 * (double)M * D * F, 4.0 * (2.0 * (double)M * D + 2.0 * (double)D * F));
   SC_CHECK_LAUNCH();
   *n_part = ngrp;

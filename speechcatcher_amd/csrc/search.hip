@@ -316,18 +316,15 @@ static int decoder_layers_impl(const sc_search *sbp, void *stream, bool fuse_log
   const char *pe = sc_hook("SC_DEC_PANEL");
   const bool panel_env = !(pe && atoi(pe) == 0);
   const bool panel = panel_env && sc_proj_ln_proj_supported(d);
-  const char *fe = sc_hook("SC_FFN_FUSED");      // =0: two GEMMs with the hidden activations in HBM
-  const bool ffn_fused = !(fe && atoi(fe) == 0) && sc_ffn_ln_supported(d, F) &&
-                         sc_workspace_bytes(stream) >= (size_t)(F / 128) * 80 * d * sizeof(float);
+  // (otherwise: two GEMMs with the hidden activations in HBM)
+  const bool ffn_fused = sc_ffn_ln_supported(d, F) && sc_workspace_bytes(stream) >= (size_t)(F / 128) * 80 * d * sizeof(float);
   // the FFN's reduce kernel also projects what consumes its LayerNorm (next layer's Q|K|V, output
   // layer): needs the row panels, the fused FFN, lane-packed weights and a workspace for all rows.
   // x then ping-pongs between dx and dxn (the reduce kernel must not update x in place), and the
   // LayerNorm before the FFN goes to dq (free after the cross-attention).
-  const char *qe = sc_hook("SC_FFN_PROJ");
-  const bool chain = !(qe && atoi(qe) == 0) && panel && ffn_fused && sb.layers[0].wqkv_q &&
+  const bool chain = panel && ffn_fused && sb.layers[0].wqkv_q &&
                      sc_workspace_bytes(stream) >= (size_t)(F / 128) * n * d * sizeof(float);
   int rc;
-#define SC_TRY(call) do { rc = (call); if (rc != SC_OK) return rc; } while (0)
   float *x = sb.dx, *xalt = sb.dxn;
   float *ffn_in = chain ? sb.dq : sb.dxn;
   // LN1 of layer 0 is the only stand-alone LayerNorm; every other LayerNorm is
@@ -580,27 +577,6 @@ static size_t pow2_keys_bytes(int V) {
   return np * sizeof(unsigned long long);
 }
 static size_t fuse_topw_lds(int V) { return 2 * (size_t)V * sizeof(float) + pow2_keys_bytes(V); }
-
-static int allow_large_lds(const void *fn, size_t need, size_t max_bytes, const char *what) {
-  if (need + 256 <= 64 * 1024) return SC_OK;   // (256: room for the kernels' static LDS)
-  static std::mutex mu;
-  static std::unordered_map<const void *, unsigned long long> done;   // kernel -> bit per device
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-    sc_set_error("%s: no current HIP device", what);
-    return SC_ERR_LAUNCH;
-  }
-  std::lock_guard<std::mutex> lk(mu);
-  unsigned long long &bits = done[fn];
-  if (bits >> dev & 1ull) return SC_OK;
-  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_bytes);
-  if (e != hipSuccess) {
-    sc_set_error("%s: raising the dynamic LDS limit to %zu bytes failed: %s", what, max_bytes, hipGetErrorString(e));
-    return SC_ERR_LAUNCH;
-  }
-  bits |= 1ull << dev;
-  return SC_OK;
-}
 
 extern "C" int sc_logsoftmax_topk(const sc_search *sbp, void *stream) {
   SC_CHECK_ARG(sbp, "null");

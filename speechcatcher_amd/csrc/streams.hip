@@ -1238,9 +1238,6 @@ int tick_collect(sc_streams *b) {
     const bool accept = !(stop_eos || stop_bbd || stop_all);
     const bool take = stop_eos || stop_all || accept;
     if (kv_full && take && !(!accept && r.pidx > 1 && r.pvalid)) {   // (not accepted + rewind pending: finish_block goes back to H_in)
-      if (sc_hook("SC_DEBUG_POOL"))
-        fprintf(stderr, "[scasr] pool exhausted: stream %d L %d nhyp %d T %d fin %d pidx %d flags %d kv_rows %d iter %ld\n", s, r.L, r.nhyp,
-                r.T, (int)r.fin, r.pidx, f, b->sb.kv_rows, b->iter);
       fault_stream(b, s, SC_ERR_CAPACITY, "self-attention K|V pool exhausted (kv_pool_rows / max_tokens)");
       continue;
     }
@@ -1748,8 +1745,8 @@ extern "C" int sc_streams_create(sc_engine *e, const sc_stream_options *o, sc_st
   const size_t m_enc = (size_t)b->max_blocks * R, n = (size_t)S * W;
   int rc = SC_OK;
 #define A(ptr, count) if (rc == SC_OK) rc = b->alloc(&ptr, (size_t)(count))
-  // (SC_PRIO_DEC / SC_PRIO_ENC: test hooks for the priority A/B of profiles/r05_ab_priority.txt)
-  if (hipStreamCreateWithPriority(&b->stream, hipStreamNonBlocking, sc_hook("SC_PRIO_DEC") ? atoi(sc_hook("SC_PRIO_DEC")) : -1) != hipSuccess) {
+  // (decode chain at priority -1, encoder stream at 0: the A/B of profiles/r05_ab_priority.txt)
+  if (hipStreamCreateWithPriority(&b->stream, hipStreamNonBlocking, -1) != hipSuccess) {
     sc_set_error("sc_streams_create: hipStreamCreate failed");
     delete b;
     return SC_ERR_LAUNCH;
@@ -1891,33 +1888,20 @@ extern "C" int sc_streams_create(sc_engine *e, const sc_stream_options *o, sc_st
     // The encoder stage starts when at most 7 % of the streams are still in the step loop (small batches: at once).
     // Measured at 128 streams (docs/profiles_r1-r3/r02_encoder_overlap_sweep.txt): serial 33.4 ms per chunk step; started with
     // the first decode iteration 32.2 (its large grids delay the full-batch decode kernels); at 50 % / 25 % / 10 % /
-    // 7 % / 3 % of the streams 31.3 / 31.1 / 30.5 / 30.5 / 30.8.  SC_ENC_START overrides the percentage.
-    const char *th = sc_hook("SC_ENC_START");
-    b->enc_start_thr = S < 16 ? S : std::max(1, (int)((long)S * (th ? atoi(th) : 7) / 100));
+    // 7 % / 3 % of the streams 31.3 / 31.1 / 30.5 / 30.5 / 30.8.
+    b->enc_start_thr = S < 16 ? S : std::max(1, (int)((long)S * 7 / 100));
   }
   {
-    // second stream for the encoder side (see sc_streams::stream_enc).  SC_ENC_OVERLAP=0 keeps everything on one
-    // stream; SC_ENC_CUS=n restricts the encoder stream to the first n compute units (hipExtStreamCreateWithCUMask)
-    const char *ov = sc_hook("SC_ENC_OVERLAP");
-    if (!(ov && atoi(ov) == 0)) {
-      const char *cu = sc_hook("SC_ENC_CUS");
-      const int ncu = cu ? atoi(cu) : 0;
-      hipError_t er;
-      if (ncu > 0 && ncu < 256) {
-        uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int i = 0; i < ncu; ++i) mask[i >> 5] |= 1u << (i & 31);
-        er = hipExtStreamCreateWithCUMask(&b->stream_enc, 8, mask);
-      } else {
-        er = hipStreamCreateWithPriority(&b->stream_enc, hipStreamNonBlocking, sc_hook("SC_PRIO_ENC") ? atoi(sc_hook("SC_PRIO_ENC")) : 0);
-      }
-      if (er == hipSuccess && hipMalloc(&b->ws_enc, (size_t)128 << 20) == hipSuccess) {
-        b->owned.push_back(b->ws_enc);
-        (void)sc_set_stream_workspace(b->stream_enc, b->ws_enc, (size_t)128 << 20);
-      } else {
-        (void)hipGetLastError();
-        if (b->stream_enc) (void)hipStreamDestroy(b->stream_enc);
-        b->stream_enc = nullptr;
-      }
+    // second stream for the encoder side (see sc_streams::stream_enc); everything stays on one stream when it or its
+    // workspace cannot be created
+    const hipError_t er = hipStreamCreateWithPriority(&b->stream_enc, hipStreamNonBlocking, 0);
+    if (er == hipSuccess && hipMalloc(&b->ws_enc, (size_t)128 << 20) == hipSuccess) {
+      b->owned.push_back(b->ws_enc);
+      (void)sc_set_stream_workspace(b->stream_enc, b->ws_enc, (size_t)128 << 20);
+    } else {
+      (void)hipGetLastError();
+      if (b->stream_enc) (void)hipStreamDestroy(b->stream_enc);
+      b->stream_enc = nullptr;
     }
   }
   const size_t cm = ((size_t)S * 8 + n) * sizeof(int32_t);
@@ -1947,7 +1931,6 @@ extern "C" int sc_streams_create(sc_engine *e, const sc_stream_options *o, sc_st
     sb.kvflags = b->ring_dev + S;   // second half of the host-mapped flag array: "K|V pool exhausted" per stream
   }
   if (const char *sp = sc_hook("SC_SCAN_SPLIT_MIN")) b->scan_split_min = atoi(sp);   // tests: 0 = never, small = always
-  if (const char *sp = sc_hook("SC_SCAN_SPLIT_STREAMS")) b->scan_split_streams = atoi(sp);   // tools: bucket limit of the T-parallel scan
   memset(b->ctrlmap_host, 0, cm);
   for (size_t i = 0; i < n; ++i) b->rm_host[0][i] = b->rm_host[1][i] = (int32_t)i;
   (void)hipMemcpy(b->ctrlmap, b->ctrlmap_host, (size_t)S * 8 * sizeof(int32_t), hipMemcpyHostToDevice);
@@ -1958,7 +1941,6 @@ extern "C" int sc_streams_create(sc_engine *e, const sc_stream_options *o, sc_st
   // (the projections' split copies, i.e. proj_dtype = "split16": the feed-forward's alone leave every projection fp32)
   b->gemm_flags = (!b->eng->enc.empty() && b->eng->enc[0].wqkv_s) ? SC_GEMM_SPLIT16 : 0;
   b->row_bucket = std::max(1, S / 32);   // 32 compaction buckets (graphs): 16 -> 32 measured +1 % at 128 streams, 64 nothing more
-  if (const char *rb = sc_hook("SC_ROW_BUCKETS")) b->row_bucket = std::max(1, S / std::max(1, atoi(rb)));   // tools: sweep
   b->n_rows_step = S * W;
   b->st.assign(S, St());
   b->run.assign(S, Run());

@@ -184,3 +184,20 @@ def test_vocabulary_limit_is_checked_at_construction():
 
     with pytest.raises(_abi.ScasrError, match="vocabulary size"):
         StreamBatch(_Weights(), object.__new__(HipBackend), 1, SearchConfig(beam_size=10), max_frames=64, max_tokens=16)
+
+
+def test_every_library_switch_is_set_by_a_test_or_a_tool():
+    """A run-time switch of the library (sc_hook("SC_...") in csrc/, read only under SC_TEST_HOOKS=1) exists for a test or
+    for a script under tools/ that sets it.  One that nothing names is the leftover of a settled A/B: an untested branch
+    in a launcher, and an option left to the environment - it goes, with the code only it reaches."""
+    csrc = ROOT / "speechcatcher_amd" / "csrc"
+    hooks = set()
+    for src in sorted(csrc.iterdir()):
+        if src.suffix in (".hip", ".h"):
+            hooks |= set(re.findall(r'sc_hook\(\s*"([A-Za-z0-9_]+)"\s*\)', src.read_text()))
+    assert hooks, "no sc_hook() reads found in csrc/"
+    users = [p for d in ("tests", "tools") for p in sorted((ROOT / d).rglob("*"))
+             if p.is_file() and p.resolve() != Path(__file__).resolve() and "__pycache__" not in p.parts]
+    texts = [p.read_text(errors="ignore") for p in users]
+    unnamed = sorted(h for h in hooks if not any(re.search(rf"\b{h}\b", t) for t in texts))
+    assert not unnamed, f"switches that no file under tests/ or tools/ names: {unnamed}"

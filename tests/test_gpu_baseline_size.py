@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from speechcatcher_amd import synth
+from speechcatcher_amd.config import XL
 from test_engine_spec import make_batch
 
 pytestmark = pytest.mark.gpu
@@ -286,15 +287,36 @@ def test_stream_resident_layers_give_the_bits_of_the_head_parallel_forms(monkeyp
         _feed(sb, audio, n)
         o = sb.hypotheses_arrays(list(range(S)))
         by_kernel = sb.take_xattn_rows_by_kernel()   # cross-attention rows read by [flash, head-parallel, stream-resident] launches
+        # which launches a decode step is made of: one more chunk step (the last chunk again) without graph replay, every
+        # launch counted by kind (scasr.h: SC_PROF_*; a captured launch is not counted, hence not the steps above)
+        NK = 13
+        ms, fl, by, nn = (C.c_double * NK)(), (C.c_double * NK)(), (C.c_double * NK)(), (C.c_longlong * NK)()
+        sb.lib.sc_prof_collect_kinds(ms, fl, by, nn, NK)   # (drops what an earlier test may have left)
+        sb.set_graphs(False)
+        sb.lib.sc_prof_enable(1)
+        _feed(sb, audio[:, -CHUNK:], 1)
+        sb.lib.sc_prof_enable(0)
+        assert sb.lib.sc_prof_collect_kinds(ms, fl, by, nn, NK) == 0
         sb.close()
+        n_reduce, n_ffn, n_cross, n_stream = int(nn[4]), int(nn[9]), int(nn[11]), int(nn[12])   # PROJ_LN_PROJ, FFN_PRO, LAYER_CROSS, LAYER_STREAM
+        counts = (form, split, by_kernel, n_reduce, n_ffn, n_cross, n_stream)
         # the stream-resident kernel ran exactly when it was asked for
-        assert (by_kernel[2] > 0) if form == "1" else (by_kernel[2] == 0), (form, split, by_kernel)
+        assert (by_kernel[2] > 0) if form == "1" else (by_kernel[2] == 0), counts
+        assert (n_stream > 0 and n_cross == 0) if form == "1" else (n_stream == 0 and n_cross > 0), counts
+        assert n_ffn == n_stream + n_cross, counts     # one feed-forward launch per layer and step in either form
+        if form == "0":
+            # the launch that sums the head partials once per row (sc_dec_layer_reduce_ln, counted as PROJ_LN_PROJ like the one
+            # reduce + after_norm launch that every step ends with) ran exactly when it was asked for: in every layer of the
+            # steps whose bucket takes four heads per workgroup (SC_HPW_MIN_ROWS = 640 rows: the full batch here) - or in none
+            n_layers = XL.dec_layers
+            assert n_cross % n_layers == 0, counts
+            steps = n_cross // n_layers
+            assert (steps < n_reduce <= steps + n_cross) if split == "1" else (n_reduce == steps), counts
         return o
 
     a, b = run("1"), run("0")
     assert a["lens"][:, 0].min() >= (60 if n < 20 else 150), int(a["lens"][:, 0].min())
-    # ... and the four-head form with the head partials summed in a launch of their own (sc_dec_layer_reduce_ln, an A/B hook;
-    # no counter tells whether that launch ran)
+    # ... and the four-head form with the head partials summed in a launch of their own (sc_dec_layer_reduce_ln, an A/B hook)
     for other, what in ((b, "four heads per workgroup"), (run("0", "1"), "four heads per workgroup, partials summed once per row")):
         for key in ("n_hyps", "lens", "ids", "xpos"):
             assert np.array_equal(a[key], other[key]), (what, key)
