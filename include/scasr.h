@@ -173,7 +173,7 @@ const char *sc_last_error(void);
 /* ABI revision of this header: bumped whenever a struct layout or a signature changes incompatibly.  sc_version()
  * returns the revision the LIBRARY was built with; a host compares the two before it passes any struct
  * (speechcatcher_amd/_abi.py does at load time, the C hosts in tests/ at start-up). */
-#define SC_ABI_VERSION 7
+#define SC_ABI_VERSION 8
 int sc_version(void);
 
 /* hipGraph capture / replay of any sequence of the launches below on a
@@ -399,6 +399,37 @@ int sc_logmel(const float *pcm, int pcm_stride, const int32_t *jobs, int n_jobs,
               const double *stdv, int mvn_mode, int n_fft, int hop, int win, int n_mels,
               float *feat, void *stream);
 
+/* ---- sample-rate conversion to 16 kHz (resample.hip) --------------------------------------
+ * The reference takes 16 kHz PCM from one ffmpeg pipe per session (speechcatcher.py:574-592, speechcatcher_server.py);
+ * here the conversion is a rational polyphase FIR on the GPU, in the staging step of the stream engine:
+ *   g = gcd(rate, 16000), L = 16000 / g, M = rate / g;  fc = 0.94 min(1, L / M), W = 24 / fc, Wc = ceil(W), K = 2 Wc
+ *   h(x) = fc sinc(fc x) I0(10 sqrt(1 - (x / W)^2)) / I0(10) for |x| <= W, else 0     (Kaiser window, beta 10)
+ *   coef[p][k] = h((k - Wc + 1) - p / L), each phase row divided by its float64 sum (DC gain 1), rounded to f32
+ *   y[m] = sum_k coef[p][k] x[n0 - Wc + 1 + k],  n0 = (m M) div L, p = (m M) mod L,  x = 0 before the start and, once
+ *   the final call has been made, behind the end
+ * in fp32 and ONE order: four partial sums over k = 0, 1, 2, 3 (mod 4), each in ascending k, every product rounded
+ * before it is added (no fma), combined as (s0 + s1) + (s2 + s3).  Output m is a function of m and the signal alone:
+ * how the audio was cut into calls does not enter.  Supported: every rate in [8000, 48000] with L <= 640 (8000, 11025,
+ * 12000, 16000, 22050, 24000, 32000, 44100, 48000 among them); the look-ahead is Wc input samples (<= 1.6 ms).
+ * After N input samples a stream has produced max(0, ceil((N - Wc) L / M)) outputs, ceil(N L / M) once it is final. */
+/* design the library uses for `rate`: L, M, half width Wc, and (coef != NULL) the [L][2*Wc] f32 table.  Pure host;
+ * any of the outputs may be NULL.  SC_ERR_ARG for an unsupported rate. */
+int sc_resample_design(int rate, int *L, int *M, int *half_width, float *coef);
+/* outputs produced after n_in_total input samples (final: after the flush).  Pure host; SC_ERR_ARG (< 0) for an
+ * unsupported rate. */
+long sc_resample_out_count(int rate, long n_in_total, int is_final);
+/* kernel level: a whole signal at once (zero history, flushed), same device code as the stream path; returns n_out
+ * (<= y_cap, else SC_ERR_ARG).  16000 runs the design's filter like any other rate (the STREAM path bypasses it).  The
+ * coefficient table of a rate is uploaded on first use and kept per device for the life of the process - the one
+ * allocation a kernel-level entry point makes. */
+long sc_resample(const float *x_dev, long n_in, int rate, float *y_dev, long y_cap, void *stream);
+
+/* measurement aid (tools/resample_bench.py): hipEvent times ms[iters] (HOST) of the launch the staging step of an admission
+ * of n_jobs chunks of n_in samples at `rate` issues, after three warm-up launches, on buffers of its own - rate 16000:
+ * the scatter copy of n_jobs x n_in floats; another rate: the conversion launch for streams in mid-utterance (history
+ * read and left). */
+int sc_stage_bench(int rate, int n_jobs, int n_in, int iters, double *ms);
+
 /* ---- encoder --------------------------------------------------------------- */
 
 /* first Conv2d(1->d,3,stride 2)+ReLU (subsampling.py:87-93), channels-last out.
@@ -591,7 +622,8 @@ void sc_engine_destroy(sc_engine *engine);
 int sc_streams_create(sc_engine *engine, const sc_stream_options *options, sc_streams **out);
 void sc_streams_destroy(sc_streams *streams);
 /* One chunk step for n streams: stream_ids[i] (each stream at most once per call) gets n_samples[i] float samples
- * in +-1 from pcm[i] (HOST; NULL = already resident in the device PCM buffer, see sc_streams_pcm) with is_final[i].
+ * in +-1 from pcm[i] (HOST; NULL = already resident in the device PCM buffer, see sc_streams_pcm) with is_final[i],
+ * at the stream's input rate (sc_stream_set_input_rate; 16 kHz unless set).
  * The host chunks are staged in pinned memory and reach the device with ONE copy.  Runs frontend -> encoder ->
  * every decode block that became ready (run to completion).  status[i] (HOST out, may be NULL): 1 output, 0 the
  * reference's early `return []`, SC_ERR_CAPACITY / SC_ERR_INPUT: this stream failed and was reset (message:
@@ -658,8 +690,20 @@ int sc_align_hyps(sc_streams *streams, const int *stream_ids, int n, int nbest, 
 /* ... of a caller-given transcript ids[0..L) against the same frames of one stream */
 int sc_align_tokens(sc_streams *streams, int stream, const int32_t *ids, int L, int32_t *start, int32_t *end,
                     float *logp_mean, double *path_score, int *status);
-/* Speech2TextStreaming.reset (speech2text_streaming.py:252-263); not while the stream has a chunk outstanding */
+/* Speech2TextStreaming.reset (speech2text_streaming.py:252-263); not while the stream has a chunk outstanding.
+ * The stream's input rate stays; its sample-rate converter starts over. */
 int sc_reset(sc_streams *streams, int stream);
+/* stream level: rate of the samples sc_push / sc_submit take for this stream.  Only on a stream that is idle and has
+ * buffered nothing since its last reset; SC_ERR_ARG otherwise or for an unsupported rate.  Default 16000.
+ * A stream at another rate is converted on the GPU in the admission's staging step (one launch per admission for all
+ * such chunks; 16 kHz chunks of the same admission take the plain copy): the call then counts as one of n_out 16 kHz
+ * samples, n_out from the integer formula above.  Both the call's n_samples and its n_out must be
+ * <= max_chunk_samples + 16 hops (else SC_ERR_CAPACITY for that stream); pcm[i] == NULL (device-resident PCM) is
+ * SC_ERR_ARG on such a stream.  A final call flushes the filter and ends the utterance: the next call starts a new
+ * signal.  At most 8 distinct rates other than 16000 per sc_streams; the table of a rate is designed in float64 and
+ * uploaded when the rate is first set. */
+int sc_stream_set_input_rate(sc_streams *streams, int stream, int rate);
+int sc_stream_input_rate(const sc_streams *streams, int stream);
 int sc_stream_info(const sc_streams *streams, int stream, sc_stream_info_t *out);
 /* rows of the self-attention K|V pool per (stream, layer) this batch was created with (sc_stream_options.kv_pool_rows, or the
  * default: one row per (position, hypothesis) within min(a quarter of the free device memory, SC_KV_POOL_DEFAULT_MAX_GIB)) */

@@ -8,8 +8,9 @@ reset() after it) -> paragraphs -> ``<input>.txt`` and ``<input>.json``.
 Differences to the reference CLI, all on the host side: only ``--decoder native`` exists here; the device is a ROCm
 GPU (no CPU path); ``-n`` is the number of parallel stream slots of ONE model replica instead of worker processes
 (default 1 = the reference's behaviour on a GPU: segments decoded serially on one model, speechcatcher.py:823-825);
-input must already be 16 kHz mono 16-bit WAV (the ffmpeg conversion, microphone mode and model download are out of
-scope - pass a local model directory or a .scasr blob as ``-m``).
+input must be mono 16-bit WAV, at 16 kHz or at any rate the engine converts (8000..48000 Hz, speechcatcher_amd.resample:
+the whole recording is resampled once on the GPU and then takes the 16 kHz path); the ffmpeg conversion of other media,
+microphone mode and model download are out of scope - pass a local model directory or a .scasr blob as ``-m``.
 """
 import argparse
 import json
@@ -25,11 +26,21 @@ def read_wav_16k_mono(path):
     with wave.open(path, "rb") as f:
         ch, bits, rate = f.getnchannels(), f.getsampwidth(), f.getframerate()
         buf = f.readframes(-1)
-    if ch != 1 or bits != 2 or rate != 16000:
+    from .resample import MAX_RATE, MIN_RATE, rate_params
+    if ch != 1 or bits != 2 or rate_params(rate) is None:
         raise SystemExit(f"Error: '{path}' is {ch} channel(s), {8 * bits} bit, {rate} Hz; this entry point reads 16 kHz mono "
-                         "16-bit WAV only (the reference converts other media with ffmpeg first: "
-                         "ffmpeg -i in -ac 1 -ar 16000 out.wav)")
+                         f"16-bit WAV, or mono 16-bit WAV at {MIN_RATE}..{MAX_RATE} Hz which it resamples (the reference "
+                         "converts other media with ffmpeg first: ffmpeg -i in -ac 1 -ar 16000 out.wav)")
     return np.frombuffer(buf, dtype="<i2"), rate
+
+
+def to_16k(raw, rate, device="cuda:0"):
+    """int16 recording at ``rate`` -> int16 at 16 kHz: resampled once, whole, on the GPU (hip_backend.resample)"""
+    if rate == 16000:
+        return raw
+    from .hip_backend import resample
+    y = resample(raw.astype(np.float32) / 32768.0, rate, device).cpu().numpy()
+    return np.clip(np.rint(y * 32768.0), -32768, 32767).astype(np.int16)
 
 
 def recognize_file(speech2text, media_path, output_file="", quiet=True, progress=True, num_slots=1, chunk_length=8192,
@@ -40,6 +51,7 @@ def recognize_file(speech2text, media_path, output_file="", quiet=True, progress
     from .native import NativeStreamBatch
     from .segmenter import recognize_recording
     raw, rate = read_wav_16k_mono(media_path)
+    raw, rate = to_16k(raw, rate, speech2text.device), 16000
     seconds = len(raw) / float(rate)
     # capacities for the longest segment the endpointer may produce (it cuts at <= 180 s: simple_endpointing)
     seg_s = min(seconds, 200.0) + 2.0
@@ -91,7 +103,7 @@ def make_parser():
     p.add_argument("--token-alignment", dest="token_alignment", action="store_true",
                    help="add token_start / token_end / token_conf to the .json: token times at 40 ms resolution and a per-token "
                         "confidence from a CTC forced alignment on the GPU (token_timestamps stay as they are)")
-    p.add_argument("inputfile", nargs="?", default="", help="input recording (16 kHz mono 16-bit WAV)")
+    p.add_argument("inputfile", nargs="?", default="", help="input recording (mono 16-bit WAV, 16 kHz or 8000..48000 Hz)")
     return p
 
 

@@ -215,13 +215,20 @@ _SIGS = {
                                 c_int_p, c_int_p]),
     "sc_align_tokens": (C.c_int, [vp, C.c_int, c_int_p, C.c_int, c_int_p, c_int_p, c_float_p, c_double_p, c_int_p]),
     "sc_streams_read_ctc": (C.c_int, [vp, C.c_int, vp, C.c_int]),
+    # sample-rate conversion (resample.hip, streams.hip)
+    "sc_resample_design": (C.c_int, [C.c_int, c_int_p, c_int_p, c_int_p, c_float_p]),
+    "sc_resample_out_count": (C.c_long, [C.c_int, C.c_long, C.c_int]),
+    "sc_resample": (C.c_long, [vp, C.c_long, C.c_int, vp, C.c_long, vp]),
+    "sc_stream_set_input_rate": (C.c_int, [vp, C.c_int, C.c_int]),
+    "sc_stream_input_rate": (C.c_int, [vp, C.c_int]),
+    "sc_stage_bench": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_double_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())
 
 # revision of include/scasr.h these ctypes mirrors were written against (SC_ABI_VERSION): a library built from another
 # revision would be handed mis-laid-out structs
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 _lib = None
 

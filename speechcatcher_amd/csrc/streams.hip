@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "common.h"
+#include "resample.h"
 
 namespace {
 
@@ -117,6 +118,10 @@ struct St {
   int T_proj = 0, T_projkv = 0;
   long n_steps_total = 0;
   int T_hyp = 0;   // frames [0, T_hyp) of the decode block the live hypotheses come from (sc_align_hyps)
+  // sample-rate conversion (resample.hip): coefficient table of the stream's input rate (-1: 16 kHz, no conversion), input
+  // samples taken and 16 kHz samples produced in this utterance, history row the next launch reads (it writes the other)
+  int rs_tab = -1, rs_par = 0;
+  long rs_in = 0, rs_out = 0;
 };
 
 // a decode block of the schedule (beam_search.py:590-634): the T frames [0, T) it presents to the scorers, whether
@@ -182,6 +187,7 @@ struct EncGroup {
   int slot = 0;                              // job-table arena slot
   int stage_slot = -1;                       // pinned staging slot holding the admission's host input (-1: none)
   std::vector<long long> copy_jobs;          // [n][3] staging offset, destination offset, count (floats)
+  std::vector<sc_rs_job> rs_jobs;            // chunks of the streams whose input rate is not 16000: converted, not copied
   size_t stage_floats = 0;
   std::vector<int32_t> fe_jobs;
   int n_fe = 0, max_keep = 0;
@@ -263,6 +269,12 @@ struct sc_streams {
   bool stage_busy[N_STAGE] = {false};
   int stage_next = 0;
   long long *cjobs_host = nullptr, *cjobs_dev = nullptr;   // [N_STAGE][S*3] scatter jobs of a staging slot
+  // ---- sample-rate conversion of the streams whose input rate is not 16000 (resample.hip; one launch per admission) ----
+  sc_rs_job *rsjobs_host = nullptr, *rsjobs_dev = nullptr;   // [N_STAGE][S] jobs of a staging slot
+  float *rs_hist = nullptr;       // [2][S][SC_RS_HIST] last K - 1 input samples of every stream, flipped per call
+  sc_rs_tabs rs_tabs{};           // coefficient tables of the rates set on this handle (designed when a rate is first set)
+  int rs_rate[SC_RS_MAX_TABS] = {0};
+  int n_rs_tabs = 0;
   // ---- batched hypothesis read-back (sc_get_hyps_batch): pack kernel -> one D2H into pinned memory -------------------
   int32_t *pack_dev = nullptr, *pack_host = nullptr, *pjobs_host = nullptr, *pjobs_dev = nullptr;
   size_t pack_cap = 0;            // int32 elements
@@ -392,6 +404,12 @@ __global__ __launch_bounds__(256) void scatter_f32_kernel(const float *__restric
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) dst[dof + i] = src[so + i];
 }
 
+// nj jobs, the longest of mx floats
+void launch_scatter(const float *src, float *dst, const long long *jobs_dev, int nj, long long mx, hipStream_t st) {
+  dim3 grid((unsigned)std::min<long long>(64, (std::max<long long>(mx, 1) + 1023) / 1024), nj);
+  scatter_f32_kernel<<<grid, 256, 0, st>>>(src, dst, jobs_dev);
+}
+
 // live hypotheses of the listed streams -> one packed buffer (sc_get_hyps_batch).  jobs[j] = {hypothesis row
 // ((side*S + s)*W + h), L, destination offset (int32 units), 0}: ids at [off, off+L), positions at [off+L, off+2L),
 // then the three float64 totals (score, decoder, ctc) at the next 8-byte boundary.
@@ -444,6 +462,7 @@ void reset_stream(sc_streams *b, int s) {
   // beam_search.py:343-356).  strict: CTCPrefixScorer.impl is never cleared by the reference
   // (scorers.py:342-350: the stale table stays) and the short-segment PE counter keeps counting (A13).
   St old = b->st[s], ns;
+  ns.rs_tab = old.rs_tab;   // the input rate stays; the converter starts over (no history)
   if (b->strict) {
     ns.short_pos = old.short_pos;
     ns.T_ctc = old.T_ctc;
@@ -893,21 +912,33 @@ int project_rows(sc_streams *b, EncGroup &g) {
 // host input of an admission -> device, at once: ONE host-to-device copy of the pinned staging slot, one scatter
 // launch to the chunks' places behind what each stream has buffered (PCM ring / feature buffer)
 int stage_copy(sc_streams *b, EncGroup &g) {
-  if (g.copy_jobs.empty()) return SC_OK;
+  if (g.copy_jobs.empty() && g.rs_jobs.empty()) return SC_OK;
   hipStream_t es = b->stream_enc ? b->stream_enc : b->stream;
   const int ss = g.stage_slot;
   const size_t so = (size_t)ss * b->stage_cap, jo = (size_t)ss * b->S * 3;
   const int nj = (int)g.copy_jobs.size() / 3;
-  memcpy(b->cjobs_host + jo, g.copy_jobs.data(), g.copy_jobs.size() * sizeof(long long));
-  HIP_TRY(hipMemcpyAsync(b->stage_dev + so, b->stage_host + so, g.stage_floats * sizeof(float), hipMemcpyHostToDevice, es));
-  HIP_TRY(hipMemcpyAsync(b->cjobs_dev + jo, b->cjobs_host + jo, g.copy_jobs.size() * sizeof(long long), hipMemcpyHostToDevice, es));
-  long long mx = 1;
-  for (int j = 0; j < nj; ++j) mx = std::max(mx, g.copy_jobs[j * 3 + 2]);
-  dim3 grid((unsigned)std::min<long long>(64, (mx + 1023) / 1024), nj);
-  scatter_f32_kernel<<<grid, 256, 0, es>>>(b->stage_dev + so, g.features ? b->featbuf : b->pcm, b->cjobs_dev + jo);
+  if (g.stage_floats)
+    HIP_TRY(hipMemcpyAsync(b->stage_dev + so, b->stage_host + so, g.stage_floats * sizeof(float), hipMemcpyHostToDevice, es));
+  if (nj) {
+    memcpy(b->cjobs_host + jo, g.copy_jobs.data(), g.copy_jobs.size() * sizeof(long long));
+    HIP_TRY(hipMemcpyAsync(b->cjobs_dev + jo, b->cjobs_host + jo, g.copy_jobs.size() * sizeof(long long), hipMemcpyHostToDevice, es));
+    long long mx = 1;
+    for (int j = 0; j < nj; ++j) mx = std::max(mx, g.copy_jobs[j * 3 + 2]);
+    launch_scatter(b->stage_dev + so, g.features ? b->featbuf : b->pcm, b->cjobs_dev + jo, nj, mx, es);
+  }
+  if (!g.rs_jobs.empty()) {   // the chunks at another input rate: converted to 16 kHz on their way into the PCM ring
+    const size_t ro = (size_t)ss * b->S;
+    const int nr = (int)g.rs_jobs.size();
+    memcpy(b->rsjobs_host + ro, g.rs_jobs.data(), nr * sizeof(sc_rs_job));
+    HIP_TRY(hipMemcpyAsync(b->rsjobs_dev + ro, b->rsjobs_host + ro, nr * sizeof(sc_rs_job), hipMemcpyHostToDevice, es));
+    long long tiles = 1;
+    for (const sc_rs_job &j : g.rs_jobs) tiles = std::max(tiles, sc_rs_tiles(b->rs_tabs, j.tab, j.n_out));
+    RC_TRY(sc_rs_launch(b->rs_tabs, nullptr, b->rsjobs_dev + ro, nr, tiles, b->stage_dev + so, b->pcm, b->rs_hist, b->S, es));
+  }
   HIP_TRY(hipEventRecord(b->ev_stage[ss], es));   // the pinned slot is free again behind this
   b->stage_busy[ss] = true;
   g.copy_jobs.clear();
+  g.rs_jobs.clear();
   return SC_OK;
 }
 
@@ -1318,15 +1349,37 @@ void plan_group(sc_streams *b, const std::vector<Chunk> &chunks, bool features, 
       has_out[k] = 1;
       continue;
     }
-    if (st.pcm_end + ch.n > b->PCAP) throw StreamFault{ch.s, SC_ERR_CAPACITY, "pcm buffer capacity exceeded"};
-    if (ch.n > 0 && ch.host) {
-      if (ch.n > b->max_chunk + 16 * c.hop_length)
-        throw StreamFault{ch.s, SC_ERR_CAPACITY, "chunk is longer than max_chunk_samples allows"};
-      memcpy(stage + g.stage_floats, ch.host, (size_t)ch.n * sizeof(float));
-      g.copy_jobs.insert(g.copy_jobs.end(), {(long long)g.stage_floats, (long long)ch.s * b->PCAP + st.pcm_end, (long long)ch.n});
-      g.stage_floats += (size_t)ch.n;
+    if (st.rs_tab >= 0) {
+      // another input rate: the raw chunk is staged, the launch of stage_copy converts it and appends n_out samples - a
+      // function of the stream's sample counts alone - behind pcm_end; from here on the call is one of n_out 16 kHz samples
+      const int t = st.rs_tab;
+      const long lim = b->max_chunk + 16 * c.hop_length;
+      const long out_total = sc_rs_out_count(b->rs_tabs.L[t], b->rs_tabs.M[t], b->rs_tabs.Wc[t], st.rs_in + ch.n, ch.fin);
+      const long n_out = out_total - st.rs_out;
+      if (ch.n > lim || n_out > lim) throw StreamFault{ch.s, SC_ERR_CAPACITY, "chunk is longer than max_chunk_samples allows"};
+      if (st.pcm_end + n_out > b->PCAP) throw StreamFault{ch.s, SC_ERR_CAPACITY, "pcm buffer capacity exceeded"};
+      if (ch.n > 0 || n_out > 0) {
+        if (ch.n > 0) memcpy(stage + g.stage_floats, ch.host, (size_t)ch.n * sizeof(float));
+        g.rs_jobs.push_back(sc_rs_job{(long long)g.stage_floats, (long long)ch.n, (long long)ch.s * b->PCAP + st.pcm_end,
+                                      (long long)n_out, (long long)st.rs_out, (long long)st.rs_in, t, ch.s, st.rs_par, 0});
+        g.stage_floats += (size_t)ch.n;
+        st.rs_par ^= 1;
+      }
+      st.rs_in += ch.n;
+      st.rs_out = out_total;
+      if (ch.fin) st.rs_in = st.rs_out = 0;   // the utterance ends: the next one starts without history
+      st.pcm_end += n_out;
+    } else {
+      if (st.pcm_end + ch.n > b->PCAP) throw StreamFault{ch.s, SC_ERR_CAPACITY, "pcm buffer capacity exceeded"};
+      if (ch.n > 0 && ch.host) {
+        if (ch.n > b->max_chunk + 16 * c.hop_length)
+          throw StreamFault{ch.s, SC_ERR_CAPACITY, "chunk is longer than max_chunk_samples allows"};
+        memcpy(stage + g.stage_floats, ch.host, (size_t)ch.n * sizeof(float));
+        g.copy_jobs.insert(g.copy_jobs.end(), {(long long)g.stage_floats, (long long)ch.s * b->PCAP + st.pcm_end, (long long)ch.n});
+        g.stage_floats += (size_t)ch.n;
+      }
+      st.pcm_end += ch.n;
     }
-    st.pcm_end += ch.n;
     FePlan p = plan_frontend(c, st, ch.fin);
     if (!p.emit) continue;
     if (p.n > b->max_feat_new) throw StreamFault{ch.s, SC_ERR_CAPACITY, "chunk produces more feature frames than max_chunk_samples allows"};
@@ -1360,7 +1413,8 @@ int admit(sc_streams *b, std::vector<Chunk> chunks, bool features, bool defer, s
   const sc_config &c = b->cfg;
   RC_TRY(retire_groups(b));
   bool host_input = false;
-  for (auto &ch : chunks) host_input = host_input || (ch.host && ch.n > 0);
+  // (a stream at another input rate: its job table lives in the staging slot, also for a final call without samples)
+  for (auto &ch : chunks) host_input = host_input || (ch.host && ch.n > 0) || (!features && b->st[ch.s].rs_tab >= 0);
   int sslot = -1;
   if (host_input) {
     sslot = b->stage_next;
@@ -1378,7 +1432,10 @@ int admit(sc_streams *b, std::vector<Chunk> chunks, bool features, bool defer, s
     if (!features)
       for (auto &ch : chunks) {   // compaction moves device data: settle it before the snapshot
         St &st = b->st[ch.s];
-        if (st.pcm_end + ch.n > b->PCAP && st.pcm_start > 0) {
+        long n16 = ch.n;   // 16 kHz samples the call appends
+        if (st.rs_tab >= 0)
+          n16 = sc_rs_out_count(b->rs_tabs.L[st.rs_tab], b->rs_tabs.M[st.rs_tab], b->rs_tabs.Wc[st.rs_tab], st.rs_in + ch.n, ch.fin) - st.rs_out;
+        if (st.pcm_end + n16 > b->PCAP && st.pcm_start > 0) {
           int rc = launch_pending_groups(b);   // (a frontend that still has to read the old places)
           if (rc == SC_OK && b->stream_enc && hipStreamSynchronize(b->stream_enc) != hipSuccess) rc = SC_ERR_LAUNCH;
           if (rc == SC_OK) rc = compact_pcm(b, ch.s);
@@ -1568,6 +1625,17 @@ int check_chunks(sc_streams *b, const int *stream_ids, const int *counts, int n,
       }
     }
   }
+  return SC_OK;
+}
+
+// device-resident PCM (pcm[i] == NULL) is 16 kHz by definition: a stream with another input rate takes host samples only
+int check_resident(sc_streams *b, const int *stream_ids, const float *const *pcm, const int *counts, int n, const char *what) {
+  for (int i = 0; i < n; ++i)
+    if (b->st[stream_ids[i]].rs_tab >= 0 && counts[i] > 0 && (!pcm || !pcm[i])) {
+      sc_set_error("%s: stream %d has input rate %d: device-resident PCM (a NULL pointer) is 16 kHz only", what, stream_ids[i],
+                   b->rs_rate[b->st[stream_ids[i]].rs_tab]);
+      return SC_ERR_ARG;
+    }
   return SC_OK;
 }
 
@@ -1783,6 +1851,8 @@ extern "C" int sc_streams_create(sc_engine *e, const sc_stream_options *o, sc_st
   A(b->pack_dev, b->pack_cap);
   A(b->pjobs_dev, n * 4);
   A(b->cjobs_dev, (size_t)N_STAGE * S * 3);
+  A(b->rsjobs_dev, (size_t)N_STAGE * S);
+  A(b->rs_hist, (size_t)2 * S * SC_RS_HIST);
   sc_search &sb = b->sb;
   sb.S = S; sb.W = W; sb.K = K; sb.V = V; sb.d = d; sb.H = c.dec_heads; sb.F = F; sb.n_layers = c.dec_layers;
   sb.TCAP = b->TCAP; sb.LCAP = b->LCAP; sb.blank = c.blank_id; sb.eos = c.eos_id; sb.sos = c.sos_id;
@@ -1909,7 +1979,8 @@ extern "C" int sc_streams_create(sc_engine *e, const sc_stream_options *o, sc_st
             b->halloc(&b->rm_host[0], n) == SC_OK && b->halloc(&b->rm_host[1], n) == SC_OK &&
             b->halloc(&b->arena_host, b->slot_cap * N_ARENA) == SC_OK && b->halloc(&b->bs_host, b->bs_cap * N_RING) == SC_OK &&
             b->halloc(&b->stage_host, b->stage_cap * N_STAGE) == SC_OK && b->halloc(&b->pack_host, b->pack_cap) == SC_OK &&
-            b->halloc(&b->pjobs_host, n * 4) == SC_OK && b->halloc(&b->cjobs_host, (size_t)N_STAGE * S * 3) == SC_OK;
+            b->halloc(&b->pjobs_host, n * 4) == SC_OK && b->halloc(&b->cjobs_host, (size_t)N_STAGE * S * 3) == SC_OK &&
+            b->halloc(&b->rsjobs_host, (size_t)N_STAGE * S) == SC_OK;
   for (int i = 0; i < 2 && ok; ++i) ok = hipEventCreateWithFlags(&b->ev_iter[i], hipEventDisableTiming) == hipSuccess;
   for (int i = 0; i < N_ARENA && ok; ++i) ok = hipEventCreateWithFlags(&b->ev_group[i], hipEventDisableTiming) == hipSuccess;
   for (int i = 0; i < N_STAGE && ok; ++i) ok = hipEventCreateWithFlags(&b->ev_stage[i], hipEventDisableTiming) == hipSuccess;
@@ -1973,6 +2044,128 @@ extern "C" int sc_reset(sc_streams *b, int stream) {
   return SC_OK;
 }
 
+// Input rate of the samples sc_push / sc_submit take for a stream (default 16000: no conversion, the scatter copy).  The
+// table of a rate is designed and uploaded when the rate is first set on the handle; at most SC_RS_MAX_TABS distinct rates.
+extern "C" int sc_stream_set_input_rate(sc_streams *b, int stream, int rate) {
+  SC_CHECK_ARG(b && stream >= 0 && stream < b->S, "stream out of range");
+  SC_API_BEGIN
+  const St &cur = b->st[stream];
+  SC_CHECK_ARG(!b->job[stream].open && b->ahead[stream].empty(), "the stream has a chunk outstanding (sc_poll reports it first)");
+  SC_CHECK_ARG(cur.pcm_end == 0 && !cur.fe_started && !cur.enc_started && !cur.started && cur.rs_in == 0,
+               "the stream has buffered audio since its last reset (sc_reset first)");
+  int L, M, Wc;
+  if (!sc_rs_params(rate, &L, &M, &Wc)) {
+    sc_set_error("sc_stream_set_input_rate: unsupported input rate %d (supported: 8000..48000 Hz with 16000 / gcd(rate, 16000) <= 640)", rate);
+    return SC_ERR_ARG;
+  }
+  int t = -1;
+  if (rate != 16000) {
+    for (int i = 0; i < b->n_rs_tabs; ++i)
+      if (b->rs_rate[i] == rate) t = i;
+    if (t < 0) {
+      SC_CHECK_ARG(b->n_rs_tabs < SC_RS_MAX_TABS, "at most 8 distinct input rates per sc_streams");
+      HIP_TRY(hipSetDevice(b->eng->device));
+      std::vector<float> host((size_t)L * 2 * Wc);
+      RC_TRY(sc_resample_design(rate, nullptr, nullptr, nullptr, host.data()));
+      float *dev = nullptr;
+      RC_TRY(b->alloc(&dev, host.size()));
+      HIP_TRY(hipMemcpy(dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+      t = b->n_rs_tabs++;
+      b->rs_rate[t] = rate;
+      b->rs_tabs.coef[t] = dev;
+      b->rs_tabs.L[t] = L; b->rs_tabs.M[t] = M; b->rs_tabs.Wc[t] = Wc;
+    }
+  }
+  b->st[stream].rs_tab = t;
+  return SC_OK;
+  SC_API_END
+}
+
+extern "C" int sc_stream_input_rate(const sc_streams *b, int stream) {
+  SC_CHECK_ARG(b && stream >= 0 && stream < b->S, "stream out of range");
+  return b->st[stream].rs_tab < 0 ? 16000 : b->rs_rate[b->st[stream].rs_tab];
+}
+
+// Measurement aid (tools/resample_bench.py): what the staging step of an admission of n_jobs chunks of n_in samples launches,
+// timed by hipEvents on a stream of its own - rate 16000: scatter_f32_kernel; another rate: the resample launch for streams in
+// mid-utterance (history read and left).
+extern "C" int sc_stage_bench(int rate, int n_jobs, int n_in, int iters, double *ms) {
+  SC_CHECK_ARG(n_jobs > 0 && n_jobs <= 4096 && n_in > 0 && n_in <= (1 << 20) && iters > 0 && ms, "bad arguments");
+  SC_API_BEGIN
+  int L = 1, M = 1, Wc = 0;
+  SC_CHECK_ARG(sc_rs_params(rate, &L, &M, &Wc), "unsupported rate");
+  const bool copy = rate == 16000;
+  const long n_before = 3L * n_in, m0 = copy ? 0 : sc_rs_out_count(L, M, Wc, n_before, false);
+  const long n_out = copy ? n_in : sc_rs_out_count(L, M, Wc, n_before + n_in, false) - m0;
+  const long row = n_out + 16;
+  std::vector<float> x((size_t)n_jobs * n_in), h((size_t)2 * n_jobs * SC_RS_HIST);
+  unsigned r = 12345u;
+  for (float &v : x) v = ((r = r * 1664525u + 1013904223u) >> 8) * (1.0f / 8388608.0f) - 1.0f;
+  for (float &v : h) v = ((r = r * 1664525u + 1013904223u) >> 8) * (1.0f / 8388608.0f) - 1.0f;
+  std::vector<long long> cj((size_t)n_jobs * 3);
+  std::vector<sc_rs_job> rj(n_jobs);
+  for (int j = 0; j < n_jobs; ++j) {
+    cj[j * 3] = (long long)j * n_in; cj[j * 3 + 1] = (long long)j * row; cj[j * 3 + 2] = n_in;
+    rj[j] = sc_rs_job{(long long)j * n_in, n_in, (long long)j * row, n_out, m0, n_before, 0, j, 0, 0};
+  }
+  float *src = nullptr, *dst = nullptr, *hist = nullptr, *tab = nullptr;
+  long long *cjd = nullptr;
+  sc_rs_job *rjd = nullptr;
+  hipStream_t st = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  std::vector<float> coef((size_t)L * 2 * Wc);
+  if (!copy) RC_TRY(sc_resample_design(rate, nullptr, nullptr, nullptr, coef.data()));
+  auto cleanup = [&]() {
+    for (void *p : {(void *)src, (void *)dst, (void *)hist, (void *)tab, (void *)cjd, (void *)rjd})
+      if (p) (void)hipFree(p);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (st) (void)hipStreamDestroy(st);
+  };
+  sc_rs_tabs tabs{};
+  int rc = SC_OK;
+  auto run = [&]() -> int {
+    RC_TRY(dalloc(&src, x.size()));
+    RC_TRY(dalloc(&dst, (size_t)n_jobs * row));
+    RC_TRY(dalloc(&hist, h.size()));
+    RC_TRY(dalloc(&tab, coef.size()));
+    RC_TRY(dalloc(&cjd, cj.size()));
+    RC_TRY(dalloc(&rjd, rj.size()));
+    HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreate(&e0));
+    HIP_TRY(hipEventCreate(&e1));
+    HIP_TRY(hipMemcpy(src, x.data(), x.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(hist, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(tab, coef.data(), coef.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(cjd, cj.data(), cj.size() * sizeof(long long), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(rjd, rj.data(), rj.size() * sizeof(sc_rs_job), hipMemcpyHostToDevice));
+    tabs.coef[0] = tab; tabs.L[0] = L; tabs.M[0] = M; tabs.Wc[0] = Wc;
+    auto launch = [&]() -> int {
+      if (copy) {
+        launch_scatter(src, dst, cjd, n_jobs, n_in, st);
+        return SC_OK;
+      }
+      return sc_rs_launch(tabs, nullptr, rjd, n_jobs, sc_rs_tiles(tabs, 0, n_out), src, dst, hist, n_jobs, st);
+    };
+    for (int i = 0; i < 3; ++i) RC_TRY(launch());
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int i = 0; i < iters; ++i) {
+      HIP_TRY(hipEventRecord(e0, st));
+      RC_TRY(launch());
+      HIP_TRY(hipEventRecord(e1, st));
+      HIP_TRY(hipEventSynchronize(e1));
+      float t = 0.f;
+      HIP_TRY(hipEventElapsedTime(&t, e0, e1));
+      ms[i] = t;
+    }
+    return SC_OK;
+  };
+  rc = run();
+  cleanup();
+  return rc;
+  SC_API_END
+}
+
 extern "C" void *sc_streams_hip_stream(sc_streams *b) { return b ? (void *)b->stream : nullptr; }
 
 extern "C" float *sc_streams_pcm(sc_streams *b, long *capacity) {
@@ -2022,6 +2215,7 @@ int push_impl(sc_streams *b, const int *stream_ids, const float *const *host, co
   }
   HIP_TRY(hipSetDevice(b->eng->device));
   RC_TRY(check_chunks(b, stream_ids, counts, n, what));
+  if (!features) RC_TRY(check_resident(b, stream_ids, host, counts, n, what));
   for (int i = 0; i < n; ++i) b->snap[stream_ids[i]] = Snap();   // (queue depth > 1) a new call supersedes the copy of the last reply
   std::vector<Chunk> chunks;
   std::vector<int> streams, has_out(n, 0);
@@ -2092,6 +2286,7 @@ extern "C" int sc_submit(sc_streams *b, const int *stream_ids, const float *cons
   }
   HIP_TRY(hipSetDevice(b->eng->device));
   RC_TRY(check_chunks(b, stream_ids, n_samples, n, "sc_submit", b->queue_depth));
+  RC_TRY(check_resident(b, stream_ids, pcm, n_samples, n, "sc_submit"));
   if (n == 0) return SC_OK;
   std::vector<Chunk> chunks;
   for (int i = 0; i < n; ++i) {

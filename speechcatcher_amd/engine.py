@@ -355,6 +355,16 @@ class StreamBatch:
         for s in range(self.S):
             self.reset(s)
 
+    def set_input_rate(self, s: int, rate: int):
+        """This lock-step engine takes 16 kHz PCM only: sample-rate conversion is part of the native engine's staging
+        step (native.NativeStreamBatch.set_input_rate, csrc/resample.hip)."""
+        if int(rate) != 16000:
+            raise NotImplementedError(f"input rate {rate}: the Python lock-step engine takes 16 kHz PCM only; use the "
+                                      "native engine (speechcatcher_amd.native.NativeStreamBatch.set_input_rate)")
+
+    def input_rate(self, s: int) -> int:
+        return 16000
+
     def _init_hyp(self, s: int):
         # create_initial_hypothesis (hypothesis.py:75-91): yseq=[sos], xpos=[0]
         self.yseq[0, s, 0, 0] = self.cfg.sos_id

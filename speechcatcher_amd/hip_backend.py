@@ -14,6 +14,25 @@ def _p(t):
     return 0 if t is None else t.data_ptr()
 
 
+def resample(x, rate, device="cuda:0"):
+    """A whole float32 signal (tensor or array) at ``rate`` -> a 16 kHz device tensor: sc_resample - zero history, flushed,
+    the device code of the stream path - on torch's current stream.  Needs no HipBackend (the CLI converts a file with it)."""
+    if not torch.cuda.is_available():
+        raise _abi.ScasrError("resample needs a ROCm GPU (torch.cuda.is_available() is False)")
+    lib = _abi.load()
+    device = torch.device(device)
+    x = torch.as_tensor(x).to(device, torch.float32).contiguous().reshape(-1)
+    n_out = int(lib.sc_resample_out_count(int(rate), x.numel(), 1))
+    if n_out < 0:
+        _abi.check(n_out, "sc_resample_out_count")
+    y = torch.empty(n_out, dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        n = int(lib.sc_resample(_p(x), x.numel(), int(rate), _p(y), n_out, torch.cuda.current_stream(device).cuda_stream))
+    if n != n_out:
+        _abi.check(int(n) if n < 0 else -1, "sc_resample")
+    return y
+
+
 class HipBackend:
     name = "hip"
 
@@ -74,6 +93,10 @@ class HipBackend:
                                      _p(w.twiddle), _p(w.mean64), _p(w.std64), mode, cfg.n_fft,
                                      cfg.hop_length, cfg.win_length, cfg.n_mels, _p(featbuf),
                                      self._stream()), "sc_logmel")
+
+    def resample(self, x, rate):
+        """a whole float32 signal at ``rate`` -> 16 kHz on the device (see ``resample``)"""
+        return resample(x, rate, self.device)
 
     def conv1(self, w, featbuf, jobs, n_jobs, max_t1, c1):
         cfg = w.cfg

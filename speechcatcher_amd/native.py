@@ -288,6 +288,18 @@ class NativeStreamBatch:
     def reset(self, s: int):
         _abi.check(self.lib.sc_reset(self.handle, int(s)), "sc_reset")
 
+    def set_input_rate(self, s: int, rate: int):
+        """Rate of the samples ``push`` / ``submit`` take for stream s (default 16000; any rate of
+        speechcatcher_amd.resample): converted to 16 kHz on the GPU in the admission's staging step.  Only on an idle
+        stream that has buffered nothing since its last reset; ``reset`` keeps the rate."""
+        try:
+            _abi.check(self.lib.sc_stream_set_input_rate(self.handle, int(s), int(rate)), "sc_stream_set_input_rate")
+        except _abi.ScasrError as e:
+            raise EngineError(str(e)) from e
+
+    def input_rate(self, s: int) -> int:
+        return int(self.lib.sc_stream_input_rate(self.handle, int(s)))
+
     def reset_all(self):
         for s in range(self.S):
             self.reset(s)

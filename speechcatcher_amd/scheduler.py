@@ -20,6 +20,7 @@ import numpy as np
 
 from .engine import StreamBatch
 from .align import FeatureClock
+from .resample import OutputClock, check_input_rate
 from .speech2text_streaming import hyps_to_results, result_token_alignment
 
 EOS_ID = 1023   # hard-coded in the reference's result assembly (speech2text_streaming.py:474,500: SURVEY A4)
@@ -68,6 +69,8 @@ class StreamScheduler:
         # reply per session and call (its return value is {session: reply}); a second one of the same session (queue
         # depth > 1, or one collected inside close() of another session) waits here for the next call
         self._stash: Dict[int, Deque[list]] = {}
+        self._slot_rate: Dict[int, int] = {}                  # input rate last set on a slot (absent: 16000)
+        self._rate: Dict[int, OutputClock] = {}               # per session: its rate and its count of 16 kHz samples
         self.queue_depth = 1
         if queue_depth > 1 and hasattr(batch, "set_queue_depth"):
             batch.set_queue_depth(queue_depth)
@@ -75,19 +78,53 @@ class StreamScheduler:
         self._next_sid = 0
 
     # ---- session lifecycle -------------------------------------------------
-    def open(self) -> int:
+    def open(self, sample_rate: int = 16000) -> int:
+        """``sample_rate``: rate of the PCM this session feeds (speechcatcher_amd.resample: 8000..48000 Hz; the C++
+        engine converts it to 16 kHz on the GPU).  A slot goes back to 16000 for a later session that does not ask."""
+        sample_rate = check_input_rate(sample_rate)
         if not self._free:
             raise ServerBusy("Server busy: all stream slots are in use")
-        slot = self._free.popleft()
+        slot = self._free[0]
         if self.reset_on_open:
             self.batch.reset(slot)
+        self._set_slot_rate(slot, sample_rate)
+        self._free.popleft()
         sid = self._next_sid
         self._next_sid += 1
         self._slot_of[sid] = slot
         self._queue[sid] = deque()
         self._clock.pop(sid, None)
         self._fed.pop(sid, None)
+        self._rate[sid] = OutputClock(sample_rate)
         return sid
+
+    def _set_slot_rate(self, slot: int, rate: int):
+        if self._slot_rate.get(slot, 16000) == rate:
+            return
+        if not hasattr(self.batch, "set_input_rate"):
+            raise NotImplementedError(f"sample rate {rate}: this batch takes 16 kHz PCM only (the native engine converts)")
+        try:
+            self.batch.set_input_rate(slot, rate)
+        except NotImplementedError:   # the Python lock-step engine: 16 kHz only
+            raise
+        except RuntimeError as e:     # e.g. a slot that is never reset (strict_reference) and has audio buffered
+            raise ValueError(f"sample rate {rate} cannot be set on this stream: {e}") from e
+        self._slot_rate[slot] = rate
+
+    def sample_rate(self, sid: int) -> int:
+        return self._rate[sid].rate
+
+    def set_sample_rate(self, sid: int, sample_rate: int):
+        """Change the rate of a session that has not fed any audio yet (the Vosk ``config`` message arrives after the
+        connection is made).  ValueError for an unsupported rate or once audio has been fed."""
+        sample_rate = check_input_rate(sample_rate)
+        clock = self._rate[sid]
+        if sample_rate == clock.rate:
+            return
+        if clock.fed:
+            raise ValueError(f"the sample rate of a session can only be set before its first audio (it is {clock.rate})")
+        self._set_slot_rate(self._slot_of[sid], sample_rate)
+        self._rate[sid] = OutputClock(sample_rate)
 
     def close(self, sid: int):
         while sid in self._in_flight:        # its chunks must be reported before the slot can be reset;
@@ -99,6 +136,7 @@ class StreamScheduler:
         self._queue.pop(sid)
         self._clock.pop(sid, None)
         self._fed.pop(sid, None)
+        self._rate.pop(sid, None)
         if self.reset_on_open:
             self.batch.reset(slot)
         self._free.append(slot)
@@ -109,10 +147,11 @@ class StreamScheduler:
 
     # ---- data path -----------------------------------------------------------
     def feed(self, sid: int, pcm: np.ndarray, is_final: bool = False, finalize_all: bool = False):
-        """Queue one chunk of a session (float PCM in +-1, like the reference API)."""
+        """Queue one chunk of a session (float PCM in +-1, like the reference API) at the session's sample rate."""
         self._queue[sid].append((np.asarray(pcm, dtype=np.float32), bool(is_final), bool(finalize_all)))
+        n16 = self._rate[sid].call(int(np.shape(pcm)[0]), bool(is_final))   # the call in 16 kHz samples: the engine's clock
         if self.align_final:
-            self._fed.setdefault(sid, deque()).append((int(np.shape(pcm)[0]), bool(is_final)))
+            self._fed.setdefault(sid, deque()).append((n16, bool(is_final)))
 
     def pending(self) -> int:
         return sum(1 for sid, q in self._queue.items() if q or sid in self._in_flight or sid in self._stash)

@@ -201,18 +201,20 @@ class ServerLoop:
             else:
                 try:
                     cfg = json.loads(message).get("config", {})
-                    ses.vosk_sample_rate = int(cfg.get("sample_rate", ses.vosk_sample_rate))
+                    rate = cfg.get("sample_rate", ses.vosk_sample_rate)
                 except (ValueError, AttributeError):
-                    pass
+                    return vosk_partial("")
+                # honoured for every rate the engine converts (8000..48000 Hz: speechcatcher_amd.resample), before the
+                # session's first audio; ValueError otherwise - this client's error reply (step)
+                self.sch.set_sample_rate(ses.sid, rate)
+                ses.vosk_sample_rate = int(rate)
                 return vosk_partial("")
         elif isinstance(message, np.ndarray):
             if message.dtype != np.int16:
                 raise TypeError("audio arrays must be int16 PCM")
             data = message
         else:
-            if ses.vosk_sample_rate != 16000:
-                raise NotImplementedError("transcode to 16 kHz s16le before submitting (ffmpeg path is out of scope)")
-            data = np.frombuffer(message, dtype="<i2")
+            data = np.frombuffer(message, dtype="<i2")      # s16le at the session's sample rate
         if data.size == 0:
             return vosk_partial("") if ses.vosk else ""
         finalize = ses.endpointer.decide() or forced

@@ -255,7 +255,8 @@ class Speech2TextStreaming:
     def __init__(self, model_dir: Union[str, Path], beam_size: int = 5, ctc_weight: float = 0.3,
                  device: str = "cuda", dtype: str = "float32", use_bbd: bool = False,
                  max_frames: int = 4800, max_tokens: int = 1024, result_format: str = "native",
-                 max_chunk_samples: int = 480000, strict_reference: bool = True, _shared=None):
+                 max_chunk_samples: int = 480000, strict_reference: bool = True, _shared=None,
+                 input_sample_rate: int = 16000):
         """``max_chunk_samples``: longest single call (the reference accepts any length per call and its frame
         arithmetic depends on the call boundaries, so a long call cannot be split internally; the scratch for one
         call is sized from this: 30 s by default, ~80 MB).  ``strict_reference``: reset() behaves like the
@@ -265,7 +266,12 @@ class Speech2TextStreaming:
         sum / softmax / LayerNorm / score in fp32 (BASELINE configs[4]; `load_model(fp16=True)` stays fp32 with the
         reference's warning).  ``dtype="split16"`` (no counterpart in the reference): fp32 results - every hypothesis of
         the reference fixtures at the fp32 tolerance - with the feed-forward, encoder-projection and tiled-GEMM product
-        sums evaluated on the fp16 matrix pipe from fp16 hi + lo splits of both operands."""
+        sums evaluated on the fp16 matrix pipe from fp16 hi + lo splits of both operands.
+        ``input_sample_rate``: rate of the 1-D PCM ``__call__`` takes (8000..48000 Hz, speechcatcher_amd.resample);
+        converted to 16 kHz on the GPU, call by call, with results that do not depend on how the audio is cut into calls
+        beyond what they do at 16 kHz.  ``max_chunk_samples`` then bounds a call's samples at either rate."""
+        from .resample import check_input_rate
+        self.input_sample_rate = check_input_rate(input_sample_rate)
         self.model_dir = Path(model_dir)
         self.beam_size = beam_size
         self.ctc_weight = ctc_weight
@@ -304,6 +310,8 @@ class Speech2TextStreaming:
         except EngineError as e:
             raise _abi.ScasrError(str(e)) from e
         self.stream = 0
+        if self.input_sample_rate != 16000:
+            self.batch.set_input_rate(self.stream, self.input_sample_rate)   # reset() keeps it
         self.win_length = self.cfg.win_length
         self.hop_length = self.cfg.hop_length
         self.beam_search = _BeamSearchView(self)
@@ -313,6 +321,7 @@ class Speech2TextStreaming:
     def reset(self):
         self.batch.reset(self.stream)
         self._clock = None
+        self._out_clock = None
         self.beam_state = None
         self.processed_frames = 0
 
@@ -332,7 +341,11 @@ class Speech2TextStreaming:
             if getattr(self, "_clock", None) is None:
                 from .align import FeatureClock
                 self._clock = FeatureClock(self.cfg.win_length, self.cfg.hop_length)
-            self._clock.call(speech.shape[0], is_final)   # feature frame -> sample, for token_alignment
+            if getattr(self, "_out_clock", None) is None:
+                from .resample import OutputClock
+                self._out_clock = OutputClock(self.input_sample_rate)
+            # feature frame -> sample, for token_alignment (in the 16 kHz samples the call appended)
+            self._clock.call(self._out_clock.call(speech.shape[0], is_final), is_final)
             if not out[self.stream]:
                 return []
         elif speech.ndim == 2:
