@@ -430,6 +430,29 @@ long sc_resample(const float *x_dev, long n_in, int rate, float *y_dev, long y_c
  * read and left). */
 int sc_stage_bench(int rate, int n_jobs, int n_in, int iters, double *ms);
 
+/* ---- energy curve of a long recording (segment.hip) ----------------------------------------
+ * File mode cuts a recording of more than 60 s at low-energy points (simple_endpointing.py:81-145); the curve the cut
+ * search reads - summed log mel filterbank energies, Gaussian-smoothed, sign flipped - can be computed on the GPU
+ * (opt-in: `--segmentation gpu`, segmenter.smoothed_negative_energy(backend="gpu")).  For int16 x[0..n) at 16 kHz:
+ *   s[0] = x[0], s[i] = x[i] - 0.97 x[i-1]                      (on the int16 values, not / 32768)
+ *   F = 1 if n <= 400 else 1 + ceil((n - 400) / 160)            frames of 400 samples every 160, zeros behind the end
+ *   P_f[k] = |rfft_512(frame f, zero padded)[k]|^2 / 512, k = 0..256;  E_f[j] = sum_k P_f[k] fb[j][k], j = 0..25
+ *   E_f[j] == 0 -> 2.220446049250313e-16;  p[f] = (sum_j log E_f[j]) / 10
+ *   y[f] = - sum_{d=-80..80} w[d] p[refl(f + d)],  w[d] = exp(-d^2 / 800) / sum,  refl(i): i mod 2F, then 2F-1-i if >= F
+ * Float64 throughout, every sum in one order (k, j, d ascending), no atomics: the same input gives the same bytes. */
+/* frames of n_samples samples (F above).  Pure host; SC_ERR_ARG (< 0) for n_samples < 1. */
+long sc_segment_frame_count(long n_samples);
+/* tables the library uses: fb [26][257] (the triangular mel filters over the integer bin edges
+ * floor(513 mel2hz(m_i) / 16000), 0..8000 Hz) and gauss [161] (w above).  Pure host; either may be NULL. */
+int sc_segment_design(double *fb, double *gauss);
+/* kernel level: pcm_dev [n_samples] int16 and out_dev [out_cap] doubles are device pointers; smoothed 0 writes p[f],
+ * 1 writes y[f]; returns F (SC_ERR_ARG, before anything is launched, for a null pointer, n_samples < 1 or F > out_cap).
+ * One launch (smoothed 0) or two on `stream`.  The tables are uploaded on first use and kept per device for the life of
+ * the process; with smoothed = 1 the raw curve goes through a workspace of F doubles that is allocated on first use, grows
+ * geometrically with the requests and is kept per device as well (so smoothed calls on one device belong on one stream;
+ * growing it waits for the device).  No other allocation. */
+long sc_segment_energy(const int16_t *pcm_dev, long n_samples, int smoothed, double *out_dev, long out_cap, void *stream);
+
 /* ---- encoder --------------------------------------------------------------- */
 
 /* first Conv2d(1->d,3,stride 2)+ReLU (subsampling.py:87-93), channels-last out.

@@ -44,9 +44,10 @@ def to_16k(raw, rate, device="cuda:0"):
 
 
 def recognize_file(speech2text, media_path, output_file="", quiet=True, progress=True, num_slots=1, chunk_length=8192,
-                   token_alignment=False):
+                   token_alignment=False, segmentation="host"):
     """speechcatcher.py:358-400: recording -> text + paragraphs JSON next to the input.  ``token_alignment``: the
-    paragraphs also get token_start / token_end (seconds) and token_conf from a CTC forced alignment of each segment."""
+    paragraphs also get token_start / token_end (seconds) and token_conf from a CTC forced alignment of each segment.
+    ``segmentation``: "host" or "gpu" - where the energy curve for the cut points of a recording over 60 s is computed."""
     from .config import SearchConfig
     from .native import NativeStreamBatch
     from .segmenter import recognize_recording
@@ -63,7 +64,8 @@ def recognize_file(speech2text, media_path, output_file="", quiet=True, progress
                               max_chunk_samples=max(chunk_length, 32768), engine=speech2text.batch.engine)
     # finalize_all only with the very last chunk of the recording, like the reference CLI (speechcatcher.py:586)
     text, info = recognize_recording(batch, raw, rate, chunk_length=chunk_length, token_list=speech2text.token_list,
-                                     reference_finalize=True, token_alignment=token_alignment)
+                                     reference_finalize=True, token_alignment=token_alignment,
+                                     segmentation=segmentation)
     out_txt, out_json = (output_file or media_path) + ".txt", (output_file or media_path) + ".json"
     with open(out_txt, "w") as f:
         f.write(text)
@@ -103,6 +105,9 @@ def make_parser():
     p.add_argument("--token-alignment", dest="token_alignment", action="store_true",
                    help="add token_start / token_end / token_conf to the .json: token times at 40 ms resolution and a per-token "
                         "confidence from a CTC forced alignment on the GPU (token_timestamps stay as they are)")
+    p.add_argument("--segmentation", dest="segmentation", choices=["host", "gpu"], default="host",
+                   help="where the energy curve for the cut points of a recording over 60 s is computed: 'host' (numpy, the "
+                        "default) or 'gpu' (float64 kernels; the same cuts, without the host pass over the whole recording)")
     p.add_argument("inputfile", nargs="?", default="", help="input recording (mono 16-bit WAV, 16 kHz or 8000..48000 Hz)")
     return p
 
@@ -127,7 +132,7 @@ def main(argv=None):
                              use_bbd=not args.disable_bbd)
     recognize_file(speech2text, args.inputfile, quiet=args.quiet or not args.no_progress, progress=not args.no_progress,
                    num_slots=1 if args.num_processes < 1 else args.num_processes, chunk_length=args.chunk_length,
-                   token_alignment=args.token_alignment)
+                   token_alignment=args.token_alignment, segmentation=args.segmentation)
     return 0
 
 

@@ -222,6 +222,10 @@ _SIGS = {
     "sc_stream_set_input_rate": (C.c_int, [vp, C.c_int, C.c_int]),
     "sc_stream_input_rate": (C.c_int, [vp, C.c_int]),
     "sc_stage_bench": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_double_p]),
+    # energy curve of a long recording (segment.hip)
+    "sc_segment_frame_count": (C.c_long, [C.c_long]),
+    "sc_segment_design": (C.c_int, [c_double_p, c_double_p]),
+    "sc_segment_energy": (C.c_long, [vp, C.c_long, C.c_int, vp, C.c_long, vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())

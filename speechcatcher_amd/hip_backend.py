@@ -4,6 +4,7 @@ device memory and of the HIP stream; every pointer handed to the library is a
 raw device address."""
 import ctypes as C
 import os
+import warnings
 
 import torch
 
@@ -31,6 +32,34 @@ def resample(x, rate, device="cuda:0"):
     if n != n_out:
         _abi.check(int(n) if n < 0 else -1, "sc_resample")
     return y
+
+
+def segment_energy(raw_int16, device="cuda:0", smoothed=True):
+    """An int16 recording at 16 kHz (numpy array or torch tensor) -> the float64 numpy array of its F curve values:
+    sc_segment_energy on torch's current stream - one upload, two launches (one with ``smoothed=False``: the summed log
+    filterbank energies / 10 before the Gaussian and the sign flip), one read-back.  Needs no HipBackend
+    (segmenter.smoothed_negative_energy(backend="gpu") calls it)."""
+    if not torch.cuda.is_available():
+        raise _abi.ScasrError("segment_energy needs a ROCm GPU (torch.cuda.is_available() is False)")
+    lib = _abi.load()
+    device = torch.device(device)
+    with warnings.catch_warnings():   # a read-only array (np.frombuffer of a WAV) is only read here
+        warnings.simplefilter("ignore", UserWarning)
+        x = torch.as_tensor(raw_int16)
+    if x.dtype != torch.int16:
+        raise TypeError(f"segment_energy takes int16 samples, got {x.dtype}")
+    x = x.reshape(-1).contiguous()
+    n_frames = int(lib.sc_segment_frame_count(x.numel()))
+    if n_frames < 0:
+        _abi.check(n_frames, "sc_segment_frame_count")
+    x = x.to(device)
+    out = torch.empty(n_frames, dtype=torch.float64, device=device)
+    with torch.cuda.device(device):
+        n = int(lib.sc_segment_energy(_p(x), x.numel(), 1 if smoothed else 0, _p(out), n_frames,
+                                      torch.cuda.current_stream(device).cuda_stream))
+    if n != n_frames:
+        _abi.check(n if n < 0 else -1, "sc_segment_energy")
+    return out.cpu().numpy()
 
 
 class HipBackend:
@@ -97,6 +126,10 @@ class HipBackend:
     def resample(self, x, rate):
         """a whole float32 signal at ``rate`` -> 16 kHz on the device (see ``resample``)"""
         return resample(x, rate, self.device)
+
+    def segment_energy(self, raw_int16, smoothed=True):
+        """the energy curve of an int16 recording at 16 kHz as float64 numpy (see ``segment_energy``)"""
+        return segment_energy(raw_int16, self.device, smoothed)
 
     def conv1(self, w, featbuf, jobs, n_jobs, max_t1, c1):
         cfg = w.cfg

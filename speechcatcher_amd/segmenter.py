@@ -17,6 +17,8 @@ streams of one ``StreamBatch`` on the GPU instead of forked CPU processes.
   rectangular frames, 512-point power spectrum / NFFT, 26 triangular mel filters
   0..fs/2, log.  PARITY UNPINNED for this function (no fixture can be generated
   without the package); the cut search downstream of it is pinned.
+* ``smoothed_negative_energy(backend="gpu")`` / ``segmentation="gpu"``: the same curve from the float64 kernels of
+  csrc/segment.hip instead of the host pass (opt-in; DESIGN.md 8c, contract in tests/segment_ref.py).
 * ``plan_segments`` mirrors the chunk-aligned finalize positions of
   speechcatcher.py:430-446; ``recognize_recording`` is the file-level loop.
 """
@@ -63,9 +65,27 @@ def log_fbank_energy(data: np.ndarray, samplerate: int = 16000, winlen: float = 
     return np.log(feat)
 
 
-def smoothed_negative_energy(data: np.ndarray, samplerate: int = 16000) -> np.ndarray:
+SEGMENTATION_BACKENDS = ("host", "gpu")
+
+
+def _check_segmentation(backend: str) -> None:
+    if backend not in SEGMENTATION_BACKENDS:
+        raise ValueError(f"unknown segmentation backend {backend!r}: one of {SEGMENTATION_BACKENDS}")
+
+
+def smoothed_negative_energy(data: np.ndarray, samplerate: int = 16000, backend: str = "host") -> np.ndarray:
     """simple_endpointing.py:81-84: summed log fbank / 10, Gaussian sigma = 20 frames, sign flipped
-    (pauses become maxima)."""
+    (pauses become maxima).  ``backend="gpu"``: the same curve in float64 from the two kernels of csrc/segment.hip
+    (hip_backend.segment_energy) - int16 samples at 16 kHz only."""
+    _check_segmentation(backend)
+    if backend == "gpu":
+        if samplerate != 16000:
+            raise ValueError(f"the GPU energy curve is 16 kHz only, got {samplerate} Hz (convert first: hip_backend.resample)")
+        data = np.asarray(data)
+        if data.dtype != np.int16:
+            raise ValueError(f"the GPU energy curve takes int16 samples, got {data.dtype}")
+        from .hip_backend import segment_energy
+        return segment_energy(data, smoothed=True)
     from scipy.ndimage import gaussian_filter1d
     power = log_fbank_energy(data, samplerate).sum(axis=-1) / 10.0
     return gaussian_filter1d(power, sigma=20) * -1.0
@@ -120,9 +140,12 @@ class CutSearch:
 
 def segment_speech(data: np.ndarray, samplerate: int = 16000, average_segment_length: float = 60.0,
                    max_segment_len_sec: float = 180, beam_size: int = 10, step: int = 10,
-                   len_reward_weight: float = 12.0, energy_weight: float = 1.0) -> List[Tuple[int, int]]:
-    """simple_endpointing.py:81-145: (start, end) in 10 ms frames; no segment longer than max_segment_len_sec."""
-    energy = smoothed_negative_energy(data, samplerate)
+                   len_reward_weight: float = 12.0, energy_weight: float = 1.0,
+                   segmentation: str = "host") -> List[Tuple[int, int]]:
+    """simple_endpointing.py:81-145: (start, end) in 10 ms frames; no segment longer than max_segment_len_sec.
+    ``segmentation``: where the energy curve is computed ("host", or "gpu": smoothed_negative_energy)."""
+    _check_segmentation(segmentation)
+    energy = smoothed_negative_energy(data, samplerate, backend=segmentation)
     search = CutSearch(beam_size=beam_size, ideal_segment_len=int(average_segment_length * 100), step=step,
                        len_reward_weight=len_reward_weight, energy_weight=energy_weight)
     return constrain_segments(search.search(energy, len(energy)), max_segment_len_sec)
@@ -219,12 +242,15 @@ def merge_paragraphs(segments: List[dict]) -> Tuple[str, List[dict]]:
 
 def recognize_recording_segments(batch, raw_speech_data: np.ndarray, rate: int = 16000, chunk_length: int = 8192,
                                  token_list: Optional[List[str]] = None, reference_finalize: bool = False,
-                                 average_segment_length: float = 60.0, token_alignment: bool = False):
+                                 average_segment_length: float = 60.0, token_alignment: bool = False,
+                                 segmentation: str = "host"):
     """The segment loop of ``recognize`` (speechcatcher.py:414-497): int16 recording -> chunk-aligned sample
     ranges and the raw per-segment results of ``recognize_segments`` (before paragraph merging)."""
     assert rate == 16000
+    _check_segmentation(segmentation)
     speech = np.asarray(raw_speech_data).astype(np.float32) / 32768.0
-    segments = (segment_speech(raw_speech_data, rate, average_segment_length=average_segment_length)
+    segments = (segment_speech(raw_speech_data, rate, average_segment_length=average_segment_length,
+                               segmentation=segmentation)
                 if len(speech) > 60.0 * rate else [])
     ranges = plan_segments(len(speech), rate, segments, chunk_length)
     res = recognize_segments(batch, speech, ranges, chunk_length=chunk_length, token_list=token_list,
@@ -234,16 +260,18 @@ def recognize_recording_segments(batch, raw_speech_data: np.ndarray, rate: int =
 
 def recognize_recording(batch, raw_speech_data: np.ndarray, rate: int = 16000, chunk_length: int = 8192,
                         token_list: Optional[List[str]] = None, reference_finalize: bool = False,
-                        average_segment_length: float = 60.0, token_alignment: bool = False) -> Tuple[str, List[dict]]:
+                        average_segment_length: float = 60.0, token_alignment: bool = False,
+                        segmentation: str = "host") -> Tuple[str, List[dict]]:
     """int16 recording -> (text, per-paragraph info).  Native-decoder input scaling
     /32768 in fp32 (speechcatcher.py:421); recordings over a minute are segmented;
     the segments run as parallel streams of ``batch`` (one slot = the reference CLI with one worker:
     serial segments on one model); paragraphs are merged like the CLI does.
     ``reference_finalize``: pass finalize_all only with the last chunk of the recording, as the
     reference CLI does.  ``token_alignment``: the paragraphs also carry ``token_start`` / ``token_end`` /
-    ``token_conf`` (CTC forced alignment, next to ``token_timestamps``)."""
+    ``token_conf`` (CTC forced alignment, next to ``token_timestamps``).  ``segmentation="gpu"``: the energy curve the
+    cut search reads comes from the GPU (csrc/segment.hip) instead of the host pass."""
     ranges, res = recognize_recording_segments(batch, raw_speech_data, rate, chunk_length, token_list,
-                                               reference_finalize, average_segment_length, token_alignment)
+                                               reference_finalize, average_segment_length, token_alignment, segmentation)
     segs = [{"start": lo / rate, "end": hi / rate, "text": r["text"], "tokens": r["tokens"],
              "token_timestamps": r["token_timestamps"], **{k: r[k] for k in ALIGNMENT_KEYS if k in r}}
             for (lo, hi), r in zip(ranges, res)]
