@@ -229,9 +229,10 @@ __global__ __launch_bounds__(256 * HPW, (UNR <= 4 && WM <= 10) ? (DK > 32 ? 2 : 
     for (int h = 0; h < WM; ++h) slp[h] = anc0[(long)(live0 ? pt : 0) * W + min(h, nh - 1)];
   }
   int U0 = 0;   // HPW > 1, SELF: entries of the row list of the first 512 positions
+  int Ucur = 0; // ... and of the list that is being walked (rowfn below)
   auto early_list = [&]() {
     if constexpr (HPW > 1 && SELF)
-      U0 = mattn_build_rows<WM, true, NTH, PCS>(srows, swtot, ANC(cur, s), 0, L - 1, W, nh, tid, lane, tid >> 6, slp);
+      U0 = Ucur = mattn_build_rows<WM, true, NTH, PCS>(srows, swtot, ANC(cur, s), 0, L - 1, W, nh, tid, lane, tid >> 6, slp);
   };
   float touch = 0.f, kvtouch = 0.f;
   // (loads return in issue order: the fragments are requested right BEHIND the first batch of partial sums, which
@@ -431,8 +432,10 @@ __global__ __launch_bounds__(256 * HPW, (UNR <= 4 && WM <= 10) ? (DK > 32 ? 2 : 
   MBatch<DK, NTW> kvb0;                                  // HPW > 1, SELF: the wave's first batch, requested ahead (below)
   const long skv0 = ((long)s * sb.n_layers + p.li) * sb.kv_rows * 2 * D + head * DK;   // element offset (fp32 or fp16 pool)
   auto rowfn = [&](int idx, long &ke, unsigned &hm) {   // HPW > 1, SELF: entry idx of the shared row list as a K|V row
-    const int e = srows[min(idx, PCS * W - 1)];          // entries >= U are zero: no hypothesis
-    hm = (unsigned)e >> 16;
+    // entries >= U: no hypothesis, and the LAST row of the list for the padding's loads - a masked key still enters the
+    // P.V product (0 * v), so it must be a row that holds numbers; pool row 0 (what a zero entry names) need not be one
+    const int e = srows[min(idx, max(Ucur - 1, 0))];
+    hm = idx < Ucur ? (unsigned)e >> 16 : 0u;
     ke = skv0 + (long)(e & 0xFFFF) * 2 * D;
   };
   // ------------------------------------------------------------------ projection of the head's columns
@@ -590,6 +593,7 @@ __global__ __launch_bounds__(256 * HPW, (UNR <= 4 && WM <= 10) ? (DK > 32 ? 2 : 
         __syncthreads();  // the list is rebuilt for the next positions
         const int U = mattn_build_rows<WM, false, NTH, PCS>(srows, swtot, anc, c0, Lc, W, nh, tid, lane, tid >> 6, slp);
         urows += U;
+        Ucur = U;
         mattn_walk<DK, NTW, KVH>(st, qs, sb.skv, D, cdiv(U, 16), wave, lane, rowfn);
       }
     } else
@@ -601,8 +605,8 @@ __global__ __launch_bounds__(256 * HPW, (UNR <= 4 && WM <= 10) ? (DK > 32 ? 2 : 
       if (c0 + PCH < Lc) U = mattn_build_rows<WM, false, 256, PCH>(rows, wtot, anc, c0 + PCH, Lc, W, nh, gt, lane, wave, slp, U, 0);
       urows += U;
       mattn_walk<DK, NTW, KVH>(st, qs, sb.skv, D, cdiv(U, 16), wave, lane, [&](int idx, long &ke, unsigned &hm) {
-        const int e = rows[min(idx, 2 * PCH * W - 1)];   // entries >= U are zero: no hypothesis
-        hm = (unsigned)e >> 16;
+        const int e = rows[min(idx, max(U - 1, 0))];   // entries >= U: no hypothesis, the list's last row (see rowfn above)
+        hm = idx < U ? (unsigned)e >> 16 : 0u;
         ke = skv0 + (long)(e & 0xFFFF) * 2 * D;
       });
       if (c0 + 2 * PCH < Lc) __syncthreads();  // rows is rebuilt for the next positions

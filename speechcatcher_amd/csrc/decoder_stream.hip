@@ -592,9 +592,12 @@ __global__ __launch_bounds__(512, 2) void dec_layer_stream_kernel(DecStreamArgs 
     const int *anc = ANC(cur, s);
     const int Lc = L - 1;   // cached positions; the new token's own row is the fifth partial state
     int urows = nh + U0;
+    int Ucur = U0;   // entries of the list that is being walked
     auto rowfn = [&](int idx, long &ke, unsigned &hm) {
-      const int e = srows[min(idx, PCS * W - 1)];   // entries >= U are zero: no hypothesis
-      hm = (unsigned)e >> 16;
+      // entries >= U: no hypothesis, and the LAST row of the list for the padding's loads - a masked key still enters the
+      // P.V product (0 * v), so it must be a row that holds numbers; pool row 0 (what a zero entry names) need not be one
+      const int e = srows[min(idx, max(Ucur - 1, 0))];
+      hm = idx < Ucur ? (unsigned)e >> 16 : 0u;
       ke = skv0 + (long)(e & 0xFFFF) * 2 * D;
     };
     walk4(sb.skv, cdiv(U0, 16), rowfn);
@@ -602,6 +605,7 @@ __global__ __launch_bounds__(512, 2) void dec_layer_stream_kernel(DecStreamArgs 
       __syncthreads();   // the list is rebuilt for the next positions
       const int U = mattn_build_rows<WM, false, NTH, PCS>(srows, swtot, anc, c0, Lc, W, nh, tid, lane, wave, slp);
       urows += U;
+      Ucur = U;
       walk4(sb.skv, cdiv(U, 16), rowfn);
     }
     if (sb.stat_rows && tid == 0) atomicAdd(&sb.stat_rows[2], (unsigned long long)urows);

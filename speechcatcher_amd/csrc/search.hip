@@ -202,8 +202,10 @@ __global__ __launch_bounds__(256, (UNR <= 4 && WM <= 10 && DK <= 32) ? 4 : 1) vo
       const int U = mattn_build_rows<WM>(rows, wtot, anc, c0, Lc, W, nh, tid, lane, wave, nopre);   // (attn.h)
       urows += U;
       mattn_walk<DK, NTW, KVH>(st, qs, sb.skv, d, cdiv(U, 16), wave, lane, [&](int idx, long &ke, unsigned &hm) {
-        const int e = rows[min(idx, PCH * W - 1)];   // entries >= U are zero: no hypothesis
-        hm = (unsigned)e >> 16;
+        // entries >= U: no hypothesis, and the LAST row of the list for the padding's loads - a masked key still
+        // enters the P.V product (0 * v), so it must be a row that holds numbers; pool row 0 need not be one
+        const int e = rows[min(idx, max(U - 1, 0))];
+        hm = idx < U ? (unsigned)e >> 16 : 0u;
         ke = skv0 + (long)(e & 0xFFFF) * 2 * d;
       });
       if (ch + 1 < nchunk) __syncthreads();  // rows is rebuilt by the next chunk

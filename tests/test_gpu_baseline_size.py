@@ -286,7 +286,9 @@ def test_stream_resident_layers_give_the_bits_of_the_head_parallel_forms(monkeyp
         sb = make_batch("XL", 1234, "meanstd", beam, False, backend="native", n_streams=S, **kw)
         _feed(sb, audio, n)
         o = sb.hypotheses_arrays(list(range(S)))
-        by_kernel = sb.take_xattn_rows_by_kernel()   # cross-attention rows read by [flash, head-parallel, stream-resident] launches
+        # cross-attention rows read / distinct self-attention rows walked by [flash, head-parallel, stream-resident] launches
+        attn = sb.take_attn_counters()
+        by_kernel, self_rows = attn["cross_rows"], attn["self_distinct_rows"]
         # which launches a decode step is made of: one more chunk step (the last chunk again) without graph replay, every
         # launch counted by kind (scasr.h: SC_PROF_*; a captured launch is not counted, hence not the steps above)
         NK = 13
@@ -302,6 +304,7 @@ def test_stream_resident_layers_give_the_bits_of_the_head_parallel_forms(monkeyp
         counts = (form, split, by_kernel, n_reduce, n_ffn, n_cross, n_stream)
         # the stream-resident kernel ran exactly when it was asked for
         assert (by_kernel[2] > 0) if form == "1" else (by_kernel[2] == 0), counts
+        assert (self_rows[2] > 0) if form == "1" else (self_rows[2] == 0 and self_rows[1] > 0), (counts, self_rows)
         assert (n_stream > 0 and n_cross == 0) if form == "1" else (n_stream == 0 and n_cross > 0), counts
         assert n_ffn == n_stream + n_cross, counts     # one feed-forward launch per layer and step in either form
         if form == "0":
