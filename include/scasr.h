@@ -388,6 +388,42 @@ size_t sc_ctc_align_ws_bytes(int T);
  * `stream`: per-row logsumexp, then one wave per job. */
 int sc_ctc_align(const sc_ctc_align_job *jobs, int n_jobs, int max_T, int max_L, void *stream);
 
+/* ---- CTC speech activity (activity.hip) ----------------------------------------------------
+ * The blank posterior of a CTC row is the acoustic "nothing is being said here" signal.  For a row x[0..V) of an fp32
+ * table, promoted to float64:
+ *   m = max_v x[v];  lse = m + log(sum_v exp(x[v] - m));  p_blank = exp(x[blank] - lse)
+ * (-inf entries contribute 0; a row that holds a NaN or +inf, or nothing but -inf, is a BAD frame: p_blank = NaN).  A frame
+ * is SILENCE iff it is bad or p_blank > thr, else SPEECH.  A per-row constant does not enter, so raw-logit rows and rows the
+ * search has log-softmaxed in place give the same posteriors up to rounding.  The state of a stream is six int32 over the
+ * frames scanned so far in its utterance, numbered in the order they are scanned: */
+#define SC_ACT_N_FRAMES 0
+#define SC_ACT_N_SPEECH 1
+#define SC_ACT_N_BAD 2
+#define SC_ACT_FIRST_SPEECH 3  /* -1: none */
+#define SC_ACT_LAST_SPEECH 4   /* -1: none */
+#define SC_ACT_TRAIL_SILENCE 5 /* n_frames - 1 - last_speech, or n_frames when there was no speech */
+typedef struct sc_activity_t {
+  int32_t n_frames, n_speech, n_bad, first_speech, last_speech, trail_silence;
+} sc_activity_t;
+typedef struct sc_ctc_activity_job {
+  const float *table;   /* row t of the table at table + t * stride, V floats (device) */
+  int32_t *state;       /* [6] SC_ACT_*: read (unless restart), advanced over the span, written back (device) */
+  double *track;        /* p_blank of row t -> track[t] for t in [t0, t1) (device; NULL: not kept) */
+  int32_t *state_after; /* [6] second copy of the new state, e.g. in host-mapped memory (NULL: none) */
+  int64_t stride;       /* floats between two rows */
+  double thr;
+  int32_t V, blank, t0, t1;
+  int32_t restart;      /* != 0: the stored state is ignored, the span starts an utterance (0, 0, 0, -1, -1, 0) */
+  int32_t reserved;
+} sc_ctc_activity_job;
+#define SC_ACTIVITY_MAX_JOBS 65535
+/* jobs: device table of n_jobs entries.  ONE launch on `stream`, one workgroup per job: float64 sums in one fixed order, no
+ * atomics, one writer per output; an empty span (t0 == t1) rewrites the state unchanged.  n_jobs < 0, a null table with
+ * n_jobs > 0 or n_jobs > SC_ACTIVITY_MAX_JOBS: SC_ERR_ARG before anything is launched.  A job whose own fields are
+ * malformed (null table / state, V < 1, blank outside [0, V), t0 < 0, t1 < t0) writes nothing.  Two jobs of one call
+ * must not share a state or overlap in a track. */
+int sc_ctc_activity(const sc_ctc_activity_job *jobs, int n_jobs, void *stream);
+
 /* ---- frontend ------------------------------------------------------------ */
 
 /* STFTFrontend.forward (model/frontend/stft_frontend.py:87-154) fused with the
@@ -768,6 +804,24 @@ int sc_streams_read_enc(sc_streams *streams, int stream, float *host, int max_fr
 /* test aid: the CTC rows [0, min(T, max_rows)) of a stream's table as sc_align_hyps sees them (T: the frames of the
  * reported hypotheses' decode block) -> host [rows][vocab]; returns the number of rows */
 int sc_streams_read_ctc(sc_streams *streams, int stream, float *host, int max_rows);
+/* Acoustic activity per stream (off by default).  on != 0: every admission group issues ONE sc_ctc_activity
+ * launch right behind its CTC projection, on the encoder stream, over the CTC rows [c0, t1) each of its chunks projects
+ * (raw logits: the search's in-place log-softmax of a first block runs behind the group's event); frames are silence
+ * iff bad or p_blank > blank_threshold (in (0, 1)).  The per-stream state and the S x max_frames track of doubles live
+ * on the device and are allocated when the option is first switched on; switched off, no path does any new work.
+ * SC_ERR_ARG while any chunk is outstanding.  Switching it on (again) restarts every stream's state.
+ * strict_reference: after sc_reset the frames below the stale table's extent are not re-projected (scorers.py:342-350)
+ * and therefore not scanned - n_frames counts the frames behind them, the track keeps the stale utterance's values
+ * there. */
+int sc_streams_set_activity(sc_streams *streams, int on, double blank_threshold);
+/* state of the stream's last REPORTED chunk - the chunk whose hypotheses sc_get_hyps returns - over every frame the
+ * encoder had emitted for the utterance when that chunk was admitted (a chunk that emits no frame carries its
+ * predecessor's state), however many chunks are queued behind it; (0, 0, 0, -1, -1, 0) after sc_reset.  Waits for the
+ * encoder group of that chunk if it is still in flight.  SC_ERR_ARG when the option is off. */
+int sc_stream_activity(sc_streams *streams, int stream, sc_activity_t *out /*HOST*/);
+/* the p_blank track of the frames that state covers -> host [min(frames, max_frames)] doubles (index = row of the CTC
+ * table); returns the number written */
+int sc_streams_read_activity(sc_streams *streams, int stream, double *host, int max_frames);
 
 #ifdef __cplusplus
 }

@@ -79,6 +79,20 @@ class AlignJob(C.Structure):
                 + [("stride", C.c_int64)] + [(n, C.c_int32) for n in ("T", "L", "V", "blank")])
 
 
+class ActivityJob(C.Structure):
+    """sc_ctc_activity_job (include/scasr.h): one span of CTC rows scanned by sc_ctc_activity"""
+    _fields_ = ([(n, vp) for n in ("table", "state", "track", "state_after")] + [("stride", C.c_int64), ("thr", C.c_double)]
+                + [(n, C.c_int32) for n in ("V", "blank", "t0", "t1", "restart", "reserved")])
+
+
+class Activity(C.Structure):
+    """sc_activity_t (include/scasr.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("n_frames", "n_speech", "n_bad", "first_speech", "last_speech", "trail_silence")]
+
+
+ACTIVITY_FIELDS = tuple(n for n, _ in Activity._fields_)
+ACTIVITY_MAX_JOBS = 65535
+
 # SC_ALIGN_* of include/scasr.h
 ALIGN_OK, ALIGN_INFEASIBLE, ALIGN_NONFINITE, ALIGN_BAD_INPUT = 0, 1, 2, 3
 ALIGN_MAX_L = 1023
@@ -215,6 +229,11 @@ _SIGS = {
                                 c_int_p, c_int_p]),
     "sc_align_tokens": (C.c_int, [vp, C.c_int, c_int_p, C.c_int, c_int_p, c_int_p, c_float_p, c_double_p, c_int_p]),
     "sc_streams_read_ctc": (C.c_int, [vp, C.c_int, vp, C.c_int]),
+    # CTC speech activity (activity.hip, streams.hip)
+    "sc_ctc_activity": (C.c_int, [vp, C.c_int, vp]),
+    "sc_streams_set_activity": (C.c_int, [vp, C.c_int, C.c_double]),
+    "sc_stream_activity": (C.c_int, [vp, C.c_int, C.POINTER(Activity)]),
+    "sc_streams_read_activity": (C.c_int, [vp, C.c_int, vp, C.c_int]),
     # sample-rate conversion (resample.hip, streams.hip)
     "sc_resample_design": (C.c_int, [C.c_int, c_int_p, c_int_p, c_int_p, c_float_p]),
     "sc_resample_out_count": (C.c_long, [C.c_int, C.c_long, C.c_int]),

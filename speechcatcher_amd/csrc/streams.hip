@@ -137,6 +137,16 @@ struct Run {
   long job = 0;   // Job::seq of the chunk the block belongs to
 };
 
+// Acoustic activity (sc_streams_set_activity; activity.hip): the state over every frame the encoder had emitted for the
+// utterance when a chunk was admitted.  The launch that computes it belongs to the encoder group `gen`; until that group
+// has been retired the value is pending (ready = false).  T: rows of the CTC table the state covers (the track's extent).
+struct ActVal {
+  bool ready = true;
+  long gen = 0;
+  int32_t v[6] = {0, 0, 0, -1, -1, 0};
+  int T = 0;
+};
+
 // a stream's outstanding chunk (sc_push / sc_submit): open until it has been reported.  With a queue depth > 1
 // (sc_streams_set_queue_depth) further chunks of the stream wait behind it (sc_streams::ahead), in order.
 struct Job {
@@ -147,6 +157,7 @@ struct Job {
   bool fin = false;  // is_final chunk: nothing may be queued behind it
   bool dropped = false;   // failed only because an EARLIER chunk of the stream failed (the reset has happened by then)
   bool started = false;   // St::started right after THIS chunk's admission (a later admission may set it before this one is reported)
+  ActVal act;             // sc_streams_set_activity: the activity state that belongs to this chunk
 };
 
 // hypotheses of a stream's last complete chunk, copied aside when later chunks of the stream may go on decoding
@@ -193,6 +204,10 @@ struct EncGroup {
   int n_fe = 0, max_keep = 0;
   EncPlan P;
   std::vector<int32_t> ctc_rows, kv_src, kv_dst;   // eager projections of the frames the group emits
+  // activity option: per stream the span [t0, t1) of ctc_rows (one sc_ctc_activity job each, in this order); epoch = the
+  // stream's reset count when the span was planned (a state that arrives after a reset is dropped)
+  struct ActSpan { int s, t0, t1; long epoch; bool restart; };
+  std::vector<ActSpan> act;
   bool same_rows = true;
   std::vector<int> streams;                  // streams with work in this group (each at most once)
   bool empty() const { return !n_fe && !P.n_conv; }
@@ -281,6 +296,18 @@ struct sc_streams {
   // ---- CTC forced alignment (sc_align_hyps / sc_align_tokens): job table, labels, outputs, workspaces -----------------
   char *al_dev = nullptr;         // allocated on the first call, grown geometrically
   size_t al_cap = 0;
+  // ---- acoustic activity (sc_streams_set_activity): everything below is allocated when the option is first switched on ----
+  bool act_on = false;
+  double act_thr = 0.8;
+  int32_t *act_state = nullptr;   // device [S][6]: the running state of every stream (advanced group by group, encoder stream)
+  double *act_track = nullptr;    // device [S][TCAP]: p_blank per CTC row
+  sc_ctc_activity_job *act_jobs_host = nullptr, *act_jobs_dev = nullptr;   // [N_ARENA][S]: the job table of a group's launch
+  int32_t *act_out_host = nullptr, *act_out_dev = nullptr;                 // [N_ARENA][S][6] host-mapped: the jobs' states-after
+  std::vector<ActVal> act_known;  // per stream: the state after the latest RETIRED group that scanned it
+  std::vector<ActVal> act_rep;    // per stream: the state of the last reported chunk (sc_stream_activity)
+  std::vector<long> act_pending;  // per stream: the latest group that carries a span of it (0: none since the reset)
+  std::vector<long> act_epoch;    // per stream: resets so far
+  std::vector<char> act_fresh;    // per stream: the next span starts the utterance
   // ---- tick engine -----------------------------------------------------------------------------------------------------
   std::vector<St> st;
   std::vector<Run> run;
@@ -472,6 +499,12 @@ void reset_stream(sc_streams *b, int s) {
   b->run[s] = Run();
   b->bq[s].clear();
   b->snap[s] = Snap();
+  if (!b->act_epoch.empty()) {   // activity: the next span starts over; a state of the old utterance still in flight is dropped
+    b->act_epoch[s]++;
+    b->act_known[s] = b->act_rep[s] = ActVal();
+    b->act_pending[s] = 0;
+    b->act_fresh[s] = 1;
+  }
   init_hyp(b, s);
 }
 
@@ -847,6 +880,22 @@ int retire_groups(sc_streams *b) {
       sc_set_error("encoder group %ld failed: %s", g->gen, hipGetErrorString(q));
       return SC_ERR_LAUNCH;
     }
+    // activity: the states-after of the group's jobs -> the chunks they belong to (open, or reported in the meantime)
+    for (size_t i = 0; i < g->act.size(); ++i) {
+      const EncGroup::ActSpan &sp = g->act[i];
+      if (sp.epoch != b->act_epoch[sp.s]) continue;
+      ActVal &k = b->act_known[sp.s];
+      k.ready = true;
+      k.gen = g->gen;
+      k.T = sp.t1;
+      memcpy(k.v, b->act_out_host + ((size_t)g->slot * b->S + i) * 6, sizeof k.v);
+      auto fill = [&](ActVal &a) {
+        if (!a.ready && a.gen == g->gen) a = k;
+      };
+      fill(b->job[sp.s].act);
+      for (Job &j : b->ahead[sp.s]) fill(j.act);
+      fill(b->act_rep[sp.s]);
+    }
     b->gen_done = g->gen;
     b->slot_gen[g->slot] = 0;
     b->groups.pop_front();
@@ -878,6 +927,32 @@ int project_rows(sc_streams *b, EncGroup &g) {
     RC_TRY(b->itensor(g.ctc_rows, &ar));
     RC_TRY(sc_gemm(b->enc, ar, d, e->f("ctc_w"), e->f("ctc_b"), const_cast<float *>(b->sb.ctcx), ar, V, (int)g.ctc_rows.size(),
                    V, d, b->gemm_flags, 0, b->es));
+    if (!g.act.empty()) {
+      // activity: ONE launch for the group, behind the projection of the rows it reads (raw logits: the in-place
+      // log-softmax of a first block runs on the decode stream behind this group's event)
+      const int n = (int)g.act.size();
+      if (n > b->S) {   // (a group holds a stream at most once)
+        sc_set_error("activity: %d spans in a group of a batch of %d streams (internal error)", n, b->S);
+        return SC_ERR_ARG;
+      }
+      const size_t o = (size_t)g.slot * b->S;
+      for (int i = 0; i < n; ++i) {
+        const EncGroup::ActSpan &sp = g.act[i];
+        sc_ctc_activity_job &j = b->act_jobs_host[o + i];
+        j.table = b->sb.ctcx + (size_t)sp.s * b->TCAP * V;
+        j.state = b->act_state + (size_t)sp.s * 6;
+        j.track = b->act_track + (size_t)sp.s * b->TCAP;
+        j.state_after = b->act_out_dev + (o + i) * 6;
+        j.stride = V;
+        j.thr = b->act_thr;
+        j.V = V; j.blank = c.blank_id; j.t0 = sp.t0; j.t1 = sp.t1;
+        j.restart = sp.restart ? 1 : 0;
+        j.reserved = 0;
+      }
+      HIP_TRY(hipMemcpyAsync(b->act_jobs_dev + o, b->act_jobs_host + o, (size_t)n * sizeof(sc_ctc_activity_job),
+                             hipMemcpyHostToDevice, b->es));
+      RC_TRY(sc_ctc_activity(b->act_jobs_dev + o, n, b->es));
+    }
   }
   if (!g.kv_dst.empty()) {
     if (!g.same_rows || !ar) RC_TRY(b->itensor(g.kv_src, &ar));
@@ -967,6 +1042,7 @@ void merge_group(sc_streams *b, EncGroup &dst, EncGroup &src) {
   dst.n_fe += src.n_fe;
   dst.max_keep = std::max(dst.max_keep, src.max_keep);
   cat(dst.ctc_rows, src.ctc_rows); cat(dst.kv_src, src.kv_src); cat(dst.kv_dst, src.kv_dst);
+  dst.act.insert(dst.act.end(), src.act.begin(), src.act.end());
   dst.same_rows = dst.same_rows && src.same_rows;
   dst.streams.insert(dst.streams.end(), src.streams.begin(), src.streams.end());
 }
@@ -1486,6 +1562,7 @@ int admit(sc_streams *b, std::vector<Chunk> chunks, bool features, bool defer, s
     if (rc != SC_OK) return rc;
   }
   // eager projections: CTC rows / cross-attention K|V rows of every frame this admission emits
+  std::vector<int> act_new;   // activity: the streams this admission scans
   for (auto &ch : chunks) {
     St &st = b->st[ch.s];
     const int t0 = snap[ch.s].T_enc, t1 = st.T_enc;
@@ -1494,6 +1571,11 @@ int admit(sc_streams *b, std::vector<Chunk> chunks, bool features, bool defer, s
     const int c0 = std::max(t0, st.T_proj), k0 = std::max(t0, st.T_projkv);
     g->same_rows = g->same_rows && c0 == k0;
     for (int t = c0; t < t1; ++t) g->ctc_rows.push_back(ch.s * b->TCAP + t);
+    if (b->act_on && c0 < t1) {
+      g->act.push_back({ch.s, c0, t1, b->act_epoch[ch.s], b->act_fresh[ch.s] != 0});
+      b->act_fresh[ch.s] = 0;
+      act_new.push_back(ch.s);
+    }
     for (int t = k0; t < t1; ++t) {
       g->kv_src.push_back(ch.s * b->TCAP + t);
       g->kv_dst.push_back(ch.s * c.dec_layers * b->TCAP + t);
@@ -1565,6 +1647,17 @@ int admit(sc_streams *b, std::vector<Chunk> chunks, bool features, bool defer, s
     j.seq = seq_of.at(chunks[k].s);
     j.fin = chunks[k].fin;
     j.started = b->st[chunks[k].s].started;
+    if (b->act_on) {
+      const int s = chunks[k].s;
+      // this admission carries a span of the stream: its state comes with the group `gen`
+      if (gen && std::find(act_new.begin(), act_new.end(), s) != act_new.end()) b->act_pending[s] = gen;
+      if (b->act_pending[s] > b->gen_done) {   // (no span of its own: the predecessor's state, which may still be in flight)
+        j.act.ready = false;
+        j.act.gen = b->act_pending[s];
+      } else {
+        j.act = b->act_known[s];
+      }
+    }
     if (b->job[chunks[k].s].open) b->ahead[chunks[k].s].push_back(j);   // behind the stream's outstanding chunk(s)
     else b->job[chunks[k].s] = j;
     b->n_open++;
@@ -2181,6 +2274,7 @@ int report_chunk(sc_streams *b, int s) {
   Job &j = b->job[s];
   const int status = j.fault ? j.fault : j.has_out;
   if (j.fault && !j.dropped) reset_stream(b, s);   // (fault_msg[s] keeps the message: sc_stream_last_error)
+  if (b->act_on && !j.fault) b->act_rep[s] = j.act;
   if (b->snap[s].valid && b->snap[s].seq == j.seq) b->snap[s].reported = true;   // handed out: free at the next sc_poll
   b->done_at[s] = 0;
   if (b->ahead[s].empty()) j = Job();
@@ -2711,6 +2805,90 @@ extern "C" int sc_streams_read_ctc(sc_streams *b, int stream, float *host, int m
   if (host && T > 0) {
     HIP_TRY(hipMemcpyAsync(host, b->sb.ctcx + (size_t)stream * b->TCAP * V, (size_t)T * V * sizeof(float),
                            hipMemcpyDeviceToHost, b->stream_rb));
+    HIP_TRY(hipStreamSynchronize(b->stream_rb));
+  }
+  return T;
+  SC_API_END
+}
+
+// ---- acoustic activity ------------------------------------------------------------------------------------------------
+extern "C" int sc_streams_set_activity(sc_streams *b, int on, double blank_threshold) {
+  SC_CHECK_ARG(b, "null");
+  SC_API_BEGIN
+  SC_CHECK_ARG(b->n_open == 0, "chunks are outstanding");
+  if (!on) {
+    b->act_on = false;
+    return SC_OK;
+  }
+  SC_CHECK_ARG(blank_threshold > 0.0 && blank_threshold < 1.0, "blank_threshold must lie in (0, 1)");
+  HIP_TRY(hipSetDevice(b->eng->device));
+  if (!b->act_state) {
+    const size_t S = (size_t)b->S;
+    RC_TRY(b->alloc(&b->act_state, S * 6));
+    RC_TRY(b->alloc(&b->act_track, S * b->TCAP));
+    RC_TRY(b->alloc(&b->act_jobs_dev, S * N_ARENA));
+    RC_TRY(b->halloc(&b->act_jobs_host, S * N_ARENA));
+    RC_TRY(b->halloc(&b->act_out_host, S * N_ARENA * 6));
+    void *dv = nullptr;
+    if (hipHostGetDevicePointer(&dv, b->act_out_host, 0) != hipSuccess || !dv) {
+      sc_set_error("sc_streams_set_activity: the pinned state slots are not visible to the device");
+      return SC_ERR_LAUNCH;
+    }
+    b->act_out_dev = (int32_t *)dv;
+    b->act_known.assign(S, ActVal());
+    b->act_rep.assign(S, ActVal());
+    b->act_pending.assign(S, 0);
+    b->act_epoch.assign(S, 0);
+    b->act_fresh.assign(S, 1);
+  }
+  // every stream starts over: a stream in mid-utterance is scanned from its next frame on
+  for (int s = 0; s < b->S; ++s) {
+    b->act_epoch[s]++;
+    b->act_known[s] = b->act_rep[s] = ActVal();
+    b->act_pending[s] = 0;
+    b->act_fresh[s] = 1;
+  }
+  b->act_thr = blank_threshold;
+  b->act_on = true;
+  return SC_OK;
+  SC_API_END
+}
+
+// the state of the stream's last reported chunk, complete: its encoder group may still be held back or in flight
+static int activity_ready(sc_streams *b, int s) {
+  ActVal &r = b->act_rep[s];
+  if (r.ready) return SC_OK;
+  RC_TRY(wait_group(b, r.gen));
+  if (!r.ready) {
+    sc_set_error("activity state of stream %d did not arrive with its encoder group (internal error)", s);
+    return SC_ERR_LAUNCH;
+  }
+  return SC_OK;
+}
+
+extern "C" int sc_stream_activity(sc_streams *b, int stream, sc_activity_t *out) {
+  SC_CHECK_ARG(b && out && stream >= 0 && stream < b->S, "bad arguments");
+  SC_API_BEGIN
+  SC_CHECK_ARG(b->act_on, "the activity option is off (sc_streams_set_activity)");
+  HIP_TRY(hipSetDevice(b->eng->device));
+  RC_TRY(activity_ready(b, stream));
+  const int32_t *v = b->act_rep[stream].v;
+  out->n_frames = v[0]; out->n_speech = v[1]; out->n_bad = v[2];
+  out->first_speech = v[3]; out->last_speech = v[4]; out->trail_silence = v[5];
+  return SC_OK;
+  SC_API_END
+}
+
+extern "C" int sc_streams_read_activity(sc_streams *b, int stream, double *host, int max_frames) {
+  SC_CHECK_ARG(b && stream >= 0 && stream < b->S && max_frames >= 0, "bad arguments");
+  SC_API_BEGIN
+  SC_CHECK_ARG(b->act_on, "the activity option is off (sc_streams_set_activity)");
+  HIP_TRY(hipSetDevice(b->eng->device));
+  RC_TRY(activity_ready(b, stream));
+  const int T = std::min(b->act_rep[stream].T, max_frames);
+  if (host && T > 0) {   // (the group that wrote these entries has been retired; later groups write behind them)
+    HIP_TRY(hipMemcpyAsync(host, b->act_track + (size_t)stream * b->TCAP, (size_t)T * sizeof(double), hipMemcpyDeviceToHost,
+                           b->stream_rb));
     HIP_TRY(hipStreamSynchronize(b->stream_rb));
   }
   return T;

@@ -32,6 +32,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from .activity import INITIAL, advance as activity_advance, as_arrays as activity_arrays
 from .config import SearchConfig
 from .weights import PackedWeights
 
@@ -267,6 +268,7 @@ class StreamBatch:
         if self.stream is not None and hasattr(backend, "bind_stream"):
             backend.bind_stream(self.stream)
         self.st = [StreamState() for _ in range(S)]
+        self._act = None   # acoustic activity (set_activity): off
         self.reset_all()
         self.stats = {"enc_calls": 0, "dec_steps": 0, "dec_blocks": 0}
         # optional host-side phase timers (SC_TIMING=1): seconds per phase
@@ -345,6 +347,10 @@ class StreamBatch:
             ns.short_pos = old.short_pos  # A13: counter survives reset()
             ns.T_ctc = old.T_ctc          # stale CTC table (rows stay in self.ctcx)
         self.st[s] = ns
+        if self._act is not None:
+            self._act["state"][s] = INITIAL
+            self._act["proj"][s] = ns.T_ctc    # strict: the stale table's rows are not projected again, so not scanned
+            self._act["T"][s] = 0
         if getattr(self, "stream", None) is not None:
             with torch.cuda.stream(self.stream):   # same stream as the kernels that read it
                 self._init_hyp(s)
@@ -364,6 +370,67 @@ class StreamBatch:
 
     def input_rate(self, s: int) -> int:
         return 16000
+
+    # ------------------------------------------------------------------
+    # acoustic activity (the native engine: sc_streams_set_activity)
+    # ------------------------------------------------------------------
+    def set_activity(self, on: bool, blank_threshold: float = 0.8):
+        """Per-stream speech activity from the CTC table.  When on, every chunk step projects the CTC rows of the frames
+        its encoder stage emits right away (the rows the decode blocks would project one hop later: same values) and
+        scans them in float64: a frame is silence iff its row is bad or its blank posterior exceeds ``blank_threshold``.
+        Every stream's state starts over."""
+        if not on:
+            self._act = None
+            return
+        if not 0.0 < float(blank_threshold) < 1.0:
+            raise EngineError("blank_threshold must lie in (0, 1)")
+        self._act = {"thr": float(blank_threshold),
+                     "state": np.tile(np.asarray(INITIAL, np.int32), (self.S, 1)),
+                     "track": np.zeros((self.S, self.TCAP), np.float64),
+                     "proj": np.asarray([x.T_ctc for x in self.st], np.int64),
+                     "T": np.zeros(self.S, np.int64)}
+
+    def activity(self, streams: Sequence[int]):
+        """{field: int32 array [n]} (speechcatcher_amd.activity.FIELDS) of the listed streams after their last chunk"""
+        if self._act is None:
+            raise EngineError("the activity option is off (set_activity)")
+        return activity_arrays([self._act["state"][int(s)] for s in streams])
+
+    def read_activity(self, s: int) -> np.ndarray:
+        """float64 [T]: the blank posterior of every CTC row the state of stream s covers (index = row of the table)"""
+        if self._act is None:
+            raise EngineError("the activity option is off (set_activity)")
+        return self._act["track"][int(s), :int(self._act["T"][int(s)])].copy()
+
+    def _scan_activity(self, t_old: Dict[int, int]):
+        """The frames [t_old[s], T_enc) the encoder stage of this chunk step emitted: CTC rows, blank posteriors in torch
+        float64, state update."""
+        a, cfg = self._act, self.cfg
+        spans = []
+        for s, t0 in t_old.items():
+            t1 = self.st[s].T_enc
+            c0 = max(t0, int(a["proj"][s]))
+            if t1 > c0:
+                spans.append((s, c0, t1))
+                a["proj"][s] = t1
+        if not spans:
+            return
+        rows = np.concatenate([s * self.TCAP + _AR[c0:t1] for s, c0, t1 in spans])
+        ar = self._itensor(rows)
+        V, m = cfg.vocab_size, int(rows.shape[0])
+        self.be.gemm(self.enc, ar, cfg.d_model, self.w.ctc_w, self.w.ctc_b, self.ctcx, ar, V, m, V, cfg.d_model)
+        x = self.ctcx[torch.as_tensor(rows, dtype=torch.int64, device=self.dev)].to(torch.float64)
+        bad = torch.isnan(x).any(1) | (x == float("inf")).any(1) | (x.max(1).values == float("-inf"))
+        x = torch.where(bad[:, None], torch.zeros_like(x), x)
+        p = torch.exp(x[:, cfg.blank_id] - torch.logsumexp(x, 1))
+        p = torch.where(bad, torch.full_like(p, float("nan")), p).cpu().numpy()
+        o = 0
+        for s, c0, t1 in spans:
+            ps = p[o:o + t1 - c0]
+            o += t1 - c0
+            a["track"][s, c0:t1] = ps
+            a["state"][s] = activity_advance(a["state"][s], ps, a["thr"])
+            a["T"][s] = t1
 
     def _init_hyp(self, s: int):
         # create_initial_hypothesis (hypothesis.py:75-91): yseq=[sos], xpos=[0]
@@ -596,7 +663,10 @@ class StreamBatch:
         # n < 3: encoder skipped, frames discarded (beam_search.py:551-559)
         if enc_streams:
             t_ph = time.perf_counter()
+            t_old = {s: self.st[s].T_enc for s in enc_streams} if self._act is not None else None
             self._encode(enc_streams, feat_new, finals)
+            if t_old is not None:
+                self._scan_activity(t_old)
             self._tick("encode_host", t_ph)
 
     def _stage_decode(self, feat_new: Dict[int, int], finals: Dict[int, bool], t_avail: Dict[int, int]):

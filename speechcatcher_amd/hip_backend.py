@@ -312,6 +312,34 @@ class HipBackend:
         oi = out_i.cpu().numpy()
         return oi[:, 0], oi[:, 1], out_f.cpu().numpy(), ps.cpu().numpy().astype(np.float32), stt.cpu().numpy()
 
+    def ctc_activity(self, jobs, thr):
+        """Batched CTC speech-activity scan (sc_ctc_activity), one launch for all jobs.  jobs: list of
+        (table [T, V] fp32 tensor, rows may be strided; blank; t0; t1; state: six ints or None = the span starts an
+        utterance).  Returns (states [n, 6] int32: the states after the spans, p_blank: list of float64 arrays [T] with the
+        entries [t0, t1) written and NaN-free sentinels -7 elsewhere, states_after [n, 6]: the second copy)."""
+        import numpy as np
+        n = len(jobs)
+        dev = self.device
+        Tmax = max([1] + [int(j[0].shape[0]) for j in jobs])
+        state = torch.zeros((max(n, 1), 6), dtype=torch.int32, device=dev)
+        after = torch.full((max(n, 1), 6), -7, dtype=torch.int32, device=dev)
+        track = torch.full((max(n, 1), Tmax), -7.0, dtype=torch.float64, device=dev)
+        tab = (_abi.ActivityJob * max(1, n))()
+        for k, (table, blank, t0, t1, st) in enumerate(jobs):
+            assert table.dtype == torch.float32 and table.dim() == 2 and table.stride(1) == 1
+            assert 0 <= t0 <= t1 <= table.shape[0]
+            if st is not None:
+                state[k] = torch.as_tensor(np.asarray(st, np.int32))
+            j = tab[k]
+            j.table, j.state, j.track, j.state_after = table.data_ptr(), state[k].data_ptr(), track[k].data_ptr(), after[k].data_ptr()
+            j.stride, j.thr, j.V, j.blank, j.t0, j.t1 = table.stride(0), float(thr), table.shape[1], int(blank), int(t0), int(t1)
+            j.restart = 1 if st is None else 0
+        tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+        self._chk(self.lib.sc_ctc_activity(tab_dev.data_ptr(), n, self._stream()), "sc_ctc_activity")
+        torch.cuda.synchronize(dev)
+        tr = track.cpu().numpy()
+        return state.cpu().numpy()[:n], [tr[k, :int(jobs[k][0].shape[0])] for k in range(n)], after.cpu().numpy()[:n]
+
     # ------------------------------------------------------------------
     def search_struct(self, sb):
         cached = getattr(sb, "_sc_search_struct", None)

@@ -369,6 +369,36 @@ class NativeStreamBatch:
             _abi.check(T, "sc_streams_read_ctc")
         return a[:T].copy()
 
+    # ---- acoustic activity (sc_streams_set_activity) -----------------------------------------
+    def set_activity(self, on: bool, blank_threshold: float = 0.8):
+        """Per-stream speech activity from the CTC table: when on, every admission group scans the CTC rows it projects
+        (one extra launch per group) - a frame is silence iff its blank posterior exceeds ``blank_threshold`` (or the row
+        is bad).  Off by default; only while no chunk is outstanding."""
+        try:
+            _abi.check(self.lib.sc_streams_set_activity(self.handle, int(bool(on)), float(blank_threshold)),
+                       "sc_streams_set_activity")
+        except _abi.ScasrError as e:
+            raise EngineError(str(e)) from e
+
+    def activity(self, streams: Sequence[int]):
+        """{field: int32 array [n]} (n_frames, n_speech, n_bad, first_speech, last_speech, trail_silence) of the listed
+        streams' last reported chunks - the chunks whose hypotheses ``hypotheses`` returns."""
+        out = {k: np.zeros(len(streams), np.int32) for k in _abi.ACTIVITY_FIELDS}
+        a = _abi.Activity()
+        for i, s in enumerate(streams):
+            _abi.check(self.lib.sc_stream_activity(self.handle, int(s), C.byref(a)), "sc_stream_activity")
+            for k in _abi.ACTIVITY_FIELDS:
+                out[k][i] = getattr(a, k)
+        return out
+
+    def read_activity(self, s: int) -> np.ndarray:
+        """float64 [T]: the blank posterior of every CTC row the state of stream s's last reported chunk covers"""
+        a = np.zeros(self.TCAP, np.float64)
+        T = self.lib.sc_streams_read_activity(self.handle, int(s), a.ctypes.data, self.TCAP)
+        if T < 0:
+            _abi.check(T, "sc_streams_read_activity")
+        return a[:T].copy()
+
     def hypotheses_batch(self, streams: Sequence[int], nbest: Optional[int] = None):
         """{stream: [hypothesis dicts, best first]} for the listed streams, one device round trip for all."""
         a = self.hypotheses_arrays(streams, nbest)

@@ -19,6 +19,7 @@ from typing import Deque, Dict, List, Optional, Tuple
 import numpy as np
 
 from .engine import StreamBatch
+from .activity import of_stream as activity_of_stream
 from .align import FeatureClock
 from .resample import OutputClock, check_input_rate
 from .speech2text_streaming import hyps_to_results, result_token_alignment
@@ -37,10 +38,17 @@ class AlignedResults(list):
     alignment: Optional[dict] = None
 
 
+class ActivityResults(AlignedResults):
+    """the results of a reply and ``activity``: {field: int} (speechcatcher_amd.activity.FIELDS) of the session's stream
+    for that chunk - StreamScheduler(activity=True).  A final reply of a scheduler with ``align_final`` as well carries
+    both attributes."""
+    activity: Optional[dict] = None
+
+
 class StreamScheduler:
     def __init__(self, batch: StreamBatch, token_list: Optional[List[str]] = None,
                  result_format: str = "native", reset_after_final: bool = True, reset_on_open: bool = True,
-                 queue_depth: int = 1, align_final: bool = False):
+                 queue_depth: int = 1, align_final: bool = False, activity: bool = False, blank_threshold: float = 0.8):
         """``queue_depth`` > 1 (C++ engine, ``pump``): up to that many queued chunks of a session are handed to the engine
         at a time (sc_streams_set_queue_depth) - for sessions whose audio is already there (files): the encoder stage of
         the next chunk runs beside the decoding of the current one.  Replies and their order per session do not change.
@@ -54,6 +62,10 @@ class StreamScheduler:
         ``align_final`` (C++ engine): every final reply is an ``AlignedResults`` whose ``alignment`` holds the token times and
         confidences of its first result (CTC forced alignment, NativeStreamBatch.align), taken before the stream is reset."""
         self.align_final = align_final
+        # ``activity``: every reply (an exception aside) is an ``ActivityResults`` whose ``activity`` is the acoustic
+        # speech / silence state of the session's stream for that chunk (batch.set_activity(True, blank_threshold)), read
+        # before the stream is reset after a final
+        self.activity = False
         self._clock: Dict[int, FeatureClock] = {}             # align_final: per session, the calls since its last reset
         self._fed: Dict[int, Deque[Tuple[int, bool]]] = {}   # ... and its fed chunks not reported yet (length, final)
         self.reset_after_final, self.reset_on_open = reset_after_final, reset_on_open
@@ -76,6 +88,13 @@ class StreamScheduler:
             batch.set_queue_depth(queue_depth)
             self.queue_depth = queue_depth
         self._next_sid = 0
+        if activity:
+            self.enable_activity(blank_threshold)
+
+    def enable_activity(self, blank_threshold: float = 0.8):
+        """switch the ``activity`` option on (only while no chunk is at the engine; every stream's state starts over)"""
+        self.batch.set_activity(True, blank_threshold)
+        self.activity = True
 
     # ---- session lifecycle -------------------------------------------------
     def open(self, sample_rate: int = 16000) -> int:
@@ -183,6 +202,11 @@ class StreamScheduler:
                 row = {slot: i for i, slot in enumerate(want)}
             else:
                 hyps = {slot: self.batch.hypotheses(slot) for slot in want}
+        act = act_row = None
+        if self.activity:
+            act_slots = [slot for (slot, _, _) in meta.values() if not isinstance(has[slot], Exception)]
+            act_row = {slot: i for i, slot in enumerate(act_slots)}
+            act = self.batch.activity(act_slots) if act_slots else None
         for sid, (slot, fin, fa) in meta.items():
             if self.align_final:              # the stream's clock advances by the reported chunk
                 n, f = self._fed[sid].popleft()
@@ -201,6 +225,11 @@ class StreamScheduler:
             if fin and self.align_final and not isinstance(out[sid], Exception):
                 out[sid] = self._aligned(out[sid], arrays, row[slot] if arrays is not None and has[slot] is True else None,
                                          slot, fin, fa, self._clock.get(sid))
+            if act is not None:
+                res = ActivityResults(out[sid])
+                res.alignment = getattr(out[sid], "alignment", None)
+                res.activity = activity_of_stream(act, act_row[slot])
+                out[sid] = res
             if fin and self.reset_after_final:
                 self.batch.reset(slot)
                 self._clock.pop(sid, None)

@@ -25,11 +25,14 @@ Differences to the reference, on purpose:
   formats need the transport to transcode first.
 """
 import json
+import math
 from collections import deque
+from dataclasses import dataclass
 from typing import Deque, Dict, List, Optional, Union
 
 import numpy as np
 
+from .activity import FRAME_SECONDS
 from .align import merge_words
 from .scheduler import ServerBusy, StreamScheduler
 
@@ -67,6 +70,52 @@ class Endpointer:
         self.n_best_lens.append(partial_len)
 
 
+@dataclass
+class EndpointRules:
+    """Acoustic endpointing rules in SECONDS of audio (ServerLoop(acoustic_endpointing=...)); an encoder frame is
+    0.04 s, a rule of x seconds is ceil(x / 0.04) frames.  Conventional defaults, not tuned on the shipped models."""
+    silence_after_speech: float = 1.0     # finalise when speech has been seen and this much silence has followed it
+    silence_without_speech: float = 5.0   # ... when nothing but silence has come in for this long
+    max_utterance: float = 20.0           # ... whatever has been said, after this long
+
+    @staticmethod
+    def frames(seconds: float) -> int:
+        return int(math.ceil(round(seconds / FRAME_SECONDS, 6)))
+
+
+class AcousticEndpointer:
+    """Acoustic endpointing of one session: finalise after N ms of silence, from the speech / silence state of the
+    session's stream (the ``activity`` of its replies: speechcatcher_amd.activity.FIELDS) instead of "the text did not
+    grow".  Same protocol as ``Endpointer``: ``decide`` before a chunk, ``observe`` after every non-final reply; the
+    history restarts after every finalisation (``reset``)."""
+
+    def __init__(self, rules: Optional[EndpointRules] = None):
+        self.rules = rules or EndpointRules()
+        self.after_speech = EndpointRules.frames(self.rules.silence_after_speech)
+        self.without_speech = EndpointRules.frames(self.rules.silence_without_speech)
+        self.max_frames = EndpointRules.frames(self.rules.max_utterance)
+        self.last: Optional[dict] = None
+
+    def fires(self, a: dict) -> bool:
+        return ((a["n_speech"] > 0 and a["trail_silence"] >= self.after_speech)
+                or (a["n_speech"] == 0 and a["n_frames"] >= self.without_speech)
+                or a["n_frames"] >= self.max_frames)
+
+    def decide(self) -> bool:
+        """Called BEFORE a chunk is decoded: finalise this chunk?"""
+        if self.last is None or not self.fires(self.last):
+            return False
+        self.reset()
+        return True
+
+    def observe(self, activity: dict):
+        """Called after every NON-final reply with its ``activity``."""
+        self.last = dict(activity)
+
+    def reset(self):
+        self.last = None
+
+
 def vosk_partial(text: str) -> dict:
     return {"partial": text}
 
@@ -101,10 +150,12 @@ def scale_server_pcm(data: np.ndarray) -> np.ndarray:
 
 
 class _Session:
-    def __init__(self, sid: int, vosk: bool, finalize_update_iters: int, max_partial_iters: int):
+    def __init__(self, sid: int, vosk: bool, finalize_update_iters: int, max_partial_iters: int,
+                 acoustic: Optional[EndpointRules] = None):
         self.sid = sid
         self.vosk = vosk
         self.endpointer = Endpointer(finalize_update_iters, max_partial_iters)
+        self.acoustic = AcousticEndpointer(acoustic) if acoustic is not None else None
         self.inbox: Deque[Message] = deque()
         self.in_flight: Optional[dict] = None     # the chunk currently queued in the scheduler
         self.vosk_sample_rate = 16000
@@ -116,7 +167,8 @@ class ServerLoop:
 
     def __init__(self, scheduler: StreamScheduler, vosk_output_format: bool = False,
                  finalize_update_iters: int = 6, max_partial_iters: int = 42, strict_reference: bool = False,
-                 continuous: Optional[bool] = None, min_replies: int = 1, vosk_alignment: bool = False):
+                 continuous: Optional[bool] = None, min_replies: int = 1, vosk_alignment: bool = False,
+                 acoustic_endpointing: Optional[EndpointRules] = None):
         """``strict_reference``: no stream reset after a finalised utterance nor between clients, exactly like
         ``recognize_ws`` / ``process_audio_chunk`` (speechcatcher_server.py:270,359-397); the default resets.
         ``continuous`` (default: on whenever the batch has the C++ engine's submit / poll - round 4; False forces one
@@ -126,7 +178,18 @@ class ServerLoop:
         the reference's per-client handler loop (:359-397), same calls and replies per session.
         ``vosk_alignment`` (C++ engine, Vosk format): final results carry WORDS with times and confidences from a CTC
         forced alignment (vosk_result_aligned) instead of one entry per token at its block's frame with conf 1.0; a result
-        whose hypothesis cannot be aligned (more tokens than its block has frames) keeps those default entries."""
+        whose hypothesis cannot be aligned (more tokens than its block has frames) keeps those default entries.
+        ``acoustic_endpointing``: an utterance is also finalised when the acoustic rules fire (AcousticEndpointer: N ms of
+        silence from the CTC blank posterior) - finalize = text endpointer or acoustic endpointer or forced.  Switches the
+        scheduler's ``activity`` option on (blank threshold 0.8 unless the scheduler was built with another); needs the
+        reset after a final, so not with ``strict_reference``.  None (default): the reference's rule alone."""
+        if acoustic_endpointing is not None:
+            if strict_reference:
+                raise ValueError("acoustic endpointing counts the frames of an utterance from the reset after a final: "
+                                 "not with strict_reference")
+            if not scheduler.activity:
+                scheduler.enable_activity()
+        self.acoustic_rules = acoustic_endpointing
         assert scheduler.result_format == "espnet", "sessions need token positions: result_format='espnet'"
         if strict_reference:
             scheduler.reset_after_final = scheduler.reset_on_open = False
@@ -146,7 +209,7 @@ class ServerLoop:
         """Raises ServerBusy when every stream slot is taken ("Server busy,
         please try again later.", :366)."""
         sid = self.sch.open()
-        self.sessions[sid] = _Session(sid, self.vosk, self.fui, self.mpi)
+        self.sessions[sid] = _Session(sid, self.vosk, self.fui, self.mpi, self.acoustic_rules)
         return sid
 
     def disconnect(self, sid: int):
@@ -181,6 +244,8 @@ class ServerLoop:
                 # it): the transport closes this connection; every other session is untouched
                 ses.in_flight = None
                 ses.endpointer.n_best_lens = []
+                if ses.acoustic is not None:
+                    ses.acoustic.reset()
                 replies.setdefault(sid, []).append(results)
                 continue
             replies.setdefault(sid, []).append(self._reply(ses, self._finish(ses, results)))
@@ -217,7 +282,14 @@ class ServerLoop:
             data = np.frombuffer(message, dtype="<i2")      # s16le at the session's sample rate
         if data.size == 0:
             return vosk_partial("") if ses.vosk else ""
-        finalize = ses.endpointer.decide() or forced
+        finalize = ses.endpointer.decide()
+        if ses.acoustic is not None:
+            if ses.acoustic.decide() and not finalize:
+                finalize = True
+                ses.endpointer.n_best_lens = []   # a finalisation restarts both histories
+        finalize = finalize or forced
+        if finalize and ses.acoustic is not None:
+            ses.acoustic.reset()
         self.sch.feed(ses.sid, scale_server_pcm(data), is_final=finalize, finalize_all=False)
         ses.in_flight = {"finalize": finalize, "forced": forced}
         return None
@@ -226,6 +298,8 @@ class ServerLoop:
         info, ses.in_flight = ses.in_flight, None
         if info["forced"]:
             ses.endpointer.n_best_lens = []   # session.reset() after a client-forced finalize (:272-273)
+        if ses.acoustic is not None and not info["finalize"]:
+            ses.acoustic.observe(results.activity)
         if not results:
             return ""
         text, tokens, _ids, pos, _hyp = results[0]
@@ -299,5 +373,5 @@ class StepPacer:
         return replies
 
 
-__all__ = ["Endpointer", "ServerLoop", "StepPacer", "ServerBusy", "vosk_partial", "vosk_result", "vosk_result_aligned",
+__all__ = ["Endpointer", "EndpointRules", "AcousticEndpointer", "ServerLoop", "StepPacer", "ServerBusy", "vosk_partial", "vosk_result", "vosk_result_aligned",
            "scale_server_pcm"]

@@ -379,6 +379,18 @@ class Speech2TextStreaming:
             out.append(result_token_alignment(h["yseq"], is_final, al, 0, j, self.cfg, getattr(self, "_clock", None)))
         return out
 
+    def set_activity(self, on: bool = True, blank_threshold: float = 0.8):
+        """Acoustic speech activity from the CTC table (NativeStreamBatch.set_activity): off by default; between calls."""
+        self.batch.set_activity(on, blank_threshold)
+
+    def activity(self) -> dict:
+        """{n_frames, n_speech, n_bad, first_speech, last_speech, trail_silence} (encoder frames of 0.04 s) of the
+        utterance up to the last call: a frame is silence iff its CTC blank posterior exceeds the threshold of
+        ``set_activity`` (which must have been switched on before the utterance's calls).  "Finalise after N ms of
+        silence" for a single-stream user: n_speech > 0 and trail_silence * 0.04 >= N / 1000."""
+        from .activity import of_stream
+        return of_stream(self.batch.activity([self.stream]), 0)
+
     def recognize(self, speech):
         self.reset()
         return self(speech, is_final=True)
