@@ -424,6 +424,56 @@ typedef struct sc_ctc_activity_job {
  * must not share a state or overlap in a track. */
 int sc_ctc_activity(const sc_ctc_activity_job *jobs, int n_jobs, void *stream);
 
+/* ---- CTC phrase spotting (spot.hip) ---------------------------------------------------------
+ * A phrase set holds P <= SC_SPOT_MAX_PHRASES phrases; phrase p is a label sequence y[0..L), 1 <= L <= SC_SPOT_MAX_LEN,
+ * labels in [0, V) and not the blank, with a floor min_score <= 0.  It has S = 2L - 1 states (state 2i: token y[i], state
+ * 2i + 1: the blank between y[i] and y[i + 1]), each a float64 value and an int32 start; -inf / -1 at the start of an
+ * utterance.  For frame n (numbered in the order the frames are scanned) with row x, promoted to float64: a BAD row (a
+ * NaN, a +inf, or nothing but -inf) sets every state of every enabled phrase to -inf / -1; else, with m = max_v x[v] and
+ * e(s) = x[label(s)] - m, every state takes the best of { stay V[s]; V[s-1]; V[s-2] if s is even, s >= 2 and
+ * y[s/2] != y[s/2-1]; for s == 0 a fresh start 0.0 with start n } of the PREVIOUS frame - compared in this order, a later
+ * candidate taking over only if strictly greater - plus e(s), and the winner's start (-1 when the value is -inf).  The
+ * phrase FIRES iff the new value of its end state 2L - 2 is >= min_score: event (end = n, phrase, start, score), then all
+ * its states become -inf / -1.  The score is the log-ratio of the phrase's path to the frame-wise best path: a per-row
+ * constant cancels, raw logits and log-softmaxed rows mean the same.  Events are ordered by (end, phrase); the first
+ * SC_SPOT_MAX_EVENTS of an utterance are stored, n_events counts all.  tests/ctc_spot_ref.py is the contract; the kernel
+ * reproduces it bit for bit. */
+#define SC_SPOT_MAX_PHRASES 64
+#define SC_SPOT_MAX_LEN 32
+#define SC_SPOT_STATES 64      /* entries per phrase in the state block; [2L - 1, 64) stay -inf / -1 */
+#define SC_SPOT_MAX_EVENTS 64
+typedef struct sc_spot_event {
+  int32_t end, phrase, start, reserved; /* frames of the utterance, both inclusive; reserved = 0 */
+  double score;
+} sc_spot_event;
+typedef struct sc_spot_t {
+  int32_t n_frames, n_events;
+} sc_spot_t;
+typedef struct sc_ctc_spot_job {
+  const float *table;      /* row t of the table at table + t * stride, V floats (device) */
+  const int32_t *labels;   /* [P][SC_SPOT_MAX_LEN] (device) */
+  const int32_t *lens;     /* [P] (device) */
+  const double *floors;    /* [P] min_score (device) */
+  int32_t *counters;       /* [2] n_frames, n_events: read (unless restart), advanced over the span, written back (device) */
+  double *values;          /* [P][SC_SPOT_STATES] (device) */
+  int32_t *starts;         /* [P][SC_SPOT_STATES] (device) */
+  sc_spot_event *events;   /* [SC_SPOT_MAX_EVENTS]: event k of the utterance at events[k] (device) */
+  int32_t *state_after;    /* [2] second copy of the new counters, e.g. in host-mapped memory (NULL: none) */
+  int64_t stride;          /* floats between two rows, >= V */
+  uint64_t mask;           /* bit p: phrase p is enabled; a disabled phrase's states are not touched */
+  int32_t V, blank, t0, t1;
+  int32_t restart;         /* != 0: the stored state is ignored, the span starts an utterance */
+  int32_t P;
+} sc_ctc_spot_job;
+#define SC_SPOT_MAX_JOBS 65535
+/* jobs: device table of n_jobs entries.  ONE launch on `stream`, one workgroup per job; no atomics, one writer per
+ * output; an empty span (t0 == t1) rewrites the counters unchanged.  n_jobs < 0, a null table with n_jobs > 0 or
+ * n_jobs > SC_SPOT_MAX_JOBS: SC_ERR_ARG before anything is launched.  A job whose own fields are malformed (a null
+ * pointer other than state_after, V < 1, blank outside [0, V), t0 < 0, t1 < t0, stride < V, P outside [1, 64], a length
+ * outside [1, 32], a label outside [0, V) or equal to the blank) writes nothing.  Two jobs of one call must not share
+ * a state block or an events array. */
+int sc_ctc_spot(const sc_ctc_spot_job *jobs, int n_jobs, void *stream);
+
 /* ---- frontend ------------------------------------------------------------ */
 
 /* STFTFrontend.forward (model/frontend/stft_frontend.py:87-154) fused with the
@@ -822,6 +872,29 @@ int sc_stream_activity(sc_streams *streams, int stream, sc_activity_t *out /*HOS
 /* the p_blank track of the frames that state covers -> host [min(frames, max_frames)] doubles (index = row of the CTC
  * table); returns the number written */
 int sc_streams_read_activity(sc_streams *streams, int stream, double *host, int max_frames);
+/* Phrase spotting per stream (off by default).  labels: host [n_phrases][SC_SPOT_MAX_LEN] (entries behind a
+ * phrase's length are ignored), lens: host [n_phrases], min_scores: host [n_phrases] (each <= 0).  With a set in place
+ * every admission group issues ONE sc_ctc_spot launch right behind its CTC projection, on the encoder stream, over the
+ * CTC rows [c0, t1) each of its chunks projects (raw logits) - the search is not touched.  n_phrases == 0 switches the
+ * option off: no path does any new work.  Everything is allocated when a set is first given.  SC_ERR_ARG while any chunk
+ * is outstanding, for n_phrases outside [0, 64], a length outside [1, 32], a label outside the vocabulary or equal to
+ * the blank, a min_score that is not <= 0.  A new set restarts every stream's state and enables every phrase for every
+ * stream.  strict_reference: as for sc_streams_set_activity, frames that are not re-projected are not scanned. */
+int sc_streams_set_phrases(sc_streams *streams, const int32_t *labels, const int32_t *lens, const double *min_scores,
+                           int n_phrases);
+/* bit p of mask: phrase p is enabled for the stream (default: all).  Takes effect with the next chunk admitted; a phrase
+ * that is disabled keeps its states as they are.  SC_ERR_ARG when the option is off. */
+int sc_stream_set_phrase_mask(sc_streams *streams, int stream, uint64_t mask);
+/* counters of the stream's last REPORTED chunk - the chunk whose hypotheses sc_get_hyps returns - over every frame the
+ * encoder had emitted for the utterance when that chunk was admitted; (0, 0) after sc_reset.  Waits for the encoder
+ * group of that chunk if it is still in flight.  SC_ERR_ARG when the option is off. */
+int sc_stream_spot(sc_streams *streams, int stream, sc_spot_t *out /*HOST*/);
+/* the stored events that state covers, events [0, min(n_events, SC_SPOT_MAX_EVENTS, max)) of the utterance -> host;
+ * returns the number written */
+int sc_streams_read_spot_events(sc_streams *streams, int stream, sc_spot_event *host, int max);
+/* test aid: the state block of a stream as the device holds it NOW (every group issued so far; waits for them) -> host
+ * values [n_phrases][SC_SPOT_STATES], starts [n_phrases][SC_SPOT_STATES]; returns n_phrases */
+int sc_streams_read_spot_state(sc_streams *streams, int stream, double *values, int32_t *starts);
 
 #ifdef __cplusplus
 }

@@ -93,6 +93,26 @@ class Activity(C.Structure):
 ACTIVITY_FIELDS = tuple(n for n, _ in Activity._fields_)
 ACTIVITY_MAX_JOBS = 65535
 
+
+class SpotEvent(C.Structure):
+    """sc_spot_event (include/scasr.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("end", "phrase", "start", "reserved")] + [("score", C.c_double)]
+
+
+class Spot(C.Structure):
+    """sc_spot_t (include/scasr.h)"""
+    _fields_ = [("n_frames", C.c_int32), ("n_events", C.c_int32)]
+
+
+class SpotJob(C.Structure):
+    """sc_ctc_spot_job (include/scasr.h): one span of CTC rows scanned by sc_ctc_spot"""
+    _fields_ = ([(n, vp) for n in ("table", "labels", "lens", "floors", "counters", "values", "starts", "events",
+                                   "state_after")] + [("stride", C.c_int64), ("mask", C.c_uint64)]
+                + [(n, C.c_int32) for n in ("V", "blank", "t0", "t1", "restart", "P")])
+
+
+SPOT_MAX_PHRASES, SPOT_MAX_LEN, SPOT_STATES, SPOT_MAX_EVENTS, SPOT_MAX_JOBS = 64, 32, 64, 64, 65535
+
 # SC_ALIGN_* of include/scasr.h
 ALIGN_OK, ALIGN_INFEASIBLE, ALIGN_NONFINITE, ALIGN_BAD_INPUT = 0, 1, 2, 3
 ALIGN_MAX_L = 1023
@@ -234,6 +254,13 @@ _SIGS = {
     "sc_streams_set_activity": (C.c_int, [vp, C.c_int, C.c_double]),
     "sc_stream_activity": (C.c_int, [vp, C.c_int, C.POINTER(Activity)]),
     "sc_streams_read_activity": (C.c_int, [vp, C.c_int, vp, C.c_int]),
+    # CTC phrase spotting (spot.hip, streams.hip)
+    "sc_ctc_spot": (C.c_int, [vp, C.c_int, vp]),
+    "sc_streams_set_phrases": (C.c_int, [vp, vp, vp, vp, C.c_int]),
+    "sc_stream_set_phrase_mask": (C.c_int, [vp, C.c_int, C.c_uint64]),
+    "sc_stream_spot": (C.c_int, [vp, C.c_int, C.POINTER(Spot)]),
+    "sc_streams_read_spot_events": (C.c_int, [vp, C.c_int, vp, C.c_int]),
+    "sc_streams_read_spot_state": (C.c_int, [vp, C.c_int, vp, vp]),
     # sample-rate conversion (resample.hip, streams.hip)
     "sc_resample_design": (C.c_int, [C.c_int, c_int_p, c_int_p, c_int_p, c_float_p]),
     "sc_resample_out_count": (C.c_long, [C.c_int, C.c_long, C.c_int]),

@@ -147,6 +147,15 @@ struct ActVal {
   int T = 0;
 };
 
+// Phrase spotting (sc_streams_set_phrases; spot.hip): the counters (n_frames, n_events) that belong to a chunk, handed
+// over exactly like ActVal.  The events themselves stay on the device: the utterance's event k is at slot k, so the
+// first n_events of them are final whatever later groups append.
+struct SpotVal {
+  bool ready = true;
+  long gen = 0;
+  int32_t v[2] = {0, 0};
+};
+
 // a stream's outstanding chunk (sc_push / sc_submit): open until it has been reported.  With a queue depth > 1
 // (sc_streams_set_queue_depth) further chunks of the stream wait behind it (sc_streams::ahead), in order.
 struct Job {
@@ -158,6 +167,7 @@ struct Job {
   bool dropped = false;   // failed only because an EARLIER chunk of the stream failed (the reset has happened by then)
   bool started = false;   // St::started right after THIS chunk's admission (a later admission may set it before this one is reported)
   ActVal act;             // sc_streams_set_activity: the activity state that belongs to this chunk
+  SpotVal spot;           // sc_streams_set_phrases: the spotting counters that belong to this chunk
 };
 
 // hypotheses of a stream's last complete chunk, copied aside when later chunks of the stream may go on decoding
@@ -206,7 +216,9 @@ struct EncGroup {
   std::vector<int32_t> ctc_rows, kv_src, kv_dst;   // eager projections of the frames the group emits
   // activity option: per stream the span [t0, t1) of ctc_rows (one sc_ctc_activity job each, in this order); epoch = the
   // stream's reset count when the span was planned (a state that arrives after a reset is dropped)
-  struct ActSpan { int s, t0, t1; long epoch; bool restart; };
+  // (recorded when the activity or the spotting option is on; act / spot: which of the two scans it.  The spotting
+  // launch has the same job order; spot_epoch / spot_restart / mask are its own)
+  struct ActSpan { int s, t0, t1; long epoch; bool restart; bool act, spot; long spot_epoch; bool spot_restart; uint64_t mask; };
   std::vector<ActSpan> act;
   bool same_rows = true;
   std::vector<int> streams;                  // streams with work in this group (each at most once)
@@ -308,6 +320,21 @@ struct sc_streams {
   std::vector<long> act_pending;  // per stream: the latest group that carries a span of it (0: none since the reset)
   std::vector<long> act_epoch;    // per stream: resets so far
   std::vector<char> act_fresh;    // per stream: the next span starts the utterance
+  // ---- phrase spotting (sc_streams_set_phrases): everything below is allocated when a phrase set is first given ----------
+  bool spot_on = false;
+  int spot_P = 0;
+  int32_t *spot_labels = nullptr, *spot_lens = nullptr;   // device [64][32], [64]: the phrase set
+  double *spot_floors = nullptr;                          // device [64]
+  int32_t *spot_counters = nullptr;   // device [S][2]: n_frames, n_events of every stream (advanced group by group)
+  double *spot_values = nullptr;      // device [S][64][64]
+  int32_t *spot_starts = nullptr;     // device [S][64][64]
+  sc_spot_event *spot_events = nullptr;   // device [S][SC_SPOT_MAX_EVENTS]
+  sc_ctc_spot_job *spot_jobs_host = nullptr, *spot_jobs_dev = nullptr;   // [N_ARENA][S]: the job table of a group's launch
+  int32_t *spot_out_host = nullptr, *spot_out_dev = nullptr;             // [N_ARENA][S][2] host-mapped: the jobs' counters-after
+  std::vector<SpotVal> spot_known, spot_rep;   // per stream: after the latest RETIRED group / of the last reported chunk
+  std::vector<long> spot_pending, spot_epoch;  // per stream: as act_pending / act_epoch
+  std::vector<char> spot_fresh;                // per stream: the next span starts the utterance
+  std::vector<uint64_t> spot_mask;             // per stream: enabled phrases
   // ---- tick engine -----------------------------------------------------------------------------------------------------
   std::vector<St> st;
   std::vector<Run> run;
@@ -504,6 +531,12 @@ void reset_stream(sc_streams *b, int s) {
     b->act_known[s] = b->act_rep[s] = ActVal();
     b->act_pending[s] = 0;
     b->act_fresh[s] = 1;
+  }
+  if (!b->spot_epoch.empty()) {   // spotting: the same
+    b->spot_epoch[s]++;
+    b->spot_known[s] = b->spot_rep[s] = SpotVal();
+    b->spot_pending[s] = 0;
+    b->spot_fresh[s] = 1;
   }
   init_hyp(b, s);
 }
@@ -883,7 +916,19 @@ int retire_groups(sc_streams *b) {
     // activity: the states-after of the group's jobs -> the chunks they belong to (open, or reported in the meantime)
     for (size_t i = 0; i < g->act.size(); ++i) {
       const EncGroup::ActSpan &sp = g->act[i];
-      if (sp.epoch != b->act_epoch[sp.s]) continue;
+      if (sp.spot && sp.spot_epoch == b->spot_epoch[sp.s]) {   // spotting: the counters-after, handed over the same way
+        SpotVal &k = b->spot_known[sp.s];
+        k.ready = true;
+        k.gen = g->gen;
+        memcpy(k.v, b->spot_out_host + ((size_t)g->slot * b->S + i) * 2, sizeof k.v);
+        auto fill = [&](SpotVal &a) {
+          if (!a.ready && a.gen == g->gen) a = k;
+        };
+        fill(b->job[sp.s].spot);
+        for (Job &j : b->ahead[sp.s]) fill(j.spot);
+        fill(b->spot_rep[sp.s]);
+      }
+      if (!sp.act || sp.epoch != b->act_epoch[sp.s]) continue;
       ActVal &k = b->act_known[sp.s];
       k.ready = true;
       k.gen = g->gen;
@@ -927,7 +972,7 @@ int project_rows(sc_streams *b, EncGroup &g) {
     RC_TRY(b->itensor(g.ctc_rows, &ar));
     RC_TRY(sc_gemm(b->enc, ar, d, e->f("ctc_w"), e->f("ctc_b"), const_cast<float *>(b->sb.ctcx), ar, V, (int)g.ctc_rows.size(),
                    V, d, b->gemm_flags, 0, b->es));
-    if (!g.act.empty()) {
+    if (!g.act.empty() && g.act[0].act) {   // (every span of a group carries the same options)
       // activity: ONE launch for the group, behind the projection of the rows it reads (raw logits: the in-place
       // log-softmax of a first block runs on the decode stream behind this group's event)
       const int n = (int)g.act.size();
@@ -952,6 +997,34 @@ int project_rows(sc_streams *b, EncGroup &g) {
       HIP_TRY(hipMemcpyAsync(b->act_jobs_dev + o, b->act_jobs_host + o, (size_t)n * sizeof(sc_ctc_activity_job),
                              hipMemcpyHostToDevice, b->es));
       RC_TRY(sc_ctc_activity(b->act_jobs_dev + o, n, b->es));
+    }
+    if (!g.act.empty() && g.act[0].spot) {
+      // spotting: ONE launch for the group, in the same place and over the same spans
+      const int n = (int)g.act.size();
+      if (n > b->S) {
+        sc_set_error("spotting: %d spans in a group of a batch of %d streams (internal error)", n, b->S);
+        return SC_ERR_ARG;
+      }
+      const size_t o = (size_t)g.slot * b->S;
+      for (int i = 0; i < n; ++i) {
+        const EncGroup::ActSpan &sp = g.act[i];
+        sc_ctc_spot_job &j = b->spot_jobs_host[o + i];
+        j.table = b->sb.ctcx + (size_t)sp.s * b->TCAP * V;
+        j.labels = b->spot_labels; j.lens = b->spot_lens; j.floors = b->spot_floors;
+        j.counters = b->spot_counters + (size_t)sp.s * 2;
+        j.values = b->spot_values + (size_t)sp.s * SC_SPOT_MAX_PHRASES * SC_SPOT_STATES;
+        j.starts = b->spot_starts + (size_t)sp.s * SC_SPOT_MAX_PHRASES * SC_SPOT_STATES;
+        j.events = b->spot_events + (size_t)sp.s * SC_SPOT_MAX_EVENTS;
+        j.state_after = b->spot_out_dev + (o + i) * 2;
+        j.stride = V;
+        j.mask = sp.mask;
+        j.V = V; j.blank = c.blank_id; j.t0 = sp.t0; j.t1 = sp.t1;
+        j.restart = sp.spot_restart ? 1 : 0;
+        j.P = b->spot_P;
+      }
+      HIP_TRY(hipMemcpyAsync(b->spot_jobs_dev + o, b->spot_jobs_host + o, (size_t)n * sizeof(sc_ctc_spot_job),
+                             hipMemcpyHostToDevice, b->es));
+      RC_TRY(sc_ctc_spot(b->spot_jobs_dev + o, n, b->es));
     }
   }
   if (!g.kv_dst.empty()) {
@@ -1571,9 +1644,20 @@ int admit(sc_streams *b, std::vector<Chunk> chunks, bool features, bool defer, s
     const int c0 = std::max(t0, st.T_proj), k0 = std::max(t0, st.T_projkv);
     g->same_rows = g->same_rows && c0 == k0;
     for (int t = c0; t < t1; ++t) g->ctc_rows.push_back(ch.s * b->TCAP + t);
-    if (b->act_on && c0 < t1) {
-      g->act.push_back({ch.s, c0, t1, b->act_epoch[ch.s], b->act_fresh[ch.s] != 0});
-      b->act_fresh[ch.s] = 0;
+    if ((b->act_on || b->spot_on) && c0 < t1) {
+      EncGroup::ActSpan sp = {ch.s, c0, t1, 0, false, b->act_on, b->spot_on, 0, false, 0};
+      if (b->act_on) {
+        sp.epoch = b->act_epoch[ch.s];
+        sp.restart = b->act_fresh[ch.s] != 0;
+        b->act_fresh[ch.s] = 0;
+      }
+      if (b->spot_on) {
+        sp.spot_epoch = b->spot_epoch[ch.s];
+        sp.spot_restart = b->spot_fresh[ch.s] != 0;
+        sp.mask = b->spot_mask[ch.s];
+        b->spot_fresh[ch.s] = 0;
+      }
+      g->act.push_back(sp);
       act_new.push_back(ch.s);
     }
     for (int t = k0; t < t1; ++t) {
@@ -1656,6 +1740,16 @@ int admit(sc_streams *b, std::vector<Chunk> chunks, bool features, bool defer, s
         j.act.gen = b->act_pending[s];
       } else {
         j.act = b->act_known[s];
+      }
+    }
+    if (b->spot_on) {   // (the same hand-over for the spotting counters)
+      const int s = chunks[k].s;
+      if (gen && std::find(act_new.begin(), act_new.end(), s) != act_new.end()) b->spot_pending[s] = gen;
+      if (b->spot_pending[s] > b->gen_done) {
+        j.spot.ready = false;
+        j.spot.gen = b->spot_pending[s];
+      } else {
+        j.spot = b->spot_known[s];
       }
     }
     if (b->job[chunks[k].s].open) b->ahead[chunks[k].s].push_back(j);   // behind the stream's outstanding chunk(s)
@@ -2275,6 +2369,7 @@ int report_chunk(sc_streams *b, int s) {
   const int status = j.fault ? j.fault : j.has_out;
   if (j.fault && !j.dropped) reset_stream(b, s);   // (fault_msg[s] keeps the message: sc_stream_last_error)
   if (b->act_on && !j.fault) b->act_rep[s] = j.act;
+  if (b->spot_on && !j.fault) b->spot_rep[s] = j.spot;
   if (b->snap[s].valid && b->snap[s].seq == j.seq) b->snap[s].reported = true;   // handed out: free at the next sc_poll
   b->done_at[s] = 0;
   if (b->ahead[s].empty()) j = Job();
@@ -2892,6 +2987,142 @@ extern "C" int sc_streams_read_activity(sc_streams *b, int stream, double *host,
     HIP_TRY(hipStreamSynchronize(b->stream_rb));
   }
   return T;
+  SC_API_END
+}
+
+// ---- phrase spotting ----------------------------------------------------------------------------------------------------
+extern "C" int sc_streams_set_phrases(sc_streams *b, const int32_t *labels, const int32_t *lens, const double *min_scores,
+                                      int n_phrases) {
+  SC_CHECK_ARG(b, "null");
+  SC_API_BEGIN
+  SC_CHECK_ARG(b->n_open == 0, "chunks are outstanding");
+  SC_CHECK_ARG(n_phrases >= 0 && n_phrases <= SC_SPOT_MAX_PHRASES, "a phrase set holds 0..64 phrases");
+  if (n_phrases == 0) {
+    b->spot_on = false;
+    return SC_OK;
+  }
+  SC_CHECK_ARG(labels && lens && min_scores, "null phrase set");
+  const int V = b->cfg.vocab_size, blank = b->cfg.blank_id;
+  std::vector<int32_t> lab((size_t)SC_SPOT_MAX_PHRASES * SC_SPOT_MAX_LEN, 0), len(SC_SPOT_MAX_PHRASES, 0);
+  std::vector<double> fl(SC_SPOT_MAX_PHRASES, 0.0);
+  for (int p = 0; p < n_phrases; ++p) {
+    SC_CHECK_ARG(lens[p] >= 1 && lens[p] <= SC_SPOT_MAX_LEN, "a phrase has 1..32 labels");
+    SC_CHECK_ARG(min_scores[p] <= 0.0, "min_score must be <= 0");
+    for (int i = 0; i < lens[p]; ++i) {
+      const int32_t y = labels[(size_t)p * SC_SPOT_MAX_LEN + i];
+      SC_CHECK_ARG(y >= 0 && y < V && y != blank, "a label outside the vocabulary or equal to the blank");
+      lab[(size_t)p * SC_SPOT_MAX_LEN + i] = y;
+    }
+    len[p] = lens[p];
+    fl[p] = min_scores[p];
+  }
+  HIP_TRY(hipSetDevice(b->eng->device));
+  if (!b->spot_counters) {
+    const size_t S = (size_t)b->S, PS = (size_t)SC_SPOT_MAX_PHRASES * SC_SPOT_STATES;
+    RC_TRY(b->alloc(&b->spot_labels, lab.size()));
+    RC_TRY(b->alloc(&b->spot_lens, len.size()));
+    RC_TRY(b->alloc(&b->spot_floors, fl.size()));
+    RC_TRY(b->alloc(&b->spot_counters, S * 2));
+    RC_TRY(b->alloc(&b->spot_values, S * PS));
+    RC_TRY(b->alloc(&b->spot_starts, S * PS));
+    RC_TRY(b->alloc(&b->spot_events, S * SC_SPOT_MAX_EVENTS));
+    RC_TRY(b->alloc(&b->spot_jobs_dev, S * N_ARENA));
+    RC_TRY(b->halloc(&b->spot_jobs_host, S * N_ARENA));
+    RC_TRY(b->halloc(&b->spot_out_host, S * N_ARENA * 2));
+    void *dv = nullptr;
+    if (hipHostGetDevicePointer(&dv, b->spot_out_host, 0) != hipSuccess || !dv) {
+      sc_set_error("sc_streams_set_phrases: the pinned counter slots are not visible to the device");
+      return SC_ERR_LAUNCH;
+    }
+    b->spot_out_dev = (int32_t *)dv;
+    b->spot_known.assign(S, SpotVal());
+    b->spot_rep.assign(S, SpotVal());
+    b->spot_pending.assign(S, 0);
+    b->spot_epoch.assign(S, 0);
+    b->spot_fresh.assign(S, 1);
+    b->spot_mask.assign(S, ~0ull);
+  }
+  // no chunk is outstanding, so no group that reads the old set is in flight; the copies below are synchronous
+  HIP_TRY(hipStreamSynchronize(b->es));
+  HIP_TRY(hipMemcpy(b->spot_labels, lab.data(), lab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b->spot_lens, len.data(), len.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b->spot_floors, fl.data(), fl.size() * sizeof(double), hipMemcpyHostToDevice));
+  // every stream starts over: a stream in mid-utterance is scanned from its next frame on
+  for (int s = 0; s < b->S; ++s) {
+    b->spot_epoch[s]++;
+    b->spot_known[s] = b->spot_rep[s] = SpotVal();
+    b->spot_pending[s] = 0;
+    b->spot_fresh[s] = 1;
+    b->spot_mask[s] = ~0ull;
+  }
+  b->spot_P = n_phrases;
+  b->spot_on = true;
+  return SC_OK;
+  SC_API_END
+}
+
+extern "C" int sc_stream_set_phrase_mask(sc_streams *b, int stream, uint64_t mask) {
+  SC_CHECK_ARG(b && stream >= 0 && stream < b->S, "bad arguments");
+  SC_CHECK_ARG(b->spot_on, "the spotting option is off (sc_streams_set_phrases)");
+  b->spot_mask[stream] = mask;
+  return SC_OK;
+}
+
+// the counters of the stream's last reported chunk, complete: its encoder group may still be held back or in flight
+static int spot_ready(sc_streams *b, int s) {
+  SpotVal &r = b->spot_rep[s];
+  if (r.ready) return SC_OK;
+  RC_TRY(wait_group(b, r.gen));
+  if (!r.ready) {
+    sc_set_error("spotting counters of stream %d did not arrive with their encoder group (internal error)", s);
+    return SC_ERR_LAUNCH;
+  }
+  return SC_OK;
+}
+
+extern "C" int sc_stream_spot(sc_streams *b, int stream, sc_spot_t *out) {
+  SC_CHECK_ARG(b && out && stream >= 0 && stream < b->S, "bad arguments");
+  SC_API_BEGIN
+  SC_CHECK_ARG(b->spot_on, "the spotting option is off (sc_streams_set_phrases)");
+  HIP_TRY(hipSetDevice(b->eng->device));
+  RC_TRY(spot_ready(b, stream));
+  out->n_frames = b->spot_rep[stream].v[0];
+  out->n_events = b->spot_rep[stream].v[1];
+  return SC_OK;
+  SC_API_END
+}
+
+extern "C" int sc_streams_read_spot_events(sc_streams *b, int stream, sc_spot_event *host, int max) {
+  SC_CHECK_ARG(b && stream >= 0 && stream < b->S && max >= 0, "bad arguments");
+  SC_API_BEGIN
+  SC_CHECK_ARG(b->spot_on, "the spotting option is off (sc_streams_set_phrases)");
+  HIP_TRY(hipSetDevice(b->eng->device));
+  RC_TRY(spot_ready(b, stream));
+  const int n = std::min(std::min((int)b->spot_rep[stream].v[1], SC_SPOT_MAX_EVENTS), max);
+  if (host && n > 0) {   // (the group that wrote these slots has been retired; later groups write behind them)
+    HIP_TRY(hipMemcpyAsync(host, b->spot_events + (size_t)stream * SC_SPOT_MAX_EVENTS, (size_t)n * sizeof(sc_spot_event),
+                           hipMemcpyDeviceToHost, b->stream_rb));
+    HIP_TRY(hipStreamSynchronize(b->stream_rb));
+  }
+  return n;
+  SC_API_END
+}
+
+extern "C" int sc_streams_read_spot_state(sc_streams *b, int stream, double *values, int32_t *starts) {
+  SC_CHECK_ARG(b && stream >= 0 && stream < b->S && values && starts, "bad arguments");
+  SC_API_BEGIN
+  SC_CHECK_ARG(b->spot_on, "the spotting option is off (sc_streams_set_phrases)");
+  HIP_TRY(hipSetDevice(b->eng->device));
+  RC_TRY(launch_pending_groups(b));
+  HIP_TRY(hipStreamSynchronize(b->es));
+  const size_t n = (size_t)b->spot_P * SC_SPOT_STATES, o = (size_t)stream * SC_SPOT_MAX_PHRASES * SC_SPOT_STATES;
+  if (b->spot_fresh[stream]) {   // nothing of this utterance has been scanned: the block still holds the previous one
+    for (size_t i = 0; i < n; ++i) { values[i] = -INFINITY; starts[i] = -1; }
+    return b->spot_P;
+  }
+  HIP_TRY(hipMemcpy(values, b->spot_values + o, n * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(starts, b->spot_starts + o, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return b->spot_P;
   SC_API_END
 }
 

@@ -33,6 +33,7 @@ import numpy as np
 import torch
 
 from .activity import INITIAL, advance as activity_advance, as_arrays as activity_arrays
+from . import spotting
 from .config import SearchConfig
 from .weights import PackedWeights
 
@@ -269,6 +270,7 @@ class StreamBatch:
             backend.bind_stream(self.stream)
         self.st = [StreamState() for _ in range(S)]
         self._act = None   # acoustic activity (set_activity): off
+        self._spot = None  # phrase spotting (set_phrases): off
         self.reset_all()
         self.stats = {"enc_calls": 0, "dec_steps": 0, "dec_blocks": 0}
         # optional host-side phase timers (SC_TIMING=1): seconds per phase
@@ -351,6 +353,9 @@ class StreamBatch:
             self._act["state"][s] = INITIAL
             self._act["proj"][s] = ns.T_ctc    # strict: the stale table's rows are not projected again, so not scanned
             self._act["T"][s] = 0
+        if self._spot is not None:
+            self._spot["state"][s] = spotting.initial(self._spot["set"].P)
+            self._spot["proj"][s] = ns.T_ctc
         if getattr(self, "stream", None) is not None:
             with torch.cuda.stream(self.stream):   # same stream as the kernels that read it
                 self._init_hyp(s)
@@ -402,24 +407,78 @@ class StreamBatch:
             raise EngineError("the activity option is off (set_activity)")
         return self._act["track"][int(s), :int(self._act["T"][int(s)])].copy()
 
+    # ------------------------------------------------------------------
+    # phrase spotting (the native engine: sc_streams_set_phrases)
+    # ------------------------------------------------------------------
+    def set_phrases(self, phrases, min_scores=None):
+        """Phrase spotting from the CTC table: ``phrases`` is a list of up to 64 token-id sequences (1..32 ids, no
+        blank), ``min_scores`` their floors (default -2.0 per token).  With a set in place every chunk step projects the
+        CTC rows of the frames its encoder stage emits right away (as set_activity does) and runs the recurrence of
+        speechcatcher_amd.spotting over them in numpy float64; the search is not touched.  An empty list or None
+        switches the option off.  Every stream's state starts over."""
+        if not phrases:
+            self._spot = None
+            return
+        try:
+            ps = spotting.PhraseSet(phrases, min_scores, self.cfg.vocab_size, self.cfg.blank_id)
+        except ValueError as e:
+            raise EngineError(str(e)) from e
+        self._spot = {"set": ps, "state": [spotting.initial(ps.P) for _ in range(self.S)],
+                      "mask": [spotting.ALL] * self.S, "proj": np.asarray([x.T_ctc for x in self.st], np.int64)}
+
+    def set_phrase_mask(self, s: int, mask: int):
+        """bit p of ``mask``: phrase p is enabled for stream s (default: all); from the next chunk on"""
+        if self._spot is None:
+            raise EngineError("the spotting option is off (set_phrases)")
+        self._spot["mask"][int(s)] = int(mask) & spotting.ALL
+
+    def spot(self, streams: Sequence[int]):
+        """{"n_frames", "n_events": int32 array [n]} of the listed streams after their last chunk"""
+        if self._spot is None:
+            raise EngineError("the spotting option is off (set_phrases)")
+        st = [self._spot["state"][int(s)] for s in streams]
+        return {k: np.asarray([x[k] for x in st], np.int32) for k in ("n_frames", "n_events")}
+
+    def spot_events(self, s: int):
+        """[(end, phrase, start, score)]: the stored events of stream s's utterance so far, ordered by (end, phrase)"""
+        if self._spot is None:
+            raise EngineError("the spotting option is off (set_phrases)")
+        return list(self._spot["state"][int(s)]["events"])
+
+    def read_spot_state(self, s: int):
+        """test aid: (values [P, 64] float64, starts [P, 64] int32) of stream s"""
+        st = self._spot["state"][int(s)]
+        return st["values"].copy(), st["starts"].copy()
+
     def _scan_activity(self, t_old: Dict[int, int]):
-        """The frames [t_old[s], T_enc) the encoder stage of this chunk step emitted: CTC rows, blank posteriors in torch
-        float64, state update."""
-        a, cfg = self._act, self.cfg
+        """The frames [t_old[s], T_enc) the encoder stage of this chunk step emitted: CTC rows, then blank posteriors in
+        torch float64 and the activity state update (set_activity) and / or the spotting recurrence (set_phrases)."""
+        a, sp, cfg = self._act, self._spot, self.cfg
+        proj = a["proj"] if a is not None else sp["proj"]   # (both options project the same rows: one watermark)
         spans = []
         for s, t0 in t_old.items():
             t1 = self.st[s].T_enc
-            c0 = max(t0, int(a["proj"][s]))
+            c0 = max(t0, int(proj[s]))
             if t1 > c0:
                 spans.append((s, c0, t1))
-                a["proj"][s] = t1
+                proj[s] = t1
+                if a is not None and sp is not None:
+                    sp["proj"][s] = t1
         if not spans:
             return
         rows = np.concatenate([s * self.TCAP + _AR[c0:t1] for s, c0, t1 in spans])
         ar = self._itensor(rows)
         V, m = cfg.vocab_size, int(rows.shape[0])
         self.be.gemm(self.enc, ar, cfg.d_model, self.w.ctc_w, self.w.ctc_b, self.ctcx, ar, V, m, V, cfg.d_model)
-        x = self.ctcx[torch.as_tensor(rows, dtype=torch.int64, device=self.dev)].to(torch.float64)
+        x32 = self.ctcx[torch.as_tensor(rows, dtype=torch.int64, device=self.dev)]
+        if sp is not None:
+            xs, o = x32.cpu().numpy(), 0
+            for s, c0, t1 in spans:
+                spotting.advance(sp["state"][s], xs[o:o + t1 - c0], cfg.blank_id, sp["set"], sp["mask"][s])
+                o += t1 - c0
+        if a is None:
+            return
+        x = x32.to(torch.float64)
         bad = torch.isnan(x).any(1) | (x == float("inf")).any(1) | (x.max(1).values == float("-inf"))
         x = torch.where(bad[:, None], torch.zeros_like(x), x)
         p = torch.exp(x[:, cfg.blank_id] - torch.logsumexp(x, 1))
@@ -663,7 +722,8 @@ class StreamBatch:
         # n < 3: encoder skipped, frames discarded (beam_search.py:551-559)
         if enc_streams:
             t_ph = time.perf_counter()
-            t_old = {s: self.st[s].T_enc for s in enc_streams} if self._act is not None else None
+            t_old = ({s: self.st[s].T_enc for s in enc_streams}
+                     if self._act is not None or self._spot is not None else None)
             self._encode(enc_streams, feat_new, finals)
             if t_old is not None:
                 self._scan_activity(t_old)

@@ -340,6 +340,63 @@ class HipBackend:
         tr = track.cpu().numpy()
         return state.cpu().numpy()[:n], [tr[k, :int(jobs[k][0].shape[0])] for k in range(n)], after.cpu().numpy()[:n]
 
+    def ctc_spot(self, jobs, labels, lens, floors, tweak=None):
+        """Batched CTC phrase-spotting scan (sc_ctc_spot) on the caller's tables, one launch for all jobs.  labels
+        [P, 32] int32, lens [P] int32, floors [P] float64: the phrase set (speechcatcher_amd.spotting.PhraseSet).  jobs:
+        list of (table [T, V] fp32 tensor, rows may be strided; blank; t0; t1; state: a dict as returned here or None =
+        the span starts an utterance; mask).  Returns (states: list of {n_frames, n_events, values [P, 64] float64,
+        starts [P, 64] int32, events: the stored (end, phrase, start, score), raw_events: the events array as int32
+        [64, 6]}, counters_after [n, 2] int32: the second
+        copy, -7 where a job wrote nothing).  ``tweak(k, job)``: test aid, edits the sc_ctc_spot_job of job k before the
+        launch; a job that starts an utterance is handed a state block filled with -7, so what it leaves unwritten shows."""
+        import numpy as np
+        n = len(jobs)
+        dev = self.device
+        P = int(np.asarray(lens).shape[0])
+        NS, NE = _abi.SPOT_STATES, _abi.SPOT_MAX_EVENTS
+        lab_d = torch.as_tensor(np.ascontiguousarray(labels, np.int32).reshape(P, _abi.SPOT_MAX_LEN)).to(dev)
+        len_d = torch.as_tensor(np.ascontiguousarray(lens, np.int32)).to(dev)
+        flo_d = torch.as_tensor(np.ascontiguousarray(floors, np.float64)).to(dev)
+        cnt = np.full((max(n, 1), 2), -7, np.int32)
+        val = np.full((max(n, 1), P, NS), -7.0, np.float64)
+        sta = np.full((max(n, 1), P, NS), -7, np.int32)
+        evt = np.zeros((max(n, 1), NE, 6), np.int32)       # sc_spot_event: four int32 and a double
+        evt[:] = -7
+        for k, job in enumerate(jobs):
+            st = job[4]
+            if st is not None:
+                cnt[k] = (st["n_frames"], st["n_events"])
+                val[k], sta[k] = st["values"], st["starts"]
+                for i, (end, ph, start, score) in enumerate(st["events"]):
+                    evt[k, i, :4] = (end, ph, start, 0)
+                    evt[k, i, 4:] = np.frombuffer(np.float64(score).tobytes(), np.int32)
+        cnt_d, val_d, sta_d, evt_d = (torch.as_tensor(a).to(dev) for a in (cnt, val, sta, evt))
+        after = torch.full((max(n, 1), 2), -7, dtype=torch.int32, device=dev)
+        tab = (_abi.SpotJob * max(1, n))()
+        for k, (table, blank, t0, t1, st, mask) in enumerate(jobs):
+            assert table.dtype == torch.float32 and table.dim() == 2 and table.stride(1) == 1
+            assert 0 <= t0 <= t1 <= table.shape[0]
+            j = tab[k]
+            j.table, j.labels, j.lens, j.floors = table.data_ptr(), lab_d.data_ptr(), len_d.data_ptr(), flo_d.data_ptr()
+            j.counters, j.values, j.starts = cnt_d[k].data_ptr(), val_d[k].data_ptr(), sta_d[k].data_ptr()
+            j.events, j.state_after = evt_d[k].data_ptr(), after[k].data_ptr()
+            j.stride, j.mask, j.V, j.blank = table.stride(0), int(mask) & ((1 << 64) - 1), table.shape[1], int(blank)
+            j.t0, j.t1, j.restart, j.P = int(t0), int(t1), 1 if st is None else 0, P
+            if tweak is not None:
+                tweak(k, j)
+        tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+        self._chk(self.lib.sc_ctc_spot(tab_dev.data_ptr(), n, self._stream()), "sc_ctc_spot")
+        torch.cuda.synchronize(dev)
+        cnt, val, sta, evt = (a.cpu().numpy() for a in (cnt_d, val_d, sta_d, evt_d))
+        out = []
+        for k in range(n):
+            ne = int(cnt[k, 1])
+            ev = [(int(e[0]), int(e[1]), int(e[2]), float(np.frombuffer(e[4:].tobytes(), np.float64)[0]))
+                  for e in evt[k, :max(0, min(ne, NE))]]
+            out.append({"n_frames": int(cnt[k, 0]), "n_events": ne, "values": val[k], "starts": sta[k], "events": ev,
+                        "raw_events": evt[k]})
+        return out, after.cpu().numpy()[:n]
+
     # ------------------------------------------------------------------
     def search_struct(self, sb):
         cached = getattr(sb, "_sc_search_struct", None)

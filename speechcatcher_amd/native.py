@@ -399,6 +399,66 @@ class NativeStreamBatch:
             _abi.check(T, "sc_streams_read_activity")
         return a[:T].copy()
 
+    # ---- phrase spotting (sc_streams_set_phrases) --------------------------------------------
+    def set_phrases(self, phrases, min_scores=None):
+        """Phrase spotting from the CTC table: ``phrases`` is a list of up to 64 token-id sequences (1..32 ids, no
+        blank), ``min_scores`` their floors (default -2.0 per token).  With a set in place every admission group scans
+        the CTC rows it projects (one extra launch per group); the search is not touched.  An empty list or None
+        switches the option off (the default).  Only while no chunk is outstanding; every stream's state starts over."""
+        from .spotting import PhraseSet
+        try:
+            if not phrases:
+                _abi.check(self.lib.sc_streams_set_phrases(self.handle, None, None, None, 0), "sc_streams_set_phrases")
+                self._phrases = None
+                return
+            ps = PhraseSet(phrases, min_scores, self.cfg.vocab_size, self.cfg.blank_id)
+            _abi.check(self.lib.sc_streams_set_phrases(self.handle, ps.labels.ctypes.data, ps.lens.ctypes.data,
+                                                       ps.floors.ctypes.data, ps.P), "sc_streams_set_phrases")
+            self._phrases = ps
+        except (_abi.ScasrError, ValueError) as e:
+            raise EngineError(str(e)) from e
+
+    def set_phrase_mask(self, s: int, mask: int):
+        """bit p of ``mask``: phrase p is enabled for stream s (default: all); from the next chunk on"""
+        try:
+            _abi.check(self.lib.sc_stream_set_phrase_mask(self.handle, int(s), int(mask) & ((1 << 64) - 1)),
+                       "sc_stream_set_phrase_mask")
+        except _abi.ScasrError as e:
+            raise EngineError(str(e)) from e
+
+    def spot(self, streams: Sequence[int]):
+        """{"n_frames", "n_events": int32 array [n]} of the listed streams' last reported chunks"""
+        out = {k: np.zeros(len(streams), np.int32) for k in ("n_frames", "n_events")}
+        a = _abi.Spot()
+        for i, s in enumerate(streams):
+            try:
+                _abi.check(self.lib.sc_stream_spot(self.handle, int(s), C.byref(a)), "sc_stream_spot")
+            except _abi.ScasrError as e:
+                raise EngineError(str(e)) from e
+            out["n_frames"][i], out["n_events"][i] = a.n_frames, a.n_events
+        return out
+
+    def spot_events(self, s: int):
+        """[(end, phrase, start, score)]: the stored events (the utterance's first 64) the state of stream s's last
+        reported chunk covers, ordered by (end, phrase); frames of the utterance, both inclusive"""
+        ev = (_abi.SpotEvent * _abi.SPOT_MAX_EVENTS)()
+        n = self.lib.sc_streams_read_spot_events(self.handle, int(s), C.addressof(ev), _abi.SPOT_MAX_EVENTS)
+        if n < 0:
+            try:
+                _abi.check(n, "sc_streams_read_spot_events")
+            except _abi.ScasrError as e:
+                raise EngineError(str(e)) from e
+        return [(e.end, e.phrase, e.start, e.score) for e in ev[:n]]
+
+    def read_spot_state(self, s: int):
+        """test aid: (values [P, 64] float64, starts [P, 64] int32) of stream s as the device holds them now"""
+        P = self._phrases.P
+        v, st = np.zeros((P, _abi.SPOT_STATES), np.float64), np.zeros((P, _abi.SPOT_STATES), np.int32)
+        n = self.lib.sc_streams_read_spot_state(self.handle, int(s), v.ctypes.data, st.ctypes.data)
+        if n < 0:
+            _abi.check(n, "sc_streams_read_spot_state")
+        return v, st
+
     def hypotheses_batch(self, streams: Sequence[int], nbest: Optional[int] = None):
         """{stream: [hypothesis dicts, best first]} for the listed streams, one device round trip for all."""
         a = self.hypotheses_arrays(streams, nbest)

@@ -19,6 +19,7 @@ from typing import Deque, Dict, List, Optional, Tuple
 import numpy as np
 
 from .engine import StreamBatch
+from . import spotting
 from .activity import of_stream as activity_of_stream
 from .align import FeatureClock
 from .resample import OutputClock, check_input_rate
@@ -45,10 +46,19 @@ class ActivityResults(AlignedResults):
     activity: Optional[dict] = None
 
 
+class SpottingResults(ActivityResults):
+    """the results of a reply and ``detections``: the phrase-spotting events of the session's stream that are new since
+    the session's previous reply - StreamScheduler(phrases=...).  Each is {"phrase": index in the set, "start", "end":
+    encoder frames of the utterance (both inclusive), "score", "start_s", "end_s": seconds of the utterance's audio}.
+    ``alignment`` / ``activity`` are carried as well when those options are on."""
+    detections: Optional[list] = None
+
+
 class StreamScheduler:
     def __init__(self, batch: StreamBatch, token_list: Optional[List[str]] = None,
                  result_format: str = "native", reset_after_final: bool = True, reset_on_open: bool = True,
-                 queue_depth: int = 1, align_final: bool = False, activity: bool = False, blank_threshold: float = 0.8):
+                 queue_depth: int = 1, align_final: bool = False, activity: bool = False, blank_threshold: float = 0.8,
+                 phrases=None, min_scores=None):
         """``queue_depth`` > 1 (C++ engine, ``pump``): up to that many queued chunks of a session are handed to the engine
         at a time (sc_streams_set_queue_depth) - for sessions whose audio is already there (files): the encoder stage of
         the next chunk runs beside the decoding of the current one.  Replies and their order per session do not change.
@@ -66,6 +76,11 @@ class StreamScheduler:
         # speech / silence state of the session's stream for that chunk (batch.set_activity(True, blank_threshold)), read
         # before the stream is reset after a final
         self.activity = False
+        # ``phrases`` (token-id sequences; ``min_scores``: their floors): every reply (an exception aside) is a
+        # ``SpottingResults`` whose ``detections`` are the events new since the session's previous reply
+        # (batch.set_phrases), read before the stream is reset after a final
+        self.spotting = False
+        self._spot_seen: Dict[int, int] = {}                  # per session: events of its utterance handed out so far
         self._clock: Dict[int, FeatureClock] = {}             # align_final: per session, the calls since its last reset
         self._fed: Dict[int, Deque[Tuple[int, bool]]] = {}   # ... and its fed chunks not reported yet (length, final)
         self.reset_after_final, self.reset_on_open = reset_after_final, reset_on_open
@@ -90,11 +105,23 @@ class StreamScheduler:
         self._next_sid = 0
         if activity:
             self.enable_activity(blank_threshold)
+        if phrases:
+            self.enable_spotting(phrases, min_scores)
 
     def enable_activity(self, blank_threshold: float = 0.8):
         """switch the ``activity`` option on (only while no chunk is at the engine; every stream's state starts over)"""
         self.batch.set_activity(True, blank_threshold)
         self.activity = True
+
+    def enable_spotting(self, phrases, min_scores=None):
+        """switch the ``phrases`` option on (only while no chunk is at the engine; every stream's state starts over)"""
+        self.batch.set_phrases(phrases, min_scores)
+        self.spotting = True
+        self._spot_seen.clear()
+
+    @property
+    def _clocked(self) -> bool:   # the options that need the sessions' feature clocks
+        return self.align_final or self.spotting
 
     # ---- session lifecycle -------------------------------------------------
     def open(self, sample_rate: int = 16000) -> int:
@@ -115,6 +142,7 @@ class StreamScheduler:
         self._clock.pop(sid, None)
         self._fed.pop(sid, None)
         self._rate[sid] = OutputClock(sample_rate)
+        self._spot_seen.pop(sid, None)
         return sid
 
     def _set_slot_rate(self, slot: int, rate: int):
@@ -156,6 +184,7 @@ class StreamScheduler:
         self._clock.pop(sid, None)
         self._fed.pop(sid, None)
         self._rate.pop(sid, None)
+        self._spot_seen.pop(sid, None)
         if self.reset_on_open:
             self.batch.reset(slot)
         self._free.append(slot)
@@ -169,7 +198,7 @@ class StreamScheduler:
         """Queue one chunk of a session (float PCM in +-1, like the reference API) at the session's sample rate."""
         self._queue[sid].append((np.asarray(pcm, dtype=np.float32), bool(is_final), bool(finalize_all)))
         n16 = self._rate[sid].call(int(np.shape(pcm)[0]), bool(is_final))   # the call in 16 kHz samples: the engine's clock
-        if self.align_final:
+        if self._clocked:
             self._fed.setdefault(sid, deque()).append((n16, bool(is_final)))
 
     def pending(self) -> int:
@@ -208,13 +237,14 @@ class StreamScheduler:
             act_row = {slot: i for i, slot in enumerate(act_slots)}
             act = self.batch.activity(act_slots) if act_slots else None
         for sid, (slot, fin, fa) in meta.items():
-            if self.align_final:              # the stream's clock advances by the reported chunk
+            if self._clocked and self._fed.get(sid):   # the stream's clock advances by the reported chunk
                 n, f = self._fed[sid].popleft()
                 cfg = self.batch.cfg
                 self._clock.setdefault(sid, FeatureClock(cfg.win_length, cfg.hop_length)).call(n, f)
             if isinstance(has[slot], Exception):
                 out[sid] = has[slot]          # the engine has reset the stream
                 self._clock.pop(sid, None)
+                self._spot_seen.pop(sid, None)
                 continue
             if not has[slot]:
                 out[sid] = []
@@ -230,9 +260,32 @@ class StreamScheduler:
                 res.alignment = getattr(out[sid], "alignment", None)
                 res.activity = activity_of_stream(act, act_row[slot])
                 out[sid] = res
+            if self.spotting:
+                res = SpottingResults(out[sid])
+                res.alignment = getattr(out[sid], "alignment", None)
+                res.activity = getattr(out[sid], "activity", None)
+                res.detections = self._detections(sid, slot)
+                out[sid] = res
             if fin and self.reset_after_final:
                 self.batch.reset(slot)
                 self._clock.pop(sid, None)
+                self._spot_seen.pop(sid, None)
+        return out
+
+    def _detections(self, sid: int, slot: int) -> list:
+        """the stored events of the session's utterance that have not gone out yet (each goes out once)"""
+        seen = self._spot_seen.get(sid, 0)
+        n = min(int(self.batch.spot([slot])["n_events"][0]), spotting.MAX_EVENTS)
+        if n <= seen:
+            return []
+        cfg = self.batch.cfg
+        new = self.batch.spot_events(slot)[seen:n]
+        self._spot_seen[sid] = n
+        out = spotting.event_dicts(new)
+        secs = spotting.event_dicts(new, self._clock.get(sid) or FeatureClock(cfg.win_length, cfg.hop_length),
+                                    cfg.subsample, cfg.sample_rate)
+        for d, t in zip(out, secs):
+            d["start_s"], d["end_s"] = t["start"], t["end"]
         return out
 
     def _aligned(self, res: list, arrays, i, slot: int, fin: bool, fa: bool, clock) -> "AlignedResults":

@@ -116,6 +116,24 @@ class AcousticEndpointer:
         self.last = None
 
 
+def spotting_set(spotting: dict):
+    """{name: ids or [ids, ...]} -> (phrases: list of id sequences, names: the name each stands for).  Several id
+    sequences may stand for one phrase (other tokenisations of it)."""
+    phrases, names = [], []
+    for name, ids in spotting.items():
+        seqs = ids if len(ids) and isinstance(ids[0], (list, tuple, np.ndarray)) else [ids]
+        for y in seqs:
+            phrases.append([int(t) for t in y])
+            names.append(name)
+    return phrases, names
+
+
+def spotted_message(detections, names) -> dict:
+    """{"spotted": [{"phrase", "start", "end", "score"}]}: the phrase's name, start / end in seconds of the utterance"""
+    return {"spotted": [{"phrase": names[d["phrase"]], "start": round(d["start_s"], 3), "end": round(d["end_s"], 3),
+                         "score": d["score"]} for d in detections]}
+
+
 def vosk_partial(text: str) -> dict:
     return {"partial": text}
 
@@ -168,7 +186,8 @@ class ServerLoop:
     def __init__(self, scheduler: StreamScheduler, vosk_output_format: bool = False,
                  finalize_update_iters: int = 6, max_partial_iters: int = 42, strict_reference: bool = False,
                  continuous: Optional[bool] = None, min_replies: int = 1, vosk_alignment: bool = False,
-                 acoustic_endpointing: Optional[EndpointRules] = None):
+                 acoustic_endpointing: Optional[EndpointRules] = None, spotting: Optional[dict] = None,
+                 spotting_min_scores: Optional[dict] = None):
         """``strict_reference``: no stream reset after a finalised utterance nor between clients, exactly like
         ``recognize_ws`` / ``process_audio_chunk`` (speechcatcher_server.py:270,359-397); the default resets.
         ``continuous`` (default: on whenever the batch has the C++ engine's submit / poll - round 4; False forces one
@@ -182,7 +201,22 @@ class ServerLoop:
         ``acoustic_endpointing``: an utterance is also finalised when the acoustic rules fire (AcousticEndpointer: N ms of
         silence from the CTC blank posterior) - finalize = text endpointer or acoustic endpointer or forced.  Switches the
         scheduler's ``activity`` option on (blank threshold 0.8 unless the scheduler was built with another); needs the
-        reset after a final, so not with ``strict_reference``.  None (default): the reference's rule alone."""
+        reset after a final, so not with ``strict_reference``.  None (default): the reference's rule alone.
+        ``spotting``: {name: token ids, or a list of id sequences that all stand for the name} - phrase spotting from the
+        CTC table (the scheduler's ``phrases`` option; floors: ``spotting_min_scores`` {name: min_score}, default -2.0
+        per token).  When phrases were detected in the frames of a chunk, a {"spotted": [{"phrase", "start", "end",
+        "score"}]} message (seconds of the utterance) goes out in front of that chunk's reply.  Counts the frames of an
+        utterance from the reset after a final, so not with ``strict_reference``.  None (default): no such message."""
+        self.spot_names = None
+        if spotting:
+            if strict_reference:
+                raise ValueError("phrase spotting counts the frames of an utterance from the reset after a final: "
+                                 "not with strict_reference")
+            phrases, self.spot_names = spotting_set(spotting)
+            floors = None
+            if spotting_min_scores is not None:
+                floors = [float(spotting_min_scores.get(n, -2.0 * len(y))) for y, n in zip(phrases, self.spot_names)]
+            scheduler.enable_spotting(phrases, floors)
         if acoustic_endpointing is not None:
             if strict_reference:
                 raise ValueError("acoustic endpointing counts the frames of an utterance from the reset after a final: "
@@ -248,6 +282,8 @@ class ServerLoop:
                     ses.acoustic.reset()
                 replies.setdefault(sid, []).append(results)
                 continue
+            if self.spot_names is not None and getattr(results, "detections", None):
+                replies.setdefault(sid, []).append(spotted_message(results.detections, self.spot_names))
             replies.setdefault(sid, []).append(self._reply(ses, self._finish(ses, results)))
         return replies
 
@@ -374,4 +410,5 @@ class StepPacer:
 
 
 __all__ = ["Endpointer", "EndpointRules", "AcousticEndpointer", "ServerLoop", "StepPacer", "ServerBusy", "vosk_partial", "vosk_result", "vosk_result_aligned",
+           "spotting_set", "spotted_message",
            "scale_server_pcm"]

@@ -391,6 +391,17 @@ class Speech2TextStreaming:
         from .activity import of_stream
         return of_stream(self.batch.activity([self.stream]), 0)
 
+    def set_phrases(self, phrases, min_scores=None):
+        """Phrase spotting from the CTC table (NativeStreamBatch.set_phrases): ``phrases`` is a list of token-id
+        sequences (speechcatcher_amd.spotting.phrase_ids for text), an empty list switches it off; between calls."""
+        self.batch.set_phrases(phrases, min_scores)
+
+    def detections(self) -> list:
+        """[{"phrase": index, "start", "end": encoder frames of 0.04 s (both inclusive), "score"}]: the phrases spotted
+        in the utterance up to the last call (its first 64), ordered by (end, phrase)"""
+        from .spotting import event_dicts
+        return event_dicts(self.batch.spot_events(self.stream))
+
     def recognize(self, speech):
         self.reset()
         return self(speech, is_final=True)
