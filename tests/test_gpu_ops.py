@@ -540,10 +540,15 @@ def _lockstep_run(hip, case, n_calls=None, **kw):
 
 
 def _dump(ls, name):
-    import os
     rep = {"max_abs_diff": ls.report, "calls": ls.calls, "failures": ls.failures[:50],
            "int_mismatch": ls.int_mismatch[:50]}
     print(json.dumps(rep, indent=1))
+    write_report(name, rep)
+
+
+def write_report(name, rep):
+    """the numbers of a test as <name>.json in the folder where the GPU tests leave their reports"""
+    import os
     os.makedirs("gpurun_out", exist_ok=True)
     with open(f"gpurun_out/{name}.json", "w") as f:
         json.dump(rep, f, indent=1)
