@@ -198,7 +198,10 @@ int sc_gemm(const float *A, const int32_t *a_rows, int lda, const float *W, cons
 /* sc_gemm followed by LayerNorm of the produced rows (pre-LN transformer:
  * x += proj(...); xn = LN(x): decoder_layer.py:101-123, transformer_decoder.py:243).
  * ln_out[m*ld_ln ..] = LN(C[c_rows[m]]).  The LayerNorm is fused into the
- * split-K reduce when the workspace is set. */
+ * split-K reduce when the workspace is set.  N must be a multiple of 4 and at most 1024, ldc and
+ * ld_ln multiples of 4 (what the LayerNorm kernels cover): anything else is refused with SC_ERR_ARG
+ * before a launch.  K >= 2560 is cut into 8 slices whatever M is (row slabs when the partial sums of
+ * all rows do not fit the workspace), so C has the bits sc_gemm gives. */
 int sc_gemm_ln(const float *A, const int32_t *a_rows, int lda, const float *W, const float *bias,
                float *C, const int32_t *c_rows, int ldc, int M, int N, int K, int flags, int conv_f1,
                const float *ln_g, const float *ln_b, float ln_eps, float *ln_out, int ld_ln,

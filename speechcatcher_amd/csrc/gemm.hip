@@ -96,15 +96,16 @@ __global__ __launch_bounds__(256) void gemm_mfma_kernel(GemmArgs g) {
   // columns compute garbage that the epilogue never stores.  Only the "-1 =
   // zero row" gather entries need masking, done with a select on the VALUE so
   // that hipcc does not branch around each load (which costs a vmcnt(0) wait
-  // per load and serialises the whole K loop).
+  // per load and serialises the whole K loop).  A select, not a product with
+  // 0: the clamped row the load falls on may hold NaN or inf, and 0 * NaN is NaN.
   long abase[AI];
-  float amask[AI];
+  bool azero[AI];
 #pragma unroll
   for (int i = 0; i < AI; ++i) {
     int m = m0 + lr + RP * i;
     m = m < g.M ? m : g.M - 1;
     int row = g.a_rows ? g.a_rows[m] : m;
-    amask[i] = row < 0 ? 0.f : 1.f;
+    azero[i] = row < 0;
     abase[i] = (long)(row < 0 ? 0 : row) * g.lda;
   }
   long wbase[BI];
@@ -143,7 +144,7 @@ __global__ __launch_bounds__(256) void gemm_mfma_kernel(GemmArgs g) {
 #pragma unroll
       for (int i = 0; i < AI; ++i) {
         h16x4 hi, lo;
-        ffn_split4(make_float4(ra[i].x * amask[i], ra[i].y * amask[i], ra[i].z * amask[i], ra[i].w * amask[i]), hi, lo);
+        ffn_split4(azero[i] ? make_float4(0.f, 0.f, 0.f, 0.f) : ra[i], hi, lo);
         *reinterpret_cast<h16x4 *>(AsH + (lr + RP * i) * LDH + kq * 4) = hi;
         *reinterpret_cast<h16x4 *>(AsL + (lr + RP * i) * LDH + kq * 4) = lo;
       }
@@ -158,10 +159,10 @@ __global__ __launch_bounds__(256) void gemm_mfma_kernel(GemmArgs g) {
 #pragma unroll
       for (int i = 0; i < AI; ++i) {
         float *p = As + (kq * 4) * LDA_S + lr + RP * i;
-        p[0] = ra[i].x * amask[i];
-        p[LDA_S] = ra[i].y * amask[i];
-        p[2 * LDA_S] = ra[i].z * amask[i];
-        p[3 * LDA_S] = ra[i].w * amask[i];
+        p[0] = azero[i] ? 0.f : ra[i].x;
+        p[LDA_S] = azero[i] ? 0.f : ra[i].y;
+        p[2 * LDA_S] = azero[i] ? 0.f : ra[i].z;
+        p[3 * LDA_S] = azero[i] ? 0.f : ra[i].w;
       }
 #pragma unroll
       for (int i = 0; i < BI; ++i) {
@@ -643,7 +644,7 @@ static int gemm_dispatch(GemmArgs &g, bool force_part, int *ksplit_out, int *var
   } else {
     // tile size by a small cost model in cycles (wave quantisation dominates these small GEMMs): it changes which
     // workgroup computes an element, not how
-    if (K >= 2560 && can_part_any && (size_t)8 * M * N * sizeof(float) <= g_ws_bytes) ksplit = 8;   // (callers slab M: gemm_slab_rows)
+    if (K >= 2560 && can_part_any && (size_t)8 * M * N * sizeof(float) <= g_ws_bytes) ksplit = 8;   // (sc_gemm and sc_gemm_ln slab M: gemm_slab_rows)
     const double c0 = 4.0;
     double best = 1e30;
     variant = 3;
@@ -763,31 +764,39 @@ int sc_gemm_colblocks(const float *A, const int32_t *a_rows, int lda, const floa
 
 // GEMM whose output rows are immediately layer-normalised (pre-LN transformer:
 // x += proj(...); xn = LN(x)).  ln_out[m] (dense, leading dim ld_ln) receives
-// LN(C[c_rows[m]]).  Fused into the split-K reduce when possible, otherwise
-// GEMM followed by a LayerNorm launch.
+// LN(C[c_rows[m]]).  Fused into the split-K reduce when the partial sums can go
+// through the workspace, otherwise GEMM followed by a LayerNorm launch.
 extern "C" int sc_gemm_ln(const float *A, const int32_t *a_rows, int lda, const float *W,
                           const float *bias, float *C, const int32_t *c_rows, int ldc, int M, int N,
                           int K, int flags, int conv_f1, const float *ln_g, const float *ln_b,
                           float ln_eps, float *ln_out, int ld_ln, void *stream) {
   SC_CHECK_ARG(A && W && C && ln_g && ln_b && ln_out, "null pointer");
   SC_CHECK_ARG(M >= 0 && N > 0 && K > 0 && lda > 0 && ldc >= N && ld_ln >= N, "bad dimensions");
+  // what the LayerNorm kernels cover (one wave per row), refused BEFORE anything is launched: sc_layernorm used to refuse
+  // it after the GEMM had written C
+  SC_CHECK_ARG(N % 4 == 0 && N <= 1024 && ldc % 4 == 0 && ld_ln % 4 == 0,
+               "LayerNorm rows: N must be a multiple of 4, <= 1024, ldc and ld_ln multiples of 4");
   if (M == 0) return SC_OK;
-  GemmArgs g{A, a_rows, lda, W, bias, C, c_rows, ldc, M, N, K, flags, conv_f1, nullptr, K};
   hipStream_t st = (hipStream_t)stream;
   resolve_workspace(stream);
-  const bool fusable = N <= 1024 && N % 4 == 0 && ld_ln % 4 == 0;
-  int ksplit = 0, variant = 0;
-  gemm_dispatch(g, fusable, &ksplit, &variant, st);
-  if (ksplit > 0 && fusable) {
-    gemm_splitk_reduce_ln_kernel<<<cdiv(M, 4), 256, 0, st>>>(g, ksplit, ln_g, ln_b, ln_eps, ln_out, ld_ln);
-    SC_CHECK_LAUNCH();
-    return SC_OK;
-  }
-  if (ksplit > 0) {
-    const long n4 = (long)M * (N / 4);
-    gemm_splitk_reduce_kernel<<<dim3((unsigned)((n4 + 255) / 256)), 256, 0, st>>>(g, ksplit);
+  // row slabs like sc_gemm: the K split never gives way to the row count (the LayerNorm is per row, a slab is independent)
+  const int slab = gemm_slab_rows(M, N, K);
+  bool fused = false;
+  for (int m0 = 0; m0 < M; m0 += slab) {
+    const int mm = M - m0 < slab ? M - m0 : slab;
+    GemmArgs g{a_rows ? A : A + (long)m0 * lda, a_rows ? a_rows + m0 : nullptr, lda, W, bias, c_rows ? C : C + (long)m0 * ldc,
+               c_rows ? c_rows + m0 : nullptr, ldc, mm, N, K, flags, conv_f1, nullptr, K};
+    int ksplit = 0, variant = 0;
+    gemm_dispatch(g, true, &ksplit, &variant, st);
+    if (ksplit > 0) {   // partial sums in the workspace: the reduce kernel normalises the rows it has just summed
+      // ln_out rows follow the table's entries (SC_GEMM_LN_AT_CROWS with a table) or the row number, which restarts per slab
+      float *lo = (c_rows && (flags & SC_GEMM_LN_AT_CROWS)) ? ln_out : ln_out + (long)m0 * ld_ln;
+      gemm_splitk_reduce_ln_kernel<<<cdiv(mm, 4), 256, 0, st>>>(g, ksplit, ln_g, ln_b, ln_eps, lo, ld_ln);
+      fused = true;
+    }
   }
   SC_CHECK_LAUNCH();
+  if (fused) return SC_OK;   // (no workspace, an unaligned operand or the scalar kernel: the same for every slab)
   return sc_layernorm(C, c_rows, ldc, ln_out, (flags & SC_GEMM_LN_AT_CROWS) ? c_rows : nullptr, ld_ln, M, N, ln_g,
                       ln_b, ln_eps, stream);
 }
