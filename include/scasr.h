@@ -173,7 +173,7 @@ const char *sc_last_error(void);
 /* ABI revision of this header: bumped whenever a struct layout or a signature changes incompatibly.  sc_version()
  * returns the revision the LIBRARY was built with; a host compares the two before it passes any struct
  * (speechcatcher_amd/_abi.py does at load time, the C hosts in tests/ at start-up). */
-#define SC_ABI_VERSION 8
+#define SC_ABI_VERSION 9
 int sc_version(void);
 
 /* hipGraph capture / replay of any sequence of the launches below on a
@@ -476,6 +476,45 @@ typedef struct sc_ctc_spot_job {
  * outside [1, 32], a label outside [0, V) or equal to the blank) writes nothing.  Two jobs of one call must not share
  * a state block or an events array. */
 int sc_ctc_spot(const sc_ctc_spot_job *jobs, int n_jobs, void *stream);
+
+/* ---- CTC draft transcript (draft.hip) --------------------------------------------------------
+ * The collapsed arg-max path of the CTC rows: token ids with frame times and a posterior, known as soon as the encoder
+ * has emitted the frames.  For a row x[0..V) of an fp32 table: a row that holds a NaN or +inf, or nothing but -inf, is a
+ * BAD frame; else k = argmax_v x[v] on the fp32 values, the LOWEST index among ties, and p = exp(x[k] - lse) with x
+ * promoted to float64 and lse = m + log(sum_v exp(x[v] - m)) as for sc_ctc_activity.  A per-row constant cancels: raw
+ * logits and log-softmaxed rows give the same labels unless fp32 rounding creates a tie.  Frames are numbered in the
+ * order they are scanned.  For frame n: a bad row or k == blank closes the open token, if any (a bad row also counts in
+ * n_bad); k == open_id sets open_end = n and open_conf = max(open_conf, p); any other k closes the open token, if any,
+ * and opens (k, n, n, p).  Closed = written to the token store at slot n_closed (counted, not written, at or beyond the
+ * capacity), then n_closed += 1; a stored token is never touched again.  The draft of a state is its stored tokens
+ * followed by the open token, if any.  tests/ctc_draft_ref.py is the contract: every int32 equal, conf within 1e-12 (the
+ * lanes sum in another order than v ascending). */
+typedef struct sc_draft_t {
+  int32_t n_frames, n_closed, n_bad;
+  int32_t open_id, open_start, open_end; /* -1: no open token */
+  double open_conf;                      /* 0.0: no open token */
+} sc_draft_t;
+typedef struct sc_draft_token {
+  int32_t id, start, end, reserved; /* frames of the utterance, both inclusive; reserved = 0 */
+  double conf;                      /* the largest arg-max posterior among the token's frames */
+} sc_draft_token;
+typedef struct sc_ctc_draft_job {
+  const float *table;      /* row t of the table at table + t * stride, V floats (device) */
+  sc_draft_t *state;       /* read (unless restart), advanced over the span, written back (device) */
+  sc_draft_token *tokens;  /* [capacity]: token k of the utterance at tokens[k] (device; may be NULL when capacity == 0) */
+  sc_draft_t *state_after; /* second copy of the new state, e.g. in host-mapped memory (NULL: none) */
+  int64_t stride;          /* floats between two rows, >= V */
+  int32_t V, blank, t0, t1;
+  int32_t restart;         /* != 0: the stored state is ignored, the span starts an utterance (0, 0, 0, -1, -1, -1, 0.0) */
+  int32_t capacity;        /* slots of the token store, >= 0 */
+} sc_ctc_draft_job;
+#define SC_DRAFT_MAX_JOBS 65535
+/* jobs: device table of n_jobs entries.  ONE launch on `stream`, one workgroup per job; no atomics, one writer per
+ * output; an empty span (t0 == t1) rewrites the state unchanged.  n_jobs < 0, a null table with n_jobs > 0 or
+ * n_jobs > SC_DRAFT_MAX_JOBS: SC_ERR_ARG before anything is launched.  A job whose own fields are malformed (null table /
+ * state, a null store with capacity > 0, V < 1, blank outside [0, V), t0 < 0, t1 < t0, stride < V, capacity < 0) writes
+ * nothing.  Two jobs of one call must not share a state or a token store. */
+int sc_ctc_draft(const sc_ctc_draft_job *jobs, int n_jobs, void *stream);
 
 /* ---- frontend ------------------------------------------------------------ */
 
@@ -898,6 +937,22 @@ int sc_streams_read_spot_events(sc_streams *streams, int stream, sc_spot_event *
 /* test aid: the state block of a stream as the device holds it NOW (every group issued so far; waits for them) -> host
  * values [n_phrases][SC_SPOT_STATES], starts [n_phrases][SC_SPOT_STATES]; returns n_phrases */
 int sc_streams_read_spot_state(sc_streams *streams, int stream, double *values, int32_t *starts);
+/* Draft transcript per stream (off by default).  on != 0: every admission group issues ONE sc_ctc_draft
+ * launch right behind its CTC projection (behind the activity and spotting launches where those are on), on the encoder
+ * stream, over the CTC rows [c0, t1) each of its chunks projects (raw logits) - the search is not touched.  The state
+ * (S x 32 bytes) and the token store (S x max_frames tokens: a frame opens at most one token, so it cannot overflow) are
+ * allocated when the option is first switched on; off: no path does any new work.  SC_ERR_ARG while any chunk is
+ * outstanding.  Switching it on restarts every stream's state.  sc_reset touches nothing on the device: the stream's next
+ * span starts the utterance.  strict_reference: as for sc_streams_set_activity, frames that are not re-projected are not
+ * scanned. */
+int sc_streams_set_draft(sc_streams *streams, int on);
+/* state of the stream's last REPORTED chunk - the chunk whose hypotheses sc_get_hyps returns - over every frame the
+ * encoder had emitted for the utterance when that chunk was admitted; (0, 0, 0, -1, -1, -1, 0.0) after sc_reset.  Waits
+ * for the encoder group of that chunk if it is still in flight.  SC_ERR_ARG when the option is off. */
+int sc_stream_draft(sc_streams *streams, int stream, sc_draft_t *out /*HOST*/);
+/* the draft of that state -> host: its stored tokens [0, min(n_closed, max)), then its open token, if any, where room
+ * is left; returns the number written */
+int sc_streams_read_draft(sc_streams *streams, int stream, sc_draft_token *host, int max);
 
 #ifdef __cplusplus
 }

@@ -113,6 +113,28 @@ class SpotJob(C.Structure):
 
 SPOT_MAX_PHRASES, SPOT_MAX_LEN, SPOT_STATES, SPOT_MAX_EVENTS, SPOT_MAX_JOBS = 64, 32, 64, 64, 65535
 
+
+
+class Draft(C.Structure):
+    """sc_draft_t (include/scasr.h)"""
+    _fields_ = ([(n, C.c_int32) for n in ("n_frames", "n_closed", "n_bad", "open_id", "open_start", "open_end")]
+                + [("open_conf", C.c_double)])
+
+
+class DraftToken(C.Structure):
+    """sc_draft_token (include/scasr.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("id", "start", "end", "reserved")] + [("conf", C.c_double)]
+
+
+class DraftJob(C.Structure):
+    """sc_ctc_draft_job (include/scasr.h): one span of CTC rows scanned by sc_ctc_draft"""
+    _fields_ = ([(n, vp) for n in ("table", "state", "tokens", "state_after")] + [("stride", C.c_int64)]
+                + [(n, C.c_int32) for n in ("V", "blank", "t0", "t1", "restart", "capacity")])
+
+
+DRAFT_FIELDS = tuple(n for n, _ in Draft._fields_)
+DRAFT_MAX_JOBS = 65535
+
 # SC_ALIGN_* of include/scasr.h
 ALIGN_OK, ALIGN_INFEASIBLE, ALIGN_NONFINITE, ALIGN_BAD_INPUT = 0, 1, 2, 3
 ALIGN_MAX_L = 1023
@@ -261,6 +283,11 @@ _SIGS = {
     "sc_stream_spot": (C.c_int, [vp, C.c_int, C.POINTER(Spot)]),
     "sc_streams_read_spot_events": (C.c_int, [vp, C.c_int, vp, C.c_int]),
     "sc_streams_read_spot_state": (C.c_int, [vp, C.c_int, vp, vp]),
+    # CTC draft transcript (draft.hip, streams.hip)
+    "sc_ctc_draft": (C.c_int, [vp, C.c_int, vp]),
+    "sc_streams_set_draft": (C.c_int, [vp, C.c_int]),
+    "sc_stream_draft": (C.c_int, [vp, C.c_int, C.POINTER(Draft)]),
+    "sc_streams_read_draft": (C.c_int, [vp, C.c_int, vp, C.c_int]),
     # sample-rate conversion (resample.hip, streams.hip)
     "sc_resample_design": (C.c_int, [C.c_int, c_int_p, c_int_p, c_int_p, c_float_p]),
     "sc_resample_out_count": (C.c_long, [C.c_int, C.c_long, C.c_int]),
@@ -278,7 +305,7 @@ EXPORTED_SYMBOLS = tuple(_SIGS.keys())
 
 # revision of include/scasr.h these ctypes mirrors were written against (SC_ABI_VERSION): a library built from another
 # revision would be handed mis-laid-out structs
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _lib = None
 

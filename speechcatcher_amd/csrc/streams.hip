@@ -156,6 +156,15 @@ struct SpotVal {
   int32_t v[2] = {0, 0};
 };
 
+// Draft transcript (sc_streams_set_draft; draft.hip): the greedy state that belongs to a chunk, handed over exactly like
+// ActVal.  The tokens stay on the device: the utterance's token k is at slot k and is never touched once stored, so the
+// first n_closed of them are final whatever later groups append; the open token travels in the state.
+struct DraftVal {
+  bool ready = true;
+  long gen = 0;
+  sc_draft_t v = {0, 0, 0, -1, -1, -1, 0.0};
+};
+
 // a stream's outstanding chunk (sc_push / sc_submit): open until it has been reported.  With a queue depth > 1
 // (sc_streams_set_queue_depth) further chunks of the stream wait behind it (sc_streams::ahead), in order.
 struct Job {
@@ -168,6 +177,7 @@ struct Job {
   bool started = false;   // St::started right after THIS chunk's admission (a later admission may set it before this one is reported)
   ActVal act;             // sc_streams_set_activity: the activity state that belongs to this chunk
   SpotVal spot;           // sc_streams_set_phrases: the spotting counters that belong to this chunk
+  DraftVal draft;         // sc_streams_set_draft: the draft state that belongs to this chunk
 };
 
 // hypotheses of a stream's last complete chunk, copied aside when later chunks of the stream may go on decoding
@@ -217,8 +227,12 @@ struct EncGroup {
   // activity option: per stream the span [t0, t1) of ctc_rows (one sc_ctc_activity job each, in this order); epoch = the
   // stream's reset count when the span was planned (a state that arrives after a reset is dropped)
   // (recorded when the activity or the spotting option is on; act / spot: which of the two scans it.  The spotting
-  // launch has the same job order; spot_epoch / spot_restart / mask are its own)
-  struct ActSpan { int s, t0, t1; long epoch; bool restart; bool act, spot; long spot_epoch; bool spot_restart; uint64_t mask; };
+  // launch has the same job order; spot_epoch / spot_restart / mask are its own, and so are draft / draft_epoch /
+  // draft_restart of the draft launch)
+  struct ActSpan {
+    int s, t0, t1; long epoch; bool restart; bool act, spot; long spot_epoch; bool spot_restart; uint64_t mask;
+    bool draft; long draft_epoch; bool draft_restart;
+  };
   std::vector<ActSpan> act;
   bool same_rows = true;
   std::vector<int> streams;                  // streams with work in this group (each at most once)
@@ -335,6 +349,15 @@ struct sc_streams {
   std::vector<long> spot_pending, spot_epoch;  // per stream: as act_pending / act_epoch
   std::vector<char> spot_fresh;                // per stream: the next span starts the utterance
   std::vector<uint64_t> spot_mask;             // per stream: enabled phrases
+  // ---- draft transcript (sc_streams_set_draft): everything below is allocated when the option is first switched on --------
+  bool draft_on = false;
+  sc_draft_t *draft_state = nullptr;        // device [S]: the running state of every stream (advanced group by group)
+  sc_draft_token *draft_tokens = nullptr;   // device [S][TCAP]: a frame opens at most one token, so the store cannot overflow
+  sc_ctc_draft_job *draft_jobs_host = nullptr, *draft_jobs_dev = nullptr;   // [N_ARENA][S]: the job table of a group's launch
+  sc_draft_t *draft_out_host = nullptr, *draft_out_dev = nullptr;           // [N_ARENA][S] host-mapped: the jobs' states-after
+  std::vector<DraftVal> draft_known, draft_rep;   // per stream: after the latest RETIRED group / of the last reported chunk
+  std::vector<long> draft_pending, draft_epoch;   // per stream: as act_pending / act_epoch
+  std::vector<char> draft_fresh;                  // per stream: the next span starts the utterance
   // ---- tick engine -----------------------------------------------------------------------------------------------------
   std::vector<St> st;
   std::vector<Run> run;
@@ -537,6 +560,12 @@ void reset_stream(sc_streams *b, int s) {
     b->spot_known[s] = b->spot_rep[s] = SpotVal();
     b->spot_pending[s] = 0;
     b->spot_fresh[s] = 1;
+  }
+  if (!b->draft_epoch.empty()) {   // draft: the same
+    b->draft_epoch[s]++;
+    b->draft_known[s] = b->draft_rep[s] = DraftVal();
+    b->draft_pending[s] = 0;
+    b->draft_fresh[s] = 1;
   }
   init_hyp(b, s);
 }
@@ -928,6 +957,18 @@ int retire_groups(sc_streams *b) {
         for (Job &j : b->ahead[sp.s]) fill(j.spot);
         fill(b->spot_rep[sp.s]);
       }
+      if (sp.draft && sp.draft_epoch == b->draft_epoch[sp.s]) {   // draft: the state-after, handed over the same way
+        DraftVal &k = b->draft_known[sp.s];
+        k.ready = true;
+        k.gen = g->gen;
+        k.v = b->draft_out_host[(size_t)g->slot * b->S + i];
+        auto fill = [&](DraftVal &a) {
+          if (!a.ready && a.gen == g->gen) a = k;
+        };
+        fill(b->job[sp.s].draft);
+        for (Job &j : b->ahead[sp.s]) fill(j.draft);
+        fill(b->draft_rep[sp.s]);
+      }
       if (!sp.act || sp.epoch != b->act_epoch[sp.s]) continue;
       ActVal &k = b->act_known[sp.s];
       k.ready = true;
@@ -1025,6 +1066,30 @@ int project_rows(sc_streams *b, EncGroup &g) {
       HIP_TRY(hipMemcpyAsync(b->spot_jobs_dev + o, b->spot_jobs_host + o, (size_t)n * sizeof(sc_ctc_spot_job),
                              hipMemcpyHostToDevice, b->es));
       RC_TRY(sc_ctc_spot(b->spot_jobs_dev + o, n, b->es));
+    }
+    if (!g.act.empty() && g.act[0].draft) {
+      // draft: ONE launch for the group, in the same place and over the same spans
+      const int n = (int)g.act.size();
+      if (n > b->S) {
+        sc_set_error("draft: %d spans in a group of a batch of %d streams (internal error)", n, b->S);
+        return SC_ERR_ARG;
+      }
+      const size_t o = (size_t)g.slot * b->S;
+      for (int i = 0; i < n; ++i) {
+        const EncGroup::ActSpan &sp = g.act[i];
+        sc_ctc_draft_job &j = b->draft_jobs_host[o + i];
+        j.table = b->sb.ctcx + (size_t)sp.s * b->TCAP * V;
+        j.state = b->draft_state + sp.s;
+        j.tokens = b->draft_tokens + (size_t)sp.s * b->TCAP;
+        j.state_after = b->draft_out_dev + (o + i);
+        j.stride = V;
+        j.V = V; j.blank = c.blank_id; j.t0 = sp.t0; j.t1 = sp.t1;
+        j.restart = sp.draft_restart ? 1 : 0;
+        j.capacity = b->TCAP;
+      }
+      HIP_TRY(hipMemcpyAsync(b->draft_jobs_dev + o, b->draft_jobs_host + o, (size_t)n * sizeof(sc_ctc_draft_job),
+                             hipMemcpyHostToDevice, b->es));
+      RC_TRY(sc_ctc_draft(b->draft_jobs_dev + o, n, b->es));
     }
   }
   if (!g.kv_dst.empty()) {
@@ -1644,8 +1709,8 @@ int admit(sc_streams *b, std::vector<Chunk> chunks, bool features, bool defer, s
     const int c0 = std::max(t0, st.T_proj), k0 = std::max(t0, st.T_projkv);
     g->same_rows = g->same_rows && c0 == k0;
     for (int t = c0; t < t1; ++t) g->ctc_rows.push_back(ch.s * b->TCAP + t);
-    if ((b->act_on || b->spot_on) && c0 < t1) {
-      EncGroup::ActSpan sp = {ch.s, c0, t1, 0, false, b->act_on, b->spot_on, 0, false, 0};
+    if ((b->act_on || b->spot_on || b->draft_on) && c0 < t1) {
+      EncGroup::ActSpan sp = {ch.s, c0, t1, 0, false, b->act_on, b->spot_on, 0, false, 0, b->draft_on, 0, false};
       if (b->act_on) {
         sp.epoch = b->act_epoch[ch.s];
         sp.restart = b->act_fresh[ch.s] != 0;
@@ -1656,6 +1721,11 @@ int admit(sc_streams *b, std::vector<Chunk> chunks, bool features, bool defer, s
         sp.spot_restart = b->spot_fresh[ch.s] != 0;
         sp.mask = b->spot_mask[ch.s];
         b->spot_fresh[ch.s] = 0;
+      }
+      if (b->draft_on) {
+        sp.draft_epoch = b->draft_epoch[ch.s];
+        sp.draft_restart = b->draft_fresh[ch.s] != 0;
+        b->draft_fresh[ch.s] = 0;
       }
       g->act.push_back(sp);
       act_new.push_back(ch.s);
@@ -1750,6 +1820,16 @@ int admit(sc_streams *b, std::vector<Chunk> chunks, bool features, bool defer, s
         j.spot.gen = b->spot_pending[s];
       } else {
         j.spot = b->spot_known[s];
+      }
+    }
+    if (b->draft_on) {   // (and for the draft state)
+      const int s = chunks[k].s;
+      if (gen && std::find(act_new.begin(), act_new.end(), s) != act_new.end()) b->draft_pending[s] = gen;
+      if (b->draft_pending[s] > b->gen_done) {
+        j.draft.ready = false;
+        j.draft.gen = b->draft_pending[s];
+      } else {
+        j.draft = b->draft_known[s];
       }
     }
     if (b->job[chunks[k].s].open) b->ahead[chunks[k].s].push_back(j);   // behind the stream's outstanding chunk(s)
@@ -2370,6 +2450,7 @@ int report_chunk(sc_streams *b, int s) {
   if (j.fault && !j.dropped) reset_stream(b, s);   // (fault_msg[s] keeps the message: sc_stream_last_error)
   if (b->act_on && !j.fault) b->act_rep[s] = j.act;
   if (b->spot_on && !j.fault) b->spot_rep[s] = j.spot;
+  if (b->draft_on && !j.fault) b->draft_rep[s] = j.draft;
   if (b->snap[s].valid && b->snap[s].seq == j.seq) b->snap[s].reported = true;   // handed out: free at the next sc_poll
   b->done_at[s] = 0;
   if (b->ahead[s].empty()) j = Job();
@@ -3123,6 +3204,91 @@ extern "C" int sc_streams_read_spot_state(sc_streams *b, int stream, double *val
   HIP_TRY(hipMemcpy(values, b->spot_values + o, n * sizeof(double), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(starts, b->spot_starts + o, n * sizeof(int32_t), hipMemcpyDeviceToHost));
   return b->spot_P;
+  SC_API_END
+}
+
+// ---- draft transcript ---------------------------------------------------------------------------------------------------
+extern "C" int sc_streams_set_draft(sc_streams *b, int on) {
+  SC_CHECK_ARG(b, "null");
+  SC_API_BEGIN
+  SC_CHECK_ARG(b->n_open == 0, "chunks are outstanding");
+  if (!on) {
+    b->draft_on = false;
+    return SC_OK;
+  }
+  HIP_TRY(hipSetDevice(b->eng->device));
+  if (!b->draft_state) {
+    const size_t S = (size_t)b->S;
+    RC_TRY(b->alloc(&b->draft_state, S));
+    RC_TRY(b->alloc(&b->draft_tokens, S * b->TCAP));
+    RC_TRY(b->alloc(&b->draft_jobs_dev, S * N_ARENA));
+    RC_TRY(b->halloc(&b->draft_jobs_host, S * N_ARENA));
+    RC_TRY(b->halloc(&b->draft_out_host, S * N_ARENA));
+    void *dv = nullptr;
+    if (hipHostGetDevicePointer(&dv, b->draft_out_host, 0) != hipSuccess || !dv) {
+      sc_set_error("sc_streams_set_draft: the pinned state slots are not visible to the device");
+      return SC_ERR_LAUNCH;
+    }
+    b->draft_out_dev = (sc_draft_t *)dv;
+    b->draft_known.assign(S, DraftVal());
+    b->draft_rep.assign(S, DraftVal());
+    b->draft_pending.assign(S, 0);
+    b->draft_epoch.assign(S, 0);
+    b->draft_fresh.assign(S, 1);
+  }
+  // every stream starts over: a stream in mid-utterance is scanned from its next frame on
+  for (int s = 0; s < b->S; ++s) {
+    b->draft_epoch[s]++;
+    b->draft_known[s] = b->draft_rep[s] = DraftVal();
+    b->draft_pending[s] = 0;
+    b->draft_fresh[s] = 1;
+  }
+  b->draft_on = true;
+  return SC_OK;
+  SC_API_END
+}
+
+// the state of the stream's last reported chunk, complete: its encoder group may still be held back or in flight
+static int draft_ready(sc_streams *b, int s) {
+  DraftVal &r = b->draft_rep[s];
+  if (r.ready) return SC_OK;
+  RC_TRY(wait_group(b, r.gen));
+  if (!r.ready) {
+    sc_set_error("draft state of stream %d did not arrive with its encoder group (internal error)", s);
+    return SC_ERR_LAUNCH;
+  }
+  return SC_OK;
+}
+
+extern "C" int sc_stream_draft(sc_streams *b, int stream, sc_draft_t *out) {
+  SC_CHECK_ARG(b && out && stream >= 0 && stream < b->S, "bad arguments");
+  SC_API_BEGIN
+  SC_CHECK_ARG(b->draft_on, "the draft option is off (sc_streams_set_draft)");
+  HIP_TRY(hipSetDevice(b->eng->device));
+  RC_TRY(draft_ready(b, stream));
+  *out = b->draft_rep[stream].v;
+  return SC_OK;
+  SC_API_END
+}
+
+extern "C" int sc_streams_read_draft(sc_streams *b, int stream, sc_draft_token *host, int max) {
+  SC_CHECK_ARG(b && stream >= 0 && stream < b->S && max >= 0, "bad arguments");
+  SC_API_BEGIN
+  SC_CHECK_ARG(b->draft_on, "the draft option is off (sc_streams_set_draft)");
+  HIP_TRY(hipSetDevice(b->eng->device));
+  RC_TRY(draft_ready(b, stream));
+  const sc_draft_t &v = b->draft_rep[stream].v;
+  int n = std::min(std::min((int)v.n_closed, b->TCAP), max);
+  if (host && n > 0) {   // (the group that wrote these slots has been retired; later groups write behind them)
+    HIP_TRY(hipMemcpyAsync(host, b->draft_tokens + (size_t)stream * b->TCAP, (size_t)n * sizeof(sc_draft_token),
+                           hipMemcpyDeviceToHost, b->stream_rb));
+    HIP_TRY(hipStreamSynchronize(b->stream_rb));
+  }
+  if (host && v.open_id >= 0 && n < max) {
+    sc_draft_token &t = host[n++];
+    t.id = v.open_id; t.start = v.open_start; t.end = v.open_end; t.reserved = 0; t.conf = v.open_conf;
+  }
+  return n;
   SC_API_END
 }
 

@@ -34,6 +34,7 @@ import torch
 
 from .activity import INITIAL, advance as activity_advance, as_arrays as activity_arrays
 from . import spotting
+from . import draft as draft_mod
 from .config import SearchConfig
 from .weights import PackedWeights
 
@@ -271,6 +272,7 @@ class StreamBatch:
         self.st = [StreamState() for _ in range(S)]
         self._act = None   # acoustic activity (set_activity): off
         self._spot = None  # phrase spotting (set_phrases): off
+        self._draft = None  # draft transcript (set_draft): off
         self.reset_all()
         self.stats = {"enc_calls": 0, "dec_steps": 0, "dec_blocks": 0}
         # optional host-side phase timers (SC_TIMING=1): seconds per phase
@@ -356,6 +358,9 @@ class StreamBatch:
         if self._spot is not None:
             self._spot["state"][s] = spotting.initial(self._spot["set"].P)
             self._spot["proj"][s] = ns.T_ctc
+        if self._draft is not None:
+            self._draft["state"][s] = draft_mod.initial()
+            self._draft["proj"][s] = ns.T_ctc
         if getattr(self, "stream", None) is not None:
             with torch.cuda.stream(self.stream):   # same stream as the kernels that read it
                 self._init_hyp(s)
@@ -450,20 +455,47 @@ class StreamBatch:
         st = self._spot["state"][int(s)]
         return st["values"].copy(), st["starts"].copy()
 
+    # ------------------------------------------------------------------
+    # draft transcript (the native engine: sc_streams_set_draft)
+    # ------------------------------------------------------------------
+    def set_draft(self, on: bool = True):
+        """Draft transcript from the CTC table: when on, every chunk step projects the CTC rows of the frames its
+        encoder stage emits right away (as set_activity does) and runs the greedy collapse of speechcatcher_amd.draft
+        over them in numpy float64; the search is not touched.  Every stream's state starts over."""
+        if not on:
+            self._draft = None
+            return
+        self._draft = {"state": [draft_mod.initial() for _ in range(self.S)],
+                       "proj": np.asarray([x.T_ctc for x in self.st], np.int64)}
+
+    def draft(self, streams: Sequence[int]):
+        """{field: array [n]} (speechcatcher_amd.draft.FIELDS; int32, open_conf float64) of the listed streams after
+        their last chunk"""
+        if self._draft is None:
+            raise EngineError("the draft option is off (set_draft)")
+        return draft_mod.as_arrays([self._draft["state"][int(s)] for s in streams])
+
+    def draft_tokens(self, s: int):
+        """[(id, start, end, conf)]: the draft of stream s's utterance so far - the closed tokens, then the open one"""
+        if self._draft is None:
+            raise EngineError("the draft option is off (set_draft)")
+        return draft_mod.tokens_of(self._draft["state"][int(s)])
+
     def _scan_activity(self, t_old: Dict[int, int]):
         """The frames [t_old[s], T_enc) the encoder stage of this chunk step emitted: CTC rows, then blank posteriors in
-        torch float64 and the activity state update (set_activity) and / or the spotting recurrence (set_phrases)."""
-        a, sp, cfg = self._act, self._spot, self.cfg
-        proj = a["proj"] if a is not None else sp["proj"]   # (both options project the same rows: one watermark)
+        torch float64 and the activity state update (set_activity) and / or the spotting recurrence (set_phrases) and / or
+        the draft's greedy collapse (set_draft)."""
+        a, sp, dr, cfg = self._act, self._spot, self._draft, self.cfg
+        on = [o for o in (a, sp, dr) if o is not None]
+        proj = on[0]["proj"]   # (all options project the same rows: one watermark)
         spans = []
         for s, t0 in t_old.items():
             t1 = self.st[s].T_enc
             c0 = max(t0, int(proj[s]))
             if t1 > c0:
                 spans.append((s, c0, t1))
-                proj[s] = t1
-                if a is not None and sp is not None:
-                    sp["proj"][s] = t1
+                for o in on:
+                    o["proj"][s] = t1
         if not spans:
             return
         rows = np.concatenate([s * self.TCAP + _AR[c0:t1] for s, c0, t1 in spans])
@@ -471,10 +503,13 @@ class StreamBatch:
         V, m = cfg.vocab_size, int(rows.shape[0])
         self.be.gemm(self.enc, ar, cfg.d_model, self.w.ctc_w, self.w.ctc_b, self.ctcx, ar, V, m, V, cfg.d_model)
         x32 = self.ctcx[torch.as_tensor(rows, dtype=torch.int64, device=self.dev)]
-        if sp is not None:
+        if sp is not None or dr is not None:
             xs, o = x32.cpu().numpy(), 0
             for s, c0, t1 in spans:
-                spotting.advance(sp["state"][s], xs[o:o + t1 - c0], cfg.blank_id, sp["set"], sp["mask"][s])
+                if sp is not None:
+                    spotting.advance(sp["state"][s], xs[o:o + t1 - c0], cfg.blank_id, sp["set"], sp["mask"][s])
+                if dr is not None:
+                    draft_mod.advance(dr["state"][s], xs[o:o + t1 - c0], cfg.blank_id)
                 o += t1 - c0
         if a is None:
             return
@@ -723,7 +758,7 @@ class StreamBatch:
         if enc_streams:
             t_ph = time.perf_counter()
             t_old = ({s: self.st[s].T_enc for s in enc_streams}
-                     if self._act is not None or self._spot is not None else None)
+                     if self._act is not None or self._spot is not None or self._draft is not None else None)
             self._encode(enc_streams, feat_new, finals)
             if t_old is not None:
                 self._scan_activity(t_old)

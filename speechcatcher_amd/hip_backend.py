@@ -397,6 +397,64 @@ class HipBackend:
                         "raw_events": evt[k]})
         return out, after.cpu().numpy()[:n]
 
+    def ctc_draft(self, jobs, tweak=None, guard: int = 2):
+        """Batched CTC draft scan (sc_ctc_draft) on the caller's tables, one launch for all jobs.  jobs: list of (table
+        [T, V] fp32 tensor, rows may be strided; blank; t0; t1; state: a dict as returned here or None = the span starts
+        an utterance; capacity of the token store).  Returns (states: list of {the seven speechcatcher_amd.draft.FIELDS,
+        tokens: the stored (id, start, end, conf), raw_tokens: the store and ``guard`` slots behind it as int32 [., 6]},
+        states_after: the second copy, list of 7-tuples).  ``tweak(k, job)``: test aid, edits the sc_ctc_draft_job of job k
+        before the launch.  A job that starts an utterance is handed a state and a store filled with -7 (the second
+        copy always is), so what it leaves unwritten shows."""
+        import numpy as np
+        from .draft import FIELDS
+        n = len(jobs)
+        dev = self.device
+        st_dt = np.dtype([("i", np.int32, 6), ("conf", np.float64)])
+        tk_dt = np.dtype([("i", np.int32, 4), ("conf", np.float64)])
+        assert st_dt.itemsize == C.sizeof(_abi.Draft) == 32 and tk_dt.itemsize == C.sizeof(_abi.DraftToken) == 24
+        caps = [int(j[5]) for j in jobs]
+        off = np.concatenate([[0], np.cumsum([c + guard for c in caps])]).astype(np.int64)
+        state = np.zeros(max(n, 1), st_dt)
+        state.view(np.int32)[:] = -7
+        after = state.copy()
+        store = np.zeros(max(int(off[-1]), 1), tk_dt)
+        store.view(np.int32)[:] = -7
+        for k, job in enumerate(jobs):
+            st = job[4]
+            if st is not None:
+                state[k]["i"] = [st[f] for f in FIELDS[:6]]
+                state[k]["conf"] = st["open_conf"]
+                for i, (tid, a, b, c) in enumerate(st["tokens"]):
+                    store[off[k] + i] = ((tid, a, b, 0), c)
+        state_d, after_d, store_d = (torch.as_tensor(a.view(np.uint8).copy()).to(dev) for a in (state, after, store))
+        tab = (_abi.DraftJob * max(1, n))()
+        for k, (table, blank, t0, t1, st, cap) in enumerate(jobs):
+            assert table.dtype == torch.float32 and table.dim() == 2 and table.stride(1) == 1
+            assert 0 <= t0 <= t1 <= table.shape[0]
+            j = tab[k]
+            j.table, j.state, j.state_after = table.data_ptr(), state_d.data_ptr() + 32 * k, after_d.data_ptr() + 32 * k
+            j.tokens = store_d.data_ptr() + 24 * int(off[k])
+            j.stride, j.V, j.blank, j.t0, j.t1 = table.stride(0), table.shape[1], int(blank), int(t0), int(t1)
+            j.restart, j.capacity = 1 if st is None else 0, int(cap)
+            if tweak is not None:
+                tweak(k, j)
+        tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+        self._chk(self.lib.sc_ctc_draft(tab_dev.data_ptr(), n, self._stream()), "sc_ctc_draft")
+        torch.cuda.synchronize(dev)
+        state, after = (a.cpu().numpy().view(st_dt) for a in (state_d, after_d))
+        store = store_d.cpu().numpy().view(tk_dt)
+        out, aft = [], []
+        for k in range(n):
+            d = {f: int(state[k]["i"][i]) for i, f in enumerate(FIELDS[:6])}
+            d["open_conf"] = float(state[k]["conf"])
+            mine = store[off[k]:off[k + 1]]
+            d["tokens"] = [(int(t["i"][0]), int(t["i"][1]), int(t["i"][2]), float(t["conf"]))
+                           for t in mine[:max(0, min(d["n_closed"], caps[k]))]]
+            d["raw_tokens"] = mine.view(np.int32).reshape(-1, 6).copy()
+            out.append(d)
+            aft.append(tuple(int(v) for v in after[k]["i"]) + (float(after[k]["conf"]),))
+        return out, aft
+
     # ------------------------------------------------------------------
     def search_struct(self, sb):
         cached = getattr(sb, "_sc_search_struct", None)

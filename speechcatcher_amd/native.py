@@ -459,6 +459,42 @@ class NativeStreamBatch:
             _abi.check(n, "sc_streams_read_spot_state")
         return v, st
 
+    # ---- draft transcript (sc_streams_set_draft) ---------------------------------------------
+    def set_draft(self, on: bool = True):
+        """Draft transcript from the CTC table: when on, every admission group runs the greedy collapse over the CTC rows
+        it projects (one extra launch per group); the search is not touched.  Off by default; only while no chunk is
+        outstanding; every stream's state starts over."""
+        try:
+            _abi.check(self.lib.sc_streams_set_draft(self.handle, int(bool(on))), "sc_streams_set_draft")
+        except _abi.ScasrError as e:
+            raise EngineError(str(e)) from e
+
+    def draft(self, streams: Sequence[int]):
+        """{field: array [n]} (speechcatcher_amd.draft.FIELDS; int32, open_conf float64) of the listed streams' last
+        reported chunks - the chunks whose hypotheses ``hypotheses`` returns."""
+        out = {k: np.zeros(len(streams), np.float64 if k == "open_conf" else np.int32) for k in _abi.DRAFT_FIELDS}
+        a = _abi.Draft()
+        for i, s in enumerate(streams):
+            try:
+                _abi.check(self.lib.sc_stream_draft(self.handle, int(s), C.byref(a)), "sc_stream_draft")
+            except _abi.ScasrError as e:
+                raise EngineError(str(e)) from e
+            for k in _abi.DRAFT_FIELDS:
+                out[k][i] = getattr(a, k)
+        return out
+
+    def draft_tokens(self, s: int):
+        """[(id, start, end, conf)]: the draft the state of stream s's last reported chunk covers - the closed tokens,
+        then the open one; frames of the utterance, both inclusive"""
+        tk = (_abi.DraftToken * (self.TCAP + 1))()
+        n = self.lib.sc_streams_read_draft(self.handle, int(s), C.addressof(tk), self.TCAP + 1)
+        if n < 0:
+            try:
+                _abi.check(n, "sc_streams_read_draft")
+            except _abi.ScasrError as e:
+                raise EngineError(str(e)) from e
+        return [(t.id, t.start, t.end, t.conf) for t in tk[:n]]
+
     def hypotheses_batch(self, streams: Sequence[int], nbest: Optional[int] = None):
         """{stream: [hypothesis dicts, best first]} for the listed streams, one device round trip for all."""
         a = self.hypotheses_arrays(streams, nbest)

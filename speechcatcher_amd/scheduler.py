@@ -20,6 +20,7 @@ import numpy as np
 
 from .engine import StreamBatch
 from . import spotting
+from . import draft as draft_mod
 from .activity import of_stream as activity_of_stream
 from .align import FeatureClock
 from .resample import OutputClock, check_input_rate
@@ -54,11 +55,24 @@ class SpottingResults(ActivityResults):
     detections: Optional[list] = None
 
 
+class DraftResults(SpottingResults):
+    """the results of a reply, ``draft``: the draft transcript of the session's stream for that chunk (the collapsed
+    arg-max path of every CTC frame the encoder had emitted when the chunk was admitted) and ``ahead``: the part of it
+    behind the search's last token - StreamScheduler(draft=True).  Each token is {"id", "start", "end": encoder frames
+    of the utterance (both inclusive), "conf", "start_s", "end_s": seconds of the utterance's audio, "token": its text
+    when the scheduler has a token list}.  ``ahead`` = speechcatcher_amd.draft.ahead(draft, h) with h the frame position
+    the reply carries for its first result's last token (result_format "espnet"; 0 for an empty result and for the
+    "native" format, which carries no positions): a heuristic for splicing.  ``alignment`` / ``activity`` /
+    ``detections`` are carried as well when those options are on."""
+    draft: Optional[list] = None
+    ahead: Optional[list] = None
+
+
 class StreamScheduler:
     def __init__(self, batch: StreamBatch, token_list: Optional[List[str]] = None,
                  result_format: str = "native", reset_after_final: bool = True, reset_on_open: bool = True,
                  queue_depth: int = 1, align_final: bool = False, activity: bool = False, blank_threshold: float = 0.8,
-                 phrases=None, min_scores=None):
+                 phrases=None, min_scores=None, draft: bool = False):
         """``queue_depth`` > 1 (C++ engine, ``pump``): up to that many queued chunks of a session are handed to the engine
         at a time (sc_streams_set_queue_depth) - for sessions whose audio is already there (files): the encoder stage of
         the next chunk runs beside the decoding of the current one.  Replies and their order per session do not change.
@@ -80,6 +94,9 @@ class StreamScheduler:
         # ``SpottingResults`` whose ``detections`` are the events new since the session's previous reply
         # (batch.set_phrases), read before the stream is reset after a final
         self.spotting = False
+        # ``draft``: every reply (an exception aside) is a ``DraftResults`` (batch.set_draft), read before the stream is
+        # reset after a final
+        self.draft = False
         self._spot_seen: Dict[int, int] = {}                  # per session: events of its utterance handed out so far
         self._clock: Dict[int, FeatureClock] = {}             # align_final: per session, the calls since its last reset
         self._fed: Dict[int, Deque[Tuple[int, bool]]] = {}   # ... and its fed chunks not reported yet (length, final)
@@ -107,6 +124,8 @@ class StreamScheduler:
             self.enable_activity(blank_threshold)
         if phrases:
             self.enable_spotting(phrases, min_scores)
+        if draft:
+            self.enable_draft()
 
     def enable_activity(self, blank_threshold: float = 0.8):
         """switch the ``activity`` option on (only while no chunk is at the engine; every stream's state starts over)"""
@@ -119,9 +138,14 @@ class StreamScheduler:
         self.spotting = True
         self._spot_seen.clear()
 
+    def enable_draft(self):
+        """switch the ``draft`` option on (only while no chunk is at the engine; every stream's state starts over)"""
+        self.batch.set_draft(True)
+        self.draft = True
+
     @property
     def _clocked(self) -> bool:   # the options that need the sessions' feature clocks
-        return self.align_final or self.spotting
+        return self.align_final or self.spotting or self.draft
 
     # ---- session lifecycle -------------------------------------------------
     def open(self, sample_rate: int = 16000) -> int:
@@ -266,10 +290,29 @@ class StreamScheduler:
                 res.activity = getattr(out[sid], "activity", None)
                 res.detections = self._detections(sid, slot)
                 out[sid] = res
+            if self.draft:
+                res = DraftResults(out[sid])
+                for k in ("alignment", "activity", "detections"):
+                    setattr(res, k, getattr(out[sid], k, None))
+                res.draft = self._draft_tokens(sid, slot)
+                pos = out[sid][0][3] if out[sid] and len(out[sid][0]) > 3 else None
+                res.ahead = draft_mod.ahead(res.draft, pos[-1] if pos else 0)
+                out[sid] = res
             if fin and self.reset_after_final:
                 self.batch.reset(slot)
                 self._clock.pop(sid, None)
                 self._spot_seen.pop(sid, None)
+        return out
+
+    def _draft_tokens(self, sid: int, slot: int) -> list:
+        """the draft of the session's stream as token dicts: frames, and seconds by the session's feature clock"""
+        cfg = self.batch.cfg
+        toks = self.batch.draft_tokens(slot)
+        out = draft_mod.token_dicts(toks, names=self.token_list)
+        secs = draft_mod.token_dicts(toks, self._clock.get(sid) or FeatureClock(cfg.win_length, cfg.hop_length),
+                                     cfg.subsample, cfg.sample_rate)
+        for d, t in zip(out, secs):
+            d["start_s"], d["end_s"] = t["start"], t["end"]
         return out
 
     def _detections(self, sid: int, slot: int) -> list:

@@ -138,6 +138,18 @@ def vosk_partial(text: str) -> dict:
     return {"partial": text}
 
 
+def vosk_partial_ahead(text: str, ahead: list) -> dict:
+    """a partial with the draft tokens that lie behind the search's last token (DraftResults.ahead): their text, and one
+    entry per token with start / end in seconds of the utterance and conf = its arg-max posterior"""
+    words = [{"word": str(d.get("token", d["id"])).replace("▁", " "), "start": round(d["start_s"], 3),
+              "end": round(d["end_s"], 3), "conf": d["conf"]} for d in ahead]
+    if ahead and "token" in ahead[0]:
+        text_ahead = "".join(d["token"] for d in ahead).replace("▁", " ").strip()
+    else:
+        text_ahead = " ".join(str(d["id"]) for d in ahead)
+    return {"partial": text, "ahead": text_ahead, "ahead_result": words}
+
+
 def vosk_result(tokens: List[str], token_pos: Optional[List[int]] = None) -> dict:
     """Final result in Vosk style (speechcatcher_server.py:298-328): one entry
     per output token (not per word), "▁" is the sentencepiece space."""
@@ -187,7 +199,7 @@ class ServerLoop:
                  finalize_update_iters: int = 6, max_partial_iters: int = 42, strict_reference: bool = False,
                  continuous: Optional[bool] = None, min_replies: int = 1, vosk_alignment: bool = False,
                  acoustic_endpointing: Optional[EndpointRules] = None, spotting: Optional[dict] = None,
-                 spotting_min_scores: Optional[dict] = None):
+                 spotting_min_scores: Optional[dict] = None, draft_partials: bool = False):
         """``strict_reference``: no stream reset after a finalised utterance nor between clients, exactly like
         ``recognize_ws`` / ``process_audio_chunk`` (speechcatcher_server.py:270,359-397); the default resets.
         ``continuous`` (default: on whenever the batch has the C++ engine's submit / poll - round 4; False forces one
@@ -206,7 +218,20 @@ class ServerLoop:
         CTC table (the scheduler's ``phrases`` option; floors: ``spotting_min_scores`` {name: min_score}, default -2.0
         per token).  When phrases were detected in the frames of a chunk, a {"spotted": [{"phrase", "start", "end",
         "score"}]} message (seconds of the utterance) goes out in front of that chunk's reply.  Counts the frames of an
-        utterance from the reset after a final, so not with ``strict_reference``.  None (default): no such message."""
+        utterance from the reset after a final, so not with ``strict_reference``.  None (default): no such message.
+        ``draft_partials`` (Vosk format): a partial becomes {"partial": text, "ahead": text of the draft tokens behind the
+        search's last token, "ahead_result": [{"word", "start", "end", "conf"}]} (the scheduler's ``draft`` option:
+        the greedy CTC transcript of the newest frames, which the blockwise search has not reached yet).  Finals are
+        unchanged.  Counts the frames of an utterance from the reset after a final, so not with ``strict_reference``.
+        False (default): partials as they are."""
+        self.draft_partials = False
+        if draft_partials:
+            if strict_reference:
+                raise ValueError("draft partials count the frames of an utterance from the reset after a final: "
+                                 "not with strict_reference")
+            if not scheduler.draft:
+                scheduler.enable_draft()
+            self.draft_partials = True
         self.spot_names = None
         if spotting:
             if strict_reference:
@@ -337,6 +362,12 @@ class ServerLoop:
         if ses.acoustic is not None and not info["finalize"]:
             ses.acoustic.observe(results.activity)
         if not results:
+            if ses.vosk and self.draft_partials and not info["finalize"]:
+                # no hypothesis yet: the partial of the last reply (an empty one behind a final), and the draft
+                last = ses.last["partial"] if isinstance(ses.last, dict) and "partial" in ses.last else ""
+                return vosk_partial_ahead(last, getattr(results, "ahead", None) or [])
+            if self.draft_partials and isinstance(ses.last, dict) and "ahead" in ses.last:
+                ses.last = vosk_partial(ses.last["partial"])   # a final without a hypothesis repeats the partial alone
             return ""
         text, tokens, _ids, pos, _hyp = results[0]
         if info["finalize"]:
@@ -349,6 +380,8 @@ class ServerLoop:
                 return vosk_result_aligned(tokens, al)
             return vosk_result(tokens, pos) if ses.vosk else text
         ses.endpointer.observe(len(text))
+        if ses.vosk and self.draft_partials:
+            return vosk_partial_ahead(text, getattr(results, "ahead", None) or [])
         return vosk_partial(text) if ses.vosk else text
 
     @staticmethod
@@ -410,5 +443,5 @@ class StepPacer:
 
 
 __all__ = ["Endpointer", "EndpointRules", "AcousticEndpointer", "ServerLoop", "StepPacer", "ServerBusy", "vosk_partial", "vosk_result", "vosk_result_aligned",
-           "spotting_set", "spotted_message",
+           "spotting_set", "spotted_message", "vosk_partial_ahead",
            "scale_server_pcm"]

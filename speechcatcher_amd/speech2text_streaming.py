@@ -402,6 +402,17 @@ class Speech2TextStreaming:
         from .spotting import event_dicts
         return event_dicts(self.batch.spot_events(self.stream))
 
+    def set_draft(self, on: bool = True):
+        """Draft transcript from the CTC table (NativeStreamBatch.set_draft): the greedy transcript of every frame the
+        encoder has emitted, ahead of the blockwise search; between calls."""
+        self.batch.set_draft(on)
+
+    def draft(self) -> list:
+        """[{"id", "start", "end": encoder frames of 0.04 s (both inclusive), "conf"}]: the draft of the utterance up to
+        the last call - the closed tokens, then the open one"""
+        from .draft import token_dicts
+        return token_dicts(self.batch.draft_tokens(self.stream))
+
     def recognize(self, speech):
         self.reset()
         return self(speech, is_final=True)
