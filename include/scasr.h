@@ -173,7 +173,7 @@ const char *sc_last_error(void);
 /* ABI revision of this header: bumped whenever a struct layout or a signature changes incompatibly.  sc_version()
  * returns the revision the LIBRARY was built with; a host compares the two before it passes any struct
  * (speechcatcher_amd/_abi.py does at load time, the C hosts in tests/ at start-up). */
-#define SC_ABI_VERSION 9
+#define SC_ABI_VERSION 10
 int sc_version(void);
 
 /* hipGraph capture / replay of any sequence of the launches below on a
@@ -516,6 +516,60 @@ typedef struct sc_ctc_draft_job {
  * nothing.  Two jobs of one call must not share a state or a token store. */
 int sc_ctc_draft(const sc_ctc_draft_job *jobs, int n_jobs, void *stream);
 
+/* ---- wire-format audio in (pcm.hip) -----------------------------------------------------------
+ * A chunk is n sample FRAMES of `channels` interleaved little-endian codes, starting at ANY byte address.  Every format
+ * but SC_PCM_F32 gives an integer v per code with full scale 2^B:
+ *   SC_PCM_S16LE  the int16, B = 15;   SC_PCM_S24LE  3 packed bytes, sign-extended, B = 23;   SC_PCM_U8  b - 128, B = 7
+ *   SC_PCM_MULAW  u = ~b & 0xFF; mag = ((((u & 15) << 3) + 0x84) << ((u >> 4) & 7)) - 0x84; v = u & 0x80 ? -mag : mag, B = 15
+ *   SC_PCM_ALAW   a = b ^ 0x55; e = (a >> 4) & 7; mag = e ? (((a & 15) << 4) + 0x108) << (e - 1) : ((a & 15) << 4) + 8;
+ *                 v = a & 0x80 ? mag : -mag, B = 15            (G.711: Python 3.10 audioop.ulaw2lin / alaw2lin)
+ * channel in [0, channels): m = v[channel], C = 1;  channel == SC_PCM_MIX: m = the exact integer sum over the channels,
+ * C = channels.  x = RN_fp32(m / C), the exact quotient rounded ONCE (m is never rounded to fp32 first).  The sample is
+ * x * 2^-B (SC_PCM_SCALE_FULL, exact) or fp32(RN_half(x)) * 2^-15 (SC_PCM_SCALE_SERVER, B = 15 formats only: the
+ * reference server's float16 conversion, speechcatcher_server.py).  SC_PCM_F32: a selected channel passes its bits
+ * through, NaNs included; a mix is RN_fp32(s / C), s the fp32 sum of the channels in ascending order with every add
+ * rounded, and the canonical quiet NaN 0x7fc00000 when that is a NaN; SC_PCM_SCALE_FULL only.
+ * The LEVEL of the integer formats, cumulative over an utterance and exact in any order: frames += n,
+ * peak = max(peak, |m|), sum_abs += |m|, clipped += frames in which a contributing channel's v sits at its format's
+ * extreme (s16 -32768 / 32767, s24 -2^23 / 2^23 - 1, u8 -128 / 127, mu-law |v| = 32124, A-law |v| = 32256),
+ * full_scale = C 2^B.  SC_PCM_F32 leaves the counts as they are and sets full_scale = 0.
+ * tests/pcm_ref.py is the contract; the kernel reproduces it bit for bit. */
+#define SC_PCM_F32 0
+#define SC_PCM_S16LE 1
+#define SC_PCM_S24LE 2
+#define SC_PCM_U8 3
+#define SC_PCM_MULAW 4
+#define SC_PCM_ALAW 5
+#define SC_PCM_N_FORMATS 6
+#define SC_PCM_MIX (-1)
+#define SC_PCM_MAX_CHANNELS 8
+#define SC_PCM_SCALE_FULL 0
+#define SC_PCM_SCALE_SERVER 1
+typedef struct sc_input_level_t {
+  int64_t frames, clipped, sum_abs;
+  int32_t peak, full_scale;
+} sc_input_level_t;
+typedef struct sc_pcm_job {
+  const void *src;               /* the coded bytes (device); the chunk starts at src + offset, any alignment */
+  float *dst;                    /* [n] decoded samples (device) */
+  sc_input_level_t *level;       /* read (unless restart), advanced over the chunk, written back (device) */
+  sc_input_level_t *level_after; /* second copy of the new level, e.g. in host-mapped memory (NULL: none) */
+  int64_t offset;                /* bytes, >= 0 */
+  int32_t format, channels, channel, scale;
+  int32_t n;                     /* sample frames, >= 0 */
+  int32_t restart;               /* != 0: the stored level is ignored, the chunk starts an utterance (all zero) */
+} sc_pcm_job;
+#define SC_PCM_MAX_JOBS 65535
+/* jobs: device table of n_jobs entries.  ONE launch on `stream`, one workgroup of 256 threads per job; no atomics, one
+ * writer per output, nothing is written behind dst + n; n == 0 rewrites the level unchanged.  n_jobs < 0, a null table
+ * with n_jobs > 0 or n_jobs > SC_PCM_MAX_JOBS: SC_ERR_ARG before anything is launched.  A job whose own fields are
+ * malformed (a null pointer other than level_after, a format outside [0, SC_PCM_N_FORMATS), channels outside [1, 8],
+ * channel outside [-1, channels), a scale the format does not take, offset < 0, n < 0) writes nothing.  Two jobs of one
+ * call must not share a level or overlap in dst. */
+int sc_pcm_decode(const sc_pcm_job *jobs, int n_jobs, void *stream);
+/* bytes of one sample frame (pure host); SC_ERR_ARG (< 0) for a format or a channel count out of range */
+int sc_pcm_bytes_per_frame(int format, int channels);
+
 /* ---- frontend ------------------------------------------------------------ */
 
 /* STFTFrontend.forward (model/frontend/stft_frontend.py:87-154) fused with the
@@ -855,6 +909,33 @@ int sc_reset(sc_streams *streams, int stream);
  * uploaded when the rate is first set. */
 int sc_stream_set_input_rate(sc_streams *streams, int stream, int rate);
 int sc_stream_input_rate(const sc_streams *streams, int stream);
+/* stream level: wire format of the audio a stream takes (pcm.hip above) - format SC_PCM_*, channels 1..8
+ * interleaved, channel in [0, channels) or SC_PCM_MIX, scale SC_PCM_SCALE_* (SC_PCM_SCALE_SERVER only with S16LE / MULAW /
+ * ALAW).  The preconditions of sc_stream_set_input_rate: an idle stream that has buffered nothing since its last reset;
+ * SC_ERR_ARG otherwise or for a value out of range.  Default (SC_PCM_F32, 1, 0, SC_PCM_SCALE_FULL): mono floats, today's
+ * path.  The format survives sc_reset and composes with the input rate: the decoded samples are what a float chunk
+ * would have been - scattered into the PCM ring at 16 kHz, the converter's input at another rate.  A stream with any
+ * other format is CODED: it takes its audio through sc_push_raw / sc_submit_raw only (sc_push / sc_submit: SC_ERR_ARG),
+ * host pointers only.  A coded chunk's bytes travel in a byte region of the admission's pinned staging slot (as large as
+ * the slot's floats; pinned and device memory for it, the job tables and S level records are allocated when a format is
+ * first set on the handle); ONE sc_pcm_decode launch per admission on the encoder stream writes the float spans reserved
+ * for them before the admission's scatter / conversion launch reads those.  n_frames and the 16 kHz sample count obey
+ * the limits of sc_stream_set_input_rate; a chunk whose bytes do not fit what is left of the byte region fails THAT stream
+ * with SC_ERR_CAPACITY (a format of at most 4 bytes per frame always fits).  An admission without coded chunks launches
+ * nothing new. */
+int sc_stream_set_input_format(sc_streams *streams, int stream, int format, int channels, int channel, int scale);
+int sc_stream_input_format(const sc_streams *streams, int stream, int *format, int *channels, int *channel, int *scale);
+/* sc_push / sc_submit with audio[i] = the bytes of n_frames[i] sample FRAMES in stream_ids[i]'s format (HOST; floats for
+ * a stream without a format: then these ARE sc_push / sc_submit) */
+int sc_push_raw(sc_streams *streams, const int *stream_ids, const void *const *audio, const int *n_frames,
+                const uint8_t *is_final, int n, int *status);
+int sc_submit_raw(sc_streams *streams, const int *stream_ids, const void *const *audio, const int *n_frames,
+                  const uint8_t *is_final, int n);
+/* input level of a coded stream, cumulative over the utterance, up to and including the stream's last REPORTED chunk - the
+ * chunk whose hypotheses sc_get_hyps returns - however many chunks are queued behind it; a stream's first chunk after
+ * sc_reset or after a final chunk starts over.  All zero after sc_reset, for a stream without a format and for SC_PCM_F32
+ * (then with full_scale = 0).  Waits for the staging step of that chunk if it is still in flight. */
+int sc_stream_input_level(sc_streams *streams, int stream, sc_input_level_t *out /*HOST*/);
 int sc_stream_info(const sc_streams *streams, int stream, sc_stream_info_t *out);
 /* rows of the self-attention K|V pool per (stream, layer) this batch was created with (sc_stream_options.kv_pool_rows, or the
  * default: one row per (position, hypothesis) within min(a quarter of the free device memory, SC_KV_POOL_DEFAULT_MAX_GIB)) */

@@ -8,50 +8,79 @@ reset() after it) -> paragraphs -> ``<input>.txt`` and ``<input>.json``.
 Differences to the reference CLI, all on the host side: only ``--decoder native`` exists here; the device is a ROCm
 GPU (no CPU path); ``-n`` is the number of parallel stream slots of ONE model replica instead of worker processes
 (default 1 = the reference's behaviour on a GPU: segments decoded serially on one model, speechcatcher.py:823-825);
-input must be mono 16-bit WAV, at 16 kHz or at any rate the engine converts (8000..48000 Hz, speechcatcher_amd.resample:
-the whole recording is resampled once on the GPU and then takes the 16 kHz path); the ffmpeg conversion of other media,
-microphone mode and model download are out of scope - pass a local model directory or a .scasr blob as ``-m``.
+input must be a RIFF/WAVE file - 8 / 16 / 24-bit PCM, 32-bit float, A-law or mu-law, 1..8 channels
+(speechcatcher_amd.pcm.read_wav) - at 16 kHz or at any rate the engine converts (8000..48000 Hz, speechcatcher_amd.resample).
+Mono 16-bit files take the int16 samples as they are; anything else is decoded once, whole, on the GPU
+(hip_backend.decode_recording); the recording is then resampled once on the GPU if need be and takes the 16 kHz int16
+path.  A recording with more than one channel is refused, as it always was, unless ``--channel`` says what to decode:
+``--channel N`` one channel, ``--channel mix`` the downmix of all (two speakers of a call on two channels are two
+transcripts, not one: the choice is the caller's).  The ffmpeg conversion of other media, microphone mode and model
+download are out of scope - pass a local model directory or a .scasr blob as ``-m``.
 """
 import argparse
 import json
 import logging
 import os
 import sys
-import wave
 
 import numpy as np
 
 
-def read_wav_16k_mono(path):
-    with wave.open(path, "rb") as f:
-        ch, bits, rate = f.getnchannels(), f.getsampwidth(), f.getframerate()
-        buf = f.readframes(-1)
+def read_wav_16k_mono(path, channel=None, device="cuda:0"):
+    """A RIFF/WAVE recording -> (mono samples, rate).  Mono 16-bit PCM: its int16 samples, as they are.  Anything else the
+    reader takes (speechcatcher_amd.pcm.read_wav): float32 samples in +-1 as a device tensor, decoded once, whole, on the
+    GPU (hip_backend.decode_recording).  ``channel``: an index, or "mix" / pcm.MIX for the downmix; None refuses a
+    recording with more than one channel."""
+    from . import pcm
     from .resample import MAX_RATE, MIN_RATE, rate_params
-    if ch != 1 or bits != 2 or rate_params(rate) is None:
-        raise SystemExit(f"Error: '{path}' is {ch} channel(s), {8 * bits} bit, {rate} Hz; this entry point reads 16 kHz mono "
-                         f"16-bit WAV, or mono 16-bit WAV at {MIN_RATE}..{MAX_RATE} Hz which it resamples (the reference "
-                         "converts other media with ffmpeg first: ffmpeg -i in -ac 1 -ar 16000 out.wav)")
-    return np.frombuffer(buf, dtype="<i2"), rate
+    try:
+        wav = pcm.read_wav(path)
+    except ValueError as e:
+        raise SystemExit(f"Error: {e} (the reference converts other media with ffmpeg first: ffmpeg -i in -ac 1 -ar 16000 "
+                         "out.wav)")
+    if rate_params(wav.sample_rate) is None:
+        raise SystemExit(f"Error: '{path}' is at {wav.sample_rate} Hz; this entry point reads 16 kHz mono recordings, or WAV at "
+                         f"{MIN_RATE}..{MAX_RATE} Hz which it resamples")
+    if channel == "mix":
+        channel = pcm.MIX
+    if channel is None and wav.channels > 1:
+        raise SystemExit(f"Error: '{path}' has {wav.channels} channels; this entry point reads 16 kHz mono recordings (or mono "
+                         f"at {MIN_RATE}..{MAX_RATE} Hz) unless --channel N or --channel mix says which part of a multichannel "
+                         "recording to decode")
+    if channel is not None and not pcm.MIX <= int(channel) < wav.channels:
+        raise SystemExit(f"Error: --channel {channel}: '{path}' has {wav.channels} channel(s)")
+    if wav.format == pcm.S16LE and wav.channels == 1:
+        return np.frombuffer(wav.data, dtype="<i2"), wav.sample_rate
+    from .hip_backend import decode_recording
+    x, _level = decode_recording(wav.data, wav.format, wav.channels, 0 if channel is None else int(channel),
+                                 pcm.SCALE_FULL, device)
+    return x, wav.sample_rate
 
 
 def to_16k(raw, rate, device="cuda:0"):
-    """int16 recording at ``rate`` -> int16 at 16 kHz: resampled once, whole, on the GPU (hip_backend.resample)"""
-    if rate == 16000:
+    """recording at ``rate`` (int16, or float32 in +-1 from read_wav_16k_mono) -> int16 at 16 kHz: resampled once, whole,
+    on the GPU (hip_backend.resample) if need be"""
+    if rate == 16000 and isinstance(raw, np.ndarray) and raw.dtype == np.int16:
         return raw
-    from .hip_backend import resample
-    y = resample(raw.astype(np.float32) / 32768.0, rate, device).cpu().numpy()
+    if isinstance(raw, np.ndarray):
+        raw = raw.astype(np.float32) / 32768.0
+    if rate != 16000:
+        from .hip_backend import resample
+        raw = resample(raw, rate, device)
+    y = raw.cpu().numpy() if not isinstance(raw, np.ndarray) else raw
     return np.clip(np.rint(y * 32768.0), -32768, 32767).astype(np.int16)
 
 
 def recognize_file(speech2text, media_path, output_file="", quiet=True, progress=True, num_slots=1, chunk_length=8192,
-                   token_alignment=False, segmentation="host"):
+                   token_alignment=False, segmentation="host", channel=None):
     """speechcatcher.py:358-400: recording -> text + paragraphs JSON next to the input.  ``token_alignment``: the
     paragraphs also get token_start / token_end (seconds) and token_conf from a CTC forced alignment of each segment.
-    ``segmentation``: "host" or "gpu" - where the energy curve for the cut points of a recording over 60 s is computed."""
+    ``segmentation``: "host" or "gpu" - where the energy curve for the cut points of a recording over 60 s is computed.
+    ``channel``: what to decode of a multichannel recording - an index, or "mix" (None: such a recording is refused)."""
     from .config import SearchConfig
     from .native import NativeStreamBatch
     from .segmenter import recognize_recording
-    raw, rate = read_wav_16k_mono(media_path)
+    raw, rate = read_wav_16k_mono(media_path, channel, speech2text.device)
     raw, rate = to_16k(raw, rate, speech2text.device), 16000
     seconds = len(raw) / float(rate)
     # capacities for the longest segment the endpointer may produce (it cuts at <= 180 s: simple_endpointing)
@@ -108,7 +137,13 @@ def make_parser():
     p.add_argument("--segmentation", dest="segmentation", choices=["host", "gpu"], default="host",
                    help="where the energy curve for the cut points of a recording over 60 s is computed: 'host' (numpy, the "
                         "default) or 'gpu' (float64 kernels; the same cuts, without the host pass over the whole recording)")
-    p.add_argument("inputfile", nargs="?", default="", help="input recording (mono 16-bit WAV, 16 kHz or 8000..48000 Hz)")
+    p.add_argument("--channel", dest="channel", type=lambda v: "mix" if v == "mix" else int(v), default=None,
+                   help="what to decode of a recording with more than one channel: a channel index from 0, or 'mix' for the "
+                        "downmix of all channels (without it such a recording is refused)")
+    p.add_argument("inputfile", nargs="?", default="",
+                   help="input recording: WAV, 8 / 16 / 24-bit PCM, 32-bit float, A-law or mu-law, 1..8 channels, 16 kHz or "
+                        "8000..48000 Hz.  The recording is quantised to 16 bits before it is decoded: 24-bit and float input "
+                        "lose what lies below that")
     return p
 
 
@@ -132,7 +167,7 @@ def main(argv=None):
                              use_bbd=not args.disable_bbd)
     recognize_file(speech2text, args.inputfile, quiet=args.quiet or not args.no_progress, progress=not args.no_progress,
                    num_slots=1 if args.num_processes < 1 else args.num_processes, chunk_length=args.chunk_length,
-                   token_alignment=args.token_alignment, segmentation=args.segmentation)
+                   token_alignment=args.token_alignment, segmentation=args.segmentation, channel=args.channel)
     return 0
 
 

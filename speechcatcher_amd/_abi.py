@@ -135,6 +135,21 @@ class DraftJob(C.Structure):
 DRAFT_FIELDS = tuple(n for n, _ in Draft._fields_)
 DRAFT_MAX_JOBS = 65535
 
+class InputLevel(C.Structure):
+    """sc_input_level_t (include/scasr.h)"""
+    _fields_ = ([(n, C.c_int64) for n in ("frames", "clipped", "sum_abs")]
+                + [(n, C.c_int32) for n in ("peak", "full_scale")])
+
+
+class PcmJob(C.Structure):
+    """sc_pcm_job (include/scasr.h): one chunk of coded audio decoded by sc_pcm_decode"""
+    _fields_ = ([(n, vp) for n in ("src", "dst", "level", "level_after")] + [("offset", C.c_int64)]
+                + [(n, C.c_int32) for n in ("format", "channels", "channel", "scale", "n", "restart")])
+
+
+LEVEL_FIELDS = tuple(n for n, _ in InputLevel._fields_)
+PCM_MAX_JOBS = 65535
+
 # SC_ALIGN_* of include/scasr.h
 ALIGN_OK, ALIGN_INFEASIBLE, ALIGN_NONFINITE, ALIGN_BAD_INPUT = 0, 1, 2, 3
 ALIGN_MAX_L = 1023
@@ -288,6 +303,14 @@ _SIGS = {
     "sc_streams_set_draft": (C.c_int, [vp, C.c_int]),
     "sc_stream_draft": (C.c_int, [vp, C.c_int, C.POINTER(Draft)]),
     "sc_streams_read_draft": (C.c_int, [vp, C.c_int, vp, C.c_int]),
+    # wire-format audio in (pcm.hip)
+    "sc_pcm_decode": (C.c_int, [vp, C.c_int, vp]),
+    "sc_pcm_bytes_per_frame": (C.c_int, [C.c_int, C.c_int]),
+    "sc_stream_set_input_format": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sc_stream_input_format": (C.c_int, [vp, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p]),
+    "sc_push_raw": (C.c_int, [vp, c_int_p, C.POINTER(vp), c_int_p, C.POINTER(C.c_uint8), C.c_int, c_int_p]),
+    "sc_submit_raw": (C.c_int, [vp, c_int_p, C.POINTER(vp), c_int_p, C.POINTER(C.c_uint8), C.c_int]),
+    "sc_stream_input_level": (C.c_int, [vp, C.c_int, C.POINTER(InputLevel)]),
     # sample-rate conversion (resample.hip, streams.hip)
     "sc_resample_design": (C.c_int, [C.c_int, c_int_p, c_int_p, c_int_p, c_float_p]),
     "sc_resample_out_count": (C.c_long, [C.c_int, C.c_long, C.c_int]),
@@ -305,7 +328,7 @@ EXPORTED_SYMBOLS = tuple(_SIGS.keys())
 
 # revision of include/scasr.h these ctypes mirrors were written against (SC_ABI_VERSION): a library built from another
 # revision would be handed mis-laid-out structs
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 _lib = None
 

@@ -122,6 +122,9 @@ struct St {
   // samples taken and 16 kHz samples produced in this utterance, history row the next launch reads (it writes the other)
   int rs_tab = -1, rs_par = 0;
   long rs_in = 0, rs_out = 0;
+  // wire format of the stream's input (pcm.hip): SC_PCM_F32 with one channel is the float path - no decode launch
+  int in_fmt = SC_PCM_F32, in_ch = 1, in_sel = 0, in_scale = SC_PCM_SCALE_FULL;
+  bool coded() const { return in_fmt != SC_PCM_F32 || in_ch != 1; }
 };
 
 // a decode block of the schedule (beam_search.py:590-634): the T frames [0, T) it presents to the scorers, whether
@@ -165,6 +168,15 @@ struct DraftVal {
   sc_draft_t v = {0, 0, 0, -1, -1, -1, 0.0};
 };
 
+// Input level (sc_stream_set_input_format; pcm.hip): the cumulative level that belongs to a chunk.  The launch that computes
+// it belongs to a STAGING slot (it runs in the admission's staging step, not in an encoder group): `ticket` names the decode
+// job, and until its slot's event has fired and the state-after has been collected the value is pending (ready = false).
+struct LevelVal {
+  bool ready = true;
+  long ticket = 0;
+  sc_input_level_t v = {0, 0, 0, 0, 0};
+};
+
 // a stream's outstanding chunk (sc_push / sc_submit): open until it has been reported.  With a queue depth > 1
 // (sc_streams_set_queue_depth) further chunks of the stream wait behind it (sc_streams::ahead), in order.
 struct Job {
@@ -178,6 +190,7 @@ struct Job {
   ActVal act;             // sc_streams_set_activity: the activity state that belongs to this chunk
   SpotVal spot;           // sc_streams_set_phrases: the spotting counters that belong to this chunk
   DraftVal draft;         // sc_streams_set_draft: the draft state that belongs to this chunk
+  LevelVal level;         // sc_stream_set_input_format: the input level up to and including this chunk
 };
 
 // hypotheses of a stream's last complete chunk, copied aside when later chunks of the stream may go on decoding
@@ -220,6 +233,13 @@ struct EncGroup {
   std::vector<long long> copy_jobs;          // [n][3] staging offset, destination offset, count (floats)
   std::vector<sc_rs_job> rs_jobs;            // chunks of the streams whose input rate is not 16000: converted, not copied
   size_t stage_floats = 0;
+  // coded chunks (streams with an input format): their bytes go to the slot's byte region, ONE sc_pcm_decode launch writes
+  // the float spans reserved for them before the scatter / conversion launch reads those; pcm_spans[i] belongs to pcm_jobs[i]
+  struct PcmSpan { int s; bool fin; };
+  std::vector<sc_pcm_job> pcm_jobs;
+  std::vector<PcmSpan> pcm_spans;
+  size_t stage_bytes = 0;
+  bool stage_filled = false;                 // the host wrote floats into the slot (false: the float copy is skipped)
   std::vector<int32_t> fe_jobs;
   int n_fe = 0, max_keep = 0;
   EncPlan P;
@@ -316,6 +336,18 @@ struct sc_streams {
   sc_rs_tabs rs_tabs{};           // coefficient tables of the rates set on this handle (designed when a rate is first set)
   int rs_rate[SC_RS_MAX_TABS] = {0};
   int n_rs_tabs = 0;
+  // ---- wire-format input (sc_stream_set_input_format; pcm.hip): everything below is allocated when a format is first set ----
+  uint8_t *stageb_host = nullptr, *stageb_dev = nullptr;   // [N_STAGE][stageb_cap] byte region of a staging slot
+  size_t stageb_cap = 0;          // bytes per slot = the float slot's bytes
+  sc_pcm_job *pcmjobs_host = nullptr, *pcmjobs_dev = nullptr;             // [N_STAGE][S] decode jobs of a staging slot
+  sc_input_level_t *lvl_state = nullptr;                                  // device [S]: the running level of every stream
+  sc_input_level_t *lvl_out_host = nullptr, *lvl_out_dev = nullptr;       // [N_STAGE][S] host-mapped: the jobs' levels-after
+  struct LvlSpan { int s; long epoch, ticket; };
+  std::vector<LvlSpan> stage_lvl[N_STAGE];   // the decode jobs of the slot's latest admission, until their levels are collected
+  std::vector<LevelVal> lvl_known, lvl_rep;  // per stream: after the latest COLLECTED job / of the last reported chunk
+  std::vector<long> lvl_pending, lvl_epoch;  // per stream: ticket of its latest job not collected yet (0: none) / resets so far
+  std::vector<char> lvl_fresh;               // per stream: the next job starts the utterance
+  long lvl_ticket = 0;
   // ---- batched hypothesis read-back (sc_get_hyps_batch): pack kernel -> one D2H into pinned memory -------------------
   int32_t *pack_dev = nullptr, *pack_host = nullptr, *pjobs_host = nullptr, *pjobs_dev = nullptr;
   size_t pack_cap = 0;            // int32 elements
@@ -540,6 +572,7 @@ void reset_stream(sc_streams *b, int s) {
   // (scorers.py:342-350: the stale table stays) and the short-segment PE counter keeps counting (A13).
   St old = b->st[s], ns;
   ns.rs_tab = old.rs_tab;   // the input rate stays; the converter starts over (no history)
+  ns.in_fmt = old.in_fmt; ns.in_ch = old.in_ch; ns.in_sel = old.in_sel; ns.in_scale = old.in_scale;   // and so does the format
   if (b->strict) {
     ns.short_pos = old.short_pos;
     ns.T_ctc = old.T_ctc;
@@ -566,6 +599,12 @@ void reset_stream(sc_streams *b, int s) {
     b->draft_known[s] = b->draft_rep[s] = DraftVal();
     b->draft_pending[s] = 0;
     b->draft_fresh[s] = 1;
+  }
+  if (!b->lvl_epoch.empty()) {   // input level: the same
+    b->lvl_epoch[s]++;
+    b->lvl_known[s] = b->lvl_rep[s] = LevelVal();
+    b->lvl_pending[s] = 0;
+    b->lvl_fresh[s] = 1;
   }
   init_hyp(b, s);
 }
@@ -930,9 +969,44 @@ int prepare_decode(sc_streams *b) {
   return SC_OK;
 }
 
+// input level: the levels-after of a staging slot's decode jobs -> the chunks they belong to (open, or reported in the
+// meantime).  wait: block until the slot's launches are done; else only if its event has fired
+int collect_levels(sc_streams *b, int slot, bool wait) {
+  std::vector<sc_streams::LvlSpan> &spans = b->stage_lvl[slot];
+  if (spans.empty()) return SC_OK;
+  if (wait) HIP_TRY(hipEventSynchronize(b->ev_stage[slot]));
+  else {
+    const hipError_t q = hipEventQuery(b->ev_stage[slot]);
+    if (q == hipErrorNotReady) { (void)hipGetLastError(); return SC_OK; }
+    if (q != hipSuccess) {
+      sc_set_error("staging slot %d failed: %s", slot, hipGetErrorString(q));
+      return SC_ERR_LAUNCH;
+    }
+  }
+  for (size_t i = 0; i < spans.size(); ++i) {
+    const sc_streams::LvlSpan &sp = spans[i];
+    if (sp.epoch != b->lvl_epoch[sp.s]) continue;   // the stream has been reset since
+    LevelVal k;
+    k.ticket = sp.ticket;
+    k.v = b->lvl_out_host[(size_t)slot * b->S + i];
+    if (sp.ticket > b->lvl_known[sp.s].ticket) b->lvl_known[sp.s] = k;   // (slots are collected in any order: the latest job counts)
+    auto fill = [&](LevelVal &a) {
+      if (!a.ready && a.ticket == sp.ticket) a = k;
+    };
+    fill(b->job[sp.s].level);
+    for (Job &j : b->ahead[sp.s]) fill(j.level);
+    fill(b->lvl_rep[sp.s]);
+    if (b->lvl_pending[sp.s] == sp.ticket) b->lvl_pending[sp.s] = 0;
+  }
+  spans.clear();
+  return SC_OK;
+}
+
 // ---- encoder groups -----------------------------------------------------------------------------------------------
 // groups complete in order (one in-order stream): pop every leading group whose event has fired
 int retire_groups(sc_streams *b) {
+  if (b->lvl_state)
+    for (int i = 0; i < N_STAGE; ++i) RC_TRY(collect_levels(b, i, false));
   while (!b->groups.empty()) {
     EncGroup *g = b->groups.front();
     if (!g->launched) break;
@@ -1125,13 +1199,22 @@ int project_rows(sc_streams *b, EncGroup &g) {
 // host input of an admission -> device, at once: ONE host-to-device copy of the pinned staging slot, one scatter
 // launch to the chunks' places behind what each stream has buffered (PCM ring / feature buffer)
 int stage_copy(sc_streams *b, EncGroup &g) {
-  if (g.copy_jobs.empty() && g.rs_jobs.empty()) return SC_OK;
+  if (g.copy_jobs.empty() && g.rs_jobs.empty() && g.pcm_jobs.empty()) return SC_OK;
   hipStream_t es = b->stream_enc ? b->stream_enc : b->stream;
   const int ss = g.stage_slot;
   const size_t so = (size_t)ss * b->stage_cap, jo = (size_t)ss * b->S * 3;
   const int nj = (int)g.copy_jobs.size() / 3;
-  if (g.stage_floats)
+  if (g.stage_floats && (g.stage_filled || g.pcm_jobs.empty()))
     HIP_TRY(hipMemcpyAsync(b->stage_dev + so, b->stage_host + so, g.stage_floats * sizeof(float), hipMemcpyHostToDevice, es));
+  if (!g.pcm_jobs.empty()) {   // the coded chunks: bytes -> the float spans reserved for them, before anything reads those
+    const size_t bo = (size_t)ss * b->stageb_cap, po = (size_t)ss * b->S;
+    const int np = (int)g.pcm_jobs.size();
+    if (g.stage_bytes)
+      HIP_TRY(hipMemcpyAsync(b->stageb_dev + bo, b->stageb_host + bo, g.stage_bytes, hipMemcpyHostToDevice, es));
+    memcpy(b->pcmjobs_host + po, g.pcm_jobs.data(), np * sizeof(sc_pcm_job));
+    HIP_TRY(hipMemcpyAsync(b->pcmjobs_dev + po, b->pcmjobs_host + po, np * sizeof(sc_pcm_job), hipMemcpyHostToDevice, es));
+    RC_TRY(sc_pcm_decode(b->pcmjobs_dev + po, np, es));
+  }
   if (nj) {
     memcpy(b->cjobs_host + jo, g.copy_jobs.data(), g.copy_jobs.size() * sizeof(long long));
     HIP_TRY(hipMemcpyAsync(b->cjobs_dev + jo, b->cjobs_host + jo, g.copy_jobs.size() * sizeof(long long), hipMemcpyHostToDevice, es));
@@ -1152,6 +1235,8 @@ int stage_copy(sc_streams *b, EncGroup &g) {
   b->stage_busy[ss] = true;
   g.copy_jobs.clear();
   g.rs_jobs.clear();
+  g.pcm_jobs.clear();
+  g.pcm_spans.clear();
   return SC_OK;
 }
 
@@ -1531,7 +1616,7 @@ inline bool chunk_complete(const sc_streams *b, int s) {
 }
 
 // ---- admission ------------------------------------------------------------------------------------------------------
-struct Chunk { int s; const float *host; long n; bool fin; int pos; };
+struct Chunk { int s; const void *host; long n; bool fin; int pos; };   // host: floats, or the bytes of n frames (a coded stream)
 
 // the group that carries the stream's LATEST encoder stage (its frames are what "the frames that were there before"
 // means for the next admission: a block that only sees those still has to wait for that group)
@@ -1543,6 +1628,32 @@ void plan_group(sc_streams *b, const std::vector<Chunk> &chunks, bool features, 
                 std::map<int, bool> &finals, std::vector<int> &has_out) {
   const sc_config &c = b->cfg;
   float *stage = g.stage_slot >= 0 ? b->stage_host + (size_t)g.stage_slot * b->stage_cap : nullptr;
+  // a chunk's ch.n samples -> the float span at g.stage_floats: copied there (floats), or reserved for the decode launch and
+  // its bytes staged in the slot's byte region, every chunk at a multiple of 4 (n frames of at most 4 bytes then always fit)
+  auto stage_chunk = [&](const Chunk &ch, const St &st) {
+    if (!st.coded()) {
+      if (ch.n > 0) memcpy(stage + g.stage_floats, ch.host, (size_t)ch.n * sizeof(float));
+      g.stage_filled = g.stage_filled || ch.n > 0;
+      return;
+    }
+    const size_t nb = (size_t)ch.n * (size_t)sc_pcm_bytes_per_frame(st.in_fmt, st.in_ch);
+    if (g.stage_bytes + nb > b->stageb_cap)
+      throw StreamFault{ch.s, SC_ERR_CAPACITY, "the chunk's raw bytes do not fit the staging slot's byte region (max_chunk_samples x 4 bytes x streams)"};
+    const size_t bo = (size_t)g.stage_slot * b->stageb_cap, po = (size_t)g.stage_slot * b->S;
+    if (nb) memcpy(b->stageb_host + bo + g.stage_bytes, ch.host, nb);
+    sc_pcm_job j{};
+    j.src = b->stageb_dev + bo;
+    j.offset = (int64_t)g.stage_bytes;
+    j.dst = b->stage_dev + (size_t)g.stage_slot * b->stage_cap + g.stage_floats;
+    j.level = b->lvl_state + ch.s;
+    j.level_after = b->lvl_out_dev + po + g.pcm_jobs.size();
+    j.format = st.in_fmt; j.channels = st.in_ch; j.channel = st.in_sel; j.scale = st.in_scale;
+    j.n = (int32_t)ch.n;
+    j.restart = 0;   // (set when the plan stands: admit)
+    g.pcm_jobs.push_back(j);
+    g.pcm_spans.push_back({ch.s, ch.fin});
+    g.stage_bytes += (nb + 3) & ~size_t(3);
+  };
   for (size_t k = 0; k < chunks.size(); ++k) {
     const Chunk &ch = chunks[k];
     St &st = b->st[ch.s];
@@ -1572,8 +1683,9 @@ void plan_group(sc_streams *b, const std::vector<Chunk> &chunks, bool features, 
       const long n_out = out_total - st.rs_out;
       if (ch.n > lim || n_out > lim) throw StreamFault{ch.s, SC_ERR_CAPACITY, "chunk is longer than max_chunk_samples allows"};
       if (st.pcm_end + n_out > b->PCAP) throw StreamFault{ch.s, SC_ERR_CAPACITY, "pcm buffer capacity exceeded"};
+      if (st.coded() && !(ch.n > 0 || n_out > 0)) stage_chunk(ch, st);   // (an empty job: the level is rewritten unchanged)
       if (ch.n > 0 || n_out > 0) {
-        if (ch.n > 0) memcpy(stage + g.stage_floats, ch.host, (size_t)ch.n * sizeof(float));
+        stage_chunk(ch, st);
         g.rs_jobs.push_back(sc_rs_job{(long long)g.stage_floats, (long long)ch.n, (long long)ch.s * b->PCAP + st.pcm_end,
                                       (long long)n_out, (long long)st.rs_out, (long long)st.rs_in, t, ch.s, st.rs_par, 0});
         g.stage_floats += (size_t)ch.n;
@@ -1585,10 +1697,11 @@ void plan_group(sc_streams *b, const std::vector<Chunk> &chunks, bool features, 
       st.pcm_end += n_out;
     } else {
       if (st.pcm_end + ch.n > b->PCAP) throw StreamFault{ch.s, SC_ERR_CAPACITY, "pcm buffer capacity exceeded"};
+      if (st.coded() && !(ch.n > 0 && ch.host)) stage_chunk(ch, st);   // (an empty job: the level is rewritten unchanged)
       if (ch.n > 0 && ch.host) {
         if (ch.n > b->max_chunk + 16 * c.hop_length)
           throw StreamFault{ch.s, SC_ERR_CAPACITY, "chunk is longer than max_chunk_samples allows"};
-        memcpy(stage + g.stage_floats, ch.host, (size_t)ch.n * sizeof(float));
+        stage_chunk(ch, st);
         g.copy_jobs.insert(g.copy_jobs.end(), {(long long)g.stage_floats, (long long)ch.s * b->PCAP + st.pcm_end, (long long)ch.n});
         g.stage_floats += (size_t)ch.n;
       }
@@ -1628,13 +1741,16 @@ int admit(sc_streams *b, std::vector<Chunk> chunks, bool features, bool defer, s
   RC_TRY(retire_groups(b));
   bool host_input = false;
   // (a stream at another input rate: its job table lives in the staging slot, also for a final call without samples)
-  for (auto &ch : chunks) host_input = host_input || (ch.host && ch.n > 0) || (!features && b->st[ch.s].rs_tab >= 0);
+  // (and a stream with an input format: its decode job lives in the staging slot, also for a call without samples)
+  for (auto &ch : chunks)
+    host_input = host_input || (ch.host && ch.n > 0) || (!features && (b->st[ch.s].rs_tab >= 0 || b->st[ch.s].coded()));
   int sslot = -1;
   if (host_input) {
     sslot = b->stage_next;
     b->stage_next = (b->stage_next + 1) % N_STAGE;
     if (b->stage_busy[sslot]) HIP_TRY(hipEventSynchronize(b->ev_stage[sslot]));
     b->stage_busy[sslot] = false;
+    if (b->lvl_state) RC_TRY(collect_levels(b, sslot, false));   // (the levels of the slot's last admission, before it is reused)
   }
   std::unique_ptr<EncGroup> gp(new EncGroup);   // owned here until it joins b->groups (or is merged / dropped)
   EncGroup *g = gp.get();
@@ -1695,10 +1811,21 @@ int admit(sc_streams *b, std::vector<Chunk> chunks, bool features, bool defer, s
       }
     }
   }
+  // input level: the plan stands - which decode job starts its stream's utterance, and the ticket its level comes back with
+  std::vector<sc_streams::LvlSpan> lvl_spans;
+  for (size_t i = 0; i < g->pcm_jobs.size(); ++i) {
+    const EncGroup::PcmSpan &sp = g->pcm_spans[i];
+    g->pcm_jobs[i].restart = b->lvl_fresh[sp.s] ? 1 : 0;
+    b->lvl_fresh[sp.s] = sp.fin ? 1 : 0;   // a final chunk ends the utterance: the next job starts over
+    const long ticket = ++b->lvl_ticket;
+    lvl_spans.push_back({sp.s, b->lvl_epoch[sp.s], ticket});
+    b->lvl_pending[sp.s] = ticket;
+  }
   {
     const int rc = stage_copy(b, *g);
     if (rc != SC_OK) return rc;
   }
+  if (!lvl_spans.empty()) b->stage_lvl[sslot] = lvl_spans;   // (behind the slot's event: collect_levels reads them when it has fired)
   // eager projections: CTC rows / cross-attention K|V rows of every frame this admission emits
   std::vector<int> act_new;   // activity: the streams this admission scans
   for (auto &ch : chunks) {
@@ -1832,6 +1959,15 @@ int admit(sc_streams *b, std::vector<Chunk> chunks, bool features, bool defer, s
         j.draft = b->draft_known[s];
       }
     }
+    if (b->lvl_state) {   // (and for the input level: the ticket of the stream's latest decode job, its own if it has one)
+      const int s = chunks[k].s;
+      if (b->lvl_pending[s]) {
+        j.level.ready = false;
+        j.level.ticket = b->lvl_pending[s];
+      } else {
+        j.level = b->lvl_known[s];
+      }
+    }
     if (b->job[chunks[k].s].open) b->ahead[chunks[k].s].push_back(j);   // behind the stream's outstanding chunk(s)
     else b->job[chunks[k].s] = j;
     b->n_open++;
@@ -1896,13 +2032,25 @@ int check_chunks(sc_streams *b, const int *stream_ids, const int *counts, int n,
 }
 
 // device-resident PCM (pcm[i] == NULL) is 16 kHz by definition: a stream with another input rate takes host samples only
-int check_resident(sc_streams *b, const int *stream_ids, const float *const *pcm, const int *counts, int n, const char *what) {
-  for (int i = 0; i < n; ++i)
-    if (b->st[stream_ids[i]].rs_tab >= 0 && counts[i] > 0 && (!pcm || !pcm[i])) {
-      sc_set_error("%s: stream %d has input rate %d: device-resident PCM (a NULL pointer) is 16 kHz only", what, stream_ids[i],
-                   b->rs_rate[b->st[stream_ids[i]].rs_tab]);
+// ... and float samples: a stream with an input format takes host bytes, through the _raw calls only
+int check_resident(sc_streams *b, const int *stream_ids, const void *const *pcm, const int *counts, int n, const char *what, bool raw) {
+  for (int i = 0; i < n; ++i) {
+    const St &st = b->st[stream_ids[i]];
+    if (st.coded() && !raw) {
+      sc_set_error("%s: stream %d has an input format (sc_stream_set_input_format): its audio goes through %s_raw", what,
+                   stream_ids[i], what);
       return SC_ERR_ARG;
     }
+    if (st.coded() && counts[i] > 0 && (!pcm || !pcm[i])) {
+      sc_set_error("%s: stream %d has an input format: device-resident PCM (a NULL pointer) is mono float only", what, stream_ids[i]);
+      return SC_ERR_ARG;
+    }
+    if (st.rs_tab >= 0 && counts[i] > 0 && (!pcm || !pcm[i])) {
+      sc_set_error("%s: stream %d has input rate %d: device-resident PCM (a NULL pointer) is 16 kHz only", what, stream_ids[i],
+                   b->rs_rate[st.rs_tab]);
+      return SC_ERR_ARG;
+    }
+  }
   return SC_OK;
 }
 
@@ -2353,6 +2501,89 @@ extern "C" int sc_stream_input_rate(const sc_streams *b, int stream) {
   return b->st[stream].rs_tab < 0 ? 16000 : b->rs_rate[b->st[stream].rs_tab];
 }
 
+// Wire format of the audio sc_push_raw / sc_submit_raw take for a stream (default SC_PCM_F32, one channel: floats, no decode
+// launch).  The byte region of the staging slots, the decode job tables and the level records are allocated when a format
+// other than the default is first set on the handle.
+extern "C" int sc_stream_set_input_format(sc_streams *b, int stream, int format, int channels, int channel, int scale) {
+  SC_CHECK_ARG(b && stream >= 0 && stream < b->S, "stream out of range");
+  SC_API_BEGIN
+  const St &cur = b->st[stream];
+  SC_CHECK_ARG(!b->job[stream].open && b->ahead[stream].empty(), "the stream has a chunk outstanding (sc_poll reports it first)");
+  SC_CHECK_ARG(cur.pcm_end == 0 && !cur.fe_started && !cur.enc_started && !cur.started && cur.rs_in == 0,
+               "the stream has buffered audio since its last reset (sc_reset first)");
+  SC_CHECK_ARG(format >= 0 && format < SC_PCM_N_FORMATS, "format out of range (SC_PCM_*)");
+  SC_CHECK_ARG(channels >= 1 && channels <= SC_PCM_MAX_CHANNELS, "channels outside 1..8");
+  SC_CHECK_ARG(channel >= SC_PCM_MIX && channel < channels, "channel outside [-1, channels)");
+  const bool b15 = format == SC_PCM_S16LE || format == SC_PCM_MULAW || format == SC_PCM_ALAW;
+  SC_CHECK_ARG(scale == SC_PCM_SCALE_FULL || (scale == SC_PCM_SCALE_SERVER && b15),
+               "scale: SC_PCM_SCALE_FULL, or SC_PCM_SCALE_SERVER with S16LE / MULAW / ALAW");
+  const bool coded = format != SC_PCM_F32 || channels != 1;
+  if (coded && !b->lvl_state) {
+    HIP_TRY(hipSetDevice(b->eng->device));
+    const size_t S = b->S;
+    b->stageb_cap = b->stage_cap * sizeof(float);
+    // (a buffer a call that failed half-way has already got is kept and used: a second attempt allocates the rest only)
+    if (!b->stageb_dev) RC_TRY(b->alloc(&b->stageb_dev, b->stageb_cap * N_STAGE));
+    if (!b->stageb_host) RC_TRY(b->halloc(&b->stageb_host, b->stageb_cap * N_STAGE));
+    if (!b->pcmjobs_dev) RC_TRY(b->alloc(&b->pcmjobs_dev, S * N_STAGE));
+    if (!b->pcmjobs_host) RC_TRY(b->halloc(&b->pcmjobs_host, S * N_STAGE));
+    if (!b->lvl_out_host) RC_TRY(b->halloc(&b->lvl_out_host, S * N_STAGE));
+    void *dv = nullptr;
+    if (hipHostGetDevicePointer(&dv, b->lvl_out_host, 0) != hipSuccess || !dv) {
+      sc_set_error("sc_stream_set_input_format: the pinned level slots are not visible to the device");
+      return SC_ERR_LAUNCH;
+    }
+    b->lvl_out_dev = (sc_input_level_t *)dv;
+    b->lvl_known.assign(S, LevelVal());
+    b->lvl_rep.assign(S, LevelVal());
+    b->lvl_pending.assign(S, 0);
+    b->lvl_epoch.assign(S, 0);
+    b->lvl_fresh.assign(S, 1);
+    RC_TRY(b->alloc(&b->lvl_state, S));   // (last: its presence says that all of the above is in place)
+  }
+  St &st = b->st[stream];
+  st.in_fmt = format; st.in_ch = channels; st.in_sel = channel; st.in_scale = scale;
+  return SC_OK;
+  SC_API_END
+}
+
+extern "C" int sc_stream_input_format(const sc_streams *b, int stream, int *format, int *channels, int *channel, int *scale) {
+  SC_CHECK_ARG(b && stream >= 0 && stream < b->S, "stream out of range");
+  const St &st = b->st[stream];
+  if (format) *format = st.in_fmt;
+  if (channels) *channels = st.in_ch;
+  if (channel) *channel = st.in_sel;
+  if (scale) *scale = st.in_scale;
+  return SC_OK;
+}
+
+// level of the stream's input up to and including its last REPORTED chunk, however many chunks are queued behind it; all
+// zero after sc_reset, for a stream without a format, and on a handle where no format was ever set.  Waits for the staging
+// step of that chunk if it is still in flight.
+extern "C" int sc_stream_input_level(sc_streams *b, int stream, sc_input_level_t *out) {
+  SC_CHECK_ARG(b && stream >= 0 && stream < b->S && out, "stream out of range / null");
+  SC_API_BEGIN
+  *out = sc_input_level_t{0, 0, 0, 0, 0};
+  if (!b->lvl_state) return SC_OK;
+  LevelVal &r = b->lvl_rep[stream];
+  if (!r.ready) {
+    HIP_TRY(hipSetDevice(b->eng->device));
+    for (int i = 0; i < N_STAGE && !r.ready; ++i)
+      for (const sc_streams::LvlSpan &sp : b->stage_lvl[i])
+        if (sp.s == stream && sp.ticket == r.ticket) {
+          RC_TRY(collect_levels(b, i, true));
+          break;
+        }
+  }
+  if (!r.ready) {
+    sc_set_error("input level of stream %d did not arrive with its staging step (internal error)", stream);
+    return SC_ERR_LAUNCH;
+  }
+  *out = r.v;
+  return SC_OK;
+  SC_API_END
+}
+
 // Measurement aid (tools/resample_bench.py): what the staging step of an admission of n_jobs chunks of n_in samples launches,
 // timed by hipEvents on a stream of its own - rate 16000: scatter_f32_kernel; another rate: the resample launch for streams in
 // mid-utterance (history read and left).
@@ -2451,6 +2682,7 @@ int report_chunk(sc_streams *b, int s) {
   if (b->act_on && !j.fault) b->act_rep[s] = j.act;
   if (b->spot_on && !j.fault) b->spot_rep[s] = j.spot;
   if (b->draft_on && !j.fault) b->draft_rep[s] = j.draft;
+  if (b->lvl_state && !j.fault) b->lvl_rep[s] = j.level;
   if (b->snap[s].valid && b->snap[s].seq == j.seq) b->snap[s].reported = true;   // handed out: free at the next sc_poll
   b->done_at[s] = 0;
   if (b->ahead[s].empty()) j = Job();
@@ -2477,15 +2709,15 @@ int run_to_completion(sc_streams *b, const std::vector<int> &streams) {
   }
 }
 
-int push_impl(sc_streams *b, const int *stream_ids, const float *const *host, const int *counts, const uint8_t *is_final,
-              int n, int *status, bool features, const char *what) {
+int push_impl(sc_streams *b, const int *stream_ids, const void *const *host, const int *counts, const uint8_t *is_final,
+              int n, int *status, bool features, const char *what, bool raw = false) {
   if (b->poisoned) {
     sc_set_error("%s: the handle was left inconsistent by an earlier failed call; destroy it", what);
     return SC_ERR_LAUNCH;
   }
   HIP_TRY(hipSetDevice(b->eng->device));
   RC_TRY(check_chunks(b, stream_ids, counts, n, what));
-  if (!features) RC_TRY(check_resident(b, stream_ids, host, counts, n, what));
+  if (!features) RC_TRY(check_resident(b, stream_ids, host, counts, n, what, raw));
   for (int i = 0; i < n; ++i) b->snap[stream_ids[i]] = Snap();   // (queue depth > 1) a new call supersedes the copy of the last reply
   std::vector<Chunk> chunks;
   std::vector<int> streams, has_out(n, 0);
@@ -2527,7 +2759,17 @@ extern "C" int sc_push(sc_streams *b, const int *stream_ids, const float *const 
                        const uint8_t *is_final, int n, int *status) {
   SC_CHECK_ARG(b && stream_ids && n_samples && is_final && n >= 0, "null");
   SC_API_BEGIN
-  return push_impl(b, stream_ids, pcm, n_samples, is_final, n, status, false, "sc_push");
+  return push_impl(b, stream_ids, (const void *const *)pcm, n_samples, is_final, n, status, false, "sc_push");
+  SC_API_END
+}
+
+// sc_push for audio in the streams' wire formats (sc_stream_set_input_format): audio[i] HOST, the bytes of n_frames[i] sample
+// frames (floats in +-1 for a stream without a format: then this is sc_push)
+extern "C" int sc_push_raw(sc_streams *b, const int *stream_ids, const void *const *audio, const int *n_frames,
+                           const uint8_t *is_final, int n, int *status) {
+  SC_CHECK_ARG(b && stream_ids && n_frames && is_final && n >= 0, "null");
+  SC_API_BEGIN
+  return push_impl(b, stream_ids, audio, n_frames, is_final, n, status, false, "sc_push_raw", true);
   SC_API_END
 }
 
@@ -2538,7 +2780,7 @@ extern "C" int sc_push_features(sc_streams *b, const int *stream_ids, const floa
   SC_CHECK_ARG(b && stream_ids && feats && n_frames && is_final && n >= 0, "null");
   for (int i = 0; i < n; ++i) SC_CHECK_ARG(feats[i] || n_frames[i] == 0, "null feature matrix");
   SC_API_BEGIN
-  return push_impl(b, stream_ids, feats, n_frames, is_final, n, status, true, "sc_push_features");
+  return push_impl(b, stream_ids, (const void *const *)feats, n_frames, is_final, n, status, true, "sc_push_features");
   SC_API_END
 }
 
@@ -2546,17 +2788,17 @@ extern "C" int sc_push_features(sc_streams *b, const int *stream_ids, const floa
 // copied (the caller may free them), planned and their encoder stage is issued as ONE group; decoding happens inside
 // sc_poll.  A stream has at most one chunk outstanding: submit its next chunk after sc_poll has reported this one
 // (the reference's session loop is call -> result -> next call, speechcatcher_server.py:359-397).
-extern "C" int sc_submit(sc_streams *b, const int *stream_ids, const float *const *pcm, const int *n_samples,
-                         const uint8_t *is_final, int n) {
-  SC_CHECK_ARG(b && stream_ids && n_samples && is_final && n >= 0, "null");
+static int submit_impl(sc_streams *b, const int *stream_ids, const void *const *pcm, const int *n_samples,
+                       const uint8_t *is_final, int n, bool raw) {
   SC_API_BEGIN
+  const char *what = raw ? "sc_submit_raw" : "sc_submit";
   if (b->poisoned) {
-    sc_set_error("sc_submit: the handle was left inconsistent by an earlier failed call; destroy it");
+    sc_set_error("%s: the handle was left inconsistent by an earlier failed call; destroy it", what);
     return SC_ERR_LAUNCH;
   }
   HIP_TRY(hipSetDevice(b->eng->device));
-  RC_TRY(check_chunks(b, stream_ids, n_samples, n, "sc_submit", b->queue_depth));
-  RC_TRY(check_resident(b, stream_ids, pcm, n_samples, n, "sc_submit"));
+  RC_TRY(check_chunks(b, stream_ids, n_samples, n, what, b->queue_depth));
+  RC_TRY(check_resident(b, stream_ids, pcm, n_samples, n, what, raw));
   if (n == 0) return SC_OK;
   std::vector<Chunk> chunks;
   for (int i = 0; i < n; ++i) {
@@ -2580,6 +2822,19 @@ extern "C" int sc_submit(sc_streams *b, const int *stream_ids, const float *cons
   const int rc = admit(b, chunks, false, /*launch_now=*/true, nullptr);
   return rc == SC_OK ? SC_OK : poison(b, rc);
   SC_API_END
+}
+
+extern "C" int sc_submit(sc_streams *b, const int *stream_ids, const float *const *pcm, const int *n_samples,
+                         const uint8_t *is_final, int n) {
+  SC_CHECK_ARG(b && stream_ids && n_samples && is_final && n >= 0, "null");
+  return submit_impl(b, stream_ids, (const void *const *)pcm, n_samples, is_final, n, false);
+}
+
+// sc_submit for audio in the streams' wire formats, as sc_push_raw
+extern "C" int sc_submit_raw(sc_streams *b, const int *stream_ids, const void *const *audio, const int *n_frames,
+                             const uint8_t *is_final, int n) {
+  SC_CHECK_ARG(b && stream_ids && n_frames && is_final && n >= 0, "null");
+  return submit_impl(b, stream_ids, audio, n_frames, is_final, n, true);
 }
 
 // Continuous batching, part 2: run the engine (decode ticks over every stream that is inside a block) until at least

@@ -273,6 +273,11 @@ class StreamBatch:
         self._act = None   # acoustic activity (set_activity): off
         self._spot = None  # phrase spotting (set_phrases): off
         self._draft = None  # draft transcript (set_draft): off
+        # wire-format input (set_input_format): per stream with a format its (format, channels, channel, scale), the
+        # cumulative level of its utterance (None: nothing yet), and the streams whose last chunk was final
+        self._in_fmt: Dict[int, tuple] = {}
+        self._in_level: Dict[int, Optional[dict]] = {}
+        self._in_ended: set = set()
         self.reset_all()
         self.stats = {"enc_calls": 0, "dec_steps": 0, "dec_blocks": 0}
         # optional host-side phase timers (SC_TIMING=1): seconds per phase
@@ -351,6 +356,8 @@ class StreamBatch:
             ns.short_pos = old.short_pos  # A13: counter survives reset()
             ns.T_ctc = old.T_ctc          # stale CTC table (rows stay in self.ctcx)
         self.st[s] = ns
+        self._in_level.pop(int(s), None)   # the input level starts over; the format stays
+        self._in_ended.discard(int(s))
         if self._act is not None:
             self._act["state"][s] = INITIAL
             self._act["proj"][s] = ns.T_ctc    # strict: the stale table's rows are not projected again, so not scanned
@@ -380,6 +387,65 @@ class StreamBatch:
 
     def input_rate(self, s: int) -> int:
         return 16000
+
+    # ------------------------------------------------------------------
+    # wire-format input (the native engine: sc_stream_set_input_format, csrc/pcm.hip)
+    # ------------------------------------------------------------------
+    def set_input_format(self, s: int, format: int = 0, channels: int = 1, channel: int = -1, scale: int = 0):
+        """Wire format of the audio ``push`` takes for stream s (speechcatcher_amd.pcm).  This lock-step engine decodes on
+        the host with ``pcm.decode`` - the contract the native engine's kernel reproduces bit for bit - and keeps the
+        cumulative ``pcm.level``.  Only on a stream that has buffered nothing since its last reset; ``reset`` keeps the
+        format."""
+        from . import pcm
+        try:
+            pcm.check_args(format, channels, channel, scale)
+        except ValueError as e:
+            raise EngineError(str(e)) from e
+        st = self.st[s]
+        if st.pcm_end or st.fe_started or st.enc_started or st.started:
+            raise EngineError(f"stream {s} has buffered audio since its last reset (reset first)")
+        if int(format) != pcm.F32 or int(channels) != 1:
+            self._in_fmt[int(s)] = (int(format), int(channels), int(channel), int(scale))
+        else:
+            self._in_fmt.pop(int(s), None)
+        self._in_level.pop(int(s), None)
+
+    def input_format(self, s: int):
+        return self._in_fmt.get(int(s), (0, 1, 0, 0))
+
+    def input_level(self, s: int) -> dict:
+        """cumulative input level of stream s over its utterance, up to and including its last chunk"""
+        from . import pcm
+        return dict(self._in_level.get(int(s)) or pcm.zero_level())
+
+    def _decode_coded(self, chunks):
+        """the chunks of the streams with an input format -> float samples; returns (chunks, {stream: (level after, final)}).
+        A chunk that cannot be decoded fails like any other per-stream fault: raised, or - ``isolate_faults`` - noted for
+        that stream alone, whose chunk leaves the step."""
+        if not self._in_fmt:
+            return chunks, {}
+        from . import pcm
+        out, levels = [], {}
+        for s, samples, fin in chunks:
+            f = self._in_fmt.get(int(s))
+            if f is not None:
+                try:
+                    if isinstance(samples, torch.Tensor):
+                        samples = samples.detach().cpu().numpy()
+                    if isinstance(samples, np.ndarray) and samples.dtype.kind == "f" and not (f[0] == pcm.F32 and samples.dtype == np.float32):
+                        raise ValueError(f"input format {pcm.NAME_OF[f[0]]} takes the coded bytes, not {samples.dtype} samples")
+                    prev = None if int(s) in self._in_ended else self._in_level.get(int(s))   # behind a final: start over
+                    level = pcm.level(samples, *f, prev=prev)
+                    samples = pcm.decode(samples, *f)
+                except ValueError as e:
+                    exc = EngineError(f"stream {s}: {e}")
+                    if not self._isolate:
+                        raise exc from e
+                    self._faults[int(s)] = exc
+                    continue
+                levels[int(s)] = (level, bool(fin))
+            out.append((s, samples, fin))
+        return out, levels
 
     # ------------------------------------------------------------------
     # acoustic activity (DESIGN.md 8d; the native engine: sc_streams_set_activity)
@@ -584,21 +650,31 @@ class StreamBatch:
         object - the reference's "one failing websocket does not disturb the others"
         (speechcatcher_server.py:359-397, one model instance per client)."""
         self._isolate, self._faults = bool(isolate_faults), {}
+        levels = {}
+        if not pcm_resident:
+            chunks, levels = self._decode_coded(chunks)
         if self.stream is None:
             out, feat_new, finals = self._stage_encode_safe(chunks, pcm_resident)
             self._stage_decode(feat_new, finals, {s: self.st[s].T_enc for s in feat_new})
-            return self._finish_faults(out)
+            return self._finish_faults(out, levels)
         self._arena_off = 0
         with torch.cuda.stream(self.stream):
             out, feat_new, finals = self._stage_encode_safe(chunks, pcm_resident)
             self._stage_decode(feat_new, finals, {s: self.st[s].T_enc for s in feat_new})
         self.stream.synchronize()
-        return self._finish_faults(out)
+        return self._finish_faults(out, levels)
 
-    def _finish_faults(self, out):
+    def _finish_faults(self, out, levels=None):
         """isolate_faults: a stream that failed (capacity limit, or an input the reference itself
         dies on) is reset and reports its exception in place of the has-output flag; every other
         stream of the step is unaffected."""
+        for s, (lv, _fin) in (levels or {}).items():   # input level of the streams that were served
+            if s not in self._faults:
+                self._in_level[s] = lv
+                if _fin:
+                    self._in_ended.add(s)
+                else:
+                    self._in_ended.discard(s)
         for s, exc in self._faults.items():
             if self.stream is not None:
                 with torch.cuda.stream(self.stream):

@@ -62,6 +62,54 @@ def segment_energy(raw_int16, device="cuda:0", smoothed=True):
     return out.cpu().numpy()
 
 
+_LEVEL_DT = [("q", "<i8", 3), ("i", "<i4", 2)]   # sc_input_level_t
+
+
+def _level_dict(rec):
+    from .pcm import LEVEL_FIELDS
+    return dict(zip(LEVEL_FIELDS, [int(v) for v in rec["q"]] + [int(v) for v in rec["i"]]))
+
+
+def decode_recording(buf, fmt, channels=1, channel=-1, scale=0, device="cuda:0", frames_per_job=1 << 16):
+    """A whole recording of coded audio (bytes-like or a numpy array) -> (its float32 samples as a device tensor, its input
+    level): ONE upload and ONE sc_pcm_decode launch on torch's current stream, a job per ``frames_per_job`` frames, each
+    with a level of its own - all integer, so their sum on the host is the recording's level whatever the cut.  Needs no
+    HipBackend (the CLI decodes a file with it)."""
+    import numpy as np
+    from . import pcm
+    if not torch.cuda.is_available():
+        raise _abi.ScasrError("decode_recording needs a ROCm GPU (torch.cuda.is_available() is False)")
+    pcm.check_args(fmt, channels, channel, scale)
+    lib = _abi.load()
+    device = torch.device(device)
+    raw = pcm.as_bytes(buf)
+    bpf = pcm.bytes_per_frame(fmt, channels)
+    n = raw.size // bpf
+    if n == 0:
+        return torch.empty(0, dtype=torch.float32, device=device), pcm.level(b"", fmt, channels, channel, scale)
+    src = torch.from_numpy(raw[:n * bpf].copy()).to(device)
+    out = torch.empty(n, dtype=torch.float32, device=device)
+    n_jobs = -(-n // frames_per_job)
+    if n_jobs > _abi.PCM_MAX_JOBS:
+        raise _abi.ScasrError(f"recording of {n} frames needs more than {_abi.PCM_MAX_JOBS} jobs of {frames_per_job}")
+    levels = torch.zeros(n_jobs * 32, dtype=torch.uint8, device=device)
+    tab = (_abi.PcmJob * n_jobs)()
+    for k in range(n_jobs):
+        j, f0 = tab[k], k * frames_per_job
+        j.src, j.dst, j.level, j.level_after = src.data_ptr(), out.data_ptr() + 4 * f0, levels.data_ptr() + 32 * k, None
+        j.offset, j.format, j.channels, j.channel, j.scale = f0 * bpf, fmt, channels, channel, scale
+        j.n, j.restart = min(frames_per_job, n - f0), 1
+    tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(device)
+    with torch.cuda.device(device):
+        _abi.check(lib.sc_pcm_decode(tab_dev.data_ptr(), n_jobs, torch.cuda.current_stream(device).cuda_stream), "sc_pcm_decode")
+    torch.cuda.synchronize(device)
+    recs = np.frombuffer(levels.cpu().numpy().tobytes(), _LEVEL_DT)
+    total = pcm.zero_level()
+    for r in recs:
+        total = pcm.add_levels(total, _level_dict(r))
+    return out, total
+
+
 class HipBackend:
     name = "hip"
 
@@ -454,6 +502,55 @@ class HipBackend:
             out.append(d)
             aft.append(tuple(int(v) for v in after[k]["i"]) + (float(after[k]["conf"]),))
         return out, aft
+
+    def decode_pcm(self, jobs, tweak=None, guard: int = 4):
+        """Batched decode of coded audio (sc_pcm_decode) on the caller's buffers, one launch for all jobs.  jobs: list of
+        (src: a bytes-like object, a numpy array or a uint8 device tensor; byte offset; format; channels; channel; scale;
+        n frames; level: a dict as returned here or None = the chunk starts an utterance).  Returns (samples: list of
+        float32 arrays [n + guard] whose last ``guard`` entries were handed over as NaN with payload 0x7fc0dead - what a
+        job leaves unwritten shows -, levels: list of dicts (the five speechcatcher_amd.pcm.LEVEL_FIELDS), levels_after:
+        the second copy).  ``tweak(k, job)``: test aid, edits the sc_pcm_job of job k before the launch.  A job that
+        starts an utterance is handed a level filled with -7 (the second copy always is)."""
+        import numpy as np
+        from . import pcm
+        n = len(jobs)
+        dev = self.device
+        assert np.dtype(_LEVEL_DT).itemsize == C.sizeof(_abi.InputLevel) == 32
+        lv = np.zeros(max(n, 1), _LEVEL_DT)
+        lv.view(np.int32)[:] = -7
+        after = lv.copy()
+        srcs, outs = [], []
+        for k, (src, offset, fmt, channels, channel, scale, nf, level) in enumerate(jobs):
+            if level is not None:
+                lv[k]["q"] = [level[f] for f in pcm.LEVEL_FIELDS[:3]]
+                lv[k]["i"] = [level[f] for f in pcm.LEVEL_FIELDS[3:]]
+            if not isinstance(src, torch.Tensor):
+                src = torch.from_numpy(pcm.as_bytes(src).copy())
+            assert src.dtype == torch.uint8 and src.dim() == 1
+            srcs.append(src.to(dev) if src.numel() else torch.zeros(1, dtype=torch.uint8, device=dev))
+            o = torch.full((max(0, int(nf)) + guard,), 0x7fc0dead, dtype=torch.int32, device=dev)
+            outs.append(o)
+        lv_d, after_d = (torch.as_tensor(a.view(np.uint8).copy()).to(dev) for a in (lv, after))
+        tab = (_abi.PcmJob * max(1, n))()
+        for k, (src, offset, fmt, channels, channel, scale, nf, level) in enumerate(jobs):
+            j = tab[k]
+            j.src, j.dst, j.level, j.level_after = srcs[k].data_ptr(), outs[k].data_ptr(), lv_d.data_ptr() + 32 * k, after_d.data_ptr() + 32 * k
+            j.offset, j.format, j.channels, j.channel, j.scale = int(offset), int(fmt), int(channels), int(channel), int(scale)
+            j.n, j.restart = int(nf), 1 if level is None else 0
+            if tweak is not None:
+                tweak(k, j)
+            # the bounds of a well-formed job are checked HERE: the kernel trusts offset and n
+            if (j.src == srcs[k].data_ptr() and 0 <= j.format < pcm.N_FORMATS and 1 <= j.channels <= pcm.MAX_CHANNELS
+                    and j.n >= 0 and j.offset >= 0):
+                need = j.offset + j.n * pcm.bytes_per_frame(j.format, j.channels)
+                if need > srcs[k].numel() or j.n > outs[k].numel():
+                    raise ValueError(f"job {k}: {need} source bytes / {j.n} frames exceed its buffers")
+        tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+        self._chk(self.lib.sc_pcm_decode(tab_dev.data_ptr(), n, self._stream()), "sc_pcm_decode")
+        torch.cuda.synchronize(dev)
+        lv, after = (np.frombuffer(a.cpu().numpy().tobytes(), _LEVEL_DT) for a in (lv_d, after_d))
+        samples = [o.cpu().numpy().view(np.float32) for o in outs]
+        return samples, [_level_dict(lv[k]) for k in range(n)], [_level_dict(after[k]) for k in range(n)]
 
     # ------------------------------------------------------------------
     def search_struct(self, sb):

@@ -124,6 +124,7 @@ class NativeStreamBatch:
             raise EngineError(str(e)) from e
         self.handle = h
         self.st = _InfoList(self)
+        self._coded = {}   # stream -> (format, channels, channel, scale) of the streams with an input format
 
     # ---- StreamBatch interface ---------------------------------------------------------------------
     @property
@@ -170,6 +171,11 @@ class NativeStreamBatch:
             if pcm_resident:
                 ptrs.append(None)
                 counts.append(int(samples))
+            elif int(s) in self._coded:
+                a, n = self._coded_bytes(int(s), samples)
+                keep.append(a)
+                ptrs.append(a.ctypes.data if a.size else None)
+                counts.append(n)
             else:
                 if isinstance(samples, torch.Tensor):
                     samples = samples.detach().cpu().numpy()
@@ -179,13 +185,36 @@ class NativeStreamBatch:
                 counts.append(int(a.shape[0]))
         return ids, ptrs, counts, finals, keep
 
+    def _coded_bytes(self, s, samples):
+        """the chunk of a stream with an input format -> (contiguous uint8 array, sample frames): bytes, bytearray,
+        memoryview or an array whose bytes are the codes (integer dtypes; float32 for the f32 format)"""
+        from . import pcm
+        fmt, channels, _, _ = self._coded[s]
+        if isinstance(samples, torch.Tensor):
+            samples = samples.detach().cpu().numpy()
+        if isinstance(samples, np.ndarray) and samples.dtype.kind == "f" and not (fmt == pcm.F32 and samples.dtype == np.float32):
+            raise EngineError(f"stream {s} has input format {pcm.NAME_OF[fmt]}: it takes the coded bytes, not {samples.dtype} samples")
+        a = np.ascontiguousarray(pcm.as_bytes(samples))
+        bpf = pcm.bytes_per_frame(fmt, channels)
+        if a.size % bpf:
+            raise EngineError(f"stream {s}: {a.size} bytes are not a whole number of {bpf}-byte frames")
+        return a, a.size // bpf
+
     def push(self, chunks: Sequence[Tuple[int, Optional[np.ndarray], bool]], pcm_resident: bool = False,
              isolate_faults: bool = False):
         """One chunk step: (stream, samples, is_final); with ``pcm_resident`` the tuple carries the sample COUNT
-        and the samples already sit in the device PCM ring (write_pcm).  Returns {stream: has_output}; a stream
-        that failed carries its exception instead when ``isolate_faults`` (else it is raised)."""
+        and the samples already sit in the device PCM ring (write_pcm).  A stream with an input format
+        (``set_input_format``) takes its coded bytes: bytes, memoryview or an integer array.  Returns
+        {stream: has_output}; a stream that failed carries its exception instead when ``isolate_faults`` (else it is
+        raised)."""
         ids, ptrs, counts, finals, keep = self._gather(chunks, pcm_resident)
-        return self._call("sc_push", ids, ptrs, counts, finals, keep, isolate_faults)
+        fn = "sc_push_raw" if any(s in self._coded for s in ids) else "sc_push"
+        return self._call(fn, ids, ptrs, counts, finals, keep, isolate_faults)
+
+    def push_raw(self, chunks, isolate_faults: bool = False):
+        """``push`` through sc_push_raw whatever the streams' formats (floats for a stream without one)"""
+        ids, ptrs, counts, finals, keep = self._gather(chunks, False)
+        return self._call("sc_push_raw", ids, ptrs, counts, finals, keep, isolate_faults)
 
     def push_block(self, stream_ids: np.ndarray, pcm: np.ndarray, finals: Optional[np.ndarray] = None) -> np.ndarray:
         """sc_push for row i of a contiguous float32 matrix ``pcm`` [n, samples] -> stream ``stream_ids[i]`` without
@@ -203,17 +232,22 @@ class NativeStreamBatch:
         return status
 
     # ---- continuous batching (sc_submit / sc_poll) ---------------------------------------------------
-    def submit(self, chunks: Sequence[Tuple[int, Optional[np.ndarray], bool]], pcm_resident: bool = False):
+    def submit(self, chunks: Sequence[Tuple[int, Optional[np.ndarray], bool]], pcm_resident: bool = False, raw: bool = False):
         """Hand the engine one chunk per listed stream and return at once (the chunks are copied); their frontend +
         encoder stage is issued as one group.  A stream's next chunk may be submitted once ``poll`` has reported
         this one."""
         ids, ptrs, counts, finals, keep = self._gather(chunks, pcm_resident)
+        fn = "sc_submit_raw" if raw or any(s in self._coded for s in ids) else "sc_submit"
         a_ids, a_ptr, a_cnt, a_fin = self._marshal(ids, ptrs, counts, finals)
         try:
-            _abi.check(self.lib.sc_submit(self.handle, a_ids, a_ptr, a_cnt, a_fin, len(ids)), "sc_submit")
+            _abi.check(getattr(self.lib, fn)(self.handle, a_ids, a_ptr, a_cnt, a_fin, len(ids)), fn)
         except _abi.ScasrError as e:
             raise EngineError(str(e)) from e
         del keep
+
+    def submit_raw(self, chunks):
+        """``submit`` through sc_submit_raw whatever the streams' formats (floats for a stream without one)"""
+        self.submit(chunks, raw=True)
 
     def submit_block(self, stream_ids: np.ndarray, pcm: np.ndarray, finals: Optional[np.ndarray] = None):
         n, m = pcm.shape
@@ -299,6 +333,34 @@ class NativeStreamBatch:
 
     def input_rate(self, s: int) -> int:
         return int(self.lib.sc_stream_input_rate(self.handle, int(s)))
+
+    def set_input_format(self, s: int, format: int = 0, channels: int = 1, channel: int = -1, scale: int = 0):
+        """Wire format of the audio ``push`` / ``submit`` take for stream s (speechcatcher_amd.pcm: F32 .. ALAW, 1..8
+        interleaved channels, one channel or pcm.MIX, pcm.SCALE_FULL / SCALE_SERVER): decoded on the GPU in the admission's
+        staging step, before the copy / sample-rate conversion.  Only on an idle stream that has buffered nothing since
+        its last reset; ``reset`` keeps the format.  (F32, 1 channel) is the default: float samples, no decode launch."""
+        from . import pcm
+        try:
+            _abi.check(self.lib.sc_stream_set_input_format(self.handle, int(s), int(format), int(channels), int(channel),
+                                                           int(scale)), "sc_stream_set_input_format")
+        except _abi.ScasrError as e:
+            raise EngineError(str(e)) from e
+        if int(format) != pcm.F32 or int(channels) != 1:
+            self._coded[int(s)] = (int(format), int(channels), int(channel), int(scale))
+        else:
+            self._coded.pop(int(s), None)
+
+    def input_format(self, s: int):
+        """-> (format, channels, channel, scale) of stream s"""
+        v = [C.c_int32() for _ in range(4)]
+        _abi.check(self.lib.sc_stream_input_format(self.handle, int(s), *[C.byref(x) for x in v]), "sc_stream_input_format")
+        return tuple(int(x.value) for x in v)
+
+    def input_level(self, s: int) -> dict:
+        """cumulative input level of stream s up to and including its last reported chunk (pcm.LEVEL_FIELDS)"""
+        lv = _abi.InputLevel()
+        _abi.check(self.lib.sc_stream_input_level(self.handle, int(s), C.byref(lv)), "sc_stream_input_level")
+        return {f: int(getattr(lv, f)) for f in _abi.LEVEL_FIELDS}
 
     def reset_all(self):
         for s in range(self.S):

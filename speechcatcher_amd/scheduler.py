@@ -23,6 +23,7 @@ from . import spotting
 from . import draft as draft_mod
 from .activity import of_stream as activity_of_stream
 from .align import FeatureClock
+from . import pcm as pcm_mod
 from .resample import OutputClock, check_input_rate
 from .speech2text_streaming import hyps_to_results, result_token_alignment
 
@@ -32,6 +33,9 @@ EOS_ID = 1023   # hard-coded in the reference's result assembly (speech2text_str
 class ServerBusy(RuntimeError):
     """All stream slots are taken (the reference answers "Server busy",
     speechcatcher_server.py:365-368)."""
+
+
+_FLOAT_INPUT = (pcm_mod.F32, 1, 0, pcm_mod.SCALE_FULL)   # mono float samples: the engine's default format
 
 
 class AlignedResults(list):
@@ -68,11 +72,18 @@ class DraftResults(SpottingResults):
     ahead: Optional[list] = None
 
 
+class LevelResults(DraftResults):
+    """the results of a reply and ``level``: the input level of the session's stream up to and including that chunk
+    ({field: int}, speechcatcher_amd.pcm.LEVEL_FIELDS; all zero for a session that feeds float samples) -
+    StreamScheduler(input_level=True).  The attributes of the other options are carried as well when those are on."""
+    level: Optional[dict] = None
+
+
 class StreamScheduler:
     def __init__(self, batch: StreamBatch, token_list: Optional[List[str]] = None,
                  result_format: str = "native", reset_after_final: bool = True, reset_on_open: bool = True,
                  queue_depth: int = 1, align_final: bool = False, activity: bool = False, blank_threshold: float = 0.8,
-                 phrases=None, min_scores=None, draft: bool = False):
+                 phrases=None, min_scores=None, draft: bool = False, input_level: bool = False):
         """``queue_depth`` > 1 (C++ engine, ``pump``): up to that many queued chunks of a session are handed to the engine
         at a time (sc_streams_set_queue_depth) - for sessions whose audio is already there (files): the encoder stage of
         the next chunk runs beside the decoding of the current one.  Replies and their order per session do not change.
@@ -114,6 +125,9 @@ class StreamScheduler:
         # depth > 1, or one collected inside close() of another session) waits here for the next call
         self._stash: Dict[int, Deque[list]] = {}
         self._slot_rate: Dict[int, int] = {}                  # input rate last set on a slot (absent: 16000)
+        self._slot_fmt: Dict[int, tuple] = {}                 # input format last set on a slot (absent: float samples)
+        self._fmt: Dict[int, tuple] = {}                      # per session with a wire format: (format, channels, channel, scale)
+        self.input_level = bool(input_level)                  # replies carry the session's input level (LevelResults)
         self._rate: Dict[int, OutputClock] = {}               # per session: its rate and its count of 16 kHz samples
         self.queue_depth = 1
         if queue_depth > 1 and hasattr(batch, "set_queue_depth"):
@@ -148,16 +162,23 @@ class StreamScheduler:
         return self.align_final or self.spotting or self.draft
 
     # ---- session lifecycle -------------------------------------------------
-    def open(self, sample_rate: int = 16000) -> int:
+    def open(self, sample_rate: int = 16000, format: int = pcm_mod.F32, channels: int = 1, channel: int = pcm_mod.MIX,
+             scale: int = pcm_mod.SCALE_FULL) -> int:
         """``sample_rate``: rate of the PCM this session feeds (speechcatcher_amd.resample: 8000..48000 Hz; the C++
-        engine converts it to 16 kHz on the GPU).  A slot goes back to 16000 for a later session that does not ask."""
+        engine converts it to 16 kHz on the GPU).  A slot goes back to 16000 for a later session that does not ask.
+        ``format`` / ``channels`` / ``channel`` / ``scale``: the wire format of what the session feeds
+        (speechcatcher_amd.pcm; default: mono float samples in +-1).  With any other format ``feed`` takes the coded
+        bytes, decoded by the engine (on the GPU in the C++ engine's staging step); a slot goes back to float samples
+        for a later session that does not ask."""
         sample_rate = check_input_rate(sample_rate)
+        fmt = self._check_format(format, channels, channel, scale)
         if not self._free:
             raise ServerBusy("Server busy: all stream slots are in use")
         slot = self._free[0]
         if self.reset_on_open:
             self.batch.reset(slot)
         self._set_slot_rate(slot, sample_rate)
+        self._set_slot_format(slot, fmt)
         self._free.popleft()
         sid = self._next_sid
         self._next_sid += 1
@@ -167,7 +188,47 @@ class StreamScheduler:
         self._fed.pop(sid, None)
         self._rate[sid] = OutputClock(sample_rate)
         self._spot_seen.pop(sid, None)
+        if fmt != _FLOAT_INPUT:
+            self._fmt[sid] = fmt
         return sid
+
+    @staticmethod
+    def _check_format(format, channels, channel, scale) -> tuple:
+        try:
+            pcm_mod.check_args(format, channels, channel, scale)
+        except (ValueError, TypeError) as e:
+            raise ValueError(f"input format: {e}") from e
+        fmt = (int(format), int(channels), int(channel), int(scale))
+        return _FLOAT_INPUT if fmt[:2] == _FLOAT_INPUT[:2] else fmt
+
+    def _set_slot_format(self, slot: int, fmt: tuple):
+        if self._slot_fmt.get(slot, _FLOAT_INPUT) == fmt:
+            return
+        if not hasattr(self.batch, "set_input_format"):
+            raise NotImplementedError(f"input format {fmt}: this batch takes mono float samples only")
+        try:
+            self.batch.set_input_format(slot, *fmt)
+        except RuntimeError as e:     # e.g. a slot that is never reset (strict_reference) and has audio buffered
+            raise ValueError(f"input format {fmt} cannot be set on this stream: {e}") from e
+        self._slot_fmt[slot] = fmt
+
+    def input_format(self, sid: int) -> tuple:
+        return self._fmt.get(sid, _FLOAT_INPUT)
+
+    def set_input_format(self, sid: int, format: int = pcm_mod.F32, channels: int = 1, channel: int = pcm_mod.MIX,
+                         scale: int = pcm_mod.SCALE_FULL):
+        """Change the wire format of a session that has not fed any audio yet (the Vosk ``config`` message arrives
+        after the connection is made).  ValueError for a value out of range or once audio has been fed."""
+        fmt = self._check_format(format, channels, channel, scale)
+        if fmt == self.input_format(sid):
+            return
+        if self._rate[sid].fed:
+            raise ValueError("the input format of a session can only be set before its first audio")
+        self._set_slot_format(self._slot_of[sid], fmt)
+        if fmt != _FLOAT_INPUT:
+            self._fmt[sid] = fmt
+        else:
+            self._fmt.pop(sid, None)
 
     def _set_slot_rate(self, slot: int, rate: int):
         if self._slot_rate.get(slot, 16000) == rate:
@@ -208,6 +269,7 @@ class StreamScheduler:
         self._clock.pop(sid, None)
         self._fed.pop(sid, None)
         self._rate.pop(sid, None)
+        self._fmt.pop(sid, None)
         self._spot_seen.pop(sid, None)
         if self.reset_on_open:
             self.batch.reset(slot)
@@ -219,9 +281,21 @@ class StreamScheduler:
 
     # ---- data path -----------------------------------------------------------
     def feed(self, sid: int, pcm: np.ndarray, is_final: bool = False, finalize_all: bool = False):
-        """Queue one chunk of a session (float PCM in +-1, like the reference API) at the session's sample rate."""
-        self._queue[sid].append((np.asarray(pcm, dtype=np.float32), bool(is_final), bool(finalize_all)))
-        n16 = self._rate[sid].call(int(np.shape(pcm)[0]), bool(is_final))   # the call in 16 kHz samples: the engine's clock
+        """Queue one chunk of a session (float PCM in +-1, like the reference API) at the session's sample rate; a
+        session with a wire format (``open(format=...)``) feeds the coded bytes of whole sample frames instead: bytes,
+        memoryview or an integer array."""
+        fmt = self._fmt.get(sid)
+        if fmt is None:
+            self._queue[sid].append((np.asarray(pcm, dtype=np.float32), bool(is_final), bool(finalize_all)))
+            n_in = int(np.shape(pcm)[0])
+        else:
+            raw = pcm_mod.as_bytes(pcm).copy()
+            bpf = pcm_mod.bytes_per_frame(fmt[0], fmt[1])
+            if raw.size % bpf:
+                raise ValueError(f"{raw.size} bytes are not a whole number of {bpf}-byte sample frames")
+            self._queue[sid].append((raw, bool(is_final), bool(finalize_all)))
+            n_in = raw.size // bpf
+        n16 = self._rate[sid].call(n_in, bool(is_final))   # the call in 16 kHz samples: the engine's clock
         if self._clocked:
             self._fed.setdefault(sid, deque()).append((n16, bool(is_final)))
 
@@ -297,6 +371,12 @@ class StreamScheduler:
                 res.draft = self._draft_tokens(sid, slot)
                 pos = out[sid][0][3] if out[sid] and len(out[sid][0]) > 3 else None
                 res.ahead = draft_mod.ahead(res.draft, pos[-1] if pos else 0)
+                out[sid] = res
+            if self.input_level:
+                res = LevelResults(out[sid])
+                for k in ("alignment", "activity", "detections", "draft", "ahead"):
+                    setattr(res, k, getattr(out[sid], k, None))
+                res.level = self.batch.input_level(slot) if hasattr(self.batch, "input_level") else pcm_mod.zero_level()
                 out[sid] = res
             if fin and self.reset_after_final:
                 self.batch.reset(slot)

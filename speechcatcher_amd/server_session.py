@@ -34,6 +34,7 @@ import numpy as np
 
 from .activity import FRAME_SECONDS
 from .align import merge_words
+from . import pcm as pcm_mod
 from .scheduler import ServerBusy, StreamScheduler
 
 Message = Union[str, bytes, np.ndarray]
@@ -189,6 +190,7 @@ class _Session:
         self.inbox: Deque[Message] = deque()
         self.in_flight: Optional[dict] = None     # the chunk currently queued in the scheduler
         self.vosk_sample_rate = 16000
+        self.wire = None                          # (format, channels, channel, scale): the session hands its bytes to the engine
         self.last = vosk_partial("") if vosk else ""
 
 
@@ -199,7 +201,8 @@ class ServerLoop:
                  finalize_update_iters: int = 6, max_partial_iters: int = 42, strict_reference: bool = False,
                  continuous: Optional[bool] = None, min_replies: int = 1, vosk_alignment: bool = False,
                  acoustic_endpointing: Optional[EndpointRules] = None, spotting: Optional[dict] = None,
-                 spotting_min_scores: Optional[dict] = None, draft_partials: bool = False):
+                 spotting_min_scores: Optional[dict] = None, draft_partials: bool = False, raw_input: bool = False,
+                 input_level: bool = False):
         """``strict_reference``: no stream reset after a finalised utterance nor between clients, exactly like
         ``recognize_ws`` / ``process_audio_chunk`` (speechcatcher_server.py:270,359-397); the default resets.
         ``continuous`` (default: on whenever the batch has the C++ engine's submit / poll - round 4; False forces one
@@ -223,7 +226,19 @@ class ServerLoop:
         search's last token, "ahead_result": [{"word", "start", "end", "conf"}]} (the scheduler's ``draft`` option:
         the greedy CTC transcript of the newest frames, which the blockwise search has not reached yet).  Finals are
         unchanged.  Counts the frames of an utterance from the reset after a final, so not with ``strict_reference``.
-        False (default): partials as they are."""
+        False (default): partials as they are.
+        ``raw_input``: plain s16le sessions hand their bytes to the engine as they arrive (wire format S16LE with
+        pcm.SCALE_SERVER: the values of ``scale_server_pcm`` bit for bit, computed by the engine - on the GPU in the C++
+        engine's staging step) instead of converting every message here.  Sessions whose Vosk ``config`` names a
+        ``format`` ("s16le", "s24le", "u8", "mulaw", "alaw", "f32"), ``channels`` (1..8) or ``channel`` (an index, or
+        "mix") always do.  False (default): today's host conversion.
+        ``input_level`` (Vosk format): partial and final replies carry {"level": {frames, clipped, sum_abs, peak,
+        full_scale}} - the input level of the utterance so far (the scheduler's ``input_level`` option; all zero for a
+        session converted on the host)."""
+        self.raw_input = bool(raw_input)
+        self.input_level = bool(input_level)
+        if input_level:
+            scheduler.input_level = True
         self.draft_partials = False
         if draft_partials:
             if strict_reference:
@@ -267,8 +282,13 @@ class ServerLoop:
     def connect(self) -> int:
         """Raises ServerBusy when every stream slot is taken ("Server busy,
         please try again later.", :366)."""
-        sid = self.sch.open()
+        if self.raw_input:
+            wire = (pcm_mod.S16LE, 1, 0, pcm_mod.SCALE_SERVER)
+            sid = self.sch.open(format=wire[0], channels=wire[1], channel=wire[2], scale=wire[3])
+        else:
+            wire, sid = None, self.sch.open()
         self.sessions[sid] = _Session(sid, self.vosk, self.fui, self.mpi, self.acoustic_rules)
+        self.sessions[sid].wire = wire
         return sid
 
     def disconnect(self, sid: int):
@@ -309,7 +329,10 @@ class ServerLoop:
                 continue
             if self.spot_names is not None and getattr(results, "detections", None):
                 replies.setdefault(sid, []).append(spotted_message(results.detections, self.spot_names))
-            replies.setdefault(sid, []).append(self._reply(ses, self._finish(ses, results)))
+            reply = self._reply(ses, self._finish(ses, results))
+            if self.input_level and isinstance(reply, dict):
+                reply = dict(reply, level=dict(getattr(results, "level", None) or pcm_mod.zero_level()))
+            replies.setdefault(sid, []).append(reply)
         return replies
 
     def pending(self) -> bool:
@@ -324,17 +347,35 @@ class ServerLoop:
             if message in ('{"eof" : 1}', '{"reset" : 1}'):
                 forced = True
                 data = np.zeros(1000, dtype=np.int16)
+                if ses.wire is not None:
+                    data = pcm_mod.silence(ses.wire[0], ses.wire[1], 1000)
             else:
                 try:
                     cfg = json.loads(message).get("config", {})
                     rate = cfg.get("sample_rate", ses.vosk_sample_rate)
-                except (ValueError, AttributeError):
+                    wire = self._config_format(ses, cfg)
+                except (AttributeError, json.JSONDecodeError):
                     return vosk_partial("")
-                # honoured for every rate the engine converts (8000..48000 Hz: speechcatcher_amd.resample), before the
-                # session's first audio; ValueError otherwise - this client's error reply (step)
+                # honoured for every rate the engine converts (8000..48000 Hz: speechcatcher_amd.resample) and every
+                # wire format it decodes (speechcatcher_amd.pcm), before the session's first audio; ValueError
+                # otherwise - this client's error reply (step)
+                # - and both or neither: a rate whose format is refused does not stay
+                old_rate = self.sch.sample_rate(ses.sid)
                 self.sch.set_sample_rate(ses.sid, rate)
+                if wire is not None:
+                    try:
+                        self.sch.set_input_format(ses.sid, *wire)
+                    except (ValueError, NotImplementedError):
+                        self.sch.set_sample_rate(ses.sid, old_rate)
+                        raise
+                    ses.wire = wire
                 ses.vosk_sample_rate = int(rate)
                 return vosk_partial("")
+        elif ses.wire is not None:                          # the session's bytes go to the engine as they are
+            if isinstance(message, np.ndarray) and message.dtype.kind not in "iu" and not (
+                    ses.wire[0] == pcm_mod.F32 and message.dtype == np.float32):
+                raise TypeError("audio arrays must hold the session's coded samples (an integer dtype)")
+            data = pcm_mod.as_bytes(message)
         elif isinstance(message, np.ndarray):
             if message.dtype != np.int16:
                 raise TypeError("audio arrays must be int16 PCM")
@@ -351,9 +392,31 @@ class ServerLoop:
         finalize = finalize or forced
         if finalize and ses.acoustic is not None:
             ses.acoustic.reset()
-        self.sch.feed(ses.sid, scale_server_pcm(data), is_final=finalize, finalize_all=False)
+        self.sch.feed(ses.sid, data if ses.wire is not None else scale_server_pcm(data), is_final=finalize, finalize_all=False)
         ses.in_flight = {"finalize": finalize, "forced": forced}
         return None
+
+    def _config_format(self, ses: _Session, cfg: dict):
+        """the wire format a Vosk ``config`` asks for -> (format, channels, channel, scale), or None when it names none
+        (the session stays as it is); ValueError for an unknown value.  SCALE_SERVER where the format takes it: the
+        reference server's conversion."""
+        if not any(k in cfg for k in ("format", "channels", "channel")):
+            return None
+        cur = ses.wire or (pcm_mod.S16LE, 1, 0, pcm_mod.SCALE_SERVER)
+        name = cfg.get("format", pcm_mod.NAME_OF[cur[0]])
+        if not isinstance(name, str) or name.lower() not in pcm_mod.FORMAT_NAMES:
+            raise ValueError(f"unknown audio format {name!r} (one of {', '.join(pcm_mod.FORMAT_NAMES)})")
+        fmt = pcm_mod.FORMAT_NAMES[name.lower()]
+        channels = cfg.get("channels", cur[1])
+        channel = cfg.get("channel", pcm_mod.MIX if "channels" in cfg else cur[2])
+        if channel == "mix":
+            channel = pcm_mod.MIX
+        for what, v in (("channels", channels), ("channel", channel)):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"{what} must be an integer, got {v!r}")
+        scale = pcm_mod.SCALE_SERVER if fmt in (pcm_mod.S16LE, pcm_mod.MULAW, pcm_mod.ALAW) else pcm_mod.SCALE_FULL
+        pcm_mod.check_args(fmt, channels, channel, scale)
+        return (fmt, channels, channel, scale)
 
     def _finish(self, ses: _Session, results: list):
         info, ses.in_flight = ses.in_flight, None

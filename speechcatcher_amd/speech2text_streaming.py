@@ -256,7 +256,7 @@ class Speech2TextStreaming:
                  device: str = "cuda", dtype: str = "float32", use_bbd: bool = False,
                  max_frames: int = 4800, max_tokens: int = 1024, result_format: str = "native",
                  max_chunk_samples: int = 480000, strict_reference: bool = True, _shared=None,
-                 input_sample_rate: int = 16000):
+                 input_sample_rate: int = 16000, input_format=None):
         """``max_chunk_samples``: longest single call (the reference accepts any length per call and its frame
         arithmetic depends on the call boundaries, so a long call cannot be split internally; the scratch for one
         call is sized from this: 30 s by default, ~80 MB).  ``strict_reference``: reset() behaves like the
@@ -269,9 +269,24 @@ class Speech2TextStreaming:
         sums evaluated on the fp16 matrix pipe from fp16 hi + lo splits of both operands.
         ``input_sample_rate``: rate of the 1-D PCM ``__call__`` takes (8000..48000 Hz, speechcatcher_amd.resample);
         converted to 16 kHz on the GPU, call by call, with results that do not depend on how the audio is cut into calls
-        beyond what they do at 16 kHz.  ``max_chunk_samples`` then bounds a call's samples at either rate."""
+        beyond what they do at 16 kHz.  ``max_chunk_samples`` then bounds a call's samples at either rate.
+        ``input_format``: the wire format of what a 1-D ``__call__`` takes - a name of speechcatcher_amd.pcm.FORMAT_NAMES
+        ("s16le", "mulaw", ...) or (format, channels, channel, scale) - decoded on the GPU in the call's staging step;
+        the call then takes bytes or an integer array of whole sample frames, and ``input_level()`` reports the level of
+        the utterance so far.  None (default): float samples in +-1."""
+        from . import pcm
         from .resample import check_input_rate
         self.input_sample_rate = check_input_rate(input_sample_rate)
+        if isinstance(input_format, str):
+            if input_format.lower() not in pcm.FORMAT_NAMES:
+                raise ValueError(f"unknown input format {input_format!r} (one of {', '.join(pcm.FORMAT_NAMES)})")
+            input_format = (pcm.FORMAT_NAMES[input_format.lower()], 1, 0, pcm.SCALE_FULL)
+        if input_format is not None:
+            input_format = tuple(int(v) for v in input_format)
+            pcm.check_args(*input_format)
+            if input_format[:2] == (pcm.F32, 1):
+                input_format = None
+        self.input_format = input_format
         self.model_dir = Path(model_dir)
         self.beam_size = beam_size
         self.ctc_weight = ctc_weight
@@ -312,6 +327,8 @@ class Speech2TextStreaming:
         self.stream = 0
         if self.input_sample_rate != 16000:
             self.batch.set_input_rate(self.stream, self.input_sample_rate)   # reset() keeps it
+        if self.input_format is not None:
+            self.batch.set_input_format(self.stream, *self.input_format)     # reset() keeps it
         self.win_length = self.cfg.win_length
         self.hop_length = self.cfg.hop_length
         self.beam_search = _BeamSearchView(self)
@@ -335,9 +352,14 @@ class Speech2TextStreaming:
                  always_assemble_hyps: bool = False):
         if isinstance(speech, torch.Tensor):
             speech = speech.detach().cpu().numpy()
+        coded = None
+        if self.input_format is not None and (not isinstance(speech, np.ndarray) or speech.ndim == 1):
+            from . import pcm
+            coded = pcm.as_bytes(speech)      # the coded bytes of whole sample frames
+            speech = np.zeros(coded.size // pcm.bytes_per_frame(*self.input_format[:2]), np.float32)   # (its length: the clocks)
         speech = np.asarray(speech, dtype=np.float32)
         if speech.ndim == 1:
-            out = self.batch.push([(self.stream, speech, is_final)])
+            out = self.batch.push([(self.stream, speech if coded is None else coded, is_final)])
             if getattr(self, "_clock", None) is None:
                 from .align import FeatureClock
                 self._clock = FeatureClock(self.cfg.win_length, self.cfg.hop_length)
@@ -378,6 +400,11 @@ class Speech2TextStreaming:
                 continue
             out.append(result_token_alignment(h["yseq"], is_final, al, 0, j, self.cfg, getattr(self, "_clock", None)))
         return out
+
+    def input_level(self) -> dict:
+        """{frames, clipped, sum_abs, peak, full_scale} of the utterance's input up to the last call (``input_format``;
+        all zero for float input)"""
+        return self.batch.input_level(self.stream)
 
     def set_activity(self, on: bool = True, blank_threshold: float = 0.8):
         """Acoustic speech activity from the CTC table (NativeStreamBatch.set_activity): off by default; between calls."""
