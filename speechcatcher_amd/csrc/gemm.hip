@@ -870,12 +870,16 @@ __device__ __forceinline__ f32x4 ffn_mma_h(f32x4 acc, const h16x8 &a, const h16x
   return acc;
 }
 // WF = 2 (WS): fp32-grade arithmetic on the fp16 matrix pipe.  Every fp32 operand x is split into two fp16 numbers,
-//   hi = fp16(x),  lo = fp16((x - hi) * 2^11)        (x - hi is exact in fp32; x = hi + lo / 2^11 to ~2^-23 |x|)
+//   hi = fp16(x),  lo = fp16((x - hi) * 2^11)        (x - hi is exact in fp32)
+// x = hi + lo / 2^11 up to max(2^-23 |x|, 2^-36): the relative bound holds from 2^-14 up; below, hi is an fp16 subnormal (or
+// zero), x - hi <= 2^-25 lands in lo's own subnormals (quantum 2^-24) and the representation has the ABSOLUTE floor 2^-36
+// (1.5e-11 for every magnitude from 6e-5 down; 0 is exact).  The matrix pipe reads fp16 subnormals as they are (no flush).
 // and a product sum a.b is evaluated as  sum(a_hi b_hi) + 2^-11 (sum(a_hi b_lo) + sum(a_lo b_hi))  with three
 // v_mfma_f32_16x16x32_f16 (fp16 products are exact in the fp32 accumulators) instead of eight v_mfma_f32_16x16x4_f32:
 // 51 instead of 256 matrix-pipe cycles per 8 k values of a lane.  Only the a_lo b_lo term (<= 2^-22 |a b|) is
 // dropped: the result differs from fp32 arithmetic by a few ulp of fp32 (tests/test_gpu_ops.py), not by fp16's
-// 2^-11.  The weights are split offline (weights.py: the hi and lo halves of a lane's 8 k values take the places of
+// 2^-11 - per term |a| rho(w) + |w| rho(a) + r(a) r(w) with rho(x) = max(2^-22 |x|, 2^-36), r(x) = max(2^-11 |x|, 2^-25),
+// the error model tests/test_gpu_dense16.py holds every split form to (DESIGN.md "Canonical summation").  The weights are split offline (weights.py: the hi and lo halves of a lane's 8 k values take the places of
 // the two fp32 slabs of the fragment order, same bytes), the row tile and the hidden activations when they are staged
 // into LDS (hi8 | lo8 per 8 k values: the same 32 bytes per lane and row stride as the fp32 tile).  Operands must lie
 // within fp16's range (|x| < 65504: LayerNorm outputs and ReLU activations of any real model do).
@@ -1580,11 +1584,14 @@ static int rowtile_run(const float *A, int lda, int M, int D, const float *ln_g,
   // tile height (16*rtt rows) and column chunks per workgroup (cpw) by a cost model fitted to
   // tools/rowtile_sweep.py: a workgroup takes 4.3 + 1.0*rtt + 2.1*rtt*cpw us (+8 % for rtt = 4, whose 100 KB of LDS
   // leave it alone on its CU); tiles up to rtt = 3 fit two workgroups per CU, which then take 1.75x as long each
+  // (the fp16 form keeps an fp16 copy of the tile beside the fp32 one: the full-width form at D = 256 fits the 160 KB of LDS
+  // up to 48 rows only - 64 rows need 166912 bytes.  The cost model never took that tile there; now it cannot)
+  const int rtt_max = (w_form == 1 && full && D == 256) ? 3 : 4;
   int best_rtt = 1, best_cpw = full ? nch : 1;
   double best = 1e30;
   for (int cpw = full ? nch : 1; cpw <= nch; ++cpw) {
     if (nch % cpw) continue;
-    for (int rtt = 1; rtt <= 4; ++rtt) {
+    for (int rtt = 1; rtt <= rtt_max; ++rtt) {
       const long wgs = (long)(nch / cpw) * cdiv(M, 16 * rtt);
       const int conc = (rtt <= 3 && wgs > 256) ? 2 : 1;
       const double t_wg = (4.3 + 1.0 * rtt + 2.1 * rtt * cpw) * (rtt == 4 ? 1.08 : 1.0);
@@ -1594,7 +1601,7 @@ static int rowtile_run(const float *A, int lda, int M, int D, const float *ln_g,
   }
   if (const char *f = sc_hook("SC_ROWTILE_FORCE")) {   // tools/rowtile_bench.py sweep: "rtt,cpw"
     int r = 0, c = 0;
-    if (sscanf(f, "%d,%d", &r, &c) == 2 && r >= 1 && r <= 4 && c >= 1 && nch % c == 0) {
+    if (sscanf(f, "%d,%d", &r, &c) == 2 && r >= 1 && r <= rtt_max && c >= 1 && nch % c == 0) {
       best_rtt = r;
       if (!full) best_cpw = c;
     }

@@ -48,7 +48,8 @@ def split_panel_weight(Wp: torch.Tensor) -> torch.Tensor:
     """fp16 hi | lo split of a ``pack_panel_weight`` copy for the split-precision fused feed-forward (sc_ffn_ln_s,
     csrc/gemm.hip ffn_fused_kernel WF = 2): per (tile, ki) the first 64-lane slab holds, per lane, the fp16 roundings
     ``hi`` of its 8 k values (those of both fp32 slabs), the second slab ``fp16((w - hi) * 2**11)`` - the same bytes
-    as the fp32 copy.  w = hi + lo / 2**11 up to ~2**-23 |w|."""
+    as the fp32 copy.  w = hi + lo / 2**11 up to max(2**-23 |w|, 2**-36): below 2**-14 ``hi`` is an fp16 subnormal (or
+    zero) and the error has the absolute floor 2**-36 instead of the relative bound; 0 is exact."""
     N, K = Wp.shape
     v = Wp.reshape(-1, 2, 64, 4)
     v = torch.cat([v[:, 0], v[:, 1]], dim=-1)                 # [n][lane][8 k values]
@@ -116,7 +117,9 @@ class PackedWeights:
         ``"split16"`` (either): fp16 hi | lo splits of the fp32 weights instead (``split_panel_weight``: w1_s / w2_s,
         wqkv_s / wo_s) - the kernels split the activations the same way and evaluate every product sum with three fp16
         MFMAs: fp32-grade results (all reference fixtures at the fp32 tolerance) at a fraction of the f32 matrix-pipe
-        time.  Opt-in as well: the default computes on the f32 MFMA path.
+        time.  Every operand x is represented up to max(2**-23 |x|, 2**-36): fp32 grade from 2**-14 up, an absolute floor of
+        2**-36 below (there ``hi`` is an fp16 subnormal); tests/test_gpu_dense16.py holds the kernels to it.  Opt-in as well:
+        the default computes on the f32 MFMA path.
         ``dec_dtype="float16"`` (round 4, the decoder side of BASELINE configs[4]): fp16 copies of the decoder's attention
         projections (wqkv_pph / wq_pph / wo_pph / wo2_pph: sc_dec_layer_self / _cross) - fp16 MFMA inputs there - and the
         partial products between the decoder's kernels are stored in fp16 (sc_search.act_half).  The fp16 copy of the

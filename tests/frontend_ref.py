@@ -484,17 +484,18 @@ def xl_state_dict():
     return synth.make_state_dict(XL, 1234)
 
 
-@functools.lru_cache(maxsize=2)
-def _xl_packed(device):
+@functools.lru_cache(maxsize=4)
+def _xl_packed(device, dtype="float32"):
     from speechcatcher_amd.config import XL
     from speechcatcher_amd.weights import PackedWeights
-    return PackedWeights(xl_state_dict(), XL, device)
+    return PackedWeights(xl_state_dict(), XL, device, ffn_dtype=dtype, proj_dtype=dtype)
 
 
-def xl_weights(n_layers, device="cpu"):
+def xl_weights(n_layers, device="cpu", dtype="float32"):
     """the seeded XL weights, cut to the first `n_layers` encoder layers (a fresh object per call: backends cache their
-    layer tables on it)"""
-    w = copy.copy(_xl_packed(str(device)))
+    layer tables on it).  dtype: the weight form of the feed-forward and the attention projections (PackedWeights'
+    ffn_dtype and proj_dtype: "float32", "float16" or "split16")"""
+    w = copy.copy(_xl_packed(str(device), dtype))
     w.enc = w.enc[:n_layers]
     return w
 
