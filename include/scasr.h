@@ -173,7 +173,7 @@ const char *sc_last_error(void);
 /* ABI revision of this header: bumped whenever a struct layout or a signature changes incompatibly.  sc_version()
  * returns the revision the LIBRARY was built with; a host compares the two before it passes any struct
  * (speechcatcher_amd/_abi.py does at load time, the C hosts in tests/ at start-up). */
-#define SC_ABI_VERSION 10
+#define SC_ABI_VERSION 11
 int sc_version(void);
 
 /* hipGraph capture / replay of any sequence of the launches below on a
@@ -515,6 +515,47 @@ typedef struct sc_ctc_draft_job {
  * state, a null store with capacity > 0, V < 1, blank outside [0, V), t0 < 0, t1 < t0, stride < V, capacity < 0) writes
  * nothing.  Two jobs of one call must not share a state or a token store. */
 int sc_ctc_draft(const sc_ctc_draft_job *jobs, int n_jobs, void *stream);
+
+/* ---- CTC token alternates (alternates.hip) -----------------------------------------------------
+ * "What else could this token have been": for each of L token spans [start[k], end[k]) over the T rows of an fp32 CTC
+ * table, the K acoustically best tokens of those frames and the rank of the span's own label y[k] among them.  Per span,
+ * checked in this order: SC_ALT_NO_SPAN when start < 0, end <= start or end > T (no row is read); SC_ALT_BAD_ROW when a
+ * row OF THE SPAN is bad (a NaN, a +inf, or nothing but -inf); else SC_ALT_OK with
+ *   S[v] = ((x[start][v] + x[start+1][v]) + ...), promoted to float64 and added in ascending frame order (-inf stays -inf)
+ *   candidates: every v in [0, V) but the blank, ordered by S descending, then v ascending
+ *   alt_ids[k][j] = the j-th candidate for j < min(K, V - 1), -1 behind them
+ *   alt_logp[k][j] = (S[v] - sum_t lse_t) / (end - start), lse_t = m + log(sum_v exp(x[v] - m)) as for sc_ctc_activity,
+ *                    summed in frame order; -inf in the unused slots
+ *   own_rank[k] = the candidates strictly ahead of y[k] in that order (0: the token is the acoustic best of its own
+ *                 frames); -1 when y[k] is outside [0, V) or the blank (the rest of the span is still computed)
+ * A status other than SC_ALT_OK: ids -1, logp -inf, own_rank -1.  A per-row constant cancels inside a span: raw logits
+ * and log-softmaxed rows give the same order unless fp32 rounding creates a tie.  tests/ctc_alt_ref.py is the contract:
+ * every int32 equal (S holds only float64 adds of promoted fp32 values: the same bits), alt_logp within 1e-11. */
+#define SC_ALT_OK 0
+#define SC_ALT_NO_SPAN 1
+#define SC_ALT_BAD_ROW 2
+#define SC_ALT_MAX_K 8
+typedef struct sc_ctc_alt_job {
+  const float *emis;       /* row t of the table at emis + t * stride, V floats (device) */
+  const int32_t *labels;   /* [L] (device) */
+  const int32_t *start;    /* [L] first frame of each span (device) */
+  const int32_t *end;      /* [L] one past its last frame (device) */
+  int32_t *alt_ids;        /* [L][K] (device) */
+  double *alt_logp;        /* [L][K] (device) */
+  int32_t *own_rank;       /* [L] (device) */
+  int32_t *status;         /* [L] SC_ALT_* (device) */
+  int64_t stride;          /* floats between two rows, >= V */
+  int32_t T, V, blank, L;
+} sc_ctc_alt_job;
+#define SC_ALT_MAX_JOBS 65535
+/* jobs: device table of n_jobs entries; max_L bounds their L (max_L <= SC_ALIGN_MAX_L), 1 <= K <= SC_ALT_MAX_K.  ONE
+ * launch on `stream`, one workgroup per (job, span): float64 sums in one fixed order, no atomics, one writer per output;
+ * nothing past a job's L is written.  SC_ERR_ARG before anything is launched for n_jobs outside [0, SC_ALT_MAX_JOBS], a
+ * null table with n_jobs > 0, max_L outside [0, SC_ALIGN_MAX_L], K outside [1, SC_ALT_MAX_K].  A job whose own fields
+ * are malformed (a null pointer with L > 0, V outside [1, SC_MAX_VOCAB], blank outside [0, V), T < 0, L outside
+ * [0, max_L], stride < V) writes nothing.  Two jobs of one call must not share outputs.  The table, labels and spans are
+ * only read. */
+int sc_ctc_alternates(const sc_ctc_alt_job *jobs, int n_jobs, int max_L, int K, void *stream);
 
 /* ---- wire-format audio in (pcm.hip) -----------------------------------------------------------
  * A chunk is n sample FRAMES of `channels` interleaved little-endian codes, starting at ANY byte address.  Every format
@@ -892,6 +933,14 @@ int sc_get_hyps_batch(sc_streams *streams, const int *stream_ids, int n, int nbe
  * allocated on the first call and grows with the requests. */
 int sc_align_hyps(sc_streams *streams, const int *stream_ids, int n, int nbest, int max_len, int32_t *start,
                   int32_t *end, float *logp_mean, double *path_score, int *status, int *n_hyps);
+/* sc_align_hyps and, for every token of every hypothesis, its alternates (sc_ctc_alternates above): the
+ * alignment's launches, then ONE sc_ctc_alternates launch on the same read-back stream over the spans the alignment left
+ * on the device, one copy back.  start ... status: exactly what sc_align_hyps gives, bit for bit.  alt_ids / alt_logp
+ * [n][nbest][max_len][K], own_rank / span_status [n][nbest][max_len] (SC_ALT_*; SC_ALT_NO_SPAN for every token of a
+ * hypothesis whose alignment failed); any output but n_hyps may be NULL.  1 <= K <= SC_ALT_MAX_K. */
+int sc_alternates_hyps(sc_streams *streams, const int *stream_ids, int n, int nbest, int max_len, int K, int32_t *start,
+                       int32_t *end, float *logp_mean, double *path_score, int *status, int32_t *alt_ids,
+                       double *alt_logp, int32_t *own_rank, int32_t *span_status, int *n_hyps);
 /* ... of a caller-given transcript ids[0..L) against the same frames of one stream */
 int sc_align_tokens(sc_streams *streams, int stream, const int32_t *ids, int L, int32_t *start, int32_t *end,
                     float *logp_mean, double *path_score, int *status);

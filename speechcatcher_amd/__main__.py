@@ -72,11 +72,13 @@ def to_16k(raw, rate, device="cuda:0"):
 
 
 def recognize_file(speech2text, media_path, output_file="", quiet=True, progress=True, num_slots=1, chunk_length=8192,
-                   token_alignment=False, segmentation="host", channel=None):
+                   token_alignment=False, segmentation="host", channel=None, token_alternates=0):
     """speechcatcher.py:358-400: recording -> text + paragraphs JSON next to the input.  ``token_alignment``: the
     paragraphs also get token_start / token_end (seconds) and token_conf from a CTC forced alignment of each segment.
     ``segmentation``: "host" or "gpu" - where the energy curve for the cut points of a recording over 60 s is computed.
-    ``channel``: what to decode of a multichannel recording - an index, or "mix" (None: such a recording is refused)."""
+    ``channel``: what to decode of a multichannel recording - an index, or "mix" (None: such a recording is refused).
+    ``token_alternates`` = K > 0 (implies ``token_alignment``): the paragraphs also get token_alternates, one record per
+    token with its K acoustic alternates over the token's frames."""
     from .config import SearchConfig
     from .native import NativeStreamBatch
     from .segmenter import recognize_recording
@@ -94,7 +96,7 @@ def recognize_file(speech2text, media_path, output_file="", quiet=True, progress
     # finalize_all only with the very last chunk of the recording, like the reference CLI (speechcatcher.py:586)
     text, info = recognize_recording(batch, raw, rate, chunk_length=chunk_length, token_list=speech2text.token_list,
                                      reference_finalize=True, token_alignment=token_alignment,
-                                     segmentation=segmentation)
+                                     segmentation=segmentation, token_alternates=token_alternates)
     out_txt, out_json = (output_file or media_path) + ".txt", (output_file or media_path) + ".json"
     with open(out_txt, "w") as f:
         f.write(text)
@@ -134,6 +136,9 @@ def make_parser():
     p.add_argument("--token-alignment", dest="token_alignment", action="store_true",
                    help="add token_start / token_end / token_conf to the .json: token times at 40 ms resolution and a per-token "
                         "confidence from a CTC forced alignment on the GPU (token_timestamps stay as they are)")
+    p.add_argument("--token-alternates", dest="token_alternates", type=int, default=0, metavar="K",
+                   help="add token_alternates to the .json: per token the K (1..8) tokens that fit its frames best acoustically, "
+                        "each with a confidence, and the rank of the token itself among them (implies --token-alignment)")
     p.add_argument("--segmentation", dest="segmentation", choices=["host", "gpu"], default="host",
                    help="where the energy curve for the cut points of a recording over 60 s is computed: 'host' (numpy, the "
                         "default) or 'gpu' (float64 kernels; the same cuts, without the host pass over the whole recording)")
@@ -167,7 +172,8 @@ def main(argv=None):
                              use_bbd=not args.disable_bbd)
     recognize_file(speech2text, args.inputfile, quiet=args.quiet or not args.no_progress, progress=not args.no_progress,
                    num_slots=1 if args.num_processes < 1 else args.num_processes, chunk_length=args.chunk_length,
-                   token_alignment=args.token_alignment, segmentation=args.segmentation, channel=args.channel)
+                   token_alignment=args.token_alignment or args.token_alternates > 0, segmentation=args.segmentation,
+                   channel=args.channel, token_alternates=args.token_alternates)
     return 0
 
 

@@ -135,6 +135,18 @@ class DraftJob(C.Structure):
 DRAFT_FIELDS = tuple(n for n, _ in Draft._fields_)
 DRAFT_MAX_JOBS = 65535
 
+
+class AltJob(C.Structure):
+    """sc_ctc_alt_job (include/scasr.h): the token spans of one label sequence ranked by sc_ctc_alternates"""
+    _fields_ = ([(n, vp) for n in ("emis", "labels", "start", "end", "alt_ids", "alt_logp", "own_rank", "status")]
+                + [("stride", C.c_int64)] + [(n, C.c_int32) for n in ("T", "V", "blank", "L")])
+
+
+# SC_ALT_* of include/scasr.h
+ALT_OK, ALT_NO_SPAN, ALT_BAD_ROW = 0, 1, 2
+ALT_MAX_K, ALT_MAX_JOBS = 8, 65535
+
+
 class InputLevel(C.Structure):
     """sc_input_level_t (include/scasr.h)"""
     _fields_ = ([(n, C.c_int64) for n in ("frames", "clipped", "sum_abs")]
@@ -286,6 +298,10 @@ _SIGS = {
                                 c_int_p, c_int_p]),
     "sc_align_tokens": (C.c_int, [vp, C.c_int, c_int_p, C.c_int, c_int_p, c_int_p, c_float_p, c_double_p, c_int_p]),
     "sc_streams_read_ctc": (C.c_int, [vp, C.c_int, vp, C.c_int]),
+    # CTC token alternates (alternates.hip, streams.hip)
+    "sc_ctc_alternates": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp]),
+    "sc_alternates_hyps": (C.c_int, [vp, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_float_p,
+                                     c_double_p, c_int_p, c_int_p, c_double_p, c_int_p, c_int_p, c_int_p]),
     # CTC speech activity (activity.hip, streams.hip)
     "sc_ctc_activity": (C.c_int, [vp, C.c_int, vp]),
     "sc_streams_set_activity": (C.c_int, [vp, C.c_int, C.c_double]),
@@ -328,7 +344,7 @@ EXPORTED_SYMBOLS = tuple(_SIGS.keys())
 
 # revision of include/scasr.h these ctypes mirrors were written against (SC_ABI_VERSION): a library built from another
 # revision would be handed mis-laid-out structs
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _lib = None
 

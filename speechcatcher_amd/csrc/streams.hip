@@ -3028,11 +3028,24 @@ extern "C" int sc_get_hyps_batch(sc_streams *b, const int *stream_ids, int n, in
 // One sc_ctc_align launch pair on the read-back stream for a list of (stream, frames, labels) requests; outputs back to
 // the host.  The device area holds [job table][labels][outputs: start, end | logp_mean | path_score, status][workspaces].
 struct AlignReq { int s, T; std::vector<int32_t> y; };
-struct AlignOut { std::vector<int32_t> start, end; std::vector<float> lp; float score; int32_t status; };
+struct AlignOut {
+  std::vector<int32_t> start, end;
+  std::vector<float> lp;
+  float score;
+  int32_t status;
+  // alt_K > 0 (sc_alternates_hyps): [L][K] ids and logp, [L] own_rank and span status
+  std::vector<int32_t> alt_ids, own_rank, span_status;
+  std::vector<double> alt_logp;
+};
 
 static size_t al_round(size_t x) { return (x + 255) & ~(size_t)255; }
 
-static int run_align(sc_streams *b, const std::vector<AlignReq> &reqs, bool after_snap, std::vector<AlignOut> &out) {
+// alt_K > 0: ONE sc_ctc_alternates launch behind them reads start / end where the alignment left them on the device; its
+// job table travels in the same upload (behind the labels), its outputs come back in the same copy (behind the
+// alignment's: [alt_logp: doubles][alt_ids | own_rank | span status]).  The alignment's launches, areas and bits are the
+// same with and without it.
+static int run_align(sc_streams *b, const std::vector<AlignReq> &reqs, bool after_snap, std::vector<AlignOut> &out,
+                     int alt_K = 0) {
   const int n = (int)reqs.size();
   out.assign(n, AlignOut());
   if (n == 0) return SC_OK;
@@ -3045,9 +3058,13 @@ static int run_align(sc_streams *b, const std::vector<AlignReq> &reqs, bool afte
   }
   SC_CHECK_ARG(max_L <= SC_ALIGN_MAX_L, "a label sequence is longer than SC_ALIGN_MAX_L");
   const size_t o_lab = al_round((size_t)n * sizeof(sc_ctc_align_job));
-  const size_t o_out = o_lab + al_round(n_lab * 4);
-  const size_t n_outw = 3 * n_lab + 2 * (size_t)n;   // start, end, logp_mean per label; path_score, status per job
-  size_t o_ws = o_out + al_round(n_outw * 4), total = o_ws;
+  const size_t K = (size_t)alt_K;
+  const size_t o_alt = o_lab + al_round(n_lab * 4);   // the alternates' job table (empty without them)
+  const size_t o_out = o_alt + (alt_K ? al_round((size_t)n * sizeof(sc_ctc_alt_job)) : 0);
+  const size_t n_alw = 3 * n_lab + 2 * (size_t)n;   // start, end, logp_mean per label; path_score, status per job
+  const size_t o_altout = (n_alw * 4 + 7) & ~(size_t)7;   // (bytes behind o_out; doubles first)
+  const size_t n_outb = alt_K ? o_altout + n_lab * K * 8 + (n_lab * K + 2 * n_lab) * 4 : n_alw * 4;
+  size_t o_ws = o_out + al_round(n_outb), total = o_ws;
   for (const AlignReq &r : reqs) total += al_round(sc_ctc_align_ws_bytes(r.T));
   if (total > b->al_cap) {
     const size_t cap = std::max(total, 2 * b->al_cap);   // geometric: few reallocations (a hipFree may stall the device)
@@ -3082,15 +3099,33 @@ static int run_align(sc_streams *b, const std::vector<AlignReq> &reqs, bool afte
     j.status = od + 3 * n_lab + 2 * k + 1;
     j.stride = V;
     j.T = r.T; j.L = L; j.V = V; j.blank = b->cfg.blank_id;
+    if (alt_K) {
+      sc_ctc_alt_job &a = ((sc_ctc_alt_job *)(host.data() + o_alt))[k];
+      char *ao = D + o_out + o_altout;
+      a.emis = j.emis;
+      a.labels = j.labels;
+      a.start = j.start;
+      a.end = j.end;
+      a.alt_logp = (double *)ao + li * K;
+      int32_t *ai = (int32_t *)(ao + n_lab * K * 8);
+      a.alt_ids = ai + li * K;
+      a.own_rank = ai + n_lab * K + li;
+      a.status = ai + n_lab * K + n_lab + li;
+      a.stride = V;
+      a.T = r.T; a.V = V; a.blank = b->cfg.blank_id; a.L = L;
+    }
     li += L;
     wo += al_round(sc_ctc_align_ws_bytes(r.T));
   }
   HIP_TRY(hipMemcpyAsync(D, host.data(), o_out, hipMemcpyHostToDevice, b->stream_rb));
   if (after_snap) HIP_TRY(hipStreamWaitEvent(b->stream_rb, b->ev_snap, 0));
   RC_TRY(sc_ctc_align((const sc_ctc_align_job *)D, n, max_T, max_L, b->stream_rb));
-  std::vector<int32_t> res(n_outw);
-  HIP_TRY(hipMemcpyAsync(res.data(), D + o_out, n_outw * 4, hipMemcpyDeviceToHost, b->stream_rb));
+  if (alt_K) RC_TRY(sc_ctc_alternates((const sc_ctc_alt_job *)(D + o_alt), n, max_L, alt_K, b->stream_rb));
+  std::vector<int32_t> res((n_outb + 3) / 4 + 2);
+  HIP_TRY(hipMemcpyAsync(res.data(), D + o_out, n_outb, hipMemcpyDeviceToHost, b->stream_rb));
   HIP_TRY(hipStreamSynchronize(b->stream_rb));
+  const char *ro = (const char *)res.data() + o_altout;
+  const int32_t *ri = (const int32_t *)(ro + n_lab * K * 8);
   li = 0;
   for (int k = 0; k < n; ++k) {
     const int L = (int)reqs[k].y.size();
@@ -3101,6 +3136,13 @@ static int run_align(sc_streams *b, const std::vector<AlignReq> &reqs, bool afte
     if (L) memcpy(o.lp.data(), res.data() + 3 * li + 2 * L, (size_t)L * 4);
     memcpy(&o.score, res.data() + 3 * n_lab + 2 * k, 4);
     o.status = res[3 * n_lab + 2 * k + 1];
+    if (alt_K) {
+      o.alt_logp.resize((size_t)L * K);
+      if (L) memcpy(o.alt_logp.data(), ro + li * K * 8, (size_t)L * K * 8);
+      o.alt_ids.assign(ri + li * K, ri + (li + L) * K);
+      o.own_rank.assign(ri + n_lab * K + li, ri + n_lab * K + li + L);
+      o.span_status.assign(ri + n_lab * K + n_lab + li, ri + n_lab * K + n_lab + li + L);
+    }
     li += L;
   }
   return SC_OK;
@@ -3119,8 +3161,10 @@ static int hyp_frames(const sc_streams *b, int s, int *T, bool *snap) {
   return SC_OK;
 }
 
-extern "C" int sc_align_hyps(sc_streams *b, const int *stream_ids, int n, int nbest, int max_len, int32_t *start,
-                             int32_t *end, float *logp_mean, double *path_score, int *status, int *n_hyps) {
+// sc_align_hyps (K == 0) and sc_alternates_hyps (K > 0): the same requests, the same alignment
+static int align_hyps(sc_streams *b, const int *stream_ids, int n, int nbest, int max_len, int K, int32_t *start,
+                      int32_t *end, float *logp_mean, double *path_score, int *status, int32_t *alt_ids, double *alt_logp,
+                      int32_t *own_rank, int32_t *span_status, int *n_hyps) {
   SC_CHECK_ARG(b && stream_ids && n_hyps && n >= 0 && nbest >= 0 && max_len >= 0, "bad arguments");
   SC_API_BEGIN
   HIP_TRY(hipSetDevice(b->eng->device));
@@ -3145,12 +3189,13 @@ extern "C" int sc_align_hyps(sc_streams *b, const int *stream_ids, int n, int nb
       int a = 1, e = lens[o];                                  // without <sos> ...
       if (e > a && y[e - 1] == b->cfg.eos_id) --e;             // ... and without a trailing <eos>
       AlignReq r{stream_ids[i], T, std::vector<int32_t>(y + a, y + std::max(a, e))};
-      SC_CHECK_ARG((int)r.y.size() <= max_len || (!start && !end && !logp_mean), "max_len is smaller than the hypotheses");
+      SC_CHECK_ARG((int)r.y.size() <= max_len || (!start && !end && !logp_mean && !alt_ids && !alt_logp && !own_rank && !span_status),
+                   "max_len is smaller than the hypotheses");
       reqs.push_back(std::move(r));
     }
   }
   std::vector<AlignOut> out;
-  RC_TRY(run_align(b, reqs, any_snap, out));
+  RC_TRY(run_align(b, reqs, any_snap, out, K));
   int k = 0;
   for (int i = 0; i < n; ++i)
     for (int h = 0; h < n_hyps[i]; ++h, ++k) {
@@ -3162,9 +3207,29 @@ extern "C" int sc_align_hyps(sc_streams *b, const int *stream_ids, int n, int nb
       if (logp_mean) memcpy(logp_mean + o * max_len, a.lp.data(), L * 4);
       if (path_score) path_score[o] = a.score;
       if (status) status[o] = a.status;
+      if (K) {
+        if (alt_ids) memcpy(alt_ids + o * max_len * K, a.alt_ids.data(), L * K * 4);
+        if (alt_logp) memcpy(alt_logp + o * max_len * K, a.alt_logp.data(), L * K * 8);
+        if (own_rank) memcpy(own_rank + o * max_len, a.own_rank.data(), L * 4);
+        if (span_status) memcpy(span_status + o * max_len, a.span_status.data(), L * 4);
+      }
     }
   return SC_OK;
   SC_API_END
+}
+
+extern "C" int sc_align_hyps(sc_streams *b, const int *stream_ids, int n, int nbest, int max_len, int32_t *start,
+                             int32_t *end, float *logp_mean, double *path_score, int *status, int *n_hyps) {
+  return align_hyps(b, stream_ids, n, nbest, max_len, 0, start, end, logp_mean, path_score, status, nullptr, nullptr,
+                    nullptr, nullptr, n_hyps);
+}
+
+extern "C" int sc_alternates_hyps(sc_streams *b, const int *stream_ids, int n, int nbest, int max_len, int K,
+                                  int32_t *start, int32_t *end, float *logp_mean, double *path_score, int *status,
+                                  int32_t *alt_ids, double *alt_logp, int32_t *own_rank, int32_t *span_status, int *n_hyps) {
+  SC_CHECK_ARG(K >= 1 && K <= SC_ALT_MAX_K, "K outside [1, SC_ALT_MAX_K]");
+  return align_hyps(b, stream_ids, n, nbest, max_len, K, start, end, logp_mean, path_score, status, alt_ids, alt_logp,
+                    own_rank, span_status, n_hyps);
 }
 
 extern "C" int sc_align_tokens(sc_streams *b, int stream, const int32_t *ids, int L, int32_t *start, int32_t *end,

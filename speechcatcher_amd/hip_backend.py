@@ -503,6 +503,47 @@ class HipBackend:
             aft.append(tuple(int(v) for v in after[k]["i"]) + (float(after[k]["conf"]),))
         return out, aft
 
+    def ctc_alternates(self, jobs, K: int, max_L=None, tweak=None, guard: int = 2):
+        """Batched CTC token alternates (sc_ctc_alternates) on the caller's tables, one launch for all jobs.  jobs: list of
+        (table [T, V] fp32 tensor, rows may be strided; blank; labels, start, end: int32 sequences of one length L).
+        Returns (alt_ids [n, Lmax + guard, K] int32, alt_logp [n, Lmax + guard, K] float64, own_rank [n, Lmax + guard],
+        status [n, Lmax + guard]): every output buffer is handed over filled with -7, so what a job leaves unwritten - the
+        rows at and past its L - shows.  ``max_L``: the bound given to the launch (default: the largest L).
+        ``tweak(k, job)``: test aid, edits the sc_ctc_alt_job of job k before the launch."""
+        import numpy as np
+        n = len(jobs)
+        dev = self.device
+        Ls = [int(np.asarray(j[2]).reshape(-1).shape[0]) for j in jobs]
+        Lmax = max([0] + Ls)
+        rows = Lmax + guard
+        ids = torch.full((max(n, 1), rows, K), -7, dtype=torch.int32, device=dev)
+        logp = torch.full((max(n, 1), rows, K), -7.0, dtype=torch.float64, device=dev)
+        rank = torch.full((max(n, 1), rows), -7, dtype=torch.int32, device=dev)
+        stt = torch.full((max(n, 1), rows), -7, dtype=torch.int32, device=dev)
+        spans = np.zeros((max(n, 1), 3, max(Lmax, 1)), np.int32)
+        for k, (_, _, labels, start, end) in enumerate(jobs):
+            for r, a in enumerate((labels, start, end)):
+                a = np.asarray(a, np.int32).reshape(-1)
+                assert a.shape[0] == Ls[k]
+                spans[k, r, :Ls[k]] = a
+        spans_d = torch.as_tensor(spans).to(dev)
+        tab = (_abi.AltJob * max(1, n))()
+        for k, (table, blank, _, _, _) in enumerate(jobs):
+            assert table.dtype == torch.float32 and table.dim() == 2 and table.stride(1) == 1
+            j = tab[k]
+            j.emis = table.data_ptr()
+            j.labels, j.start, j.end = (spans_d[k, r].data_ptr() for r in range(3))
+            j.alt_ids, j.alt_logp = ids[k].data_ptr(), logp[k].data_ptr()
+            j.own_rank, j.status = rank[k].data_ptr(), stt[k].data_ptr()
+            j.stride, j.T, j.V, j.blank, j.L = table.stride(0), table.shape[0], table.shape[1], int(blank), Ls[k]
+            if tweak is not None:
+                tweak(k, j)
+        tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+        self._chk(self.lib.sc_ctc_alternates(tab_dev.data_ptr(), n, Lmax if max_L is None else int(max_L), int(K),
+                                             self._stream()), "sc_ctc_alternates")
+        torch.cuda.synchronize(dev)
+        return ids.cpu().numpy()[:n], logp.cpu().numpy()[:n], rank.cpu().numpy()[:n], stt.cpu().numpy()[:n]
+
     def decode_pcm(self, jobs, tweak=None, guard: int = 4):
         """Batched decode of coded audio (sc_pcm_decode) on the caller's buffers, one launch for all jobs.  jobs: list of
         (src: a bytes-like object, a numpy array or a uint8 device tensor; byte offset; format; channels; channel; scale;

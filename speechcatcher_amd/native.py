@@ -409,6 +409,39 @@ class NativeStreamBatch:
                                           nh.ctypes.data_as(ip)), "sc_align_hyps")
         return {"start": start, "end": end, "logp_mean": lp, "path_score": ps, "status": st, "n_hyps": nh}
 
+    def alternates(self, streams: Sequence[int], nbest: Optional[int] = None, k: int = 3):
+        """``align`` and, for every token of every hypothesis, its ``k`` acoustic alternates (sc_alternates_hyps; DESIGN.md
+        8h): the alignment's arrays exactly as ``align`` returns them, plus alt_ids [n, nbest, Lmax, k] (-1: no such
+        candidate), alt_logp [n, nbest, Lmax, k] float64 (mean log-posterior over the token's frames), own_rank
+        [n, nbest, Lmax] (candidates ahead of the token itself; 0: it is the acoustic best of its frames) and span_status
+        [n, nbest, Lmax] (_abi.ALT_*).  One call, one copy back; entries past a hypothesis' label count are undefined."""
+        nb = self.W if nbest is None else int(nbest)
+        k = int(k)
+        if not 1 <= k <= _abi.ALT_MAX_K:
+            raise ValueError(f"k must be in [1, {_abi.ALT_MAX_K}]")
+        sid = np.ascontiguousarray(streams, dtype=np.int32)
+        n = len(sid)
+        lmax = self.LCAP
+        start = np.zeros((n, nb, lmax), np.int32)
+        end = np.zeros((n, nb, lmax), np.int32)
+        lp = np.zeros((n, nb, lmax), np.float32)
+        ps = np.zeros((n, nb))
+        st = np.zeros((n, nb), np.int32)
+        nh = np.zeros(n, np.int32)
+        ai = np.full((n, nb, lmax, k), -1, np.int32)
+        al = np.full((n, nb, lmax, k), -np.inf)
+        rk = np.full((n, nb, lmax), -1, np.int32)
+        ss = np.full((n, nb, lmax), _abi.ALT_NO_SPAN, np.int32)
+        ip, dp = _abi.c_int_p, _abi.c_double_p
+        _abi.check(self.lib.sc_alternates_hyps(self.handle, sid.ctypes.data_as(ip), n, nb, lmax, k,
+                                               start.ctypes.data_as(ip), end.ctypes.data_as(ip),
+                                               lp.ctypes.data_as(_abi.c_float_p), ps.ctypes.data_as(dp),
+                                               st.ctypes.data_as(ip), ai.ctypes.data_as(ip), al.ctypes.data_as(dp),
+                                               rk.ctypes.data_as(ip), ss.ctypes.data_as(ip), nh.ctypes.data_as(ip)),
+                   "sc_alternates_hyps")
+        return {"start": start, "end": end, "logp_mean": lp, "path_score": ps, "status": st, "n_hyps": nh,
+                "alt_ids": ai, "alt_logp": al, "own_rank": rk, "span_status": ss}
+
     def align_tokens(self, s: int, ids: Sequence[int]):
         """CTC forced alignment of a given transcript (token ids, no <sos> / <eos>) against the frames of stream s's
         reported hypotheses (sc_align_tokens): {"start", "end", "logp_mean": [L] arrays, "path_score", "status"}."""

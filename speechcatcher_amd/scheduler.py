@@ -21,6 +21,7 @@ import numpy as np
 from .engine import StreamBatch
 from . import spotting
 from . import draft as draft_mod
+from . import alternates as alternates_mod
 from .activity import of_stream as activity_of_stream
 from .align import FeatureClock
 from . import pcm as pcm_mod
@@ -40,7 +41,9 @@ _FLOAT_INPUT = (pcm_mod.F32, 1, 0, pcm_mod.SCALE_FULL)   # mono float samples: t
 
 class AlignedResults(list):
     """the results of a final reply (a list, like every reply) and ``alignment``: result_token_alignment of its first
-    result (None when it has none) - StreamScheduler(align_final=True)"""
+    result (None when it has none) - StreamScheduler(align_final=True).  With ``alternates=K`` the alignment also carries
+    "alternates": the records of those tokens (speechcatcher_amd.alternates.result_token_alternates); with
+    ``align_nbest`` > 1 also "nbest": result_token_alignment of each of the reply's first ``align_nbest`` results."""
     alignment: Optional[dict] = None
 
 
@@ -83,7 +86,8 @@ class StreamScheduler:
     def __init__(self, batch: StreamBatch, token_list: Optional[List[str]] = None,
                  result_format: str = "native", reset_after_final: bool = True, reset_on_open: bool = True,
                  queue_depth: int = 1, align_final: bool = False, activity: bool = False, blank_threshold: float = 0.8,
-                 phrases=None, min_scores=None, draft: bool = False, input_level: bool = False):
+                 phrases=None, min_scores=None, draft: bool = False, input_level: bool = False, alternates: int = 0,
+                 align_nbest: int = 1):
         """``queue_depth`` > 1 (C++ engine, ``pump``): up to that many queued chunks of a session are handed to the engine
         at a time (sc_streams_set_queue_depth) - for sessions whose audio is already there (files): the encoder stage of
         the next chunk runs beside the decoding of the current one.  Replies and their order per session do not change.
@@ -97,6 +101,11 @@ class StreamScheduler:
         ``align_final`` (C++ engine): every final reply is an ``AlignedResults`` whose ``alignment`` holds the token times and
         confidences of its first result (CTC forced alignment, NativeStreamBatch.align), taken before the stream is reset."""
         self.align_final = align_final
+        # ``alternates`` = K > 0 (C++ engine; implies ``align_final``): the ``alignment`` of a final reply also carries
+        # "alternates", the K acoustic alternates of every token of its first result, from ONE call in place of ``align``
+        # (NativeStreamBatch.alternates).  ``align_nbest`` = N > 1: the final's alignment covers its first N results
+        # ("nbest"; what ServerLoop(vosk_alternatives=N) formats)
+        self.alternates, self.align_nbest = 0, max(1, int(align_nbest))
         # ``activity``: every reply (an exception aside) is an ``ActivityResults`` whose ``activity`` is the acoustic
         # speech / silence state of the session's stream for that chunk (batch.set_activity(True, blank_threshold)), read
         # before the stream is reset after a final
@@ -140,6 +149,8 @@ class StreamScheduler:
             self.enable_spotting(phrases, min_scores)
         if draft:
             self.enable_draft()
+        if alternates:
+            self.enable_alternates(alternates)
 
     def enable_activity(self, blank_threshold: float = 0.8):
         """switch the ``activity`` option on (only while no chunk is at the engine; every stream's state starts over)"""
@@ -156,6 +167,16 @@ class StreamScheduler:
         """switch the ``draft`` option on (only while no chunk is at the engine; every stream's state starts over)"""
         self.batch.set_draft(True)
         self.draft = True
+
+    def enable_alternates(self, k: int):
+        """switch the ``alternates`` option on (and ``align_final`` with it)"""
+        if not hasattr(self.batch, "alternates"):
+            raise NotImplementedError("token alternates are computed by the C++ engine (NativeStreamBatch.alternates); "
+                                      "the Python lock-step engine has none")
+        if not 1 <= int(k) <= alternates_mod.MAX_K:
+            raise ValueError(f"alternates must be in [1, {alternates_mod.MAX_K}]")
+        self.alternates = int(k)
+        self.align_final = True
 
     @property
     def _clocked(self) -> bool:   # the options that need the sessions' feature clocks
@@ -416,11 +437,22 @@ class StreamScheduler:
         if not res or arrays is None:
             return out
         # the hypothesis behind res[0]: the first one _select_hyps keeps
-        j = next(j for j in range(int(arrays["n_hyps"][i]))
-                 if (fin and fa) or int(arrays["ids"][i, j, int(arrays["lens"][i, j]) - 1]) == EOS_ID)
-        al = self.batch.align([slot], j + 1)
-        L = int(arrays["lens"][i, j])
-        out.alignment = result_token_alignment(arrays["ids"][i, j, :L].tolist(), fin, al, 0, j, self.batch.cfg, clock)
+        # (with align_nbest > 1: the hypotheses behind res[:align_nbest], in the order _select_hyps keeps them)
+        js = [j for j in range(int(arrays["n_hyps"][i]))
+              if (fin and fa) or int(arrays["ids"][i, j, int(arrays["lens"][i, j]) - 1]) == EOS_ID][:self.align_nbest]
+        j = js[0]
+        if self.alternates:
+            al = self.batch.alternates([slot], js[-1] + 1, self.alternates)
+        else:
+            al = self.batch.align([slot], js[-1] + 1)
+        ys = [arrays["ids"][i, q, :int(arrays["lens"][i, q])].tolist() for q in js]
+        out.alignment = result_token_alignment(ys[0], fin, al, 0, j, self.batch.cfg, clock)
+        if self.alternates:
+            out.alignment["alternates"] = alternates_mod.result_token_alternates(ys[0], fin, al, 0, j, self.batch.cfg,
+                                                                                 self.token_list)
+        if self.align_nbest > 1:
+            out.alignment["nbest"] = [dict(out.alignment)] + [
+                result_token_alignment(y, fin, al, 0, q, self.batch.cfg, clock) for y, q in zip(ys[1:], js[1:])]
         return out
 
     def step(self) -> Dict[int, list]:
@@ -517,7 +549,7 @@ def _select_hyps(a: dict, i: int, is_final: bool, finalize_all: bool) -> List[di
 def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tuple[int, int]],
                        chunk_length: int = 8192, token_list: Optional[List[str]] = None,
                        frames_per_second: float = 24.0, finalize_all_last_only: bool = False,
-                       queue_depth: int = 1, token_alignment: bool = False) -> List[dict]:
+                       queue_depth: int = 1, token_alignment: bool = False, token_alternates: int = 0) -> List[dict]:
     """Decode the (start, end) sample ranges of one recording as PARALLEL streams
     of one batch instead of the reference's process pool over segments
     (speechcatcher/speechcatcher.py:474-497, chunk loop :574-592; SURVEY 8(f)
@@ -526,11 +558,14 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
     convention: encoder-frame position / 24.0 s + segment start
     (speechcatcher.py:48,509-536).  ``token_alignment`` (C++ engine): every segment also gets ``token_start`` /
     ``token_end`` / ``token_conf`` per token, from a CTC forced alignment of its result (seconds of the recording; None
-    for a token without one)."""
+    for a token without one).  ``token_alternates`` = K > 0 (implies ``token_alignment``): also ``token_alternates``,
+    one record per token with its K acoustic alternates (speechcatcher_amd.alternates)."""
+    token_alignment = token_alignment or token_alternates > 0
     # queue_depth > 1 (C++ engine): that many chunks of a segment at the engine - the audio is all there.  Measured: worth
     # +6..12 % when the search is decode-heavy (no block-boundary detection, <= 32 segments), nothing to -8 % with
     # detection on (the CLI's default), hence off by default (DESIGN section 4)
-    sch = StreamScheduler(batch, token_list, result_format="espnet", queue_depth=queue_depth, align_final=token_alignment)
+    sch = StreamScheduler(batch, token_list, result_format="espnet", queue_depth=queue_depth, align_final=token_alignment,
+                          alternates=token_alternates)
     out: List[Optional[dict]] = [None] * len(segments)
     todo = list(enumerate(segments))
     sid_to_seg: Dict[int, int] = {}
@@ -571,5 +606,11 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
                     out[idx]["token_start"] = [None if a is None else start_s + a for a in al["start_s"]]
                     out[idx]["token_end"] = [None if b is None else start_s + b for b in al["end_s"]]
                     out[idx]["token_conf"] = list(al["conf"])
+                    if token_alternates:
+                        recs = al.get("alternates")
+                        if recs is None:   # no alignment: records without alternates
+                            recs = [alternates_mod.token_record(t, None, None, [], [], token_list)
+                                    for t in out[idx]["token_ids"]]
+                        out[idx]["token_alternates"] = list(recs)
                 sch.close(sid)
     return out  # type: ignore[return-value]

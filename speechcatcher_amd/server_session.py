@@ -34,6 +34,7 @@ import numpy as np
 
 from .activity import FRAME_SECONDS
 from .align import merge_words
+from . import alternates as alternates_mod
 from . import pcm as pcm_mod
 from .scheduler import ServerBusy, StreamScheduler
 
@@ -174,6 +175,24 @@ def vosk_result_aligned(tokens: List[str], alignment: dict) -> dict:
             "text": "".join(tokens).replace("▁", " ").strip()}
 
 
+def _aligned_keep(alignment: dict) -> List[int]:
+    return [k for k in range(len(alignment["start_s"])) if alignment["start_s"][k] is not None]
+
+
+def vosk_words(tokens: List[str], token_pos, alignment: Optional[dict], aligned: bool, records=None) -> List[dict]:
+    """the "result" entries of one hypothesis: vosk_result_aligned's words when ``aligned`` and it has an alignment, else
+    vosk_result's entry per token; with ``records`` (one per token: speechcatcher_amd.alternates) every entry also carries
+    "tokens", the records of the tokens it is made of"""
+    if aligned and alignment is not None and any(a is not None for a in alignment["start_s"]):
+        words = vosk_result_aligned(tokens, alignment)["result"]
+        if records is not None:
+            keep = _aligned_keep(alignment)
+            words = alternates_mod.attach_word_tokens(words, [tokens[k] for k in keep], [records[k] for k in keep])
+        return words
+    words = vosk_result(tokens, token_pos)["result"]
+    return alternates_mod.attach_entry_tokens(words, records) if records is not None else words
+
+
 def scale_server_pcm(data: np.ndarray) -> np.ndarray:
     """int16 -> the float values the reference server feeds its model:
     ``astype(float16) / 32767.0`` (rounded to float16), then fp32."""
@@ -191,6 +210,7 @@ class _Session:
         self.in_flight: Optional[dict] = None     # the chunk currently queued in the scheduler
         self.vosk_sample_rate = 16000
         self.wire = None                          # (format, channels, channel, scale): the session hands its bytes to the engine
+        self.max_alternatives = 0                 # Vosk config.max_alternatives (ServerLoop(vosk_alternatives=N))
         self.last = vosk_partial("") if vosk else ""
 
 
@@ -202,7 +222,7 @@ class ServerLoop:
                  continuous: Optional[bool] = None, min_replies: int = 1, vosk_alignment: bool = False,
                  acoustic_endpointing: Optional[EndpointRules] = None, spotting: Optional[dict] = None,
                  spotting_min_scores: Optional[dict] = None, draft_partials: bool = False, raw_input: bool = False,
-                 input_level: bool = False):
+                 input_level: bool = False, vosk_alternatives: int = 0, token_alternates: int = 0):
         """``strict_reference``: no stream reset after a finalised utterance nor between clients, exactly like
         ``recognize_ws`` / ``process_audio_chunk`` (speechcatcher_server.py:270,359-397); the default resets.
         ``continuous`` (default: on whenever the batch has the C++ engine's submit / poll - round 4; False forces one
@@ -234,7 +254,28 @@ class ServerLoop:
         "mix") always do.  False (default): today's host conversion.
         ``input_level`` (Vosk format): partial and final replies carry {"level": {frames, clipped, sum_abs, peak,
         full_scale}} - the input level of the utterance so far (the scheduler's ``input_level`` option; all zero for a
-        session converted on the host)."""
+        session converted on the host).
+        ``vosk_alternatives`` = N > 0 (C++ engine, Vosk format): a session whose Vosk ``config`` carries
+        ``max_alternatives`` = m > 0 (values above N count as N) gets its finals as {"alternatives": [{"text",
+        "confidence", "result": [word entries]}, ...]}: the results the final reply holds, best first and at most m,
+        confidence = speechcatcher_amd.alternates.nbest_posterior of their total scores, word times from the forced
+        alignment of each (one call for all of them; a hypothesis that cannot be aligned keeps an entry per token).  m = 0
+        or the option off: today's message.
+        ``token_alternates`` = K > 0 (C++ engine, Vosk format): the word entries of a final - of its first alternative, or
+        of the classic result - carry "tokens": per token of the word {"id", "token", "conf", "own_rank", "alternates":
+        [{"id", "token", "conf"}]}, the K tokens that fit the token's frames best acoustically (the scheduler's
+        ``alternates`` option)."""
+        self.vosk_alternatives = int(vosk_alternatives) if vosk_output_format else 0
+        self.token_alternates = int(token_alternates) if vosk_output_format else 0
+        if self.vosk_alternatives < 0:
+            raise ValueError("vosk_alternatives must be >= 0")
+        if self.token_alternates:
+            scheduler.enable_alternates(self.token_alternates)
+        if self.vosk_alternatives:
+            if not hasattr(scheduler.batch, "align"):
+                raise NotImplementedError("n-best alternatives take their word times from the C++ engine's forced alignment")
+            scheduler.align_final = True
+            scheduler.align_nbest = max(scheduler.align_nbest, self.vosk_alternatives)
         self.raw_input = bool(raw_input)
         self.input_level = bool(input_level)
         if input_level:
@@ -354,6 +395,7 @@ class ServerLoop:
                     cfg = json.loads(message).get("config", {})
                     rate = cfg.get("sample_rate", ses.vosk_sample_rate)
                     wire = self._config_format(ses, cfg)
+                    max_alt = self._config_alternatives(ses, cfg)
                 except (AttributeError, json.JSONDecodeError):
                     return vosk_partial("")
                 # honoured for every rate the engine converts (8000..48000 Hz: speechcatcher_amd.resample) and every
@@ -370,6 +412,7 @@ class ServerLoop:
                         raise
                     ses.wire = wire
                 ses.vosk_sample_rate = int(rate)
+                ses.max_alternatives = max_alt
                 return vosk_partial("")
         elif ses.wire is not None:                          # the session's bytes go to the engine as they are
             if isinstance(message, np.ndarray) and message.dtype.kind not in "iu" and not (
@@ -418,6 +461,39 @@ class ServerLoop:
         pcm_mod.check_args(fmt, channels, channel, scale)
         return (fmt, channels, channel, scale)
 
+    def _config_alternatives(self, ses: _Session, cfg: dict) -> int:
+        """the ``max_alternatives`` a Vosk ``config`` asks for, at most ``vosk_alternatives`` (the session's own when the
+        message names none; 0 with the option off); ValueError for anything but a non-negative integer"""
+        if "max_alternatives" not in cfg or not self.vosk_alternatives:
+            return ses.max_alternatives
+        m = cfg["max_alternatives"]
+        if isinstance(m, bool) or not isinstance(m, int) or m < 0:
+            raise ValueError(f"max_alternatives must be a non-negative integer, got {m!r}")
+        return min(m, self.vosk_alternatives)
+
+    def _final_message(self, ses: _Session, results: list) -> dict:
+        """the Vosk final of a reply with results: the classic {"result", "text"}, or {"alternatives": [...]} for a
+        session that asked for them; with ``token_alternates`` the first hypothesis' entries carry their token records"""
+        _text, tokens, _ids, pos, _hyp = results[0]
+        al = getattr(results, "alignment", None)
+        records = al.get("alternates") if self.token_alternates and al is not None else None
+        if records is not None and len(records) != len(tokens):
+            records = None
+        aligned = self.vosk_alignment or (ses.max_alternatives > 0 and self.vosk_alternatives > 0)
+        if ses.max_alternatives > 0 and self.vosk_alternatives > 0:
+            res = list(results[:ses.max_alternatives])
+            nbest = (al or {}).get("nbest") or [al]
+            texts, words = [], []
+            for r, (_t, toks, _i, p, _h) in enumerate(res):
+                texts.append("".join(toks).replace("▁", " ").strip())
+                words.append(vosk_words(toks, p, nbest[r] if r < len(nbest) else None, True, records if r == 0 else None))
+            return alternates_mod.vosk_alternatives(texts, [r[4]["score"] for r in res], words)
+        if records is None:   # today's message
+            if self.vosk_alignment and al is not None and any(a is not None for a in al["start_s"]):
+                return vosk_result_aligned(tokens, al)
+            return vosk_result(tokens, pos)
+        return {"result": vosk_words(tokens, pos, al, aligned, records), "text": "".join(tokens).replace("▁", " ").strip()}
+
     def _finish(self, ses: _Session, results: list):
         info, ses.in_flight = ses.in_flight, None
         if info["forced"]:
@@ -438,10 +514,7 @@ class ServerLoop:
                 if text[-1] not in ".!?":
                     text += "."
                 text += "\n"
-            al = getattr(results, "alignment", None)
-            if ses.vosk and self.vosk_alignment and al is not None and any(a is not None for a in al["start_s"]):
-                return vosk_result_aligned(tokens, al)
-            return vosk_result(tokens, pos) if ses.vosk else text
+            return self._final_message(ses, results) if ses.vosk else text
         ses.endpointer.observe(len(text))
         if ses.vosk and self.draft_partials:
             return vosk_partial_ahead(text, getattr(results, "ahead", None) or [])
@@ -455,7 +528,7 @@ class ServerLoop:
             ses.last = transcription
             return transcription
         if ses.vosk:
-            if isinstance(ses.last, dict) and "result" in ses.last:
+            if isinstance(ses.last, dict) and ("result" in ses.last or "alternatives" in ses.last):
                 ses.last = vosk_partial("")
             return ses.last
         return transcription
