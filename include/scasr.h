@@ -173,7 +173,7 @@ const char *sc_last_error(void);
 /* ABI revision of this header: bumped whenever a struct layout or a signature changes incompatibly.  sc_version()
  * returns the revision the LIBRARY was built with; a host compares the two before it passes any struct
  * (speechcatcher_amd/_abi.py does at load time, the C hosts in tests/ at start-up). */
-#define SC_ABI_VERSION 11
+#define SC_ABI_VERSION 12
 int sc_version(void);
 
 /* hipGraph capture / replay of any sequence of the launches below on a
@@ -557,6 +557,47 @@ typedef struct sc_ctc_alt_job {
  * only read. */
 int sc_ctc_alternates(const sc_ctc_alt_job *jobs, int n_jobs, int max_L, int K, void *stream);
 
+/* ---- stable partials: committed prefix and token stability of a beam (commit.hip) -----------------
+ * A job is the live beam of one stream: n_hyp <= SC_COMMIT_MAX_HYPS hypotheses of one length L, best first, row h at
+ * yseq + h * row_stride (only [0, L) of a row is read), their total scores at score[h * score_stride].  Every
+ * hypothesis of a later reply descends from one of them, so what all of them share cannot change any more:
+ *   agree[h]      length of the common prefix of row h and row 0 (agree[0] = L)
+ *   commit        min_h agree[h]; L with SC_COMMIT_FINAL in flags
+ *   w[h]          exp(score[h] - the largest finite score); a NaN or an infinity: 0 and SC_COMMIT_NONFINITE in status;
+ *                 no finite score at all: every w = 1
+ *   Z             ((w[0] + w[1]) + ...), ascending h
+ *   stability[i - from], from <= i < L: (the sum, ascending h, of the w[h] with agree[h] > i) / Z - the share of the
+ *                 beam's mass that agrees with row 0 up to and including token i; 1.0 with SC_COMMIT_FINAL
+ *   ids / pos     yseq[0][from .. L), xpos[0][from .. L); totals: score / score_dec / score_ctc of row 0
+ * stability is exactly 1.0 below commit (the same sum as Z) and never rises with i.  tests/hyp_commit_ref.py is the
+ * contract: every int32 equal, stability within 1e-12. */
+#define SC_COMMIT_MAX_HYPS 16
+#define SC_COMMIT_FINAL 1      /* flags */
+#define SC_COMMIT_NONFINITE 1  /* status */
+typedef struct sc_hyp_commit_job {
+  const int32_t *yseq;      /* row h at yseq + h * row_stride, L ids (device) */
+  const int32_t *xpos;      /* the same layout */
+  const double *score;      /* total of row h at score[h * score_stride] (device) */
+  const double *score_dec;  /* the same layout; only row 0's is read */
+  const double *score_ctc;
+  int32_t *header;          /* [4] L, commit, n_hyp, status (device) */
+  int32_t *agree;           /* [n_hyp] (device) */
+  int32_t *ids;             /* [L - from] (device) */
+  int32_t *pos;             /* [L - from] (device) */
+  double *stability;        /* [L - from] (device) */
+  double *totals;           /* [3] (device) */
+  int64_t row_stride;       /* int32 elements between two rows, >= L */
+  int64_t score_stride;     /* doubles between two rows' scores: 1 for separate arrays, 3 for {total, dec, ctc} triples */
+  int32_t n_hyp, L, from, flags;
+} sc_hyp_commit_job;
+#define SC_COMMIT_MAX_JOBS 65535
+/* jobs: device table of n_jobs entries.  ONE launch on `stream`, one workgroup per job: no atomics, one writer per
+ * output, float64 sums in ascending h; nothing outside the sizes above is written.  SC_ERR_ARG before anything is
+ * launched for n_jobs outside [0, SC_COMMIT_MAX_JOBS] or a null table with n_jobs > 0.  A job whose own fields are
+ * malformed (a null pointer, n_hyp outside [1, SC_COMMIT_MAX_HYPS], L < 0, from outside [0, L], row_stride < L,
+ * score_stride < 1) writes nothing.  Two jobs of one call must not share outputs.  The rows and scores are only read. */
+int sc_hyp_commit(const sc_hyp_commit_job *jobs, int n_jobs, void *stream);
+
 /* ---- wire-format audio in (pcm.hip) -----------------------------------------------------------
  * A chunk is n sample FRAMES of `channels` interleaved little-endian codes, starting at ANY byte address.  Every format
  * but SC_PCM_F32 gives an integer v per code with full scale 2^B:
@@ -925,6 +966,19 @@ int sc_get_hyps(sc_streams *streams, int stream, int nbest, int max_len, int32_t
  * lens / scores / score_dec / score_ctc [n][nbest], n_hyps [n]; any output but n_hyps may be NULL. */
 int sc_get_hyps_batch(sc_streams *streams, const int *stream_ids, int n, int nbest, int max_len, int32_t *ids,
                       int32_t *xpos, int *lens, int *n_hyps, double *scores, double *score_dec, double *score_ctc);
+/* What a caller that already holds the first from[i] tokens of stream i's best hypothesis still needs, and how much of
+ * it is final (sc_hyp_commit above): for the hypotheses sc_get_hyps_batch would return (same rules: the
+ * snapshot with a queue depth > 1, an error for a stream inside a decode block or listed twice) L[i], commit[i] - the
+ * length of the prefix all live hypotheses share, which no later chunk changes -, n_hyps[i], and the tail of the best
+ * one: ids / xpos / stability [n][max_tail], the first L[i] - from[i] of each row written, scores [n][3] (total,
+ * decoder, ctc), status [n] (SC_COMMIT_*).  final[i] != 0 (final may be NULL): the chunk was the utterance's last, all
+ * of the best hypothesis is committed.  A stream that has not started: n_hyps = L = commit = 0.  SC_ERR_ARG for
+ * from[i] > L[i], L[i] - from[i] > max_tail, or more than SC_COMMIT_MAX_HYPS live hypotheses.  ONE job-table upload,
+ * ONE launch and ONE copy back into pinned memory, on the read-back stream; the call keeps no state and changes none.
+ * Any output may be NULL. */
+int sc_get_hyps_delta(sc_streams *streams, const int *stream_ids, int n, const int *from, const int *final,
+                      int max_tail, int32_t *L, int32_t *commit, int32_t *n_hyps, int32_t *ids, int32_t *xpos,
+                      double *stability, double *scores, int32_t *status);
 /* CTC forced alignment of the hypotheses sc_get_hyps_batch would return (same rules: the snapshot with a queue depth
  * > 1, an error for a stream inside a decode block), best first, against the stream's own CTC rows: the T frames of
  * the decode block the hypotheses come from.  Labels: yseq without <sos> and without a trailing <eos>.  Outputs

@@ -147,6 +147,18 @@ ALT_OK, ALT_NO_SPAN, ALT_BAD_ROW = 0, 1, 2
 ALT_MAX_K, ALT_MAX_JOBS = 8, 65535
 
 
+class CommitJob(C.Structure):
+    """sc_hyp_commit_job (include/scasr.h): the live beam of one stream handed to sc_hyp_commit"""
+    _fields_ = ([(n, vp) for n in ("yseq", "xpos", "score", "score_dec", "score_ctc", "header", "agree", "ids", "pos",
+                                   "stability", "totals")]
+                + [("row_stride", C.c_int64), ("score_stride", C.c_int64)]
+                + [(n, C.c_int32) for n in ("n_hyp", "L", "frm", "flags")])
+
+
+# SC_COMMIT_* of include/scasr.h
+COMMIT_MAX_HYPS, COMMIT_FINAL, COMMIT_NONFINITE, COMMIT_MAX_JOBS = 16, 1, 1, 65535
+
+
 class InputLevel(C.Structure):
     """sc_input_level_t (include/scasr.h)"""
     _fields_ = ([(n, C.c_int64) for n in ("frames", "clipped", "sum_abs")]
@@ -302,6 +314,10 @@ _SIGS = {
     "sc_ctc_alternates": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp]),
     "sc_alternates_hyps": (C.c_int, [vp, c_int_p, C.c_int, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_float_p,
                                      c_double_p, c_int_p, c_int_p, c_double_p, c_int_p, c_int_p, c_int_p]),
+    # stable partials (commit.hip, streams.hip)
+    "sc_hyp_commit": (C.c_int, [vp, C.c_int, vp]),
+    "sc_get_hyps_delta": (C.c_int, [vp, c_int_p, C.c_int, c_int_p, c_int_p, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p,
+                                    c_int_p, c_double_p, c_double_p, c_int_p]),
     # CTC speech activity (activity.hip, streams.hip)
     "sc_ctc_activity": (C.c_int, [vp, C.c_int, vp]),
     "sc_streams_set_activity": (C.c_int, [vp, C.c_int, C.c_double]),
@@ -344,7 +360,7 @@ EXPORTED_SYMBOLS = tuple(_SIGS.keys())
 
 # revision of include/scasr.h these ctypes mirrors were written against (SC_ABI_VERSION): a library built from another
 # revision would be handed mis-laid-out structs
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 _lib = None
 

@@ -262,6 +262,7 @@ struct EncGroup {
 constexpr int N_ARENA = 8;   // job-table arena slots = encoder groups that can be in flight
 constexpr int N_STAGE = 4;   // pinned staging slots for host input (a slot is free again when its H2D copy is done)
 constexpr int N_RING = 4;    // block-start tables (ctrl rows, log-softmax row lists): pinned ring
+constexpr int CM_FIXED = 4 + SC_COMMIT_MAX_HYPS + 6;   // sc_get_hyps_delta, int32 per job: header, agree, three float64 totals
 
 struct sc_streams {
   sc_engine *eng = nullptr;
@@ -351,6 +352,10 @@ struct sc_streams {
   // ---- batched hypothesis read-back (sc_get_hyps_batch): pack kernel -> one D2H into pinned memory -------------------
   int32_t *pack_dev = nullptr, *pack_host = nullptr, *pjobs_host = nullptr, *pjobs_dev = nullptr;
   size_t pack_cap = 0;            // int32 elements
+  // ---- stable partials (sc_get_hyps_delta): job table and packed outputs, one job per stream; allocated on the first call ----
+  sc_hyp_commit_job *cmjobs_host = nullptr, *cmjobs_dev = nullptr;   // [S]
+  int32_t *cm_dev = nullptr, *cm_host = nullptr;
+  size_t cm_cap = 0;              // int32 elements
   // ---- CTC forced alignment (sc_align_hyps / sc_align_tokens): job table, labels, outputs, workspaces -----------------
   char *al_dev = nullptr;         // allocated on the first call, grown geometrically
   size_t al_cap = 0;
@@ -3020,6 +3025,128 @@ extern "C" int sc_get_hyps_batch(sc_streams *b, const int *stream_ids, int n, in
       if (score_dec) score_dec[o] = sc[1];
       if (score_ctc) score_ctc[o] = sc[2];
     }
+  return SC_OK;
+  SC_API_END
+}
+
+// ---- stable partials ----------------------------------------------------------------------------------
+// The committed prefix of the listed streams' live beams and the tails of their best hypotheses behind from[i]: ONE
+// job-table upload, ONE sc_hyp_commit launch, ONE copy back, all on the read-back stream as sc_get_hyps_batch does it.  A
+// job's outputs lie packed at an even int32 offset of cm_dev: [header: 4][agree: SC_COMMIT_MAX_HYPS][totals: 3 doubles]
+// [stability: t doubles][ids: t][positions: t] with t = L - from.  Reads the engine's state, changes none.
+extern "C" int sc_get_hyps_delta(sc_streams *b, const int *stream_ids, int n, const int *from, const int *final,
+                                 int max_tail, int32_t *L_out, int32_t *commit, int32_t *n_hyps, int32_t *ids,
+                                 int32_t *xpos, double *stability, double *scores, int32_t *status) {
+  SC_CHECK_ARG(b && stream_ids && from && n >= 0 && max_tail >= 0, "bad arguments");
+  SC_API_BEGIN
+  HIP_TRY(hipSetDevice(b->eng->device));
+  SC_CHECK_ARG(n <= b->S, "more streams listed than the batch has");
+  if (!b->cmjobs_host) {   // the first call (the last of the four allocations marks them done): a handle that never asks holds none
+    b->cm_cap = (size_t)b->S * (4 * (size_t)b->LCAP + CM_FIXED + 2);
+    RC_TRY(b->alloc(&b->cm_dev, b->cm_cap));
+    RC_TRY(b->alloc(&b->cmjobs_dev, (size_t)b->S));
+    RC_TRY(b->halloc(&b->cm_host, b->cm_cap));
+    RC_TRY(b->halloc(&b->cmjobs_host, (size_t)b->S));
+  }
+  std::vector<char> listed(b->S, 0);
+  std::vector<int> job_of(n, -1);
+  std::vector<size_t> offs;
+  size_t off = 0;
+  int m = 0;
+  bool from_snapshot = false;
+  for (int i = 0; i < n; ++i) {
+    const int s = stream_ids[i];
+    SC_CHECK_ARG(s >= 0 && s < b->S, "stream out of range");
+    SC_CHECK_ARG(!listed[s], "a stream is listed twice");
+    listed[s] = 1;
+    const Snap &sn = b->snap[s];
+    int nh, L;
+    size_t row;
+    if (sn.valid) {   // queue depth > 1: the copy taken when the stream's last reported chunk completed
+      nh = sn.nhyp; L = sn.L; row = (size_t)s * b->W;
+      from_snapshot = from_snapshot || nh > 0;
+    } else {
+      SC_CHECK_ARG(!b->run[s].inblk && b->bq[s].empty(), "stream is inside a decode block (its chunk has not been reported yet)");
+      const St &st = b->st[s];
+      nh = st.started ? st.nhyp : 0; L = st.L; row = ((size_t)st.cur * b->S + s) * b->W;
+    }
+    if (nh == 0) {
+      SC_CHECK_ARG(from[i] == 0, "from is beyond the hypotheses");
+      continue;
+    }
+    SC_CHECK_ARG(nh <= SC_COMMIT_MAX_HYPS, "more than SC_COMMIT_MAX_HYPS live hypotheses");
+    SC_CHECK_ARG(from[i] >= 0 && from[i] <= L, "from is beyond the hypotheses");
+    const int t = L - from[i];
+    SC_CHECK_ARG(t <= max_tail, "max_tail is smaller than the tail");
+    sc_hyp_commit_job &j = b->cmjobs_host[m];
+    int32_t *o = b->cm_dev + off;
+    if (sn.valid) {
+      j.yseq = b->snap_yseq + row * b->LCAP;
+      j.xpos = b->snap_xpos + row * b->LCAP;
+      j.score = b->snap_score + row * 3;
+      j.score_dec = j.score + 1;
+      j.score_ctc = j.score + 2;
+      j.score_stride = 3;
+    } else {
+      j.yseq = b->sb.yseq + row * b->LCAP;
+      j.xpos = b->sb.xpos + row * b->LCAP;
+      j.score = b->sb.score + row;
+      j.score_dec = b->sb.sc_dec + row;
+      j.score_ctc = b->sb.sc_ctc + row;
+      j.score_stride = 1;
+    }
+    j.header = o;
+    j.agree = o + 4;
+    j.totals = (double *)(o + 4 + SC_COMMIT_MAX_HYPS);
+    j.stability = j.totals + 3;
+    j.ids = o + CM_FIXED + 2 * (size_t)t;
+    j.pos = j.ids + t;
+    j.row_stride = b->LCAP;
+    j.n_hyp = nh; j.L = L; j.from = from[i];
+    j.flags = (final && final[i]) ? SC_COMMIT_FINAL : 0;
+    job_of[i] = m++;
+    offs.push_back(off);
+    off += ((size_t)CM_FIXED + 4 * (size_t)t + 1) & ~(size_t)1;
+  }
+  SC_CHECK_ARG(off <= b->cm_cap, "tails exceed the read-back buffer");
+  if (m > 0) {
+    // on the read-back stream: a decode step of OTHER streams may be in flight on the batch's stream (sc_poll); the
+    // listed streams' last steps have been collected (host-synchronised) by then
+    const int rc = [&]() -> int {
+      HIP_TRY(hipMemcpyAsync(b->cmjobs_dev, b->cmjobs_host, (size_t)m * sizeof(sc_hyp_commit_job), hipMemcpyHostToDevice, b->stream_rb));
+      if (from_snapshot) HIP_TRY(hipStreamWaitEvent(b->stream_rb, b->ev_snap, 0));   // the copies are written on the batch's stream
+      RC_TRY(sc_hyp_commit(b->cmjobs_dev, m, b->stream_rb));
+      HIP_TRY(hipMemcpyAsync(b->cm_host, b->cm_dev, off * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream_rb));
+      HIP_TRY(hipStreamSynchronize(b->stream_rb));
+      return SC_OK;
+    }();
+    if (rc != SC_OK) {   // nothing of this call may still read the pinned job table when the next call fills it
+      (void)hipStreamSynchronize(b->stream_rb);
+      return rc;
+    }
+  }
+  for (int i = 0; i < n; ++i) {
+    const int k = job_of[i];
+    if (k < 0) {
+      if (L_out) L_out[i] = 0;
+      if (commit) commit[i] = 0;
+      if (n_hyps) n_hyps[i] = 0;
+      if (status) status[i] = 0;
+      if (scores) scores[3 * i] = scores[3 * i + 1] = scores[3 * i + 2] = 0.0;
+      continue;
+    }
+    const int32_t *src = b->cm_host + offs[k];
+    const size_t t = (size_t)(b->cmjobs_host[k].L - from[i]);
+    if (L_out) L_out[i] = src[0];
+    if (commit) commit[i] = src[1];
+    if (n_hyps) n_hyps[i] = src[2];
+    if (status) status[i] = src[3];
+    const double *d = (const double *)(src + 4 + SC_COMMIT_MAX_HYPS);
+    if (scores) memcpy(scores + 3 * (size_t)i, d, 3 * sizeof(double));
+    if (stability) memcpy(stability + (size_t)i * max_tail, d + 3, t * sizeof(double));
+    if (ids) memcpy(ids + (size_t)i * max_tail, src + CM_FIXED + 2 * t, t * 4);
+    if (xpos) memcpy(xpos + (size_t)i * max_tail, src + CM_FIXED + 3 * t, t * 4);
+  }
   return SC_OK;
   SC_API_END
 }

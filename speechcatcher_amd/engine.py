@@ -35,6 +35,7 @@ import torch
 from .activity import INITIAL, advance as activity_advance, as_arrays as activity_arrays
 from . import spotting
 from . import draft as draft_mod
+from . import commit as commit_mod
 from .config import SearchConfig
 from .weights import PackedWeights
 
@@ -1325,3 +1326,39 @@ class StreamBatch:
         scc = self.sc_ctc[c, s, :n].cpu().numpy()
         return [{"yseq": ys[i].tolist(), "score": float(sc[i]), "score_dec": float(sd[i]),
                  "score_ctc": float(scc[i]), "xpos": xp[i].tolist()} for i in range(n)]
+
+    def hyps_delta(self, streams: Sequence[int], from_: Sequence[int], final: Sequence[int] = ()):
+        """Stable partials (the native engine: sc_get_hyps_delta): {stream: {"L", "commit", "tokens", "xpos",
+        "stability", "score", "score_dec", "score_ctc", "n_hyp", "status"}} - of stream s's live hypotheses the length L,
+        the length ``commit`` of the prefix all of them share (no later chunk changes it), and the best one from token
+        ``from_[i]`` on with the share of the beam's mass behind each of those tokens.  ``final``: the listed streams
+        whose chunk was the utterance's last.  speechcatcher_amd.commit over ``hypotheses``, or - with a backend that has
+        one - the backend's ``hyp_commit`` over the device rows, one launch for all streams.  Changes nothing."""
+        streams = [int(s) for s in streams]
+        frm = [int(f) for f in from_]
+        if len(frm) != len(streams) or len(set(streams)) != len(streams):
+            raise EngineError("one from per stream, every stream at most once")
+        fset = {int(s) for s in final}
+        out, jobs, owners = {}, [], []
+        on_device = hasattr(self.be, "hyp_commit")
+        for s, f in zip(streams, frm):
+            st = self.st[s]
+            L = st.L if st.started else 0
+            if not 0 <= f <= L:
+                raise EngineError(f"stream {s}: from = {f} is outside [0, {L}]")
+            if not st.started or st.nhyp == 0:
+                out[s] = commit_mod.empty_delta()
+            elif on_device:
+                c, n = st.cur, st.nhyp
+                jobs.append((self.yseq[c, s, :n], self.xpos[c, s, :n],
+                             (self.score[c, s, :n], self.sc_dec[c, s, :n], self.sc_ctc[c, s, :n]), L, f, s in fset))
+                owners.append(s)
+            else:
+                out[s] = commit_mod.of_hypotheses(self.hypotheses(s), f, s in fset)
+        if jobs:
+            for s, d in zip(owners, self.be.hyp_commit(jobs)):
+                d.pop("raw", None)
+                out[s] = d
+        for d in out.values():
+            d.pop("agree", None)
+        return {s: out[s] for s in streams}

@@ -544,6 +544,63 @@ class HipBackend:
         torch.cuda.synchronize(dev)
         return ids.cpu().numpy()[:n], logp.cpu().numpy()[:n], rank.cpu().numpy()[:n], stt.cpu().numpy()[:n]
 
+    def hyp_commit(self, jobs, tweak=None, guard: int = 2):
+        """Committed prefix and token stability of beams (sc_hyp_commit) on the caller's device arrays, one
+        launch for all jobs.  jobs: list of (yseq, xpos: int32 device tensors [n, >= L], rows may be strided; scores:
+        either one float64 tensor [n, 3] of (total, decoder, ctc) triples or three float64 tensors [n]; L; from; final).
+        Returns one dict per job: "L", "commit", "n_hyp", "status", "agree" [n], "tokens" / "xpos" / "stability"
+        [L - from], "score", "score_dec", "score_ctc", and "raw": the job's output buffers whole (header [4 + guard],
+        agree [16 + guard], ids / pos / stability [L - from + guard], totals [3 + guard]) - every buffer is handed over
+        filled with -7, so what a job leaves unwritten shows.  ``tweak(k, job)``: test aid, edits the sc_hyp_commit_job of
+        job k before the launch."""
+        import numpy as np
+        n = len(jobs)
+        dev = self.device
+        tails = [max(0, int(j[3]) - int(j[4])) for j in jobs]
+        ti = np.concatenate([[0], np.cumsum([t + guard for t in tails])]).astype(np.int64)
+        H = _abi.COMMIT_MAX_HYPS
+        head = torch.full((max(n, 1), 4 + guard), -7, dtype=torch.int32, device=dev)
+        agree = torch.full((max(n, 1), H + guard), -7, dtype=torch.int32, device=dev)
+        tot = torch.full((max(n, 1), 3 + guard), -7.0, dtype=torch.float64, device=dev)
+        ids = torch.full((max(int(ti[-1]), 1),), -7, dtype=torch.int32, device=dev)
+        pos = torch.full((max(int(ti[-1]), 1),), -7, dtype=torch.int32, device=dev)
+        stab = torch.full((max(int(ti[-1]), 1),), -7.0, dtype=torch.float64, device=dev)
+        tab = (_abi.CommitJob * max(1, n))()
+        for k, (ys, xp, sc, L, frm, final) in enumerate(jobs):
+            assert ys.dtype == xp.dtype == torch.int32 and ys.dim() == xp.dim() == 2 and ys.stride(1) == xp.stride(1) == 1
+            assert ys.shape[0] == xp.shape[0] and ys.stride(0) == xp.stride(0) and L <= ys.shape[1]
+            j = tab[k]
+            j.yseq, j.xpos, j.row_stride = ys.data_ptr(), xp.data_ptr(), ys.stride(0)
+            if isinstance(sc, (tuple, list)):
+                assert all(a.dtype == torch.float64 and a.dim() == 1 and a.stride(0) == 1 for a in sc)
+                j.score, j.score_dec, j.score_ctc = (a.data_ptr() for a in sc)
+                j.score_stride = 1
+            else:
+                assert sc.dtype == torch.float64 and sc.dim() == 2 and sc.shape[1] == 3 and sc.is_contiguous()
+                j.score, j.score_dec, j.score_ctc = (sc.data_ptr() + 8 * c for c in range(3))
+                j.score_stride = 3
+            j.header, j.agree, j.totals = head[k].data_ptr(), agree[k].data_ptr(), tot[k].data_ptr()
+            j.ids, j.pos = ids.data_ptr() + 4 * int(ti[k]), pos.data_ptr() + 4 * int(ti[k])
+            j.stability = stab.data_ptr() + 8 * int(ti[k])
+            j.n_hyp, j.L, j.frm, j.flags = ys.shape[0], int(L), int(frm), _abi.COMMIT_FINAL if final else 0
+            if tweak is not None:
+                tweak(k, j)
+        tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+        self._chk(self.lib.sc_hyp_commit(tab_dev.data_ptr(), n, self._stream()), "sc_hyp_commit")
+        torch.cuda.synchronize(dev)
+        head, agree, tot, ids, pos, stab = (a.cpu().numpy() for a in (head, agree, tot, ids, pos, stab))
+        out = []
+        for k in range(n):
+            a, b, t = int(ti[k]), int(ti[k + 1]), tails[k]
+            nh = max(0, min(int(head[k, 2]), H))
+            out.append({"L": int(head[k, 0]), "commit": int(head[k, 1]), "n_hyp": int(head[k, 2]),
+                        "status": int(head[k, 3]), "agree": agree[k, :nh].copy(), "tokens": ids[a:a + t].copy(),
+                        "xpos": pos[a:a + t].copy(), "stability": stab[a:a + t].copy(), "score": float(tot[k, 0]),
+                        "score_dec": float(tot[k, 1]), "score_ctc": float(tot[k, 2]),
+                        "raw": {"header": head[k].copy(), "agree": agree[k].copy(), "ids": ids[a:b].copy(),
+                                "pos": pos[a:b].copy(), "stability": stab[a:b].copy(), "totals": tot[k].copy()}})
+        return out
+
     def decode_pcm(self, jobs, tweak=None, guard: int = 4):
         """Batched decode of coded audio (sc_pcm_decode) on the caller's buffers, one launch for all jobs.  jobs: list of
         (src: a bytes-like object, a numpy array or a uint8 device tensor; byte offset; format; channels; channel; scale;

@@ -604,6 +604,54 @@ class NativeStreamBatch:
             out[int(s)] = hy
         return out
 
+    def hyps_delta_arrays(self, streams: Sequence[int], from_: Sequence[int], final: Sequence[int] = ()):
+        """sc_get_hyps_delta as numpy arrays, one device round trip for all listed streams: L / commit / n_hyps / status
+        [n] int32, ids / xpos [n, max_tail] int32 and stability [n, max_tail] float64 (row i: its first L[i] - from_[i]
+        entries; the rest is undefined), scores [n, 3] (total, decoder, ctc).  ``final``: the listed streams whose chunk was the utterance's last."""
+        sid = np.ascontiguousarray(streams, dtype=np.int32)
+        frm = np.ascontiguousarray(from_, dtype=np.int32)
+        n = len(sid)
+        if frm.shape != (n,):
+            raise ValueError("one from per stream")
+        fin = np.zeros(n, np.int32)
+        if len(final):
+            fin[np.isin(sid, np.asarray(list(final), np.int32))] = 1
+        mt = max(1, self.LCAP - (int(frm.min()) if n else 0))
+        ints = np.zeros((4, n), np.int32)
+        # (not zeroed: the call writes the tails, the rest of a row is never touched - nor its pages)
+        tails = np.empty((2, n, mt), np.int32)
+        stab, sc = np.empty((n, mt)), np.zeros((n, 3))
+        ip, dp = _abi.c_int_p, _abi.c_double_p
+        try:
+            _abi.check(self.lib.sc_get_hyps_delta(self.handle, sid.ctypes.data_as(ip), n, frm.ctypes.data_as(ip),
+                                                  fin.ctypes.data_as(ip), mt, ints[0].ctypes.data_as(ip),
+                                                  ints[1].ctypes.data_as(ip), ints[2].ctypes.data_as(ip),
+                                                  tails[0].ctypes.data_as(ip), tails[1].ctypes.data_as(ip),
+                                                  stab.ctypes.data_as(dp), sc.ctypes.data_as(dp), ints[3].ctypes.data_as(ip)),
+                       "sc_get_hyps_delta")
+        except _abi.ScasrError as e:
+            raise EngineError(str(e)) from e
+        return {"L": ints[0], "commit": ints[1], "n_hyps": ints[2], "status": ints[3], "from": frm, "ids": tails[0],
+                "xpos": tails[1], "stability": stab, "scores": sc}
+
+    def hyps_delta(self, streams: Sequence[int], from_: Sequence[int], final: Sequence[int] = ()):
+        """Stable partials (sc_get_hyps_delta): {stream: {"L", "commit", "tokens", "xpos", "stability",
+        "score", "score_dec", "score_ctc", "n_hyp", "status"}} for the listed streams - of the hypotheses
+        ``hypotheses_batch`` would return, the length L, the length ``commit`` of the prefix all live hypotheses share (no
+        later chunk changes it), and the best hypothesis from token ``from_[i]`` on with the share of the beam's mass
+        behind each of those tokens.  ``final``: the listed streams whose chunk was the utterance's last (everything is
+        committed).  One launch and one copy back for all; only the tails travel.  The call changes nothing."""
+        a = self.hyps_delta_arrays(streams, from_, final)
+        out = {}
+        for i, s in enumerate(streams):
+            t = int(a["L"][i]) - int(a["from"][i]) if a["n_hyps"][i] else 0
+            sc = a["scores"][i]
+            out[int(s)] = {"L": int(a["L"][i]), "commit": int(a["commit"][i]), "tokens": a["ids"][i, :t],
+                           "xpos": a["xpos"][i, :t], "stability": a["stability"][i, :t], "score": float(sc[0]),
+                           "score_dec": float(sc[1]), "score_ctc": float(sc[2]), "n_hyp": int(a["n_hyps"][i]),
+                           "status": int(a["status"][i])}
+        return out
+
     def hypotheses(self, s: int):
         """Live hypotheses of stream s: list of dicts (yseq, score, score_dec, score_ctc, xpos), best first."""
         return self.hypotheses_batch([int(s)])[int(s)]

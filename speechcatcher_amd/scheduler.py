@@ -22,6 +22,7 @@ from .engine import StreamBatch
 from . import spotting
 from . import draft as draft_mod
 from . import alternates as alternates_mod
+from . import commit as commit_mod
 from .activity import of_stream as activity_of_stream
 from .align import FeatureClock
 from . import pcm as pcm_mod
@@ -82,12 +83,22 @@ class LevelResults(DraftResults):
     level: Optional[dict] = None
 
 
+class StableResults(LevelResults):
+    """the results of a reply and ``stable``: {"committed": n, "tokens": ids, "stability": values} of the session's stream
+    for that chunk - StreamScheduler(stable_partials=True).  ``tokens`` is the best live hypothesis (the <sos> first); its
+    first n tokens are committed: every live hypothesis has them, so no later chunk of the utterance changes them, and n
+    only grows.  ``stability`` holds one value per token behind them: the share of the beam's probability
+    mass that agrees with the best hypothesis up to and including that token.  A final reply commits everything.  The
+    attributes of the other options are carried as well when those are on."""
+    stable: Optional[dict] = None
+
+
 class StreamScheduler:
     def __init__(self, batch: StreamBatch, token_list: Optional[List[str]] = None,
                  result_format: str = "native", reset_after_final: bool = True, reset_on_open: bool = True,
                  queue_depth: int = 1, align_final: bool = False, activity: bool = False, blank_threshold: float = 0.8,
                  phrases=None, min_scores=None, draft: bool = False, input_level: bool = False, alternates: int = 0,
-                 align_nbest: int = 1):
+                 align_nbest: int = 1, stable_partials: bool = False):
         """``queue_depth`` > 1 (C++ engine, ``pump``): up to that many queued chunks of a session are handed to the engine
         at a time (sc_streams_set_queue_depth) - for sessions whose audio is already there (files): the encoder stage of
         the next chunk runs beside the decoding of the current one.  Replies and their order per session do not change.
@@ -117,6 +128,11 @@ class StreamScheduler:
         # ``draft``: every reply (an exception aside) is a ``DraftResults`` (batch.set_draft), read before the stream is
         # reset after a final
         self.draft = False
+        # ``stable_partials``: every reply (an exception aside) is a ``StableResults``.  The scheduler owns one
+        # commit.StablePrefix per session and asks the engine only for the tokens behind what that holds
+        # (batch.hyps_delta: one call for all sessions of a reply round)
+        self.stable_partials = False
+        self._stable: Dict[int, commit_mod.StablePrefix] = {}
         self._spot_seen: Dict[int, int] = {}                  # per session: events of its utterance handed out so far
         self._clock: Dict[int, FeatureClock] = {}             # align_final: per session, the calls since its last reset
         self._fed: Dict[int, Deque[Tuple[int, bool]]] = {}   # ... and its fed chunks not reported yet (length, final)
@@ -151,6 +167,8 @@ class StreamScheduler:
             self.enable_draft()
         if alternates:
             self.enable_alternates(alternates)
+        if stable_partials:
+            self.enable_stable_partials()
 
     def enable_activity(self, blank_threshold: float = 0.8):
         """switch the ``activity`` option on (only while no chunk is at the engine; every stream's state starts over)"""
@@ -167,6 +185,14 @@ class StreamScheduler:
         """switch the ``draft`` option on (only while no chunk is at the engine; every stream's state starts over)"""
         self.batch.set_draft(True)
         self.draft = True
+
+    def enable_stable_partials(self):
+        """switch the ``stable_partials`` option on (every session's tracker starts over)"""
+        if self.batch.W > commit_mod.MAX_HYPS:
+            raise ValueError(f"stable partials compare a beam of at most {commit_mod.MAX_HYPS} hypotheses "
+                             f"(this batch has beam {self.batch.W})")
+        self.stable_partials = True
+        self._stable.clear()
 
     def enable_alternates(self, k: int):
         """switch the ``alternates`` option on (and ``align_final`` with it)"""
@@ -209,6 +235,7 @@ class StreamScheduler:
         self._fed.pop(sid, None)
         self._rate[sid] = OutputClock(sample_rate)
         self._spot_seen.pop(sid, None)
+        self._stable.pop(sid, None)
         if fmt != _FLOAT_INPUT:
             self._fmt[sid] = fmt
         return sid
@@ -292,6 +319,7 @@ class StreamScheduler:
         self._rate.pop(sid, None)
         self._fmt.pop(sid, None)
         self._spot_seen.pop(sid, None)
+        self._stable.pop(sid, None)
         if self.reset_on_open:
             self.batch.reset(slot)
         self._free.append(slot)
@@ -355,6 +383,13 @@ class StreamScheduler:
             act_slots = [slot for (slot, _, _) in meta.values() if not isinstance(has[slot], Exception)]
             act_row = {slot: i for i, slot in enumerate(act_slots)}
             act = self.batch.activity(act_slots) if act_slots else None
+        delta = None
+        if self.stable_partials:
+            ask = [(sid, slot) for sid, (slot, _, _) in meta.items() if not isinstance(has[slot], Exception)]
+            if ask:
+                held = [self._stable.setdefault(sid, commit_mod.StablePrefix()).next_from for sid, _ in ask]
+                delta = self.batch.hyps_delta([slot for _, slot in ask], held,
+                                              final=[slot for sid, slot in ask if meta[sid][1]])
         for sid, (slot, fin, fa) in meta.items():
             if self._clocked and self._fed.get(sid):   # the stream's clock advances by the reported chunk
                 n, f = self._fed[sid].popleft()
@@ -364,6 +399,7 @@ class StreamScheduler:
                 out[sid] = has[slot]          # the engine has reset the stream
                 self._clock.pop(sid, None)
                 self._spot_seen.pop(sid, None)
+                self._stable.pop(sid, None)
                 continue
             if not has[slot]:
                 out[sid] = []
@@ -398,6 +434,12 @@ class StreamScheduler:
                 for k in ("alignment", "activity", "detections", "draft", "ahead"):
                     setattr(res, k, getattr(out[sid], k, None))
                 res.level = self.batch.input_level(slot) if hasattr(self.batch, "input_level") else pcm_mod.zero_level()
+                out[sid] = res
+            if delta is not None:
+                res = StableResults(out[sid])
+                for k in ("alignment", "activity", "detections", "draft", "ahead", "level"):
+                    setattr(res, k, getattr(out[sid], k, None))
+                res.stable = self._stable[sid].update(delta[slot], final=fin).state()   # (a final starts the tracker over)
                 out[sid] = res
             if fin and self.reset_after_final:
                 self.batch.reset(slot)

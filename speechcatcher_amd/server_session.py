@@ -37,6 +37,7 @@ from .align import merge_words
 from . import alternates as alternates_mod
 from . import pcm as pcm_mod
 from .scheduler import ServerBusy, StreamScheduler
+from .speech2text_streaming import TEXT_SKIP_IDS
 
 Message = Union[str, bytes, np.ndarray]
 FRAMES_PER_SECOND = 24.0   # speechcatcher.py:48
@@ -211,6 +212,8 @@ class _Session:
         self.vosk_sample_rate = 16000
         self.wire = None                          # (format, channels, channel, scale): the session hands its bytes to the engine
         self.max_alternatives = 0                 # Vosk config.max_alternatives (ServerLoop(vosk_alternatives=N))
+        self.stable_n = 0                         # ServerLoop(stable_partials=True): committed tokens put into text so far
+        self.stable_text = ""                     # ... and their text (the "▁" of the pieces already turned into spaces)
         self.last = vosk_partial("") if vosk else ""
 
 
@@ -222,7 +225,8 @@ class ServerLoop:
                  continuous: Optional[bool] = None, min_replies: int = 1, vosk_alignment: bool = False,
                  acoustic_endpointing: Optional[EndpointRules] = None, spotting: Optional[dict] = None,
                  spotting_min_scores: Optional[dict] = None, draft_partials: bool = False, raw_input: bool = False,
-                 input_level: bool = False, vosk_alternatives: int = 0, token_alternates: int = 0):
+                 input_level: bool = False, vosk_alternatives: int = 0, token_alternates: int = 0,
+                 stable_partials: bool = False):
         """``strict_reference``: no stream reset after a finalised utterance nor between clients, exactly like
         ``recognize_ws`` / ``process_audio_chunk`` (speechcatcher_server.py:270,359-397); the default resets.
         ``continuous`` (default: on whenever the batch has the C++ engine's submit / poll - round 4; False forces one
@@ -264,7 +268,16 @@ class ServerLoop:
         ``token_alternates`` = K > 0 (C++ engine, Vosk format): the word entries of a final - of its first alternative, or
         of the classic result - carry "tokens": per token of the word {"id", "token", "conf", "own_rank", "alternates":
         [{"id", "token", "conf"}]}, the K tokens that fit the token's frames best acoustically (the scheduler's
-        ``alternates`` option)."""
+        ``alternates`` option).
+        ``stable_partials`` (Vosk format): a partial becomes {"partial": text, "stable": text of the committed tokens,
+        "stability": [one value per token of the best hypothesis behind them]} (the scheduler's ``stable_partials``
+        option): ``stable`` is what every live hypothesis of the beam begins with - no later chunk of the
+        utterance changes it and it only grows -, ``stability`` the share of the beam's mass behind each open token.
+        The session keeps the committed text and puts only the newly committed tokens into text.  Composes with
+        ``draft_partials`` (the ``ahead`` keys stay).  Finals are unchanged.  False (default): partials as they are."""
+        self.stable_partials = bool(stable_partials) and vosk_output_format
+        if self.stable_partials and not scheduler.stable_partials:
+            scheduler.enable_stable_partials()
         self.vosk_alternatives = int(vosk_alternatives) if vosk_output_format else 0
         self.token_alternates = int(token_alternates) if vosk_output_format else 0
         if self.vosk_alternatives < 0:
@@ -364,6 +377,7 @@ class ServerLoop:
                 # it): the transport closes this connection; every other session is untouched
                 ses.in_flight = None
                 ses.endpointer.n_best_lens = []
+                ses.stable_n, ses.stable_text = 0, ""
                 if ses.acoustic is not None:
                     ses.acoustic.reset()
                 replies.setdefault(sid, []).append(results)
@@ -494,7 +508,37 @@ class ServerLoop:
             return vosk_result(tokens, pos)
         return {"result": vosk_words(tokens, pos, al, aligned, records), "text": "".join(tokens).replace("▁", " ").strip()}
 
+    def _stable_keys(self, ses: _Session, results, message: dict, finalize: bool) -> dict:
+        """``message`` with the "stable" and "stability" keys of a partial; a final starts the session's text over"""
+        st = getattr(results, "stable", None)
+        if finalize or st is None:
+            ses.stable_n, ses.stable_text = 0, ""
+            return message
+        names = self.sch.token_list
+        # hyps_to_results' selection: yseq without its first token (the <sos>), without the ids a transcript leaves out
+        new = [t for t in st["tokens"][max(ses.stable_n, 1):st["committed"]] if t not in TEXT_SKIP_IDS]
+        if names is not None:
+            ses.stable_text += "".join(names[t] for t in new).replace("▁", " ")
+        else:
+            ses.stable_text += "".join(f" {t}" for t in new)
+        ses.stable_n = st["committed"]
+        return dict(message, stable=ses.stable_text.strip(), stability=[float(v) for v in st["stability"]])
+
     def _finish(self, ses: _Session, results: list):
+        finalize = ses.in_flight["finalize"]
+        out = self._finish_plain(ses, results)
+        if not (ses.vosk and self.stable_partials):
+            return out
+        if finalize:
+            if not out and isinstance(ses.last, dict) and "stable" in ses.last:
+                # a final without a hypothesis repeats the partial alone
+                ses.last = {k: v for k, v in ses.last.items() if k not in ("stable", "stability")}
+            return self._stable_keys(ses, results, out, True)
+        if not out:   # no hypothesis yet: the partial of the last reply (an empty one behind a final)
+            out = vosk_partial(ses.last["partial"] if isinstance(ses.last, dict) and "partial" in ses.last else "")
+        return self._stable_keys(ses, results, out, False)
+
+    def _finish_plain(self, ses: _Session, results: list):
         info, ses.in_flight = ses.in_flight, None
         if info["forced"]:
             ses.endpointer.n_best_lens = []   # session.reset() after a client-forced finalize (:272-273)

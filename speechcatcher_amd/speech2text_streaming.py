@@ -189,6 +189,11 @@ class _BeamStateView:
         self.output_index = 0
 
 
+# token ids a transcript leaves out (blank, <unk>, and <sos/eos> hard-coded as 1023 - A4, as hyps_to_results restates it);
+# the one filter behind hyps_to_results, result_token_alignment and the "stable" text of ServerLoop(stable_partials=True)
+TEXT_SKIP_IDS = (0, 1, 1023)
+
+
 def hyps_to_results(hyps, is_final, finalize_all, token_list, fmt="native"):
     """speech2text_streaming.py:466-539 (EOS id hard-coded 1023: A4;
     non-final calls use a fresh output_index 0: A5)."""
@@ -208,7 +213,7 @@ def hyps_to_results(hyps, is_final, finalize_all, token_list, fmt="native"):
             ids, pos = ys[1:end], xp[1:end]
             if ids and ids[-1] == 1023:
                 ids, pos = ids[:-1], pos[:-1]
-        keep = [(t, p) for t, p in zip(ids, pos) if t not in (0, 1, 1023)]
+        keep = [(t, p) for t, p in zip(ids, pos) if t not in TEXT_SKIP_IDS]
         ids = [t for t, _ in keep]
         pos = [p for _, p in keep]
         if token_list is not None:
@@ -239,7 +244,7 @@ def result_token_alignment(ys, is_final, al, i, j, cfg, clock=None) -> dict:
     if ids and ids[-1] == 1023:
         ids = ids[:-1]
     n_lab = len(ys) - 1 - (1 if ys[-1] == cfg.eos_id else 0)    # labels of the alignment: yseq without <sos> / <eos>
-    keep = [k for k, t in enumerate(ids) if t not in (0, 1, 1023)]
+    keep = [k for k, t in enumerate(ids) if t not in TEXT_SKIP_IDS]
     ok = int(al["status"][i, j]) == _abi.ALIGN_OK
     lab = [k for k in keep if ok and k < n_lab]
     st, en = [int(al["start"][i, j, k]) for k in lab], [int(al["end"][i, j, k]) for k in lab]
