@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "common.h"
+#include "handover.h"
 #include "resample.h"
 
 namespace {
@@ -140,42 +141,32 @@ struct Run {
   long job = 0;   // Job::seq of the chunk the block belongs to
 };
 
+// The side states (handover.h; DESIGN.md section 5, "Side states"): the payload each option hands over with a chunk, with
+// its value before anything of the utterance has been scanned.  A Job carries a handover::Pending of each.
 // Acoustic activity (sc_streams_set_activity; activity.hip): the state over every frame the encoder had emitted for the
-// utterance when a chunk was admitted.  The launch that computes it belongs to the encoder group `gen`; until that group
-// has been retired the value is pending (ready = false).  T: rows of the CTC table the state covers (the track's extent).
-struct ActVal {
-  bool ready = true;
-  long gen = 0;
+// utterance when the chunk was admitted.  T: rows of the CTC table the state covers (the track's extent).
+struct ActState {
   int32_t v[6] = {0, 0, 0, -1, -1, 0};
   int T = 0;
 };
-
-// Phrase spotting (sc_streams_set_phrases; spot.hip): the counters (n_frames, n_events) that belong to a chunk, handed
-// over exactly like ActVal.  The events themselves stay on the device: the utterance's event k is at slot k, so the
-// first n_events of them are final whatever later groups append.
-struct SpotVal {
-  bool ready = true;
-  long gen = 0;
+// Phrase spotting (sc_streams_set_phrases; spot.hip): the counters (n_frames, n_events).  The events themselves stay on the
+// device: the utterance's event k is at slot k, so the first n_events of them are final whatever later groups append.
+struct SpotState {
   int32_t v[2] = {0, 0};
 };
-
-// Draft transcript (sc_streams_set_draft; draft.hip): the greedy state that belongs to a chunk, handed over exactly like
-// ActVal.  The tokens stay on the device: the utterance's token k is at slot k and is never touched once stored, so the
-// first n_closed of them are final whatever later groups append; the open token travels in the state.
-struct DraftVal {
-  bool ready = true;
-  long gen = 0;
-  sc_draft_t v = {0, 0, 0, -1, -1, -1, 0.0};
+// Draft transcript (sc_streams_set_draft; draft.hip): the greedy state.  The tokens stay on the device: the utterance's
+// token k is at slot k and is never touched once stored, so the first n_closed of them are final whatever later groups
+// append; the open token travels in the state.
+struct DraftState {
+  sc_draft_t d = {0, 0, 0, -1, -1, -1, 0.0};
 };
+// Input level (sc_stream_set_input_format; pcm.hip): the cumulative level, all zero at first.  Its launch belongs to a
+// STAGING slot (it runs in the admission's staging step, not in an encoder group), so its key is a ticket that names the
+// decode job, and slots are collected in any order.
+using LevelState = sc_input_level_t;
 
-// Input level (sc_stream_set_input_format; pcm.hip): the cumulative level that belongs to a chunk.  The launch that computes
-// it belongs to a STAGING slot (it runs in the admission's staging step, not in an encoder group): `ticket` names the decode
-// job, and until its slot's event has fired and the state-after has been collected the value is pending (ready = false).
-struct LevelVal {
-  bool ready = true;
-  long ticket = 0;
-  sc_input_level_t v = {0, 0, 0, 0, 0};
-};
+// the options that scan the CTC rows of an encoder group, in launch order (EncGroup::Span::opt)
+enum { OPT_ACT, OPT_SPOT, OPT_DRAFT, N_OPT };
 
 // a stream's outstanding chunk (sc_push / sc_submit): open until it has been reported.  With a queue depth > 1
 // (sc_streams_set_queue_depth) further chunks of the stream wait behind it (sc_streams::ahead), in order.
@@ -187,10 +178,10 @@ struct Job {
   bool fin = false;  // is_final chunk: nothing may be queued behind it
   bool dropped = false;   // failed only because an EARLIER chunk of the stream failed (the reset has happened by then)
   bool started = false;   // St::started right after THIS chunk's admission (a later admission may set it before this one is reported)
-  ActVal act;             // sc_streams_set_activity: the activity state that belongs to this chunk
-  SpotVal spot;           // sc_streams_set_phrases: the spotting counters that belong to this chunk
-  DraftVal draft;         // sc_streams_set_draft: the draft state that belongs to this chunk
-  LevelVal level;         // sc_stream_set_input_format: the input level up to and including this chunk
+  handover::Pending<ActState> act;       // sc_streams_set_activity: the activity state that belongs to this chunk
+  handover::Pending<SpotState> spot;     // sc_streams_set_phrases: the spotting counters that belong to this chunk
+  handover::Pending<DraftState> draft;   // sc_streams_set_draft: the draft state that belongs to this chunk
+  handover::Pending<LevelState> level;   // sc_stream_set_input_format: the input level up to and including this chunk
 };
 
 // hypotheses of a stream's last complete chunk, copied aside when later chunks of the stream may go on decoding
@@ -207,6 +198,9 @@ int dalloc(T **p, size_t n) {
   const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
   HIP_TRY(hipMalloc((void **)p, bytes));
   HIP_TRY(hipMemset(*p, 0, bytes));
+  // (a fill of device memory may return before it has run, and the engine's streams are not ordered behind the null
+  // stream: without the wait the zeros can land on what a first launch has already written there)
+  HIP_TRY(hipStreamSynchronize(nullptr));
   return SC_OK;
 }
 
@@ -244,16 +238,15 @@ struct EncGroup {
   int n_fe = 0, max_keep = 0;
   EncPlan P;
   std::vector<int32_t> ctc_rows, kv_src, kv_dst;   // eager projections of the frames the group emits
-  // activity option: per stream the span [t0, t1) of ctc_rows (one sc_ctc_activity job each, in this order); epoch = the
-  // stream's reset count when the span was planned (a state that arrives after a reset is dropped)
-  // (recorded when the activity or the spotting option is on; act / spot: which of the two scans it.  The spotting
-  // launch has the same job order; spot_epoch / spot_restart / mask are its own, and so are draft / draft_epoch /
-  // draft_restart of the draft launch)
-  struct ActSpan {
-    int s, t0, t1; long epoch; bool restart; bool act, spot; long spot_epoch; bool spot_restart; uint64_t mask;
-    bool draft; long draft_epoch; bool draft_restart;
+  // side-state options (activity, spotting, draft): per stream the span [t0, t1) of ctc_rows that every option which is on
+  // scans, one job each and in this order in every option's launch; mask: the stream's enabled phrases (spotting);
+  // opt[o]: the span as option o planned it (every span of a group carries the same options)
+  struct Span {
+    int s = 0, t0 = 0, t1 = 0;
+    uint64_t mask = 0;
+    handover::Plan opt[N_OPT];
   };
-  std::vector<ActSpan> act;
+  std::vector<Span> spans;
   bool same_rows = true;
   std::vector<int> streams;                  // streams with work in this group (each at most once)
   bool empty() const { return !n_fe && !P.n_conv; }
@@ -345,9 +338,7 @@ struct sc_streams {
   sc_input_level_t *lvl_out_host = nullptr, *lvl_out_dev = nullptr;       // [N_STAGE][S] host-mapped: the jobs' levels-after
   struct LvlSpan { int s; long epoch, ticket; };
   std::vector<LvlSpan> stage_lvl[N_STAGE];   // the decode jobs of the slot's latest admission, until their levels are collected
-  std::vector<LevelVal> lvl_known, lvl_rep;  // per stream: after the latest COLLECTED job / of the last reported chunk
-  std::vector<long> lvl_pending, lvl_epoch;  // per stream: ticket of its latest job not collected yet (0: none) / resets so far
-  std::vector<char> lvl_fresh;               // per stream: the next job starts the utterance
+  handover::Track<LevelState> lvl;           // keyed by ticket: `pending` is the stream's latest job not collected yet
   long lvl_ticket = 0;
   // ---- batched hypothesis read-back (sc_get_hyps_batch): pack kernel -> one D2H into pinned memory -------------------
   int32_t *pack_dev = nullptr, *pack_host = nullptr, *pjobs_host = nullptr, *pjobs_dev = nullptr;
@@ -366,11 +357,7 @@ struct sc_streams {
   double *act_track = nullptr;    // device [S][TCAP]: p_blank per CTC row
   sc_ctc_activity_job *act_jobs_host = nullptr, *act_jobs_dev = nullptr;   // [N_ARENA][S]: the job table of a group's launch
   int32_t *act_out_host = nullptr, *act_out_dev = nullptr;                 // [N_ARENA][S][6] host-mapped: the jobs' states-after
-  std::vector<ActVal> act_known;  // per stream: the state after the latest RETIRED group that scanned it
-  std::vector<ActVal> act_rep;    // per stream: the state of the last reported chunk (sc_stream_activity)
-  std::vector<long> act_pending;  // per stream: the latest group that carries a span of it (0: none since the reset)
-  std::vector<long> act_epoch;    // per stream: resets so far
-  std::vector<char> act_fresh;    // per stream: the next span starts the utterance
+  handover::Track<ActState> act;  // keyed by encoder group: `known` is the state after the latest RETIRED group that scanned the stream
   // ---- phrase spotting (sc_streams_set_phrases): everything below is allocated when a phrase set is first given ----------
   bool spot_on = false;
   int spot_P = 0;
@@ -382,9 +369,7 @@ struct sc_streams {
   sc_spot_event *spot_events = nullptr;   // device [S][SC_SPOT_MAX_EVENTS]
   sc_ctc_spot_job *spot_jobs_host = nullptr, *spot_jobs_dev = nullptr;   // [N_ARENA][S]: the job table of a group's launch
   int32_t *spot_out_host = nullptr, *spot_out_dev = nullptr;             // [N_ARENA][S][2] host-mapped: the jobs' counters-after
-  std::vector<SpotVal> spot_known, spot_rep;   // per stream: after the latest RETIRED group / of the last reported chunk
-  std::vector<long> spot_pending, spot_epoch;  // per stream: as act_pending / act_epoch
-  std::vector<char> spot_fresh;                // per stream: the next span starts the utterance
+  handover::Track<SpotState> spot;             // keyed by encoder group, as act
   std::vector<uint64_t> spot_mask;             // per stream: enabled phrases
   // ---- draft transcript (sc_streams_set_draft): everything below is allocated when the option is first switched on --------
   bool draft_on = false;
@@ -392,9 +377,7 @@ struct sc_streams {
   sc_draft_token *draft_tokens = nullptr;   // device [S][TCAP]: a frame opens at most one token, so the store cannot overflow
   sc_ctc_draft_job *draft_jobs_host = nullptr, *draft_jobs_dev = nullptr;   // [N_ARENA][S]: the job table of a group's launch
   sc_draft_t *draft_out_host = nullptr, *draft_out_dev = nullptr;           // [N_ARENA][S] host-mapped: the jobs' states-after
-  std::vector<DraftVal> draft_known, draft_rep;   // per stream: after the latest RETIRED group / of the last reported chunk
-  std::vector<long> draft_pending, draft_epoch;   // per stream: as act_pending / act_epoch
-  std::vector<char> draft_fresh;                  // per stream: the next span starts the utterance
+  handover::Track<DraftState> draft;              // keyed by encoder group, as act
   // ---- tick engine -----------------------------------------------------------------------------------------------------
   std::vector<St> st;
   std::vector<Run> run;
@@ -469,6 +452,17 @@ struct sc_streams {
     HIP_TRY(hipHostMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)));
     owned_host.push_back(*p);
     memset(*p, 0, std::max<size_t>(n, 1) * sizeof(T));
+    return SC_OK;
+  }
+  template <typename T>
+  int halloc_mapped(T **host, T **dev, size_t n, const char *who, const char *what) {   // ... and its device view
+    RC_TRY(halloc(host, n));
+    void *dv = nullptr;
+    if (hipHostGetDevicePointer(&dv, *host, 0) != hipSuccess || !dv) {
+      sc_set_error("%s: the pinned %s are not visible to the device", who, what);
+      return SC_ERR_LAUNCH;
+    }
+    *dev = (T *)dv;
     return SC_OK;
   }
   int32_t *ctrl_host() { return ctrlmap_host; }              // [S][8]
@@ -587,30 +581,12 @@ void reset_stream(sc_streams *b, int s) {
   b->run[s] = Run();
   b->bq[s].clear();
   b->snap[s] = Snap();
-  if (!b->act_epoch.empty()) {   // activity: the next span starts over; a state of the old utterance still in flight is dropped
-    b->act_epoch[s]++;
-    b->act_known[s] = b->act_rep[s] = ActVal();
-    b->act_pending[s] = 0;
-    b->act_fresh[s] = 1;
-  }
-  if (!b->spot_epoch.empty()) {   // spotting: the same
-    b->spot_epoch[s]++;
-    b->spot_known[s] = b->spot_rep[s] = SpotVal();
-    b->spot_pending[s] = 0;
-    b->spot_fresh[s] = 1;
-  }
-  if (!b->draft_epoch.empty()) {   // draft: the same
-    b->draft_epoch[s]++;
-    b->draft_known[s] = b->draft_rep[s] = DraftVal();
-    b->draft_pending[s] = 0;
-    b->draft_fresh[s] = 1;
-  }
-  if (!b->lvl_epoch.empty()) {   // input level: the same
-    b->lvl_epoch[s]++;
-    b->lvl_known[s] = b->lvl_rep[s] = LevelVal();
-    b->lvl_pending[s] = 0;
-    b->lvl_fresh[s] = 1;
-  }
+  // the side states: the next span starts over; a state of the old utterance still in flight is dropped (no-ops for an
+  // option that was never switched on)
+  b->act.restart(s);
+  b->spot.restart(s);
+  b->draft.restart(s);
+  b->lvl.restart(s);
   init_hyp(b, s);
 }
 
@@ -990,18 +966,7 @@ int collect_levels(sc_streams *b, int slot, bool wait) {
   }
   for (size_t i = 0; i < spans.size(); ++i) {
     const sc_streams::LvlSpan &sp = spans[i];
-    if (sp.epoch != b->lvl_epoch[sp.s]) continue;   // the stream has been reset since
-    LevelVal k;
-    k.ticket = sp.ticket;
-    k.v = b->lvl_out_host[(size_t)slot * b->S + i];
-    if (sp.ticket > b->lvl_known[sp.s].ticket) b->lvl_known[sp.s] = k;   // (slots are collected in any order: the latest job counts)
-    auto fill = [&](LevelVal &a) {
-      if (!a.ready && a.ticket == sp.ticket) a = k;
-    };
-    fill(b->job[sp.s].level);
-    for (Job &j : b->ahead[sp.s]) fill(j.level);
-    fill(b->lvl_rep[sp.s]);
-    if (b->lvl_pending[sp.s] == sp.ticket) b->lvl_pending[sp.s] = 0;
+    b->lvl.deliver(sp.s, sp.ticket, sp.epoch, b->lvl_out_host[(size_t)slot * b->S + i], b->job[sp.s], b->ahead[sp.s], &Job::level);
   }
   spans.clear();
   return SC_OK;
@@ -1021,45 +986,24 @@ int retire_groups(sc_streams *b) {
       sc_set_error("encoder group %ld failed: %s", g->gen, hipGetErrorString(q));
       return SC_ERR_LAUNCH;
     }
-    // activity: the states-after of the group's jobs -> the chunks they belong to (open, or reported in the meantime)
-    for (size_t i = 0; i < g->act.size(); ++i) {
-      const EncGroup::ActSpan &sp = g->act[i];
-      if (sp.spot && sp.spot_epoch == b->spot_epoch[sp.s]) {   // spotting: the counters-after, handed over the same way
-        SpotVal &k = b->spot_known[sp.s];
-        k.ready = true;
-        k.gen = g->gen;
-        memcpy(k.v, b->spot_out_host + ((size_t)g->slot * b->S + i) * 2, sizeof k.v);
-        auto fill = [&](SpotVal &a) {
-          if (!a.ready && a.gen == g->gen) a = k;
-        };
-        fill(b->job[sp.s].spot);
-        for (Job &j : b->ahead[sp.s]) fill(j.spot);
-        fill(b->spot_rep[sp.s]);
+    // side states: the states-after of the group's jobs -> the chunks they belong to (open, or reported in the meantime)
+    for (size_t i = 0; i < g->spans.size(); ++i) {
+      const EncGroup::Span &sp = g->spans[i];
+      const int s = sp.s;
+      const size_t o = (size_t)g->slot * b->S + i;
+      if (sp.opt[OPT_ACT].on) {
+        ActState v;
+        v.T = sp.t1;
+        memcpy(v.v, b->act_out_host + o * 6, sizeof v.v);
+        b->act.deliver(s, g->gen, sp.opt[OPT_ACT].epoch, v, b->job[s], b->ahead[s], &Job::act);
       }
-      if (sp.draft && sp.draft_epoch == b->draft_epoch[sp.s]) {   // draft: the state-after, handed over the same way
-        DraftVal &k = b->draft_known[sp.s];
-        k.ready = true;
-        k.gen = g->gen;
-        k.v = b->draft_out_host[(size_t)g->slot * b->S + i];
-        auto fill = [&](DraftVal &a) {
-          if (!a.ready && a.gen == g->gen) a = k;
-        };
-        fill(b->job[sp.s].draft);
-        for (Job &j : b->ahead[sp.s]) fill(j.draft);
-        fill(b->draft_rep[sp.s]);
+      if (sp.opt[OPT_SPOT].on) {
+        SpotState v;
+        memcpy(v.v, b->spot_out_host + o * 2, sizeof v.v);
+        b->spot.deliver(s, g->gen, sp.opt[OPT_SPOT].epoch, v, b->job[s], b->ahead[s], &Job::spot);
       }
-      if (!sp.act || sp.epoch != b->act_epoch[sp.s]) continue;
-      ActVal &k = b->act_known[sp.s];
-      k.ready = true;
-      k.gen = g->gen;
-      k.T = sp.t1;
-      memcpy(k.v, b->act_out_host + ((size_t)g->slot * b->S + i) * 6, sizeof k.v);
-      auto fill = [&](ActVal &a) {
-        if (!a.ready && a.gen == g->gen) a = k;
-      };
-      fill(b->job[sp.s].act);
-      for (Job &j : b->ahead[sp.s]) fill(j.act);
-      fill(b->act_rep[sp.s]);
+      if (sp.opt[OPT_DRAFT].on)
+        b->draft.deliver(s, g->gen, sp.opt[OPT_DRAFT].epoch, DraftState{b->draft_out_host[o]}, b->job[s], b->ahead[s], &Job::draft);
     }
     b->gen_done = g->gen;
     b->slot_gen[g->slot] = 0;
@@ -1079,6 +1023,23 @@ int wait_group(sc_streams *b, long gen) {
   return retire_groups(b);
 }
 
+// The launch of one side-state option over the spans of a group: job i of slot g.slot's table is filled from span i (at: its
+// index in the [N_ARENA][S] tables, where its state-after slot is too), the n jobs go to the device, one launch reads them.
+template <typename J, typename Fill>
+int launch_spans(sc_streams *b, const EncGroup &g, int opt, const char *name, J *jobs_host, J *jobs_dev,
+                 int (*launch)(const J *, int, void *), Fill fill) {
+  if (g.spans.empty() || !g.spans[0].opt[opt].on) return SC_OK;   // (every span of a group carries the same options)
+  const int n = (int)g.spans.size();
+  if (n > b->S) {   // (a group holds a stream at most once)
+    sc_set_error("%s: %d spans in a group of a batch of %d streams (internal error)", name, n, b->S);
+    return SC_ERR_ARG;
+  }
+  const size_t o = (size_t)g.slot * b->S;
+  for (int i = 0; i < n; ++i) fill(jobs_host[o + i], g.spans[i], o + i);
+  HIP_TRY(hipMemcpyAsync(jobs_dev + o, jobs_host + o, (size_t)n * sizeof(J), hipMemcpyHostToDevice, b->es));
+  return launch(jobs_dev + o, n, b->es);
+}
+
 // CTC rows and cross-attention K|V rows of the frames a group emits (extend_scorers' encoder-side half,
 // beam_search.py:403-464; scorers.py:342-350 stores RAW logits - the log-softmax of a stream's first block, quirk
 // A1, is applied when that block starts).  They depend on the encoder output only, so they belong to the encoder
@@ -1092,84 +1053,47 @@ int project_rows(sc_streams *b, EncGroup &g) {
     RC_TRY(b->itensor(g.ctc_rows, &ar));
     RC_TRY(sc_gemm(b->enc, ar, d, e->f("ctc_w"), e->f("ctc_b"), const_cast<float *>(b->sb.ctcx), ar, V, (int)g.ctc_rows.size(),
                    V, d, b->gemm_flags, 0, b->es));
-    if (!g.act.empty() && g.act[0].act) {   // (every span of a group carries the same options)
-      // activity: ONE launch for the group, behind the projection of the rows it reads (raw logits: the in-place
-      // log-softmax of a first block runs on the decode stream behind this group's event)
-      const int n = (int)g.act.size();
-      if (n > b->S) {   // (a group holds a stream at most once)
-        sc_set_error("activity: %d spans in a group of a batch of %d streams (internal error)", n, b->S);
-        return SC_ERR_ARG;
-      }
-      const size_t o = (size_t)g.slot * b->S;
-      for (int i = 0; i < n; ++i) {
-        const EncGroup::ActSpan &sp = g.act[i];
-        sc_ctc_activity_job &j = b->act_jobs_host[o + i];
-        j.table = b->sb.ctcx + (size_t)sp.s * b->TCAP * V;
-        j.state = b->act_state + (size_t)sp.s * 6;
-        j.track = b->act_track + (size_t)sp.s * b->TCAP;
-        j.state_after = b->act_out_dev + (o + i) * 6;
-        j.stride = V;
-        j.thr = b->act_thr;
-        j.V = V; j.blank = c.blank_id; j.t0 = sp.t0; j.t1 = sp.t1;
-        j.restart = sp.restart ? 1 : 0;
-        j.reserved = 0;
-      }
-      HIP_TRY(hipMemcpyAsync(b->act_jobs_dev + o, b->act_jobs_host + o, (size_t)n * sizeof(sc_ctc_activity_job),
-                             hipMemcpyHostToDevice, b->es));
-      RC_TRY(sc_ctc_activity(b->act_jobs_dev + o, n, b->es));
-    }
-    if (!g.act.empty() && g.act[0].spot) {
-      // spotting: ONE launch for the group, in the same place and over the same spans
-      const int n = (int)g.act.size();
-      if (n > b->S) {
-        sc_set_error("spotting: %d spans in a group of a batch of %d streams (internal error)", n, b->S);
-        return SC_ERR_ARG;
-      }
-      const size_t o = (size_t)g.slot * b->S;
-      for (int i = 0; i < n; ++i) {
-        const EncGroup::ActSpan &sp = g.act[i];
-        sc_ctc_spot_job &j = b->spot_jobs_host[o + i];
-        j.table = b->sb.ctcx + (size_t)sp.s * b->TCAP * V;
-        j.labels = b->spot_labels; j.lens = b->spot_lens; j.floors = b->spot_floors;
-        j.counters = b->spot_counters + (size_t)sp.s * 2;
-        j.values = b->spot_values + (size_t)sp.s * SC_SPOT_MAX_PHRASES * SC_SPOT_STATES;
-        j.starts = b->spot_starts + (size_t)sp.s * SC_SPOT_MAX_PHRASES * SC_SPOT_STATES;
-        j.events = b->spot_events + (size_t)sp.s * SC_SPOT_MAX_EVENTS;
-        j.state_after = b->spot_out_dev + (o + i) * 2;
-        j.stride = V;
-        j.mask = sp.mask;
-        j.V = V; j.blank = c.blank_id; j.t0 = sp.t0; j.t1 = sp.t1;
-        j.restart = sp.spot_restart ? 1 : 0;
-        j.P = b->spot_P;
-      }
-      HIP_TRY(hipMemcpyAsync(b->spot_jobs_dev + o, b->spot_jobs_host + o, (size_t)n * sizeof(sc_ctc_spot_job),
-                             hipMemcpyHostToDevice, b->es));
-      RC_TRY(sc_ctc_spot(b->spot_jobs_dev + o, n, b->es));
-    }
-    if (!g.act.empty() && g.act[0].draft) {
-      // draft: ONE launch for the group, in the same place and over the same spans
-      const int n = (int)g.act.size();
-      if (n > b->S) {
-        sc_set_error("draft: %d spans in a group of a batch of %d streams (internal error)", n, b->S);
-        return SC_ERR_ARG;
-      }
-      const size_t o = (size_t)g.slot * b->S;
-      for (int i = 0; i < n; ++i) {
-        const EncGroup::ActSpan &sp = g.act[i];
-        sc_ctc_draft_job &j = b->draft_jobs_host[o + i];
-        j.table = b->sb.ctcx + (size_t)sp.s * b->TCAP * V;
-        j.state = b->draft_state + sp.s;
-        j.tokens = b->draft_tokens + (size_t)sp.s * b->TCAP;
-        j.state_after = b->draft_out_dev + (o + i);
-        j.stride = V;
-        j.V = V; j.blank = c.blank_id; j.t0 = sp.t0; j.t1 = sp.t1;
-        j.restart = sp.draft_restart ? 1 : 0;
-        j.capacity = b->TCAP;
-      }
-      HIP_TRY(hipMemcpyAsync(b->draft_jobs_dev + o, b->draft_jobs_host + o, (size_t)n * sizeof(sc_ctc_draft_job),
-                             hipMemcpyHostToDevice, b->es));
-      RC_TRY(sc_ctc_draft(b->draft_jobs_dev + o, n, b->es));
-    }
+    // side states: ONE launch per option for the group, behind the projection of the rows it reads (raw logits: the
+    // in-place log-softmax of a first block runs on the decode stream behind this group's event)
+    const int blank = c.blank_id;
+    RC_TRY(launch_spans(b, g, OPT_ACT, "activity", b->act_jobs_host, b->act_jobs_dev, sc_ctc_activity,
+                        [=](sc_ctc_activity_job &j, const EncGroup::Span &sp, size_t at) {
+                          j.table = b->sb.ctcx + (size_t)sp.s * b->TCAP * V;
+                          j.state = b->act_state + (size_t)sp.s * 6;
+                          j.track = b->act_track + (size_t)sp.s * b->TCAP;
+                          j.state_after = b->act_out_dev + at * 6;
+                          j.stride = V;
+                          j.thr = b->act_thr;
+                          j.V = V; j.blank = blank; j.t0 = sp.t0; j.t1 = sp.t1;
+                          j.restart = sp.opt[OPT_ACT].restart ? 1 : 0;
+                          j.reserved = 0;
+                        }));
+    RC_TRY(launch_spans(b, g, OPT_SPOT, "spotting", b->spot_jobs_host, b->spot_jobs_dev, sc_ctc_spot,
+                        [=](sc_ctc_spot_job &j, const EncGroup::Span &sp, size_t at) {
+                          j.table = b->sb.ctcx + (size_t)sp.s * b->TCAP * V;
+                          j.labels = b->spot_labels; j.lens = b->spot_lens; j.floors = b->spot_floors;
+                          j.counters = b->spot_counters + (size_t)sp.s * 2;
+                          j.values = b->spot_values + (size_t)sp.s * SC_SPOT_MAX_PHRASES * SC_SPOT_STATES;
+                          j.starts = b->spot_starts + (size_t)sp.s * SC_SPOT_MAX_PHRASES * SC_SPOT_STATES;
+                          j.events = b->spot_events + (size_t)sp.s * SC_SPOT_MAX_EVENTS;
+                          j.state_after = b->spot_out_dev + at * 2;
+                          j.stride = V;
+                          j.mask = sp.mask;
+                          j.V = V; j.blank = blank; j.t0 = sp.t0; j.t1 = sp.t1;
+                          j.restart = sp.opt[OPT_SPOT].restart ? 1 : 0;
+                          j.P = b->spot_P;
+                        }));
+    RC_TRY(launch_spans(b, g, OPT_DRAFT, "draft", b->draft_jobs_host, b->draft_jobs_dev, sc_ctc_draft,
+                        [=](sc_ctc_draft_job &j, const EncGroup::Span &sp, size_t at) {
+                          j.table = b->sb.ctcx + (size_t)sp.s * b->TCAP * V;
+                          j.state = b->draft_state + sp.s;
+                          j.tokens = b->draft_tokens + (size_t)sp.s * b->TCAP;
+                          j.state_after = b->draft_out_dev + at;
+                          j.stride = V;
+                          j.V = V; j.blank = blank; j.t0 = sp.t0; j.t1 = sp.t1;
+                          j.restart = sp.opt[OPT_DRAFT].restart ? 1 : 0;
+                          j.capacity = b->TCAP;
+                        }));
   }
   if (!g.kv_dst.empty()) {
     if (!g.same_rows || !ar) RC_TRY(b->itensor(g.kv_src, &ar));
@@ -1270,7 +1194,7 @@ void merge_group(sc_streams *b, EncGroup &dst, EncGroup &src) {
   dst.n_fe += src.n_fe;
   dst.max_keep = std::max(dst.max_keep, src.max_keep);
   cat(dst.ctc_rows, src.ctc_rows); cat(dst.kv_src, src.kv_src); cat(dst.kv_dst, src.kv_dst);
-  dst.act.insert(dst.act.end(), src.act.begin(), src.act.end());
+  dst.spans.insert(dst.spans.end(), src.spans.begin(), src.spans.end());
   dst.same_rows = dst.same_rows && src.same_rows;
   dst.streams.insert(dst.streams.end(), src.streams.begin(), src.streams.end());
 }
@@ -1820,11 +1744,11 @@ int admit(sc_streams *b, std::vector<Chunk> chunks, bool features, bool defer, s
   std::vector<sc_streams::LvlSpan> lvl_spans;
   for (size_t i = 0; i < g->pcm_jobs.size(); ++i) {
     const EncGroup::PcmSpan &sp = g->pcm_spans[i];
-    g->pcm_jobs[i].restart = b->lvl_fresh[sp.s] ? 1 : 0;
-    b->lvl_fresh[sp.s] = sp.fin ? 1 : 0;   // a final chunk ends the utterance: the next job starts over
+    const handover::Plan p = b->lvl.plan(sp.s, sp.fin);   // a final chunk ends the utterance: the next job starts over
+    g->pcm_jobs[i].restart = p.restart ? 1 : 0;
     const long ticket = ++b->lvl_ticket;
-    lvl_spans.push_back({sp.s, b->lvl_epoch[sp.s], ticket});
-    b->lvl_pending[sp.s] = ticket;
+    lvl_spans.push_back({sp.s, p.epoch, ticket});
+    b->lvl.carry(sp.s, ticket);
   }
   {
     const int rc = stage_copy(b, *g);
@@ -1832,7 +1756,7 @@ int admit(sc_streams *b, std::vector<Chunk> chunks, bool features, bool defer, s
   }
   if (!lvl_spans.empty()) b->stage_lvl[sslot] = lvl_spans;   // (behind the slot's event: collect_levels reads them when it has fired)
   // eager projections: CTC rows / cross-attention K|V rows of every frame this admission emits
-  std::vector<int> act_new;   // activity: the streams this admission scans
+  std::vector<int> act_new;   // side states: the streams this admission scans
   for (auto &ch : chunks) {
     St &st = b->st[ch.s];
     const int t0 = snap[ch.s].T_enc, t1 = st.T_enc;
@@ -1842,24 +1766,15 @@ int admit(sc_streams *b, std::vector<Chunk> chunks, bool features, bool defer, s
     g->same_rows = g->same_rows && c0 == k0;
     for (int t = c0; t < t1; ++t) g->ctc_rows.push_back(ch.s * b->TCAP + t);
     if ((b->act_on || b->spot_on || b->draft_on) && c0 < t1) {
-      EncGroup::ActSpan sp = {ch.s, c0, t1, 0, false, b->act_on, b->spot_on, 0, false, 0, b->draft_on, 0, false};
-      if (b->act_on) {
-        sp.epoch = b->act_epoch[ch.s];
-        sp.restart = b->act_fresh[ch.s] != 0;
-        b->act_fresh[ch.s] = 0;
-      }
+      EncGroup::Span sp;
+      sp.s = ch.s; sp.t0 = c0; sp.t1 = t1;
+      if (b->act_on) sp.opt[OPT_ACT] = b->act.plan(ch.s);
       if (b->spot_on) {
-        sp.spot_epoch = b->spot_epoch[ch.s];
-        sp.spot_restart = b->spot_fresh[ch.s] != 0;
+        sp.opt[OPT_SPOT] = b->spot.plan(ch.s);
         sp.mask = b->spot_mask[ch.s];
-        b->spot_fresh[ch.s] = 0;
       }
-      if (b->draft_on) {
-        sp.draft_epoch = b->draft_epoch[ch.s];
-        sp.draft_restart = b->draft_fresh[ch.s] != 0;
-        b->draft_fresh[ch.s] = 0;
-      }
-      g->act.push_back(sp);
+      if (b->draft_on) sp.opt[OPT_DRAFT] = b->draft.plan(ch.s);
+      g->spans.push_back(sp);
       act_new.push_back(ch.s);
     }
     for (int t = k0; t < t1; ++t) {
@@ -1933,45 +1848,16 @@ int admit(sc_streams *b, std::vector<Chunk> chunks, bool features, bool defer, s
     j.seq = seq_of.at(chunks[k].s);
     j.fin = chunks[k].fin;
     j.started = b->st[chunks[k].s].started;
-    if (b->act_on) {
+    {
+      // the side states the chunk starts with (handover.h).  This admission carries a span of the stream: its state comes
+      // with the group `gen`; no span of its own: the predecessor's state, which may still be in flight.  The input level
+      // comes with the ticket of the stream's latest decode job (named above), its own if it has one.
       const int s = chunks[k].s;
-      // this admission carries a span of the stream: its state comes with the group `gen`
-      if (gen && std::find(act_new.begin(), act_new.end(), s) != act_new.end()) b->act_pending[s] = gen;
-      if (b->act_pending[s] > b->gen_done) {   // (no span of its own: the predecessor's state, which may still be in flight)
-        j.act.ready = false;
-        j.act.gen = b->act_pending[s];
-      } else {
-        j.act = b->act_known[s];
-      }
-    }
-    if (b->spot_on) {   // (the same hand-over for the spotting counters)
-      const int s = chunks[k].s;
-      if (gen && std::find(act_new.begin(), act_new.end(), s) != act_new.end()) b->spot_pending[s] = gen;
-      if (b->spot_pending[s] > b->gen_done) {
-        j.spot.ready = false;
-        j.spot.gen = b->spot_pending[s];
-      } else {
-        j.spot = b->spot_known[s];
-      }
-    }
-    if (b->draft_on) {   // (and for the draft state)
-      const int s = chunks[k].s;
-      if (gen && std::find(act_new.begin(), act_new.end(), s) != act_new.end()) b->draft_pending[s] = gen;
-      if (b->draft_pending[s] > b->gen_done) {
-        j.draft.ready = false;
-        j.draft.gen = b->draft_pending[s];
-      } else {
-        j.draft = b->draft_known[s];
-      }
-    }
-    if (b->lvl_state) {   // (and for the input level: the ticket of the stream's latest decode job, its own if it has one)
-      const int s = chunks[k].s;
-      if (b->lvl_pending[s]) {
-        j.level.ready = false;
-        j.level.ticket = b->lvl_pending[s];
-      } else {
-        j.level = b->lvl_known[s];
-      }
+      const long carrier = std::find(act_new.begin(), act_new.end(), s) != act_new.end() ? gen : 0;
+      if (b->act_on) j.act = b->act.admit(s, carrier, b->gen_done);
+      if (b->spot_on) j.spot = b->spot.admit(s, carrier, b->gen_done);
+      if (b->draft_on) j.draft = b->draft.admit(s, carrier, b->gen_done);
+      if (b->lvl_state) j.level = b->lvl.admit(s, 0, 0);
     }
     if (b->job[chunks[k].s].open) b->ahead[chunks[k].s].push_back(j);   // behind the stream's outstanding chunk(s)
     else b->job[chunks[k].s] = j;
@@ -2532,18 +2418,8 @@ extern "C" int sc_stream_set_input_format(sc_streams *b, int stream, int format,
     if (!b->stageb_host) RC_TRY(b->halloc(&b->stageb_host, b->stageb_cap * N_STAGE));
     if (!b->pcmjobs_dev) RC_TRY(b->alloc(&b->pcmjobs_dev, S * N_STAGE));
     if (!b->pcmjobs_host) RC_TRY(b->halloc(&b->pcmjobs_host, S * N_STAGE));
-    if (!b->lvl_out_host) RC_TRY(b->halloc(&b->lvl_out_host, S * N_STAGE));
-    void *dv = nullptr;
-    if (hipHostGetDevicePointer(&dv, b->lvl_out_host, 0) != hipSuccess || !dv) {
-      sc_set_error("sc_stream_set_input_format: the pinned level slots are not visible to the device");
-      return SC_ERR_LAUNCH;
-    }
-    b->lvl_out_dev = (sc_input_level_t *)dv;
-    b->lvl_known.assign(S, LevelVal());
-    b->lvl_rep.assign(S, LevelVal());
-    b->lvl_pending.assign(S, 0);
-    b->lvl_epoch.assign(S, 0);
-    b->lvl_fresh.assign(S, 1);
+    if (!b->lvl_out_dev) RC_TRY(b->halloc_mapped(&b->lvl_out_host, &b->lvl_out_dev, S * N_STAGE, __func__, "level slots"));
+    b->lvl.init(b->S);
     RC_TRY(b->alloc(&b->lvl_state, S));   // (last: its presence says that all of the above is in place)
   }
   St &st = b->st[stream];
@@ -2570,12 +2446,12 @@ extern "C" int sc_stream_input_level(sc_streams *b, int stream, sc_input_level_t
   SC_API_BEGIN
   *out = sc_input_level_t{0, 0, 0, 0, 0};
   if (!b->lvl_state) return SC_OK;
-  LevelVal &r = b->lvl_rep[stream];
+  const handover::Pending<LevelState> &r = b->lvl.rep[stream];
   if (!r.ready) {
     HIP_TRY(hipSetDevice(b->eng->device));
     for (int i = 0; i < N_STAGE && !r.ready; ++i)
       for (const sc_streams::LvlSpan &sp : b->stage_lvl[i])
-        if (sp.s == stream && sp.ticket == r.ticket) {
+        if (sp.s == stream && sp.ticket == r.key) {
           RC_TRY(collect_levels(b, i, true));
           break;
         }
@@ -2684,10 +2560,12 @@ int report_chunk(sc_streams *b, int s) {
   Job &j = b->job[s];
   const int status = j.fault ? j.fault : j.has_out;
   if (j.fault && !j.dropped) reset_stream(b, s);   // (fault_msg[s] keeps the message: sc_stream_last_error)
-  if (b->act_on && !j.fault) b->act_rep[s] = j.act;
-  if (b->spot_on && !j.fault) b->spot_rep[s] = j.spot;
-  if (b->draft_on && !j.fault) b->draft_rep[s] = j.draft;
-  if (b->lvl_state && !j.fault) b->lvl_rep[s] = j.level;
+  if (!j.fault) {   // the side states of the chunk are what the readers return from now on
+    if (b->act_on) b->act.report(s, j.act);
+    if (b->spot_on) b->spot.report(s, j.spot);
+    if (b->draft_on) b->draft.report(s, j.draft);
+    if (b->lvl_state) b->lvl.report(s, j.level);
+  }
   if (b->snap[s].valid && b->snap[s].seq == j.seq) b->snap[s].reported = true;   // handed out: free at the next sc_poll
   b->done_at[s] = 0;
   if (b->ahead[s].empty()) j = Job();
@@ -3451,43 +3329,31 @@ extern "C" int sc_streams_set_activity(sc_streams *b, int on, double blank_thres
     RC_TRY(b->alloc(&b->act_track, S * b->TCAP));
     RC_TRY(b->alloc(&b->act_jobs_dev, S * N_ARENA));
     RC_TRY(b->halloc(&b->act_jobs_host, S * N_ARENA));
-    RC_TRY(b->halloc(&b->act_out_host, S * N_ARENA * 6));
-    void *dv = nullptr;
-    if (hipHostGetDevicePointer(&dv, b->act_out_host, 0) != hipSuccess || !dv) {
-      sc_set_error("sc_streams_set_activity: the pinned state slots are not visible to the device");
-      return SC_ERR_LAUNCH;
-    }
-    b->act_out_dev = (int32_t *)dv;
-    b->act_known.assign(S, ActVal());
-    b->act_rep.assign(S, ActVal());
-    b->act_pending.assign(S, 0);
-    b->act_epoch.assign(S, 0);
-    b->act_fresh.assign(S, 1);
+    RC_TRY(b->halloc_mapped(&b->act_out_host, &b->act_out_dev, S * N_ARENA * 6, __func__, "state slots"));
+    b->act.init(b->S);
   }
-  // every stream starts over: a stream in mid-utterance is scanned from its next frame on
-  for (int s = 0; s < b->S; ++s) {
-    b->act_epoch[s]++;
-    b->act_known[s] = b->act_rep[s] = ActVal();
-    b->act_pending[s] = 0;
-    b->act_fresh[s] = 1;
-  }
+  b->act.restart_all();   // every stream starts over: a stream in mid-utterance is scanned from its next frame on
   b->act_thr = blank_threshold;
   b->act_on = true;
   return SC_OK;
   SC_API_END
 }
 
-// the state of the stream's last reported chunk, complete: its encoder group may still be held back or in flight
-static int activity_ready(sc_streams *b, int s) {
-  ActVal &r = b->act_rep[s];
+// the side state of the stream's last reported chunk, complete: its encoder group may still be held back or in flight
+// (what: "activity state", whose: "its" - the words of the error text)
+template <typename V>
+static int side_ready(sc_streams *b, const handover::Pending<V> &r, int s, const char *what, const char *whose) {
   if (r.ready) return SC_OK;
-  RC_TRY(wait_group(b, r.gen));
+  RC_TRY(wait_group(b, r.key));
   if (!r.ready) {
-    sc_set_error("activity state of stream %d did not arrive with its encoder group (internal error)", s);
+    sc_set_error("%s of stream %d did not arrive with %s encoder group (internal error)", what, s, whose);
     return SC_ERR_LAUNCH;
   }
   return SC_OK;
 }
+static int activity_ready(sc_streams *b, int s) { return side_ready(b, b->act.rep[s], s, "activity state", "its"); }
+static int spot_ready(sc_streams *b, int s) { return side_ready(b, b->spot.rep[s], s, "spotting counters", "their"); }
+static int draft_ready(sc_streams *b, int s) { return side_ready(b, b->draft.rep[s], s, "draft state", "its"); }
 
 extern "C" int sc_stream_activity(sc_streams *b, int stream, sc_activity_t *out) {
   SC_CHECK_ARG(b && out && stream >= 0 && stream < b->S, "bad arguments");
@@ -3495,7 +3361,7 @@ extern "C" int sc_stream_activity(sc_streams *b, int stream, sc_activity_t *out)
   SC_CHECK_ARG(b->act_on, "the activity option is off (sc_streams_set_activity)");
   HIP_TRY(hipSetDevice(b->eng->device));
   RC_TRY(activity_ready(b, stream));
-  const int32_t *v = b->act_rep[stream].v;
+  const int32_t *v = b->act.rep[stream].v.v;
   out->n_frames = v[0]; out->n_speech = v[1]; out->n_bad = v[2];
   out->first_speech = v[3]; out->last_speech = v[4]; out->trail_silence = v[5];
   return SC_OK;
@@ -3508,7 +3374,7 @@ extern "C" int sc_streams_read_activity(sc_streams *b, int stream, double *host,
   SC_CHECK_ARG(b->act_on, "the activity option is off (sc_streams_set_activity)");
   HIP_TRY(hipSetDevice(b->eng->device));
   RC_TRY(activity_ready(b, stream));
-  const int T = std::min(b->act_rep[stream].T, max_frames);
+  const int T = std::min(b->act.rep[stream].v.T, max_frames);
   if (host && T > 0) {   // (the group that wrote these entries has been retired; later groups write behind them)
     HIP_TRY(hipMemcpyAsync(host, b->act_track + (size_t)stream * b->TCAP, (size_t)T * sizeof(double), hipMemcpyDeviceToHost,
                            b->stream_rb));
@@ -3556,33 +3422,16 @@ extern "C" int sc_streams_set_phrases(sc_streams *b, const int32_t *labels, cons
     RC_TRY(b->alloc(&b->spot_events, S * SC_SPOT_MAX_EVENTS));
     RC_TRY(b->alloc(&b->spot_jobs_dev, S * N_ARENA));
     RC_TRY(b->halloc(&b->spot_jobs_host, S * N_ARENA));
-    RC_TRY(b->halloc(&b->spot_out_host, S * N_ARENA * 2));
-    void *dv = nullptr;
-    if (hipHostGetDevicePointer(&dv, b->spot_out_host, 0) != hipSuccess || !dv) {
-      sc_set_error("sc_streams_set_phrases: the pinned counter slots are not visible to the device");
-      return SC_ERR_LAUNCH;
-    }
-    b->spot_out_dev = (int32_t *)dv;
-    b->spot_known.assign(S, SpotVal());
-    b->spot_rep.assign(S, SpotVal());
-    b->spot_pending.assign(S, 0);
-    b->spot_epoch.assign(S, 0);
-    b->spot_fresh.assign(S, 1);
-    b->spot_mask.assign(S, ~0ull);
+    RC_TRY(b->halloc_mapped(&b->spot_out_host, &b->spot_out_dev, S * N_ARENA * 2, __func__, "counter slots"));
+    b->spot.init(b->S);
   }
   // no chunk is outstanding, so no group that reads the old set is in flight; the copies below are synchronous
   HIP_TRY(hipStreamSynchronize(b->es));
   HIP_TRY(hipMemcpy(b->spot_labels, lab.data(), lab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(b->spot_lens, len.data(), len.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(b->spot_floors, fl.data(), fl.size() * sizeof(double), hipMemcpyHostToDevice));
-  // every stream starts over: a stream in mid-utterance is scanned from its next frame on
-  for (int s = 0; s < b->S; ++s) {
-    b->spot_epoch[s]++;
-    b->spot_known[s] = b->spot_rep[s] = SpotVal();
-    b->spot_pending[s] = 0;
-    b->spot_fresh[s] = 1;
-    b->spot_mask[s] = ~0ull;
-  }
+  b->spot.restart_all();   // every stream starts over: a stream in mid-utterance is scanned from its next frame on
+  b->spot_mask.assign(b->S, ~0ull);
   b->spot_P = n_phrases;
   b->spot_on = true;
   return SC_OK;
@@ -3596,26 +3445,14 @@ extern "C" int sc_stream_set_phrase_mask(sc_streams *b, int stream, uint64_t mas
   return SC_OK;
 }
 
-// the counters of the stream's last reported chunk, complete: its encoder group may still be held back or in flight
-static int spot_ready(sc_streams *b, int s) {
-  SpotVal &r = b->spot_rep[s];
-  if (r.ready) return SC_OK;
-  RC_TRY(wait_group(b, r.gen));
-  if (!r.ready) {
-    sc_set_error("spotting counters of stream %d did not arrive with their encoder group (internal error)", s);
-    return SC_ERR_LAUNCH;
-  }
-  return SC_OK;
-}
-
 extern "C" int sc_stream_spot(sc_streams *b, int stream, sc_spot_t *out) {
   SC_CHECK_ARG(b && out && stream >= 0 && stream < b->S, "bad arguments");
   SC_API_BEGIN
   SC_CHECK_ARG(b->spot_on, "the spotting option is off (sc_streams_set_phrases)");
   HIP_TRY(hipSetDevice(b->eng->device));
   RC_TRY(spot_ready(b, stream));
-  out->n_frames = b->spot_rep[stream].v[0];
-  out->n_events = b->spot_rep[stream].v[1];
+  out->n_frames = b->spot.rep[stream].v.v[0];
+  out->n_events = b->spot.rep[stream].v.v[1];
   return SC_OK;
   SC_API_END
 }
@@ -3626,7 +3463,7 @@ extern "C" int sc_streams_read_spot_events(sc_streams *b, int stream, sc_spot_ev
   SC_CHECK_ARG(b->spot_on, "the spotting option is off (sc_streams_set_phrases)");
   HIP_TRY(hipSetDevice(b->eng->device));
   RC_TRY(spot_ready(b, stream));
-  const int n = std::min(std::min((int)b->spot_rep[stream].v[1], SC_SPOT_MAX_EVENTS), max);
+  const int n = std::min(std::min((int)b->spot.rep[stream].v.v[1], SC_SPOT_MAX_EVENTS), max);
   if (host && n > 0) {   // (the group that wrote these slots has been retired; later groups write behind them)
     HIP_TRY(hipMemcpyAsync(host, b->spot_events + (size_t)stream * SC_SPOT_MAX_EVENTS, (size_t)n * sizeof(sc_spot_event),
                            hipMemcpyDeviceToHost, b->stream_rb));
@@ -3644,7 +3481,7 @@ extern "C" int sc_streams_read_spot_state(sc_streams *b, int stream, double *val
   RC_TRY(launch_pending_groups(b));
   HIP_TRY(hipStreamSynchronize(b->es));
   const size_t n = (size_t)b->spot_P * SC_SPOT_STATES, o = (size_t)stream * SC_SPOT_MAX_PHRASES * SC_SPOT_STATES;
-  if (b->spot_fresh[stream]) {   // nothing of this utterance has been scanned: the block still holds the previous one
+  if (b->spot.fresh[stream]) {   // nothing of this utterance has been scanned: the block still holds the previous one
     for (size_t i = 0; i < n; ++i) { values[i] = -INFINITY; starts[i] = -1; }
     return b->spot_P;
   }
@@ -3670,41 +3507,13 @@ extern "C" int sc_streams_set_draft(sc_streams *b, int on) {
     RC_TRY(b->alloc(&b->draft_tokens, S * b->TCAP));
     RC_TRY(b->alloc(&b->draft_jobs_dev, S * N_ARENA));
     RC_TRY(b->halloc(&b->draft_jobs_host, S * N_ARENA));
-    RC_TRY(b->halloc(&b->draft_out_host, S * N_ARENA));
-    void *dv = nullptr;
-    if (hipHostGetDevicePointer(&dv, b->draft_out_host, 0) != hipSuccess || !dv) {
-      sc_set_error("sc_streams_set_draft: the pinned state slots are not visible to the device");
-      return SC_ERR_LAUNCH;
-    }
-    b->draft_out_dev = (sc_draft_t *)dv;
-    b->draft_known.assign(S, DraftVal());
-    b->draft_rep.assign(S, DraftVal());
-    b->draft_pending.assign(S, 0);
-    b->draft_epoch.assign(S, 0);
-    b->draft_fresh.assign(S, 1);
+    RC_TRY(b->halloc_mapped(&b->draft_out_host, &b->draft_out_dev, S * N_ARENA, __func__, "state slots"));
+    b->draft.init(b->S);
   }
-  // every stream starts over: a stream in mid-utterance is scanned from its next frame on
-  for (int s = 0; s < b->S; ++s) {
-    b->draft_epoch[s]++;
-    b->draft_known[s] = b->draft_rep[s] = DraftVal();
-    b->draft_pending[s] = 0;
-    b->draft_fresh[s] = 1;
-  }
+  b->draft.restart_all();   // every stream starts over: a stream in mid-utterance is scanned from its next frame on
   b->draft_on = true;
   return SC_OK;
   SC_API_END
-}
-
-// the state of the stream's last reported chunk, complete: its encoder group may still be held back or in flight
-static int draft_ready(sc_streams *b, int s) {
-  DraftVal &r = b->draft_rep[s];
-  if (r.ready) return SC_OK;
-  RC_TRY(wait_group(b, r.gen));
-  if (!r.ready) {
-    sc_set_error("draft state of stream %d did not arrive with its encoder group (internal error)", s);
-    return SC_ERR_LAUNCH;
-  }
-  return SC_OK;
 }
 
 extern "C" int sc_stream_draft(sc_streams *b, int stream, sc_draft_t *out) {
@@ -3713,7 +3522,7 @@ extern "C" int sc_stream_draft(sc_streams *b, int stream, sc_draft_t *out) {
   SC_CHECK_ARG(b->draft_on, "the draft option is off (sc_streams_set_draft)");
   HIP_TRY(hipSetDevice(b->eng->device));
   RC_TRY(draft_ready(b, stream));
-  *out = b->draft_rep[stream].v;
+  *out = b->draft.rep[stream].v.d;
   return SC_OK;
   SC_API_END
 }
@@ -3724,7 +3533,7 @@ extern "C" int sc_streams_read_draft(sc_streams *b, int stream, sc_draft_token *
   SC_CHECK_ARG(b->draft_on, "the draft option is off (sc_streams_set_draft)");
   HIP_TRY(hipSetDevice(b->eng->device));
   RC_TRY(draft_ready(b, stream));
-  const sc_draft_t &v = b->draft_rep[stream].v;
+  const sc_draft_t &v = b->draft.rep[stream].v.d;
   int n = std::min(std::min((int)v.n_closed, b->TCAP), max);
   if (host && n > 0) {   // (the group that wrote these slots has been retired; later groups write behind them)
     HIP_TRY(hipMemcpyAsync(host, b->draft_tokens + (size_t)stream * b->TCAP, (size_t)n * sizeof(sc_draft_token),
