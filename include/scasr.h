@@ -516,6 +516,85 @@ typedef struct sc_ctc_draft_job {
  * nothing.  Two jobs of one call must not share a state or a token store. */
 int sc_ctc_draft(const sc_ctc_draft_job *jobs, int n_jobs, void *stream);
 
+/* ---- CTC prefix beam search (ctc_beam.hip) ----------------------------------------------------
+ * An n-best list of token prefixes with their CTC prefix probabilities, from the rows the draft reads.  The state of a
+ * stream holds n_entries <= B entries, best first: the prefix `node` of the stream's prefix tree (0: the empty prefix),
+ * its last token (-1: none), its length, the node of the prefix without that token (-1: none) and the float64 log
+ * probabilities pb / pnb of the prefix with the path ending in blank / in `last`; the unused slots hold
+ * (-1, -1, 0, -1, -inf, -inf).  The tree is a store of (parent, token, frame) records, node k of the utterance at slot k
+ * ((-1, -1, -1) at slot 0), never touched once stored; a node at or beyond the capacity is counted, not written.  A state
+ * of more than B entries is cut to its first B.  Frames are numbered in the order they are scanned.  For frame n with row
+ * x[0..V): a BAD row (a NaN, a +inf, or nothing but -inf) counts in n_bad and n_frames and changes nothing else; else,
+ * with lse as for sc_ctc_activity, lp(v) = (double)x[v] - lse and lae(a, b) = max + log1p(exp(min - max)) (the other
+ * argument when one is -inf):
+ *   candidates   the C non-blank tokens with the largest x, compared as fp32, the lowest index among ties, none at -inf
+ *   stay         tot_i = lae(pb_i, pnb_i);  pb'_i = tot_i + lp(blank);  pnb'_i = pnb_i + lp(last_i) if last_i is a
+ *                candidate, else -inf
+ *   extension    of entry i by candidate c: ext = (c == last_i ? pb_i : tot_i) + lp(c); if an entry j has
+ *                parent_j == node_i and last_j == c: pnb'_j = lae(pnb'_j, ext), else a new prefix (-inf, ext)
+ *   prune        the B best by total = lae(pb', pnb'), none at -inf; total descending, then stays before new prefixes,
+ *                then the lower rank i, then the lower token; kept new prefixes become the nodes n_nodes, n_nodes + 1,
+ *                ... in that order with the record (node_i, c, n)
+ * tests/ctc_beam_ref.py is the contract: every int32 equal wherever no prune decision is a near-tie, pb / pnb within
+ * 64 n_frames 2^-53 max(1, |value|) (the lanes sum lse in another order than v ascending); chained spans give the bits
+ * of one span. */
+#define SC_BEAM_MAX 16             /* B and C are at most this */
+typedef struct sc_beam_entry {
+  int32_t node, last, len, parent;
+  double pb, pnb;
+} sc_beam_entry;
+typedef struct sc_beam_t {
+  int32_t n_frames, n_bad, n_nodes, n_entries;
+  sc_beam_entry e[SC_BEAM_MAX];
+} sc_beam_t;
+typedef struct sc_beam_node {
+  int32_t parent, token, frame, reserved; /* frame of the utterance at which the token was first emitted; reserved = 0 */
+} sc_beam_node;
+typedef struct sc_ctc_beam_job {
+  const float *table;      /* row t of the table at table + t * stride, V floats (device) */
+  sc_beam_t *state;        /* read (unless restart), advanced over the span, written back (device) */
+  sc_beam_node *nodes;     /* [capacity]: node k of the utterance at nodes[k] (device; may be NULL when capacity == 0) */
+  sc_beam_t *state_after;  /* second copy of the new state, e.g. in host-mapped memory (NULL: none) */
+  int64_t stride;          /* floats between two rows, >= V */
+  int32_t V, blank, t0, t1;
+  int32_t restart;         /* != 0: the stored state is ignored, the span starts an utterance (node 0 is stored) */
+  int32_t capacity;        /* slots of the node store, >= 0; 1 + B * frames of the utterance cannot overflow */
+  int32_t B, C;            /* entries kept, candidate tokens per frame: both in [1, SC_BEAM_MAX] */
+} sc_ctc_beam_job;
+#define SC_BEAM_MAX_JOBS 65535
+/* jobs: device table of n_jobs entries.  ONE launch on `stream`, one workgroup per job; no atomics, one writer per
+ * output; an empty span (t0 == t1) rewrites the state (cut to B entries).  n_jobs < 0, a null table with n_jobs > 0 or
+ * n_jobs > SC_BEAM_MAX_JOBS: SC_ERR_ARG before anything is launched.  A job whose own fields are malformed (null table /
+ * state, a null store with capacity > 0, V < 1, blank outside [0, V), t0 < 0, t1 < t0, stride < V, capacity < 0, B or C
+ * outside [1, SC_BEAM_MAX], a stored n_entries outside [0, SC_BEAM_MAX] without restart) writes nothing.  Two jobs of one
+ * call must not share a state or a node store. */
+int sc_ctc_beam(const sc_ctc_beam_job *jobs, int n_jobs, void *stream);
+
+/* Entries of beam states as token sequences: entry `rank` of *state, walked up its parent chain.  header[0] = the
+ * entry's len (-1 unless SC_BEAM_PACK_OK / _TRUNCATED), header[1] = status, header[2] = node, header[3] = last;
+ * scores[0..2) = pb, pnb (NaN without an entry); ids / frames [0, min(len, max_len)): the tokens and the frames of their
+ * first emission, in order.  SC_BEAM_PACK_NO_ENTRY: rank outside [0, n_entries); SC_BEAM_PACK_TRUNCATED: len > max_len,
+ * the first max_len tokens are written; SC_BEAM_PACK_BROKEN: a node of the chain lies at or beyond the capacity or
+ * n_nodes, or the chain does not end at node 0 after len steps - ids and frames are then unspecified inside
+ * [0, min(len, max_len)).  Nothing is written outside those sizes. */
+#define SC_BEAM_PACK_OK 0
+#define SC_BEAM_PACK_NO_ENTRY 1
+#define SC_BEAM_PACK_TRUNCATED 2
+#define SC_BEAM_PACK_BROKEN 3
+typedef struct sc_ctc_beam_pack_job {
+  const sc_beam_t *state;    /* (device) */
+  const sc_beam_node *nodes; /* [capacity] (device; may be NULL when capacity == 0) */
+  int32_t *ids;              /* [max_len] (device; may be NULL when max_len == 0) */
+  int32_t *frames;           /* [max_len] */
+  int32_t *header;           /* [4] len, status, node, last (device) */
+  double *scores;            /* [2] pb, pnb (device) */
+  int32_t capacity, rank, max_len, reserved;
+} sc_ctc_beam_pack_job;
+/* jobs: device table of n_jobs entries.  ONE launch on `stream`, one thread per job; the states and stores are only
+ * read.  SC_ERR_ARG before anything is launched as for sc_ctc_beam.  A malformed job (a null state / header / scores, a
+ * null ids / frames with max_len > 0, a null store with capacity > 0, capacity < 0, max_len < 0) writes nothing. */
+int sc_ctc_beam_pack(const sc_ctc_beam_pack_job *jobs, int n_jobs, void *stream);
+
 /* ---- CTC token alternates (alternates.hip) -----------------------------------------------------
  * "What else could this token have been": for each of L token spans [start[k], end[k]) over the T rows of an fp32 CTC
  * table, the K acoustically best tokens of those frames and the rank of the span's own label y[k] among them.  Per span,
@@ -1137,6 +1216,41 @@ int sc_stream_draft(sc_streams *streams, int stream, sc_draft_t *out /*HOST*/);
 /* the draft of that state -> host: its stored tokens [0, min(n_closed, max)), then its open token, if any, where room
  * is left; returns the number written */
 int sc_streams_read_draft(sc_streams *streams, int stream, sc_draft_token *host, int max);
+/* CTC prefix beam search per stream (off by default).  beam >= 1: every admission group issues ONE
+ * sc_ctc_beam launch with B = beam, C = candidates (both in [1, SC_BEAM_MAX]) right behind its CTC projection (behind the
+ * activity, spotting and draft launches where those are on), on the encoder stream, over the CTC rows [c0, t1) each of its
+ * chunks projects (raw logits) - the attention search is not touched.  The states (S x 528 bytes) and the node stores
+ * (S x (1 + beam * max_frames) records: a frame adds at most `beam` nodes, so they cannot overflow) are allocated when the
+ * option is first switched on, the stores again when `beam` grows; beam == 0 switches it off: no path does any new work.
+ * SC_ERR_ARG while any chunk is outstanding.  Switching it on restarts every stream's state.  sc_reset touches nothing on
+ * the device: the stream's next span starts the utterance.  strict_reference: as for sc_streams_set_activity, frames that
+ * are not re-projected are not searched. */
+int sc_streams_set_ctc_beam(sc_streams *streams, int beam, int candidates);
+/* state of the stream's last REPORTED chunk over every frame the encoder had emitted for the utterance when that chunk
+ * was admitted; the initial state after sc_reset.  Waits for the encoder group of that chunk if it is still in flight.
+ * SC_ERR_ARG when the option is off. */
+int sc_stream_ctc_beam(sc_streams *streams, int stream, sc_beam_t *out /*HOST*/);
+/* the first nbest <= SC_BEAM_MAX entries of those states as token sequences, for n listed streams (each at most once) with
+ * ONE sc_ctc_beam_pack launch and ONE copy back: header [n][nbest][4] (len, SC_BEAM_PACK_* status, node, last), ids /
+ * frames [n][nbest][max_len] (the tokens and the frames of their first emission; only [0, min(len, max_len)) of a row is
+ * written), scores [n][nbest][2] (pb, pnb).  ids, frames and scores may be NULL. */
+int sc_ctc_beam_hyps(sc_streams *streams, const int *stream_ids, int n, int nbest, int max_len, int32_t *header /*HOST*/,
+                     int32_t *ids /*HOST*/, int32_t *frames /*HOST*/, double *scores /*HOST*/);
+/* Decoder-free streams.  SC_DECODER_NONE: the stream is served from its CTC rows alone.  Admission queues
+ * no decode block for it and lists no cross-attention K|V rows for its frames; the front end, the encoder, the CTC rows,
+ * every side option and the reply status are those of any stream, a chunk is complete at once (the side-state readers
+ * wait for its encoder group), sc_get_hyps returns the initial hypothesis and sc_stream_info.decode_steps stays 0.  The
+ * other streams of the batch are not touched: the same launches for them, the same bits.  The mode outlives sc_reset.
+ * SC_ERR_ARG unless the stream is idle and has taken nothing of its utterance (as for sc_stream_set_input_rate). */
+#define SC_DECODER_FULL 0
+#define SC_DECODER_NONE 1
+int sc_stream_set_decoder(sc_streams *streams, int stream, int mode);
+/* test aid: the CTC rows [0, min(rows projected, max_rows)) of the stream's utterance as the device holds them NOW (every
+ * group issued so far; waits for them) -> host [.][vocab]; raw logits for a SC_DECODER_NONE stream, whose rows no decode
+ * block touches.  Returns the number of rows. */
+int sc_streams_read_ctc_projected(sc_streams *streams, int stream, float *host /*HOST*/, int max_rows);
+/* the stream's decoder mode, SC_DECODER_*; SC_ERR_ARG for a null handle or a stream out of range */
+int sc_stream_decoder(const sc_streams *streams, int stream);
 
 #ifdef __cplusplus
 }

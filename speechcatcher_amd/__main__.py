@@ -72,13 +72,20 @@ def to_16k(raw, rate, device="cuda:0"):
 
 
 def recognize_file(speech2text, media_path, output_file="", quiet=True, progress=True, num_slots=1, chunk_length=8192,
-                   token_alignment=False, segmentation="host", channel=None, token_alternates=0):
+                   token_alignment=False, segmentation="host", channel=None, token_alternates=0, ctc_beam=0,
+                   ctc_only=False):
     """speechcatcher.py:358-400: recording -> text + paragraphs JSON next to the input.  ``token_alignment``: the
     paragraphs also get token_start / token_end (seconds) and token_conf from a CTC forced alignment of each segment.
     ``segmentation``: "host" or "gpu" - where the energy curve for the cut points of a recording over 60 s is computed.
     ``channel``: what to decode of a multichannel recording - an index, or "mix" (None: such a recording is refused).
     ``token_alternates`` = K > 0 (implies ``token_alignment``): the paragraphs also get token_alternates, one record per
-    token with its K acoustic alternates over the token's frames."""
+    token with its K acoustic alternates over the token's frames.  ``ctc_beam`` = B > 0: the paragraphs also get ctc_nbest,
+    per segment the n-best list of the CTC prefix beam search; ``ctc_only``: the segments are decoded by that search alone,
+    with no attention decoder step (B = 8 unless ``ctc_beam`` says otherwise; not with ``token_alternates``)."""
+    if ctc_only and token_alternates:
+        raise SystemExit("Error: --ctc-only has no forced alignment to rank token alternates in: not with --token-alternates")
+    if not 0 <= int(ctc_beam) <= 16:
+        raise SystemExit("Error: --ctc-beam must lie in [1, 16]")
     from .config import SearchConfig
     from .native import NativeStreamBatch
     from .segmenter import recognize_recording
@@ -96,7 +103,8 @@ def recognize_file(speech2text, media_path, output_file="", quiet=True, progress
     # finalize_all only with the very last chunk of the recording, like the reference CLI (speechcatcher.py:586)
     text, info = recognize_recording(batch, raw, rate, chunk_length=chunk_length, token_list=speech2text.token_list,
                                      reference_finalize=True, token_alignment=token_alignment,
-                                     segmentation=segmentation, token_alternates=token_alternates)
+                                     segmentation=segmentation, token_alternates=token_alternates,
+                                     ctc_beam=int(ctc_beam) or None, ctc_only=ctc_only)
     out_txt, out_json = (output_file or media_path) + ".txt", (output_file or media_path) + ".json"
     with open(out_txt, "w") as f:
         f.write(text)
@@ -139,6 +147,12 @@ def make_parser():
     p.add_argument("--token-alternates", dest="token_alternates", type=int, default=0, metavar="K",
                    help="add token_alternates to the .json: per token the K (1..8) tokens that fit its frames best acoustically, "
                         "each with a confidence, and the rank of the token itself among them (implies --token-alignment)")
+    p.add_argument("--ctc-beam", dest="ctc_beam", type=int, default=0, metavar="B",
+                   help="add ctc_nbest to the .json: per segment the B (1..16) best transcripts of a CTC prefix beam search over "
+                        "the encoder's CTC output, each with its log probability and its share of the listed mass")
+    p.add_argument("--ctc-only", dest="ctc_only", action="store_true",
+                   help="decode with the CTC prefix beam search alone: no attention decoder step, the transcript is the beam's "
+                        "best (B = 8 unless --ctc-beam says otherwise; not with --token-alternates)")
     p.add_argument("--segmentation", dest="segmentation", choices=["host", "gpu"], default="host",
                    help="where the energy curve for the cut points of a recording over 60 s is computed: 'host' (numpy, the "
                         "default) or 'gpu' (float64 kernels; the same cuts, without the host pass over the whole recording)")
@@ -173,7 +187,8 @@ def main(argv=None):
     recognize_file(speech2text, args.inputfile, quiet=args.quiet or not args.no_progress, progress=not args.no_progress,
                    num_slots=1 if args.num_processes < 1 else args.num_processes, chunk_length=args.chunk_length,
                    token_alignment=args.token_alignment or args.token_alternates > 0, segmentation=args.segmentation,
-                   channel=args.channel, token_alternates=args.token_alternates)
+                   channel=args.channel, token_alternates=args.token_alternates, ctc_beam=args.ctc_beam,
+                   ctc_only=args.ctc_only)
     return 0
 
 

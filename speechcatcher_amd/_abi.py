@@ -135,6 +135,39 @@ class DraftJob(C.Structure):
 DRAFT_FIELDS = tuple(n for n, _ in Draft._fields_)
 DRAFT_MAX_JOBS = 65535
 
+BEAM_MAX, BEAM_MAX_JOBS = 16, 65535
+# SC_BEAM_PACK_* of include/scasr.h
+BEAM_PACK_OK, BEAM_PACK_NO_ENTRY, BEAM_PACK_TRUNCATED, BEAM_PACK_BROKEN = 0, 1, 2, 3
+# SC_DECODER_* of include/scasr.h
+DECODER_FULL, DECODER_NONE = 0, 1
+
+
+class BeamEntry(C.Structure):
+    """sc_beam_entry (include/scasr.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("node", "last", "len", "parent")] + [("pb", C.c_double), ("pnb", C.c_double)]
+
+
+class Beam(C.Structure):
+    """sc_beam_t (include/scasr.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("n_frames", "n_bad", "n_nodes", "n_entries")] + [("e", BeamEntry * BEAM_MAX)]
+
+
+class BeamNode(C.Structure):
+    """sc_beam_node (include/scasr.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("parent", "token", "frame", "reserved")]
+
+
+class BeamJob(C.Structure):
+    """sc_ctc_beam_job (include/scasr.h): one span of CTC rows searched by sc_ctc_beam"""
+    _fields_ = ([(n, vp) for n in ("table", "state", "nodes", "state_after")] + [("stride", C.c_int64)]
+                + [(n, C.c_int32) for n in ("V", "blank", "t0", "t1", "restart", "capacity", "B", "C")])
+
+
+class BeamPackJob(C.Structure):
+    """sc_ctc_beam_pack_job (include/scasr.h): one entry of a beam state walked up its parent chain"""
+    _fields_ = ([(n, vp) for n in ("state", "nodes", "ids", "frames", "header", "scores")]
+                + [(n, C.c_int32) for n in ("capacity", "rank", "max_len", "reserved")])
+
 
 class AltJob(C.Structure):
     """sc_ctc_alt_job (include/scasr.h): the token spans of one label sequence ranked by sc_ctc_alternates"""
@@ -335,6 +368,15 @@ _SIGS = {
     "sc_streams_set_draft": (C.c_int, [vp, C.c_int]),
     "sc_stream_draft": (C.c_int, [vp, C.c_int, C.POINTER(Draft)]),
     "sc_streams_read_draft": (C.c_int, [vp, C.c_int, vp, C.c_int]),
+    # CTC prefix beam search (ctc_beam.hip, streams.hip)
+    "sc_ctc_beam": (C.c_int, [vp, C.c_int, vp]),
+    "sc_ctc_beam_pack": (C.c_int, [vp, C.c_int, vp]),
+    "sc_streams_set_ctc_beam": (C.c_int, [vp, C.c_int, C.c_int]),
+    "sc_stream_ctc_beam": (C.c_int, [vp, C.c_int, C.POINTER(Beam)]),
+    "sc_ctc_beam_hyps": (C.c_int, [vp, c_int_p, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "sc_stream_set_decoder": (C.c_int, [vp, C.c_int, C.c_int]),
+    "sc_stream_decoder": (C.c_int, [vp, C.c_int]),
+    "sc_streams_read_ctc_projected": (C.c_int, [vp, C.c_int, vp, C.c_int]),
     # wire-format audio in (pcm.hip)
     "sc_pcm_decode": (C.c_int, [vp, C.c_int, vp]),
     "sc_pcm_bytes_per_frame": (C.c_int, [C.c_int, C.c_int]),

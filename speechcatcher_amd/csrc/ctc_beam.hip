@@ -1,0 +1,375 @@
+// CTC prefix beam search (sc_ctc_beam, sc_ctc_beam_pack): an n-best list of token prefixes with their CTC prefix
+// probabilities from the rows of a CTC table, and the running beam of a stream over them.  tests/ctc_beam_ref.py is the
+// contract.
+//
+// One launch per call, one workgroup of BM_WAVES = 16 wave64 per job, the job's span [t0, t1) in tiles of BM_TILE frames:
+//   row pass   the waves take the tile's rows in turn.  Lanes stride over V with an online (max, sum of exp(x - max)) in
+//              float64, combined by an xor butterfly: lse.  The C candidates come in C rounds: every lane's best entry
+//              that lies BEHIND the previous round's winner in the order (x descending, index ascending), the wave's best
+//              of those by a butterfly whose merge prefers the lower index on equal values - exact in any order, ties
+//              included.  A lane keeps its first BM_CACHE entries in registers (V <= 1024: the whole row), the rounds
+//              read the rest again.  Lane 0 writes the candidate ids, their lp and lp(blank) to LDS; BM_BAD for a bad row.
+//   beam pass  wave 0 walks the tile frame by frame, the beam in LDS (two buffers).  Lane j holds entry j for the stay
+//              and looks its parent up among the <= 16 entries: the extension that merges into it is added to its pnb'
+//              and stamped in a (parent, candidate) table.  The lanes then hold the ne (nc + 1) items (entry, stay or
+//              candidate), up to BM_ITEMS each: total and tie key to LDS, rank = the items that precede it, counted over
+//              all items (broadcast reads).  The items of rank < B are written to the other buffer at their rank; a
+//              __ballot over the new prefixes numbers their nodes, one lane each stores its record.
+// No atomics; every output has one writer; plain vector stores.  The table is only read.
+#include "common.h"
+
+namespace {
+
+constexpr int BM_WAVES = 16;   // a group's jobs hold about 16 rows each: one row per wave (8 waves - 256 registers a lane,
+                               // no spill in the beam pass, two rows per wave - measured 6 % slower: DESIGN.md 8j)
+constexpr int BM_UNROLL = 4;
+constexpr int BM_TILE = 256;   // frames whose candidates the workgroup holds in LDS between the two passes
+constexpr int BM_MAX = SC_BEAM_MAX;
+constexpr int BM_CACHE = 16;   // entries of a row a lane keeps in registers for the candidate rounds
+constexpr int BM_ITEMS = (BM_MAX * (BM_MAX + 1) + 63) / 64;   // items per lane
+constexpr int BM_BAD = -1;     // candidate count of a bad row
+
+__device__ __forceinline__ void wave_sync() {   // LDS written by some lanes of the wave is read by others behind this
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ double lae(double a, double b) {
+  if (a == -INFINITY) return b;
+  if (b == -INFINITY) return a;
+  const double hi = a >= b ? a : b, lo = a >= b ? b : a;
+  return hi + log1p(exp(lo - hi));
+}
+
+// candidates of one row, computed by one wave: their count (every lane returns it; BM_BAD: a bad row); lane 0 writes
+// ids[0..count), lp[0..count) and *lp_blank
+__device__ __forceinline__ int row_candidates(const float *__restrict__ row, int V, int blank, int C, int lane, int *ids,
+                                              double *lp, double *lp_blank) {
+  double m = -INFINITY, s = 0.0;
+  bool bad = false;
+  float xv[BM_CACHE];
+#pragma unroll
+  for (int k = 0; k < BM_CACHE; ++k) xv[k] = -INFINITY;
+  // BM_UNROLL values per lane at a time: their loads are in flight together, the running sum is rescaled at most once
+  // per batch (to the batch's maximum)
+  auto batch = [&](int v0, float *keep) {
+    float xf[BM_UNROLL];
+    double x[BM_UNROLL];
+#pragma unroll
+    for (int k = 0; k < BM_UNROLL; ++k) {
+      const int v = v0 + 64 * k;
+      xf[k] = v < V ? row[v] : -INFINITY;
+      x[k] = (double)xf[k];
+      if (keep) keep[k] = v == blank ? -INFINITY : xf[k];   // (the blank is no candidate: -inf in the cache)
+    }
+    double cm = x[0];
+#pragma unroll
+    for (int k = 0; k < BM_UNROLL; ++k) {
+      bad |= (x[k] != x[k]) || x[k] == INFINITY;
+      if (x[k] > cm) cm = x[k];
+    }
+    if (cm > m) {
+      s = m == -INFINITY ? 0.0 : s * exp(m - cm);
+      m = cm;
+    }
+    if (m > -INFINITY) {   // (a -inf entry adds exp(-inf) = 0; a bad row's sum is never used)
+#pragma unroll
+      for (int k = 0; k < BM_UNROLL; ++k) s += exp(x[k] - m);
+    }
+  };
+#pragma unroll
+  for (int b = 0; b < BM_CACHE / BM_UNROLL; ++b)
+    if (lane + 64 * BM_UNROLL * b < V) batch(lane + 64 * BM_UNROLL * b, xv + BM_UNROLL * b);
+  for (int v0 = lane + 64 * BM_CACHE; v0 < V; v0 += 64 * BM_UNROLL) batch(v0, nullptr);
+  const bool any_bad = __any(bad);
+  double M = m;
+  for (int o = 32; o > 0; o >>= 1) M = fmax(M, __shfl_xor(M, o));
+  if (any_bad || M == -INFINITY) return BM_BAD;   // (wave-uniform)
+  double sum = m == -INFINITY ? 0.0 : s * exp(m - M);
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+  const double lse = M + log(sum);
+  if (lane == 0) *lp_blank = (double)row[blank] - lse;
+  // round r: the best entry behind (pv, pi), the winner of round r - 1, in the order (x descending, index ascending)
+  float pv = INFINITY;
+  int pi = -1, nc = 0;
+  for (int r = 0; r < C; ++r) {
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    // a lane sees its v ascending, so "strictly greater" keeps the lowest index
+#pragma unroll
+    for (int k = 0; k < BM_CACHE; ++k) {
+      const int v = lane + 64 * k;
+      const float x = xv[k];
+      if ((x < pv || (x == pv && v > pi)) && x > bv) { bv = x; bi = v; }
+    }
+    for (int v = lane + 64 * BM_CACHE; v < V; v += 64) {
+      const float x = row[v];
+      if (v != blank && (x < pv || (x == pv && v > pi)) && x > bv) { bv = x; bi = v; }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o);
+      const int oi = __shfl_xor(bi, o);
+      if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    if (bi == 0x7fffffff) break;   // (wave-uniform) nothing finite is left
+    if (lane == 0) {
+      ids[r] = bi;
+      lp[r] = (double)bv - lse;
+    }
+    pv = bv;
+    pi = bi;
+    nc = r + 1;
+  }
+  return nc;
+}
+
+__device__ __forceinline__ sc_beam_entry empty_entry() {
+  sc_beam_entry e;
+  e.node = -1; e.last = -1; e.len = 0; e.parent = -1; e.pb = -INFINITY; e.pnb = -INFINITY;
+  return e;
+}
+
+__global__ __launch_bounds__(BM_WAVES * 64) void ctc_beam_kernel(const sc_ctc_beam_job *__restrict__ jobs) {
+  __shared__ double clp[BM_TILE][BM_MAX];
+  __shared__ int cid[BM_TILE][BM_MAX];
+  __shared__ double blp[BM_TILE];
+  __shared__ int cn[BM_TILE];
+  __shared__ sc_beam_entry ent[2][BM_MAX];
+  __shared__ double s_tot[BM_MAX], s_total2[BM_MAX], s_pb2[BM_MAX], s_pnb2[BM_MAX];
+  __shared__ double it_tot[BM_MAX * (BM_MAX + 1)];
+  __shared__ unsigned long long it_key[BM_MAX * (BM_MAX + 1)];
+  __shared__ int mrg[BM_MAX * BM_MAX];
+  const sc_ctc_beam_job j = jobs[blockIdx.x];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  // a malformed job writes nothing (the host-side entry point cannot see the device table)
+  if (!j.table || !j.state || j.V < 1 || j.blank < 0 || j.blank >= j.V || j.t0 < 0 || j.t1 < j.t0 || j.stride < j.V ||
+      j.capacity < 0 || (j.capacity > 0 && !j.nodes) || j.B < 1 || j.B > BM_MAX || j.C < 1 || j.C > BM_MAX)
+    return;
+  int stored = 1;
+  if (!j.restart) {
+    stored = j.state->n_entries;   // (every thread reads it: the decision is uniform over the workgroup)
+    if (stored < 0 || stored > BM_MAX) return;
+  }
+  __syncthreads();   // every wave has read the count before wave 0 may rewrite it (an empty span has no other barrier)
+
+  // the state: counters wave-uniform in wave 0's registers, the entries in ent[p]
+  int n = 0, n_bad = 0, n_nodes = 1, ne = min(stored, j.B), p = 0, f = 0;
+  if (wave == 0) {
+    if (!j.restart) {
+      n = j.state->n_frames; n_bad = j.state->n_bad; n_nodes = j.state->n_nodes;
+      if (lane < ne) ent[0][lane] = j.state->e[lane];
+    } else {
+      if (lane == 0) {
+        sc_beam_entry e = empty_entry();
+        e.node = 0; e.pb = 0.0;
+        ent[0][0] = e;
+        if (j.capacity > 0) {
+          sc_beam_node r;
+          r.parent = -1; r.token = -1; r.frame = -1; r.reserved = 0;
+          j.nodes[0] = r;
+        }
+      }
+    }
+    for (int k = lane; k < BM_MAX * BM_MAX; k += 64) mrg[k] = 0;
+    wave_sync();
+  }
+  for (int tb = j.t0; tb < j.t1; tb += BM_TILE) {
+    const int nt = min(BM_TILE, j.t1 - tb);
+    for (int i = wave; i < nt; i += BM_WAVES) {
+      const int c = row_candidates(j.table + (size_t)(tb + i) * (size_t)j.stride, j.V, j.blank, j.C, lane, cid[i], clp[i],
+                                   &blp[i]);
+      if (lane == 0) cn[i] = c;
+    }
+    __syncthreads();
+    if (wave == 0) {
+      for (int i = 0; i < nt; ++i, ++n) {
+        const int nc = cn[i];
+        if (nc == BM_BAD) {   // (wave-uniform)
+          ++n_bad;
+          continue;
+        }
+        ++f;
+        const double lpb = blp[i];
+        // ---- the stay of entry `lane`, and the extension that merges into it
+        sc_beam_entry me = empty_entry();
+        int kk = -1;
+        double lpl = 0.0, tot = -INFINITY;
+        if (lane < ne) {
+          me = ent[p][lane];
+          for (int k = 0; k < nc; ++k)
+            if (cid[i][k] == me.last) kk = k;
+          if (kk >= 0) lpl = clp[i][kk];
+          tot = lae(me.pb, me.pnb);
+          s_tot[lane] = tot;
+        }
+        wave_sync();
+        if (lane < ne) {
+          const double pb2 = tot + lpb;
+          double pnb2 = kk >= 0 ? me.pnb + lpl : -INFINITY;
+          if (kk >= 0 && me.parent >= 0) {
+            for (int ii = 0; ii < ne; ++ii) {
+              if (ent[p][ii].node == me.parent) {   // (node ids are unique in a beam: at most one)
+                const double ext = (me.last == ent[p][ii].last ? ent[p][ii].pb : s_tot[ii]) + lpl;
+                pnb2 = lae(pnb2, ext);
+                mrg[ii * BM_MAX + kk] = f;
+              }
+            }
+          }
+          s_pb2[lane] = pb2;
+          s_pnb2[lane] = pnb2;
+          s_total2[lane] = lae(pb2, pnb2);
+        }
+        wave_sync();
+        // ---- the items: total and tie key (stay / new prefix, rank of the entry, token)
+        const int per = nc + 1, M = ne * per;
+        double my_t[BM_ITEMS];
+        unsigned long long my_k[BM_ITEMS];
+        int cnt[BM_ITEMS];
+#pragma unroll
+        for (int q = 0; q < BM_ITEMS; ++q) {
+          const int s = lane + 64 * q;
+          my_t[q] = -INFINITY;
+          my_k[q] = 0ull;
+          cnt[q] = 0;
+          if (s < M) {
+            const int ii = s / per, k = s - ii * per;
+            if (k == 0) {
+              my_t[q] = s_total2[ii];
+              my_k[q] = (unsigned long long)ii << 32;
+            } else {
+              const int c = cid[i][k - 1];
+              if (mrg[ii * BM_MAX + k - 1] != f) my_t[q] = (c == ent[p][ii].last ? ent[p][ii].pb : s_tot[ii]) + clp[i][k - 1];
+              my_k[q] = ((unsigned long long)(BM_MAX + ii) << 32) | (unsigned)c;
+            }
+            it_tot[s] = my_t[q];
+            it_key[s] = my_k[q];
+          }
+        }
+        wave_sync();
+        // ---- rank = the items that precede it: total descending, then the key ascending
+        for (int s2 = 0; s2 < M; ++s2) {
+          const double t2 = it_tot[s2];
+          const unsigned long long k2 = it_key[s2];
+#pragma unroll
+          for (int q = 0; q < BM_ITEMS; ++q) cnt[q] += (t2 > my_t[q] || (t2 == my_t[q] && k2 < my_k[q])) ? 1 : 0;
+        }
+        int finite = 0;
+#pragma unroll
+        for (int q = 0; q < BM_ITEMS; ++q) {
+          const bool live = my_t[q] > -INFINITY;
+          finite += __popcll(__ballot(live));
+          if (live && cnt[q] < j.B) {
+            const int s = lane + 64 * q, ii = s / per, k = s - ii * per;
+            const sc_beam_entry src = ent[p][ii];
+            sc_beam_entry e;
+            if (k == 0) {
+              e = src;
+              e.pb = s_pb2[ii];
+              e.pnb = s_pnb2[ii];
+            } else {
+              e.node = -1;   // numbered below
+              e.last = cid[i][k - 1];
+              e.len = src.len + 1;
+              e.parent = src.node;
+              e.pb = -INFINITY;
+              e.pnb = my_t[q];
+            }
+            ent[p ^ 1][cnt[q]] = e;
+          }
+        }
+        wave_sync();
+        ne = min(j.B, finite);
+        p ^= 1;
+        // ---- the new prefixes become nodes, in rank order
+        const bool fresh = lane < ne && ent[p][lane].node < 0;
+        const unsigned long long mf = __ballot(fresh);
+        if (fresh) {
+          const int id = n_nodes + __popcll(mf & ((1ull << lane) - 1ull));
+          ent[p][lane].node = id;
+          if (id < j.capacity) {
+            sc_beam_node r;
+            r.parent = ent[p][lane].parent; r.token = ent[p][lane].last; r.frame = n; r.reserved = 0;
+            j.nodes[id] = r;
+          }
+        }
+        n_nodes += __popcll(mf);
+        wave_sync();
+      }
+    }
+    __syncthreads();   // the tile is free for the next row pass
+  }
+  if (wave == 0) {
+    if (lane < BM_MAX) {
+      const sc_beam_entry e = lane < ne ? ent[p][lane] : empty_entry();
+      j.state->e[lane] = e;
+      if (j.state_after) j.state_after->e[lane] = e;
+    }
+    if (lane == 0) {
+      j.state->n_frames = n; j.state->n_bad = n_bad; j.state->n_nodes = n_nodes; j.state->n_entries = ne;
+      if (j.state_after) {
+        j.state_after->n_frames = n; j.state_after->n_bad = n_bad; j.state_after->n_nodes = n_nodes;
+        j.state_after->n_entries = ne;
+      }
+    }
+  }
+}
+
+constexpr int PK_THREADS = 64;
+
+__global__ __launch_bounds__(PK_THREADS) void ctc_beam_pack_kernel(const sc_ctc_beam_pack_job *__restrict__ jobs, int n_jobs) {
+  const int k = blockIdx.x * PK_THREADS + threadIdx.x;
+  if (k >= n_jobs) return;
+  const sc_ctc_beam_pack_job j = jobs[k];
+  if (!j.state || !j.header || !j.scores || j.capacity < 0 || j.max_len < 0 || (j.max_len > 0 && (!j.ids || !j.frames)) ||
+      (j.capacity > 0 && !j.nodes))
+    return;
+  const int ne = j.state->n_entries, nn = j.state->n_nodes;
+  if (j.rank < 0 || j.rank >= ne || j.rank >= BM_MAX) {
+    j.header[0] = -1; j.header[1] = SC_BEAM_PACK_NO_ENTRY; j.header[2] = -1; j.header[3] = -1;
+    j.scores[0] = NAN; j.scores[1] = NAN;
+    return;
+  }
+  const sc_beam_entry e = j.state->e[j.rank];
+  const int stored = min(nn, j.capacity);
+  int node = e.node, status = e.len > j.max_len ? SC_BEAM_PACK_TRUNCATED : SC_BEAM_PACK_OK;
+  if (e.len < 0) status = SC_BEAM_PACK_BROKEN;
+  for (int pos = e.len - 1; pos >= 0 && status != SC_BEAM_PACK_BROKEN; --pos) {
+    if (node < 1 || node >= stored) {
+      status = SC_BEAM_PACK_BROKEN;
+      break;
+    }
+    const sc_beam_node r = j.nodes[node];
+    if (pos < j.max_len) {
+      j.ids[pos] = r.token;
+      j.frames[pos] = r.frame;
+    }
+    node = r.parent;
+  }
+  if (status != SC_BEAM_PACK_BROKEN && node != 0) status = SC_BEAM_PACK_BROKEN;
+  j.header[0] = status == SC_BEAM_PACK_BROKEN ? -1 : e.len;
+  j.header[1] = status; j.header[2] = e.node; j.header[3] = e.last;
+  j.scores[0] = e.pb; j.scores[1] = e.pnb;
+}
+
+}  // namespace
+
+extern "C" int sc_ctc_beam(const sc_ctc_beam_job *jobs, int n_jobs, void *stream) {
+  SC_CHECK_ARG(n_jobs >= 0, "negative job count");
+  SC_CHECK_ARG(n_jobs == 0 || jobs, "null job table");
+  SC_CHECK_ARG(n_jobs <= SC_BEAM_MAX_JOBS, "more than SC_BEAM_MAX_JOBS jobs");
+  if (n_jobs == 0) return SC_OK;
+  ctc_beam_kernel<<<n_jobs, BM_WAVES * 64, 0, (hipStream_t)stream>>>(jobs);
+  SC_CHECK_LAUNCH();
+  return SC_OK;
+}
+
+extern "C" int sc_ctc_beam_pack(const sc_ctc_beam_pack_job *jobs, int n_jobs, void *stream) {
+  SC_CHECK_ARG(n_jobs >= 0, "negative job count");
+  SC_CHECK_ARG(n_jobs == 0 || jobs, "null job table");
+  SC_CHECK_ARG(n_jobs <= SC_BEAM_MAX_JOBS, "more than SC_BEAM_MAX_JOBS jobs");
+  if (n_jobs == 0) return SC_OK;
+  ctc_beam_pack_kernel<<<cdiv(n_jobs, PK_THREADS), PK_THREADS, 0, (hipStream_t)stream>>>(jobs, n_jobs);
+  SC_CHECK_LAUNCH();
+  return SC_OK;
+}

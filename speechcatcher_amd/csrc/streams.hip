@@ -126,6 +126,8 @@ struct St {
   // wire format of the stream's input (pcm.hip): SC_PCM_F32 with one channel is the float path - no decode launch
   int in_fmt = SC_PCM_F32, in_ch = 1, in_sel = 0, in_scale = SC_PCM_SCALE_FULL;
   bool coded() const { return in_fmt != SC_PCM_F32 || in_ch != 1; }
+  // SC_DECODER_NONE (sc_stream_set_decoder): admission queues no decode block and lists no cross-attention K|V rows
+  bool no_dec = false;
 };
 
 // a decode block of the schedule (beam_search.py:590-634): the T frames [0, T) it presents to the scorers, whether
@@ -160,13 +162,25 @@ struct SpotState {
 struct DraftState {
   sc_draft_t d = {0, 0, 0, -1, -1, -1, 0.0};
 };
+// CTC prefix beam search (sc_streams_set_ctc_beam; ctc_beam.hip): the beam - counters and entries.  The prefix tree stays
+// on the device: the utterance's node k is at slot k and is never touched once stored, so the chains of a reported state's
+// entries are final whatever later groups append.
+struct BeamState {
+  sc_beam_t d;
+  BeamState() {
+    d.n_frames = 0; d.n_bad = 0; d.n_nodes = 1; d.n_entries = 1;
+    for (sc_beam_entry &e : d.e) e = sc_beam_entry{-1, -1, 0, -1, -INFINITY, -INFINITY};
+    d.e[0] = sc_beam_entry{0, -1, 0, -1, 0.0, -INFINITY};
+  }
+  explicit BeamState(const sc_beam_t &v) : d(v) {}
+};
 // Input level (sc_stream_set_input_format; pcm.hip): the cumulative level, all zero at first.  Its launch belongs to a
 // STAGING slot (it runs in the admission's staging step, not in an encoder group), so its key is a ticket that names the
 // decode job, and slots are collected in any order.
 using LevelState = sc_input_level_t;
 
 // the options that scan the CTC rows of an encoder group, in launch order (EncGroup::Span::opt)
-enum { OPT_ACT, OPT_SPOT, OPT_DRAFT, N_OPT };
+enum { OPT_ACT, OPT_SPOT, OPT_DRAFT, OPT_BEAM, N_OPT };
 
 // a stream's outstanding chunk (sc_push / sc_submit): open until it has been reported.  With a queue depth > 1
 // (sc_streams_set_queue_depth) further chunks of the stream wait behind it (sc_streams::ahead), in order.
@@ -181,6 +195,7 @@ struct Job {
   handover::Pending<ActState> act;       // sc_streams_set_activity: the activity state that belongs to this chunk
   handover::Pending<SpotState> spot;     // sc_streams_set_phrases: the spotting counters that belong to this chunk
   handover::Pending<DraftState> draft;   // sc_streams_set_draft: the draft state that belongs to this chunk
+  handover::Pending<BeamState> beam;     // sc_streams_set_ctc_beam: the beam that belongs to this chunk
   handover::Pending<LevelState> level;   // sc_stream_set_input_format: the input level up to and including this chunk
 };
 
@@ -238,7 +253,7 @@ struct EncGroup {
   int n_fe = 0, max_keep = 0;
   EncPlan P;
   std::vector<int32_t> ctc_rows, kv_src, kv_dst;   // eager projections of the frames the group emits
-  // side-state options (activity, spotting, draft): per stream the span [t0, t1) of ctc_rows that every option which is on
+  // side-state options (activity, spotting, draft, beam): per stream the span [t0, t1) of ctc_rows that every option which is on
   // scans, one job each and in this order in every option's launch; mask: the stream's enabled phrases (spotting);
   // opt[o]: the span as option o planned it (every span of a group carries the same options)
   struct Span {
@@ -378,6 +393,18 @@ struct sc_streams {
   sc_ctc_draft_job *draft_jobs_host = nullptr, *draft_jobs_dev = nullptr;   // [N_ARENA][S]: the job table of a group's launch
   sc_draft_t *draft_out_host = nullptr, *draft_out_dev = nullptr;           // [N_ARENA][S] host-mapped: the jobs' states-after
   handover::Track<DraftState> draft;              // keyed by encoder group, as act
+  // ---- CTC prefix beam search (sc_streams_set_ctc_beam): everything below is allocated when the option is first switched on ----
+  bool beam_on = false;
+  int beam_B = 0, beam_C = 0;
+  int beam_nodes_B = 0;                     // the B the node store was sized for
+  sc_beam_t *beam_state = nullptr;          // device [S]: the running state of every stream (advanced group by group)
+  sc_beam_node *beam_nodes = nullptr;       // device [S][1 + beam_nodes_B * TCAP]: a frame adds at most B nodes, so the store cannot overflow
+  sc_ctc_beam_job *beam_jobs_host = nullptr, *beam_jobs_dev = nullptr;   // [N_ARENA][S]: the job table of a group's launch
+  sc_beam_t *beam_out_host = nullptr, *beam_out_dev = nullptr;           // [N_ARENA][S] host-mapped: the jobs' states-after
+  handover::Track<BeamState> beam;          // keyed by encoder group, as act
+  char *bh_dev = nullptr, *bh_host = nullptr;   // sc_ctc_beam_hyps: states, pack jobs and packed outputs; grown geometrically
+  size_t bh_cap = 0;
+  size_t beam_ncap() const { return 1 + (size_t)beam_nodes_B * TCAP; }
   // ---- tick engine -----------------------------------------------------------------------------------------------------
   std::vector<St> st;
   std::vector<Run> run;
@@ -439,6 +466,9 @@ struct sc_streams {
     if (stream_rb) (void)hipStreamDestroy(stream_rb);
     if (stream) (void)hipStreamDestroy(stream);
     if (al_dev) (void)hipFree(al_dev);
+    if (beam_nodes) (void)hipFree(beam_nodes);
+    if (bh_dev) (void)hipFree(bh_dev);
+    if (bh_host) (void)hipHostFree(bh_host);
   }
 
   template <typename T>
@@ -572,6 +602,7 @@ void reset_stream(sc_streams *b, int s) {
   St old = b->st[s], ns;
   ns.rs_tab = old.rs_tab;   // the input rate stays; the converter starts over (no history)
   ns.in_fmt = old.in_fmt; ns.in_ch = old.in_ch; ns.in_sel = old.in_sel; ns.in_scale = old.in_scale;   // and so does the format
+  ns.no_dec = old.no_dec;   // ... and the decoder mode
   if (b->strict) {
     ns.short_pos = old.short_pos;
     ns.T_ctc = old.T_ctc;
@@ -586,6 +617,7 @@ void reset_stream(sc_streams *b, int s) {
   b->act.restart(s);
   b->spot.restart(s);
   b->draft.restart(s);
+  b->beam.restart(s);
   b->lvl.restart(s);
   init_hyp(b, s);
 }
@@ -1004,6 +1036,8 @@ int retire_groups(sc_streams *b) {
       }
       if (sp.opt[OPT_DRAFT].on)
         b->draft.deliver(s, g->gen, sp.opt[OPT_DRAFT].epoch, DraftState{b->draft_out_host[o]}, b->job[s], b->ahead[s], &Job::draft);
+      if (sp.opt[OPT_BEAM].on)
+        b->beam.deliver(s, g->gen, sp.opt[OPT_BEAM].epoch, BeamState(b->beam_out_host[o]), b->job[s], b->ahead[s], &Job::beam);
     }
     b->gen_done = g->gen;
     b->slot_gen[g->slot] = 0;
@@ -1093,6 +1127,18 @@ int project_rows(sc_streams *b, EncGroup &g) {
                           j.V = V; j.blank = blank; j.t0 = sp.t0; j.t1 = sp.t1;
                           j.restart = sp.opt[OPT_DRAFT].restart ? 1 : 0;
                           j.capacity = b->TCAP;
+                        }));
+    RC_TRY(launch_spans(b, g, OPT_BEAM, "beam", b->beam_jobs_host, b->beam_jobs_dev, sc_ctc_beam,
+                        [=](sc_ctc_beam_job &j, const EncGroup::Span &sp, size_t at) {
+                          j.table = b->sb.ctcx + (size_t)sp.s * b->TCAP * V;
+                          j.state = b->beam_state + sp.s;
+                          j.nodes = b->beam_nodes + (size_t)sp.s * b->beam_ncap();
+                          j.state_after = b->beam_out_dev + at;
+                          j.stride = V;
+                          j.V = V; j.blank = blank; j.t0 = sp.t0; j.t1 = sp.t1;
+                          j.restart = sp.opt[OPT_BEAM].restart ? 1 : 0;
+                          j.capacity = (int32_t)b->beam_ncap();
+                          j.B = b->beam_B; j.C = b->beam_C;
                         }));
   }
   if (!g.kv_dst.empty()) {
@@ -1765,7 +1811,7 @@ int admit(sc_streams *b, std::vector<Chunk> chunks, bool features, bool defer, s
     const int c0 = std::max(t0, st.T_proj), k0 = std::max(t0, st.T_projkv);
     g->same_rows = g->same_rows && c0 == k0;
     for (int t = c0; t < t1; ++t) g->ctc_rows.push_back(ch.s * b->TCAP + t);
-    if ((b->act_on || b->spot_on || b->draft_on) && c0 < t1) {
+    if ((b->act_on || b->spot_on || b->draft_on || b->beam_on) && c0 < t1) {
       EncGroup::Span sp;
       sp.s = ch.s; sp.t0 = c0; sp.t1 = t1;
       if (b->act_on) sp.opt[OPT_ACT] = b->act.plan(ch.s);
@@ -1774,12 +1820,17 @@ int admit(sc_streams *b, std::vector<Chunk> chunks, bool features, bool defer, s
         sp.mask = b->spot_mask[ch.s];
       }
       if (b->draft_on) sp.opt[OPT_DRAFT] = b->draft.plan(ch.s);
+      if (b->beam_on) sp.opt[OPT_BEAM] = b->beam.plan(ch.s);
       g->spans.push_back(sp);
       act_new.push_back(ch.s);
     }
-    for (int t = k0; t < t1; ++t) {
-      g->kv_src.push_back(ch.s * b->TCAP + t);
-      g->kv_dst.push_back(ch.s * c.dec_layers * b->TCAP + t);
+    if (st.no_dec) {   // a decoder-free stream: no K|V rows (the group's two row lists differ from here on)
+      g->same_rows = g->same_rows && c0 >= t1;
+    } else {
+      for (int t = k0; t < t1; ++t) {
+        g->kv_src.push_back(ch.s * b->TCAP + t);
+        g->kv_dst.push_back(ch.s * c.dec_layers * b->TCAP + t);
+      }
     }
     st.T_proj = std::max(st.T_proj, t1);
     st.T_projkv = std::max(st.T_projkv, t1);
@@ -1827,6 +1878,7 @@ int admit(sc_streams *b, std::vector<Chunk> chunks, bool features, bool defer, s
   for (auto &kv : feat_new) {
     const int s = kv.first;
     St &st = b->st[s];
+    if (st.no_dec) continue;   // a decoder-free stream: its chunks have no blocks and are complete at once
     std::deque<Blk> &q = b->bq[s];
     int pb = st.processed_block + (b->run[s].inblk && !b->run[s].fin ? 1 : 0);
     for (auto &k : q) pb += k.fin ? 0 : 1;
@@ -1857,6 +1909,7 @@ int admit(sc_streams *b, std::vector<Chunk> chunks, bool features, bool defer, s
       if (b->act_on) j.act = b->act.admit(s, carrier, b->gen_done);
       if (b->spot_on) j.spot = b->spot.admit(s, carrier, b->gen_done);
       if (b->draft_on) j.draft = b->draft.admit(s, carrier, b->gen_done);
+      if (b->beam_on) j.beam = b->beam.admit(s, carrier, b->gen_done);
       if (b->lvl_state) j.level = b->lvl.admit(s, 0, 0);
     }
     if (b->job[chunks[k].s].open) b->ahead[chunks[k].s].push_back(j);   // behind the stream's outstanding chunk(s)
@@ -2387,6 +2440,27 @@ extern "C" int sc_stream_set_input_rate(sc_streams *b, int stream, int rate) {
   SC_API_END
 }
 
+// Decoder mode of a stream (default SC_DECODER_FULL).  SC_DECODER_NONE: the stream is served from its CTC rows alone - the
+// front end, the encoder, the CTC projection and every side option run as for any stream, but admission queues no decode
+// block and projects no cross-attention K|V rows for its frames.
+extern "C" int sc_stream_set_decoder(sc_streams *b, int stream, int mode) {
+  SC_CHECK_ARG(b && stream >= 0 && stream < b->S, "stream out of range");
+  SC_API_BEGIN
+  SC_CHECK_ARG(mode == SC_DECODER_FULL || mode == SC_DECODER_NONE, "mode is neither SC_DECODER_FULL nor SC_DECODER_NONE");
+  const St &cur = b->st[stream];
+  SC_CHECK_ARG(!b->job[stream].open && b->ahead[stream].empty(), "the stream has a chunk outstanding (sc_poll reports it first)");
+  SC_CHECK_ARG(cur.pcm_end == 0 && !cur.fe_started && !cur.enc_started && !cur.started && cur.rs_in == 0,
+               "the stream has buffered audio since its last reset (sc_reset first)");
+  b->st[stream].no_dec = mode == SC_DECODER_NONE;
+  return SC_OK;
+  SC_API_END
+}
+
+extern "C" int sc_stream_decoder(const sc_streams *b, int stream) {
+  if (!b || stream < 0 || stream >= b->S) return SC_ERR_ARG;
+  return b->st[stream].no_dec ? SC_DECODER_NONE : SC_DECODER_FULL;
+}
+
 extern "C" int sc_stream_input_rate(const sc_streams *b, int stream) {
   SC_CHECK_ARG(b && stream >= 0 && stream < b->S, "stream out of range");
   return b->st[stream].rs_tab < 0 ? 16000 : b->rs_rate[b->st[stream].rs_tab];
@@ -2564,6 +2638,7 @@ int report_chunk(sc_streams *b, int s) {
     if (b->act_on) b->act.report(s, j.act);
     if (b->spot_on) b->spot.report(s, j.spot);
     if (b->draft_on) b->draft.report(s, j.draft);
+    if (b->beam_on) b->beam.report(s, j.beam);
     if (b->lvl_state) b->lvl.report(s, j.level);
   }
   if (b->snap[s].valid && b->snap[s].seq == j.seq) b->snap[s].reported = true;   // handed out: free at the next sc_poll
@@ -3312,6 +3387,22 @@ extern "C" int sc_streams_read_ctc(sc_streams *b, int stream, float *host, int m
   SC_API_END
 }
 
+// test aid: the CTC rows projected for the stream's utterance so far, as the device holds them NOW (every group issued so
+// far; waits for them) - raw logits for a decoder-free stream, whose rows no decode block touches
+extern "C" int sc_streams_read_ctc_projected(sc_streams *b, int stream, float *host, int max_rows) {
+  SC_CHECK_ARG(b && stream >= 0 && stream < b->S && max_rows >= 0, "bad arguments");
+  SC_API_BEGIN
+  HIP_TRY(hipSetDevice(b->eng->device));
+  RC_TRY(launch_pending_groups(b));
+  HIP_TRY(hipStreamSynchronize(b->es));
+  const int T = std::min(std::min(b->st[stream].T_proj, b->TCAP), max_rows);
+  const size_t V = (size_t)b->cfg.vocab_size;
+  if (host && T > 0)
+    HIP_TRY(hipMemcpy(host, b->sb.ctcx + (size_t)stream * b->TCAP * V, (size_t)T * V * sizeof(float), hipMemcpyDeviceToHost));
+  return T;
+  SC_API_END
+}
+
 // ---- acoustic activity ------------------------------------------------------------------------------------------------
 extern "C" int sc_streams_set_activity(sc_streams *b, int on, double blank_threshold) {
   SC_CHECK_ARG(b, "null");
@@ -3354,6 +3445,7 @@ static int side_ready(sc_streams *b, const handover::Pending<V> &r, int s, const
 static int activity_ready(sc_streams *b, int s) { return side_ready(b, b->act.rep[s], s, "activity state", "its"); }
 static int spot_ready(sc_streams *b, int s) { return side_ready(b, b->spot.rep[s], s, "spotting counters", "their"); }
 static int draft_ready(sc_streams *b, int s) { return side_ready(b, b->draft.rep[s], s, "draft state", "its"); }
+static int beam_ready(sc_streams *b, int s) { return side_ready(b, b->beam.rep[s], s, "beam state", "its"); }
 
 extern "C" int sc_stream_activity(sc_streams *b, int stream, sc_activity_t *out) {
   SC_CHECK_ARG(b && out && stream >= 0 && stream < b->S, "bad arguments");
@@ -3545,6 +3637,126 @@ extern "C" int sc_streams_read_draft(sc_streams *b, int stream, sc_draft_token *
     t.id = v.open_id; t.start = v.open_start; t.end = v.open_end; t.reserved = 0; t.conf = v.open_conf;
   }
   return n;
+  SC_API_END
+}
+
+// ---- CTC prefix beam search -----------------------------------------------------------------------------------------------
+extern "C" int sc_streams_set_ctc_beam(sc_streams *b, int beam, int candidates) {
+  SC_CHECK_ARG(b, "null");
+  SC_API_BEGIN
+  SC_CHECK_ARG(b->n_open == 0, "chunks are outstanding");
+  if (!beam) {
+    b->beam_on = false;
+    return SC_OK;
+  }
+  SC_CHECK_ARG(beam >= 1 && beam <= SC_BEAM_MAX && candidates >= 1 && candidates <= SC_BEAM_MAX,
+               "beam and candidates must lie in [1, SC_BEAM_MAX]");
+  SC_CHECK_ARG(1 + (size_t)beam * b->TCAP <= 0x7fffffffu, "the node store exceeds 2^31 records");
+  HIP_TRY(hipSetDevice(b->eng->device));
+  if (!b->beam_state) {
+    const size_t S = (size_t)b->S;
+    RC_TRY(b->alloc(&b->beam_state, S));
+    RC_TRY(b->alloc(&b->beam_jobs_dev, S * N_ARENA));
+    RC_TRY(b->halloc(&b->beam_jobs_host, S * N_ARENA));
+    RC_TRY(b->halloc_mapped(&b->beam_out_host, &b->beam_out_dev, S * N_ARENA, __func__, "state slots"));
+    b->beam.init(b->S);
+  }
+  if (beam > b->beam_nodes_B) {   // the node store grows with B (no chunk is outstanding; a group may still be in flight)
+    HIP_TRY(hipStreamSynchronize(b->es));
+    if (b->beam_nodes) (void)hipFree(b->beam_nodes);
+    b->beam_nodes = nullptr;
+    b->beam_nodes_B = 0;
+    RC_TRY(dalloc(&b->beam_nodes, (size_t)b->S * (1 + (size_t)beam * b->TCAP)));
+    b->beam_nodes_B = beam;
+  }
+  b->beam.restart_all();   // every stream starts over: a stream in mid-utterance is searched from its next frame on
+  b->beam_B = beam;
+  b->beam_C = candidates;
+  b->beam_on = true;
+  return SC_OK;
+  SC_API_END
+}
+
+extern "C" int sc_stream_ctc_beam(sc_streams *b, int stream, sc_beam_t *out) {
+  SC_CHECK_ARG(b && out && stream >= 0 && stream < b->S, "bad arguments");
+  SC_API_BEGIN
+  SC_CHECK_ARG(b->beam_on, "the beam option is off (sc_streams_set_ctc_beam)");
+  HIP_TRY(hipSetDevice(b->eng->device));
+  RC_TRY(beam_ready(b, stream));
+  *out = b->beam.rep[stream].v.d;
+  return SC_OK;
+  SC_API_END
+}
+
+// The first nbest entries of the listed streams' reported beams as token sequences: the states and ONE job table go up,
+// ONE sc_ctc_beam_pack launch walks the chains, ONE copy comes back, all on the read-back stream as sc_get_hyps_batch
+// does it.  header [n][nbest][4] (len, SC_BEAM_PACK_* status, node, last), ids / frames [n][nbest][max_len], scores
+// [n][nbest][2] (pb, pnb); any of ids / frames / scores may be NULL.
+extern "C" int sc_ctc_beam_hyps(sc_streams *b, const int *stream_ids, int n, int nbest, int max_len, int32_t *header,
+                                int32_t *ids, int32_t *frames, double *scores) {
+  SC_CHECK_ARG(b && stream_ids && header && n >= 0 && nbest >= 0 && nbest <= SC_BEAM_MAX && max_len >= 0, "bad arguments");
+  SC_API_BEGIN
+  SC_CHECK_ARG(b->beam_on, "the beam option is off (sc_streams_set_ctc_beam)");
+  SC_CHECK_ARG(n <= b->S, "more streams listed than the batch has");
+  HIP_TRY(hipSetDevice(b->eng->device));
+  const size_t m = (size_t)n * nbest;
+  if (m == 0) return SC_OK;
+  SC_CHECK_ARG(m <= SC_BEAM_MAX_JOBS, "more than SC_BEAM_MAX_JOBS entries asked for");
+  std::vector<char> listed(b->S, 0);
+  for (int i = 0; i < n; ++i) {
+    const int s = stream_ids[i];
+    SC_CHECK_ARG(s >= 0 && s < b->S, "stream out of range");
+    SC_CHECK_ARG(!listed[s], "a stream is listed twice");
+    listed[s] = 1;
+    RC_TRY(beam_ready(b, s));
+  }
+  // [states: n][jobs: m] go up; [scores: m][2] doubles, [header: m][4], [ids: m][max_len], [frames: m][max_len] come back
+  const size_t o_jobs = (size_t)n * sizeof(sc_beam_t), o_sc = o_jobs + m * sizeof(sc_ctc_beam_pack_job),
+               o_head = o_sc + m * 2 * sizeof(double), o_ids = o_head + m * 4 * sizeof(int32_t),
+               o_frames = o_ids + m * max_len * sizeof(int32_t), need = o_frames + m * max_len * sizeof(int32_t);
+  if (need > b->bh_cap) {
+    HIP_TRY(hipStreamSynchronize(b->stream_rb));
+    if (b->bh_dev) (void)hipFree(b->bh_dev);
+    if (b->bh_host) (void)hipHostFree(b->bh_host);
+    const size_t cap = std::max(need, 2 * b->bh_cap);
+    b->bh_dev = b->bh_host = nullptr;
+    b->bh_cap = 0;
+    HIP_TRY(hipMalloc((void **)&b->bh_dev, cap));
+    HIP_TRY(hipHostMalloc((void **)&b->bh_host, cap));
+    b->bh_cap = cap;
+  }
+  sc_beam_t *st_host = (sc_beam_t *)b->bh_host;
+  sc_ctc_beam_pack_job *jobs = (sc_ctc_beam_pack_job *)(b->bh_host + o_jobs);
+  for (int i = 0; i < n; ++i) {
+    const int s = stream_ids[i];
+    st_host[i] = b->beam.rep[s].v.d;
+    for (int r = 0; r < nbest; ++r) {
+      const size_t k = (size_t)i * nbest + r;
+      sc_ctc_beam_pack_job &j = jobs[k];
+      j.state = (const sc_beam_t *)b->bh_dev + i;
+      j.nodes = b->beam_nodes + (size_t)s * b->beam_ncap();
+      j.ids = (int32_t *)(b->bh_dev + o_ids) + k * max_len;
+      j.frames = (int32_t *)(b->bh_dev + o_frames) + k * max_len;
+      j.header = (int32_t *)(b->bh_dev + o_head) + k * 4;
+      j.scores = (double *)(b->bh_dev + o_sc) + k * 2;
+      j.capacity = (int32_t)b->beam_ncap(); j.rank = r; j.max_len = max_len; j.reserved = 0;
+    }
+  }
+  // (the groups that stored the nodes of these states have been retired; later groups write behind them)
+  HIP_TRY(hipMemcpyAsync(b->bh_dev, b->bh_host, o_sc, hipMemcpyHostToDevice, b->stream_rb));
+  RC_TRY(sc_ctc_beam_pack((const sc_ctc_beam_pack_job *)(b->bh_dev + o_jobs), (int)m, b->stream_rb));
+  HIP_TRY(hipMemcpyAsync(b->bh_host + o_sc, b->bh_dev + o_sc, need - o_sc, hipMemcpyDeviceToHost, b->stream_rb));
+  HIP_TRY(hipStreamSynchronize(b->stream_rb));
+  memcpy(header, b->bh_host + o_head, m * 4 * sizeof(int32_t));
+  if (scores) memcpy(scores, b->bh_host + o_sc, m * 2 * sizeof(double));
+  // (only [0, min(len, max_len)) of a row is written by the launch: the rest of the caller's rows is left as it is)
+  for (size_t k = 0; k < m; ++k) {
+    const int32_t *h = (const int32_t *)(b->bh_host + o_head) + k * 4;
+    const size_t L = (size_t)std::max(0, std::min(h[0], max_len));
+    if (ids) memcpy(ids + k * max_len, (const int32_t *)(b->bh_host + o_ids) + k * max_len, L * sizeof(int32_t));
+    if (frames) memcpy(frames + k * max_len, (const int32_t *)(b->bh_host + o_frames) + k * max_len, L * sizeof(int32_t));
+  }
+  return SC_OK;
   SC_API_END
 }
 

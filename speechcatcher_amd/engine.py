@@ -35,6 +35,7 @@ import torch
 from .activity import INITIAL, advance as activity_advance, as_arrays as activity_arrays
 from . import spotting
 from . import draft as draft_mod
+from . import ctc_beam as beam_mod
 from . import commit as commit_mod
 from .config import SearchConfig
 from .weights import PackedWeights
@@ -274,6 +275,7 @@ class StreamBatch:
         self._act = None   # acoustic activity (set_activity): off
         self._spot = None  # phrase spotting (set_phrases): off
         self._draft = None  # draft transcript (set_draft): off
+        self._beam = None   # CTC prefix beam search (set_ctc_beam): off
         # wire-format input (set_input_format): per stream with a format its (format, channels, channel, scale), the
         # cumulative level of its utterance (None: nothing yet), and the streams whose last chunk was final
         self._in_fmt: Dict[int, tuple] = {}
@@ -369,6 +371,9 @@ class StreamBatch:
         if self._draft is not None:
             self._draft["state"][s] = draft_mod.initial()
             self._draft["proj"][s] = ns.T_ctc
+        if self._beam is not None:
+            self._beam["state"][s] = None
+            self._beam["proj"][s] = ns.T_ctc
         if getattr(self, "stream", None) is not None:
             with torch.cuda.stream(self.stream):   # same stream as the kernels that read it
                 self._init_hyp(s)
@@ -548,12 +553,49 @@ class StreamBatch:
             raise EngineError("the draft option is off (set_draft)")
         return draft_mod.tokens_of(self._draft["state"][int(s)])
 
+    # ------------------------------------------------------------------
+    # CTC prefix beam search (the native engine: sc_streams_set_ctc_beam)
+    # ------------------------------------------------------------------
+    def set_ctc_beam(self, beam: int = 8, candidates: int = 8):
+        """CTC prefix beam search from the CTC table: with beam >= 1 every chunk step projects the CTC rows of the frames
+        its encoder stage emits right away (as set_activity does) and searches them with sc_ctc_beam, one launch for the
+        step's streams; the attention search is not touched.  beam = 0: off.  Every stream's state starts over."""
+        if not beam:
+            self._beam = None
+            return
+        if not hasattr(self.be, "ctc_beam"):
+            raise EngineError("set_ctc_beam needs the HIP backend (sc_ctc_beam)")
+        if not (1 <= int(beam) <= 16 and 1 <= int(candidates) <= 16):
+            raise EngineError("set_ctc_beam: beam and candidates must lie in [1, 16]")
+        self._beam = {"B": int(beam), "C": int(candidates), "state": [None] * self.S,
+                      "proj": np.asarray([x.T_ctc for x in self.st], np.int64)}
+
+    def _beam_state(self, s: int) -> dict:
+        if self._beam is None:
+            raise EngineError("the beam option is off (set_ctc_beam)")
+        st = self._beam["state"][int(s)]
+        return dict(beam_mod.initial(), nodes=[(-1, -1, -1)]) if st is None else st
+
+    def ctc_beam(self, streams: Sequence[int]):
+        """[{n_frames, n_bad, n_nodes, entries: [(node, last, len, parent, pb, pnb)] best first}] of the listed streams
+        after their last chunk"""
+        return [{k: v for k, v in self._beam_state(s).items() if k != "nodes"} for s in streams]
+
+    def ctc_beam_hyps(self, streams: Sequence[int], nbest: int = 1, max_len: Optional[int] = None):
+        """{stream: [{"ids", "frames", "pb", "pnb"}, best first]}: the first nbest entries of those states as token ids
+        with the frames of their first emission"""
+        out = {}
+        for s in streams:
+            st = self._beam_state(s)
+            out[int(s)] = beam_mod.hyps_of(st, st["nodes"], int(nbest))
+        return out
+
     def _scan_activity(self, t_old: Dict[int, int]):
         """The frames [t_old[s], T_enc) the encoder stage of this chunk step emitted: CTC rows, then blank posteriors in
         torch float64 and the activity state update (set_activity) and / or the spotting recurrence (set_phrases) and / or
         the draft's greedy collapse (set_draft)."""
-        a, sp, dr, cfg = self._act, self._spot, self._draft, self.cfg
-        on = [o for o in (a, sp, dr) if o is not None]
+        a, sp, dr, bm, cfg = self._act, self._spot, self._draft, self._beam, self.cfg
+        on = [o for o in (a, sp, dr, bm) if o is not None]
         proj = on[0]["proj"]   # (all options project the same rows: one watermark)
         spans = []
         for s, t0 in t_old.items():
@@ -569,6 +611,13 @@ class StreamBatch:
         ar = self._itensor(rows)
         V, m = cfg.vocab_size, int(rows.shape[0])
         self.be.gemm(self.enc, ar, cfg.d_model, self.w.ctc_w, self.w.ctc_b, self.ctcx, ar, V, m, V, cfg.d_model)
+        if bm is not None:   # one sc_ctc_beam launch over the step's spans, on the table itself
+            tab = self.ctcx.view(self.S, self.TCAP, V)
+            cap = 1 + bm["B"] * self.TCAP
+            got, _ = self.be.ctc_beam([(tab[s], cfg.blank_id, c0, t1, bm["state"][s], cap, bm["B"], bm["C"])
+                                       for s, c0, t1 in spans], guard=0)
+            for (s, _, _), g in zip(spans, got):
+                bm["state"][s] = {k: g[k] for k in ("n_frames", "n_bad", "n_nodes", "entries", "nodes")}
         x32 = self.ctcx[torch.as_tensor(rows, dtype=torch.int64, device=self.dev)]
         if sp is not None or dr is not None:
             xs, o = x32.cpu().numpy(), 0
@@ -835,7 +884,8 @@ class StreamBatch:
         if enc_streams:
             t_ph = time.perf_counter()
             t_old = ({s: self.st[s].T_enc for s in enc_streams}
-                     if self._act is not None or self._spot is not None or self._draft is not None else None)
+                     if self._act is not None or self._spot is not None or self._draft is not None
+                     or self._beam is not None else None)
             self._encode(enc_streams, feat_new, finals)
             if t_old is not None:
                 self._scan_activity(t_old)

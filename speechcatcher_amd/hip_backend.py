@@ -503,6 +503,124 @@ class HipBackend:
             aft.append(tuple(int(v) for v in after[k]["i"]) + (float(after[k]["conf"]),))
         return out, aft
 
+    _BEAM_ST = [("i", "<i4", 4), ("e", [("i", "<i4", 4), ("p", "<f8", 2)], 16)]   # sc_beam_t
+
+    @classmethod
+    def _beam_pack_state(cls, st, rec):
+        """a state dict of ctc_beam -> rec (one element of the sc_beam_t array); "n_entries" (test aid): the stored count
+        when it is not len(entries)"""
+        ent = st["entries"]
+        rec["i"] = (st["n_frames"], st["n_bad"], st["n_nodes"], st.get("n_entries", len(ent)))
+        for r, e in enumerate(ent):
+            rec["e"][r]["i"] = e[:4]
+            rec["e"][r]["p"] = e[4:]
+
+    def ctc_beam(self, jobs, tweak=None, guard: int = 2):
+        """Batched CTC prefix beam search (sc_ctc_beam) on the caller's tables, one launch for all jobs.  jobs: list of
+        (table [T, V] fp32 tensor, rows may be strided; blank; t0; t1; state: a dict as returned here or None = the span
+        starts an utterance; capacity of the node store; B; C).  Returns (states: list of {n_frames, n_bad, n_nodes,
+        entries: [(node, last, len, parent, pb, pnb)] best first, nodes: the stored (parent, token, frame), raw_state: the
+        sc_beam_t as a numpy record, raw_nodes: the store and ``guard`` slots behind it as int32 [., 4]}, states_after:
+        the second copies as numpy records).  ``tweak(k, job)``: test aid, edits the sc_ctc_beam_job of job k before the
+        launch.  A job that starts an utterance is handed a state and a store filled with -7 (the second copy always
+        is), so what it leaves unwritten shows."""
+        import numpy as np
+        n = len(jobs)
+        dev = self.device
+        st_dt = np.dtype(self._BEAM_ST)
+        assert st_dt.itemsize == C.sizeof(_abi.Beam) == 528 and C.sizeof(_abi.BeamNode) == 16
+        caps = [int(j[5]) for j in jobs]
+        off = np.concatenate([[0], np.cumsum([c + guard for c in caps])]).astype(np.int64)
+        state = np.zeros(max(n, 1), st_dt)
+        state.view(np.int32)[:] = -7
+        after = state.copy()
+        store = np.full((max(int(off[-1]), 1), 4), -7, np.int32)
+        for k, job in enumerate(jobs):
+            st = job[4]
+            if st is not None:
+                state[k]["e"]["i"] = (-1, -1, 0, -1)
+                state[k]["e"]["p"] = -np.inf
+                self._beam_pack_state(st, state[k])
+                for i, rec in enumerate(st["nodes"]):
+                    store[off[k] + i] = tuple(rec) + (0,)
+        state_d, after_d, store_d = (torch.as_tensor(a.view(np.uint8).copy()).to(dev) for a in (state, after, store))
+        tab = (_abi.BeamJob * max(1, n))()
+        for k, (table, blank, t0, t1, st, cap, B, Cn) in enumerate(jobs):
+            assert table.dtype == torch.float32 and table.dim() == 2 and table.stride(1) == 1
+            assert 0 <= t0 <= t1 <= table.shape[0]
+            j = tab[k]
+            j.table, j.state, j.state_after = table.data_ptr(), state_d.data_ptr() + 528 * k, after_d.data_ptr() + 528 * k
+            j.nodes = store_d.data_ptr() + 16 * int(off[k])
+            j.stride, j.V, j.blank, j.t0, j.t1 = table.stride(0), table.shape[1], int(blank), int(t0), int(t1)
+            j.restart, j.capacity, j.B, j.C = 1 if st is None else 0, int(cap), int(B), int(Cn)
+            if tweak is not None:
+                tweak(k, j)
+        tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+        self._chk(self.lib.sc_ctc_beam(tab_dev.data_ptr(), n, self._stream()), "sc_ctc_beam")
+        torch.cuda.synchronize(dev)
+        state, after = (a.cpu().numpy().view(st_dt) for a in (state_d, after_d))
+        store = store_d.cpu().numpy().view(np.int32).reshape(-1, 4)
+        out = []
+        for k in range(n):
+            r = state[k]
+            ne = max(0, min(int(r["i"][3]), _abi.BEAM_MAX))
+            d = {"n_frames": int(r["i"][0]), "n_bad": int(r["i"][1]), "n_nodes": int(r["i"][2]),
+                 "entries": [tuple(int(v) for v in e["i"]) + tuple(float(v) for v in e["p"]) for e in r["e"][:ne]],
+                 "raw_state": r.copy(), "raw_nodes": store[off[k]:off[k + 1]].copy()}
+            d["nodes"] = [tuple(int(v) for v in rec[:3]) for rec in d["raw_nodes"][:max(0, min(d["n_nodes"], caps[k]))]]
+            out.append(d)
+        return out, [after[k].copy() for k in range(n)]
+
+    def ctc_beam_pack(self, jobs, tweak=None, guard: int = 2):
+        """Entries of beam states as token sequences (sc_ctc_beam_pack), one launch for all jobs.  jobs: list of (state:
+        a dict as returned by ctc_beam; rank; max_len; capacity of the node store, None: len(state["nodes"])).  Returns
+        one dict per job: "len", "status", "node", "last", "pb", "pnb", "ids" / "frames" [min(len, max_len)], and "raw":
+        (header [4 + guard], scores [2 + guard], ids / frames [max_len + guard]) - every buffer is handed over filled
+        with -7, so what a job leaves unwritten shows.  ``tweak(k, job)``: test aid."""
+        import numpy as np
+        n = len(jobs)
+        dev = self.device
+        st_dt = np.dtype(self._BEAM_ST)
+        caps = [len(j[0]["nodes"]) if j[3] is None else int(j[3]) for j in jobs]
+        noff = np.concatenate([[0], np.cumsum([max(c, len(j[0]["nodes"])) for c, j in zip(caps, jobs)])]).astype(np.int64)
+        ooff = np.concatenate([[0], np.cumsum([int(j[2]) + guard for j in jobs])]).astype(np.int64)
+        state = np.zeros(max(n, 1), st_dt)
+        store = np.full((max(int(noff[-1]), 1), 4), -7, np.int32)
+        for k, (st, _, _, _) in enumerate(jobs):
+            state[k]["e"]["i"] = (-1, -1, 0, -1)
+            state[k]["e"]["p"] = -np.inf
+            self._beam_pack_state(st, state[k])
+            for i, rec in enumerate(st["nodes"]):
+                store[noff[k] + i] = tuple(rec) + (0,)
+        state_d, store_d = (torch.as_tensor(a.view(np.uint8).copy()).to(dev) for a in (state, store))
+        head = torch.full((max(n, 1), 4 + guard), -7, dtype=torch.int32, device=dev)
+        sc = torch.full((max(n, 1), 2 + guard), -7.0, dtype=torch.float64, device=dev)
+        ids = torch.full((max(int(ooff[-1]), 1),), -7, dtype=torch.int32, device=dev)
+        frames = torch.full((max(int(ooff[-1]), 1),), -7, dtype=torch.int32, device=dev)
+        tab = (_abi.BeamPackJob * max(1, n))()
+        for k, (st, rank, max_len, _) in enumerate(jobs):
+            j = tab[k]
+            j.state, j.nodes = state_d.data_ptr() + 528 * k, store_d.data_ptr() + 16 * int(noff[k])
+            j.ids, j.frames = ids.data_ptr() + 4 * int(ooff[k]), frames.data_ptr() + 4 * int(ooff[k])
+            j.header, j.scores = head[k].data_ptr(), sc[k].data_ptr()
+            j.capacity, j.rank, j.max_len, j.reserved = caps[k], int(rank), int(max_len), 0
+            if tweak is not None:
+                tweak(k, j)
+        tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+        self._chk(self.lib.sc_ctc_beam_pack(tab_dev.data_ptr(), n, self._stream()), "sc_ctc_beam_pack")
+        torch.cuda.synchronize(dev)
+        head, sc, ids, frames = (a.cpu().numpy() for a in (head, sc, ids, frames))
+        out = []
+        for k in range(n):
+            L = max(0, min(int(head[k, 0]), int(jobs[k][2])))
+            a = int(ooff[k])
+            out.append({"len": int(head[k, 0]), "status": int(head[k, 1]), "node": int(head[k, 2]), "last": int(head[k, 3]),
+                        "pb": float(sc[k, 0]), "pnb": float(sc[k, 1]), "ids": ids[a:a + L].tolist(),
+                        "frames": frames[a:a + L].tolist(),
+                        "raw": (head[k].copy(), sc[k].copy(), ids[a:int(ooff[k + 1])].copy(),
+                                frames[a:int(ooff[k + 1])].copy())})
+        return out
+
     def ctc_alternates(self, jobs, K: int, max_L=None, tweak=None, guard: int = 2):
         """Batched CTC token alternates (sc_ctc_alternates) on the caller's tables, one launch for all jobs.  jobs: list of
         (table [T, V] fp32 tensor, rows may be strided; blank; labels, start, end: int32 sequences of one length L).

@@ -464,6 +464,15 @@ class NativeStreamBatch:
             _abi.check(T, "sc_streams_read_ctc")
         return a[:T].copy()
 
+    def read_ctc_projected(self, s: int) -> np.ndarray:
+        """Test aid: the CTC rows projected for stream s's utterance so far, as the device holds them now -> [T, vocab]
+        (sc_streams_read_ctc_projected); raw logits for a decoder-free stream."""
+        a = np.zeros((self.TCAP, self.cfg.vocab_size), np.float32)
+        T = self.lib.sc_streams_read_ctc_projected(self.handle, int(s), a.ctypes.data, self.TCAP)
+        if T < 0:
+            _abi.check(T, "sc_streams_read_ctc_projected")
+        return a[:T].copy()
+
     # ---- acoustic activity (sc_streams_set_activity; DESIGN.md 8d) -----------------------------------------
     def set_activity(self, on: bool, blank_threshold: float = 0.8):
         """Per-stream speech activity from the CTC table: when on, every admission group scans the CTC rows it projects
@@ -589,6 +598,73 @@ class NativeStreamBatch:
             except _abi.ScasrError as e:
                 raise EngineError(str(e)) from e
         return [(t.id, t.start, t.end, t.conf) for t in tk[:n]]
+
+    def set_decoder(self, s: int, decoder: str = "full"):
+        """Decoder mode of stream s: "full" (the default) or "ctc" - a decoder-free stream, served from its CTC rows alone
+        (no decode blocks, no cross-attention K|V rows; everything else as for any stream).  Only on an idle stream that
+        has taken nothing of its utterance; the mode outlives ``reset``."""
+        mode = {"full": _abi.DECODER_FULL, "ctc": _abi.DECODER_NONE}[decoder]
+        try:
+            _abi.check(self.lib.sc_stream_set_decoder(self.handle, int(s), mode), "sc_stream_set_decoder")
+        except _abi.ScasrError as e:
+            raise EngineError(str(e)) from e
+
+    def decoder(self, s: int) -> str:
+        return "ctc" if self.lib.sc_stream_decoder(self.handle, int(s)) == _abi.DECODER_NONE else "full"
+
+    # ---- CTC prefix beam search (sc_streams_set_ctc_beam; DESIGN.md 8j) --------------------------------------
+    def set_ctc_beam(self, beam: int = 8, candidates: int = 8):
+        """CTC prefix beam search from the CTC table: with beam >= 1 every admission group searches the CTC rows it
+        projects (one extra launch per group) with `beam` entries and `candidates` tokens per frame; the attention search
+        is not touched.  beam = 0 switches it off (the default); only while no chunk is outstanding; every stream's state
+        starts over."""
+        try:
+            _abi.check(self.lib.sc_streams_set_ctc_beam(self.handle, int(beam), int(candidates)), "sc_streams_set_ctc_beam")
+        except _abi.ScasrError as e:
+            raise EngineError(str(e)) from e
+
+    def ctc_beam(self, streams: Sequence[int]):
+        """[{n_frames, n_bad, n_nodes, entries: [(node, last, len, parent, pb, pnb)] best first}] of the listed streams'
+        last reported chunks - the chunks whose hypotheses ``hypotheses`` returns."""
+        out = []
+        a = _abi.Beam()
+        for s in streams:
+            try:
+                _abi.check(self.lib.sc_stream_ctc_beam(self.handle, int(s), C.byref(a)), "sc_stream_ctc_beam")
+            except _abi.ScasrError as e:
+                raise EngineError(str(e)) from e
+            out.append({"n_frames": a.n_frames, "n_bad": a.n_bad, "n_nodes": a.n_nodes,
+                        "entries": [(e.node, e.last, e.len, e.parent, e.pb, e.pnb)
+                                    for e in a.e[:max(0, min(a.n_entries, _abi.BEAM_MAX))]]})
+        return out
+
+    def ctc_beam_hyps(self, streams: Sequence[int], nbest: int = 1, max_len: Optional[int] = None):
+        """{stream: [{"ids", "frames", "pb", "pnb", "node", "status"}, best first]}: the first nbest entries of those
+        states as token ids with the frames of their first emission - one launch and one copy back for all streams."""
+        n, nbest = len(streams), min(int(nbest), _abi.BEAM_MAX)
+        max_len = self.TCAP if max_len is None else int(max_len)
+        ids_in = np.asarray(list(streams), np.int32)
+        head = np.zeros((n, nbest, 4), np.int32)
+        ids, frames = np.zeros((n, nbest, max_len), np.int32), np.zeros((n, nbest, max_len), np.int32)
+        sc = np.zeros((n, nbest, 2), np.float64)
+        try:
+            _abi.check(self.lib.sc_ctc_beam_hyps(self.handle, ids_in.ctypes.data_as(_abi.c_int_p), n, nbest, max_len,
+                                                 head.ctypes.data, ids.ctypes.data, frames.ctypes.data, sc.ctypes.data),
+                       "sc_ctc_beam_hyps")
+        except _abi.ScasrError as e:
+            raise EngineError(str(e)) from e
+        out = {}
+        for i, s in enumerate(streams):
+            hy = []
+            for r in range(nbest):
+                L, status = int(head[i, r, 0]), int(head[i, r, 1])
+                if status == _abi.BEAM_PACK_NO_ENTRY:
+                    break
+                L = max(0, min(L, max_len))
+                hy.append({"ids": ids[i, r, :L].tolist(), "frames": frames[i, r, :L].tolist(), "pb": float(sc[i, r, 0]),
+                           "pnb": float(sc[i, r, 1]), "node": int(head[i, r, 2]), "status": status})
+            out[int(s)] = hy
+        return out
 
     def hypotheses_batch(self, streams: Sequence[int], nbest: Optional[int] = None):
         """{stream: [hypothesis dicts, best first]} for the listed streams, one device round trip for all."""

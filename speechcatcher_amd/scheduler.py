@@ -21,6 +21,7 @@ import numpy as np
 from .engine import StreamBatch
 from . import spotting
 from . import draft as draft_mod
+from . import ctc_beam as beam_mod
 from . import alternates as alternates_mod
 from . import commit as commit_mod
 from .activity import of_stream as activity_of_stream
@@ -93,12 +94,23 @@ class StableResults(LevelResults):
     stable: Optional[dict] = None
 
 
+class CtcBeamResults(StableResults):
+    """the results of a reply and ``ctc_nbest``: the n-best list of the CTC prefix beam search of the session's stream for
+    that chunk, best first - StreamScheduler(ctc_beam=B) or ctc_beam=(B, C).  Each entry is {"text", "ids",
+    "score": the prefix's log probability, "conf": its share of the listed mass, "tokens": [{"id", "start", "end":
+    encoder frames of the utterance (both inclusive; a token runs from its first emission to the frame before the next
+    token's), "start_s", "end_s": seconds of the utterance's audio, "token": its text when the scheduler has a token
+    list}]}.  For a decoder-free session (``open(decoder="ctc")``) the reply's results ARE the beam's best.  The
+    attributes of the other options are carried as well when those are on."""
+    ctc_nbest: Optional[list] = None
+
+
 class StreamScheduler:
     def __init__(self, batch: StreamBatch, token_list: Optional[List[str]] = None,
                  result_format: str = "native", reset_after_final: bool = True, reset_on_open: bool = True,
                  queue_depth: int = 1, align_final: bool = False, activity: bool = False, blank_threshold: float = 0.8,
                  phrases=None, min_scores=None, draft: bool = False, input_level: bool = False, alternates: int = 0,
-                 align_nbest: int = 1, stable_partials: bool = False):
+                 align_nbest: int = 1, stable_partials: bool = False, ctc_beam=None):
         """``queue_depth`` > 1 (C++ engine, ``pump``): up to that many queued chunks of a session are handed to the engine
         at a time (sc_streams_set_queue_depth) - for sessions whose audio is already there (files): the encoder stage of
         the next chunk runs beside the decoding of the current one.  Replies and their order per session do not change.
@@ -128,6 +140,11 @@ class StreamScheduler:
         # ``draft``: every reply (an exception aside) is a ``DraftResults`` (batch.set_draft), read before the stream is
         # reset after a final
         self.draft = False
+        # ``ctc_beam``: (B, C) when on - every reply (an exception aside) is a ``CtcBeamResults`` (batch.set_ctc_beam),
+        # read before the stream is reset after a final; sessions opened with decoder="ctc" are served from it alone
+        self.ctc_beam = None
+        self._ctc_sessions = set()
+        self._slot_dec: Dict[int, str] = {}
         # ``stable_partials``: every reply (an exception aside) is a ``StableResults``.  The scheduler owns one
         # commit.StablePrefix per session and asks the engine only for the tokens behind what that holds
         # (batch.hyps_delta: one call for all sessions of a reply round)
@@ -165,6 +182,8 @@ class StreamScheduler:
             self.enable_spotting(phrases, min_scores)
         if draft:
             self.enable_draft()
+        if beam_mod.params(ctc_beam):
+            self.enable_ctc_beam(*beam_mod.params(ctc_beam))
         if alternates:
             self.enable_alternates(alternates)
         if stable_partials:
@@ -186,6 +205,13 @@ class StreamScheduler:
         self.batch.set_draft(True)
         self.draft = True
 
+    def enable_ctc_beam(self, beam: int = beam_mod.DEFAULT[0], candidates: int = beam_mod.DEFAULT[1]):
+        """switch the ``ctc_beam`` option on (only while no chunk is at the engine; every stream's state starts over)"""
+        if not hasattr(self.batch, "set_ctc_beam"):
+            raise NotImplementedError("this batch has no CTC prefix beam search (set_ctc_beam)")
+        self.batch.set_ctc_beam(int(beam), int(candidates))
+        self.ctc_beam = (int(beam), int(candidates))
+
     def enable_stable_partials(self):
         """switch the ``stable_partials`` option on (every session's tracker starts over)"""
         if self.batch.W > commit_mod.MAX_HYPS:
@@ -206,12 +232,15 @@ class StreamScheduler:
 
     @property
     def _clocked(self) -> bool:   # the options that need the sessions' feature clocks
-        return self.align_final or self.spotting or self.draft
+        return self.align_final or self.spotting or self.draft or self.ctc_beam is not None
 
     # ---- session lifecycle -------------------------------------------------
     def open(self, sample_rate: int = 16000, format: int = pcm_mod.F32, channels: int = 1, channel: int = pcm_mod.MIX,
-             scale: int = pcm_mod.SCALE_FULL) -> int:
-        """``sample_rate``: rate of the PCM this session feeds (speechcatcher_amd.resample: 8000..48000 Hz; the C++
+             scale: int = pcm_mod.SCALE_FULL, decoder: str = "full") -> int:
+        """``decoder``: "full" - the attention search (the default) - or "ctc": a decoder-free session, served from the CTC
+        prefix beam search alone (needs the ``ctc_beam`` option and the C++ engine; its replies carry the beam's best as
+        their result; a slot goes back to "full" for a later session that does not ask).
+        ``sample_rate``: rate of the PCM this session feeds (speechcatcher_amd.resample: 8000..48000 Hz; the C++
         engine converts it to 16 kHz on the GPU).  A slot goes back to 16000 for a later session that does not ask.
         ``format`` / ``channels`` / ``channel`` / ``scale``: the wire format of what the session feeds
         (speechcatcher_amd.pcm; default: mono float samples in +-1).  With any other format ``feed`` takes the coded
@@ -219,11 +248,13 @@ class StreamScheduler:
         for a later session that does not ask."""
         sample_rate = check_input_rate(sample_rate)
         fmt = self._check_format(format, channels, channel, scale)
+        self._check_decoder(decoder)
         if not self._free:
             raise ServerBusy("Server busy: all stream slots are in use")
         slot = self._free[0]
         if self.reset_on_open:
             self.batch.reset(slot)
+        self._set_slot_decoder(slot, decoder)
         self._set_slot_rate(slot, sample_rate)
         self._set_slot_format(slot, fmt)
         self._free.popleft()
@@ -238,7 +269,46 @@ class StreamScheduler:
         self._stable.pop(sid, None)
         if fmt != _FLOAT_INPUT:
             self._fmt[sid] = fmt
+        if decoder == "ctc":
+            self._ctc_sessions.add(sid)
         return sid
+
+    def _check_decoder(self, decoder):
+        if decoder not in ("full", "ctc"):
+            raise ValueError(f'decoder must be "full" or "ctc", got {decoder!r}')
+        if decoder == "ctc" and self.ctc_beam is None:
+            raise ValueError('decoder="ctc" needs the ctc_beam option (StreamScheduler(ctc_beam=...))')
+        if decoder == "ctc" and self.alternates:
+            raise ValueError('decoder="ctc": token alternates rank the frames of a forced alignment against a decode '
+                             "block's rows, which a decoder-free session does not have")
+
+    def set_decoder(self, sid: int, decoder: str):
+        """Change the decoder of a session that has not fed any audio yet (the Vosk ``config`` message arrives after the
+        connection is made).  ValueError for an unknown value, without the ``ctc_beam`` option, or once audio has been fed."""
+        self._check_decoder(decoder)
+        if decoder == self.decoder(sid):
+            return
+        if self._rate[sid].fed:
+            raise ValueError("the decoder of a session can only be set before its first audio")
+        self._set_slot_decoder(self._slot_of[sid], decoder)
+        if decoder == "ctc":
+            self._ctc_sessions.add(sid)
+        else:
+            self._ctc_sessions.discard(sid)
+
+    def _set_slot_decoder(self, slot: int, decoder: str):
+        if self._slot_dec.get(slot, "full") == decoder:
+            return
+        if not hasattr(self.batch, "set_decoder"):
+            raise NotImplementedError('decoder="ctc": decoder-free streams are served by the C++ engine only')
+        try:
+            self.batch.set_decoder(slot, decoder)
+        except RuntimeError as e:     # e.g. a slot that is never reset (strict_reference) and has audio buffered
+            raise ValueError(f"decoder {decoder!r} cannot be set on this stream: {e}") from e
+        self._slot_dec[slot] = decoder
+
+    def decoder(self, sid: int) -> str:
+        return "ctc" if sid in self._ctc_sessions else "full"
 
     @staticmethod
     def _check_format(format, channels, channel, scale) -> tuple:
@@ -320,6 +390,7 @@ class StreamScheduler:
         self._fmt.pop(sid, None)
         self._spot_seen.pop(sid, None)
         self._stable.pop(sid, None)
+        self._ctc_sessions.discard(sid)
         if self.reset_on_open:
             self.batch.reset(slot)
         self._free.append(slot)
@@ -390,6 +461,10 @@ class StreamScheduler:
                 held = [self._stable.setdefault(sid, commit_mod.StablePrefix()).next_from for sid, _ in ask]
                 delta = self.batch.hyps_delta([slot for _, slot in ask], held,
                                               final=[slot for sid, slot in ask if meta[sid][1]])
+        beams = None
+        if self.ctc_beam is not None:   # ONE launch and one copy back for the round (sc_ctc_beam_hyps)
+            ask = [slot for (slot, _, _) in meta.values() if not isinstance(has[slot], Exception)]
+            beams = self.batch.ctc_beam_hyps(ask, self.ctc_beam[0]) if ask else {}
         for sid, (slot, fin, fa) in meta.items():
             if self._clocked and self._fed.get(sid):   # the stream's clock advances by the reported chunk
                 n, f = self._fed[sid].popleft()
@@ -407,7 +482,7 @@ class StreamScheduler:
                 out[sid] = hyps_to_results(_select_hyps(arrays, row[slot], fin, fa), fin, fa, self.token_list, self.result_format)
             else:
                 out[sid] = hyps_to_results(hyps[slot], fin, fa, self.token_list, self.result_format)
-            if fin and self.align_final and not isinstance(out[sid], Exception):
+            if fin and self.align_final and not isinstance(out[sid], Exception) and sid not in self._ctc_sessions:
                 out[sid] = self._aligned(out[sid], arrays, row[slot] if arrays is not None and has[slot] is True else None,
                                          slot, fin, fa, self._clock.get(sid))
             if act is not None:
@@ -441,11 +516,67 @@ class StreamScheduler:
                     setattr(res, k, getattr(out[sid], k, None))
                 res.stable = self._stable[sid].update(delta[slot], final=fin).state()   # (a final starts the tracker over)
                 out[sid] = res
+            if beams is not None:
+                nbest = self._ctc_nbest(sid, beams[slot])
+                # a decoder-free session: its results are the beam's entries, best first (a chunk the engine answers with
+                # nothing stays [])
+                free = sid in self._ctc_sessions
+                res = CtcBeamResults(self._ctc_results(nbest) if free and has[slot] else out[sid])
+                for k in ("alignment", "activity", "detections", "draft", "ahead", "level", "stable"):
+                    setattr(res, k, getattr(out[sid], k, None))
+                res.ctc_nbest = nbest
+                if free and fin and self.align_final and len(res):
+                    res.alignment = self._ctc_alignment(res)
+                out[sid] = res
             if fin and self.reset_after_final:
                 self.batch.reset(slot)
                 self._clock.pop(sid, None)
                 self._spot_seen.pop(sid, None)
         return out
+
+    def _ctc_nbest(self, sid: int, hyps: list) -> list:
+        """the n-best list of the session's beam (``hyps``: its entries as batch.ctc_beam_hyps gives them): frames, and
+        seconds by the session's feature clock"""
+        cfg = self.batch.cfg
+        out = beam_mod.nbest(hyps, names=self.token_list)
+        clock = self._clock.get(sid) or FeatureClock(cfg.win_length, cfg.hop_length)
+        for entry, h in zip(out, hyps):
+            secs = beam_mod.token_dicts(h, clock, cfg.subsample, cfg.sample_rate)
+            for d, t in zip(entry["tokens"], secs):
+                d["start_s"], d["end_s"] = t["start"], t["end"]
+        return out
+
+    def _ctc_results(self, nbest: list) -> list:
+        """the beam's entries as the results of a reply, best first, in the scheduler's result format - the reply's text is
+        the beam's best; no result while the best prefix is empty, and an empty prefix further down is left out"""
+        if not nbest or not nbest[0]["ids"]:
+            return []
+        out = []
+        for e in nbest:
+            if not e["ids"]:
+                continue
+            toks = [t.get("token", str(t["id"])) for t in e["tokens"]]
+            if self.result_format == "espnet":
+                out.append((e["text"], toks, list(e["ids"]), [t["start"] for t in e["tokens"]], e))
+            else:
+                out.append((e["text"], toks, list(e["ids"])))
+        return out
+
+    def _ctc_alignment(self, res: list) -> dict:
+        """``align_final`` for a decoder-free session: sc_align_tokens aligns against the rows of a stream's last decode
+        block, which such a stream does not have, so the times are the prefix tree's - a token runs from the frame at
+        which its prefix entered the beam to the frame before the next token's; conf 1.0 (the search gives a probability
+        per prefix, none per token).  The shape of result_token_alignment, "nbest" with ``align_nbest`` > 1."""
+        def one(entry):
+            t = entry["tokens"]
+            return {"token_ids": [d["id"] for d in t], "start_s": [d["start_s"] for d in t],
+                    "end_s": [d["end_s"] for d in t], "conf": [1.0] * len(t), "source": "ctc_beam"}
+
+        entries = [r[4] for r in res] if self.result_format == "espnet" else [e for e in res.ctc_nbest if e["ids"]]
+        al = one(entries[0])
+        if self.align_nbest > 1:
+            al["nbest"] = [dict(al)] + [one(e) for e in entries[1:self.align_nbest]]
+        return al
 
     def _draft_tokens(self, sid: int, slot: int) -> list:
         """the draft of the session's stream as token dicts: frames, and seconds by the session's feature clock"""
@@ -591,7 +722,8 @@ def _select_hyps(a: dict, i: int, is_final: bool, finalize_all: bool) -> List[di
 def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tuple[int, int]],
                        chunk_length: int = 8192, token_list: Optional[List[str]] = None,
                        frames_per_second: float = 24.0, finalize_all_last_only: bool = False,
-                       queue_depth: int = 1, token_alignment: bool = False, token_alternates: int = 0) -> List[dict]:
+                       queue_depth: int = 1, token_alignment: bool = False, token_alternates: int = 0,
+                       ctc_beam=None, ctc_only: bool = False) -> List[dict]:
     """Decode the (start, end) sample ranges of one recording as PARALLEL streams
     of one batch instead of the reference's process pool over segments
     (speechcatcher/speechcatcher.py:474-497, chunk loop :574-592; SURVEY 8(f)
@@ -601,20 +733,29 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
     (speechcatcher.py:48,509-536).  ``token_alignment`` (C++ engine): every segment also gets ``token_start`` /
     ``token_end`` / ``token_conf`` per token, from a CTC forced alignment of its result (seconds of the recording; None
     for a token without one).  ``token_alternates`` = K > 0 (implies ``token_alignment``): also ``token_alternates``,
-    one record per token with its K acoustic alternates (speechcatcher_amd.alternates)."""
+    one record per token with its K acoustic alternates (speechcatcher_amd.alternates).  ``ctc_beam`` = B or (B, C): every
+    segment also gets ``ctc_nbest``, the n-best list of the CTC prefix beam search over it ({"text", "score", "conf"} per
+    entry, best first).  ``ctc_only`` (implies ``ctc_beam``, default (8, 8)): the segments are decoder-free
+    streams - text, tokens and token_timestamps are the beam's best, token_start / token_end the prefix tree's frames; not
+    with ``token_alternates``."""
     token_alignment = token_alignment or token_alternates > 0
+    if ctc_only and token_alternates:
+        raise ValueError("ctc_only: token alternates rank the frames of a forced alignment against a decode block's rows, "
+                         "which a decoder-free stream does not have")
+    if ctc_only and not beam_mod.params(ctc_beam):
+        ctc_beam = beam_mod.DEFAULT
     # queue_depth > 1 (C++ engine): that many chunks of a segment at the engine - the audio is all there.  Measured: worth
     # +6..12 % when the search is decode-heavy (no block-boundary detection, <= 32 segments), nothing to -8 % with
     # detection on (the CLI's default), hence off by default (DESIGN section 4)
     sch = StreamScheduler(batch, token_list, result_format="espnet", queue_depth=queue_depth, align_final=token_alignment,
-                          alternates=token_alternates)
+                          alternates=token_alternates, ctc_beam=ctc_beam)
     out: List[Optional[dict]] = [None] * len(segments)
     todo = list(enumerate(segments))
     sid_to_seg: Dict[int, int] = {}
     while todo or sch.n_active:
         while todo and sch._free:
             idx, (a, b) = todo.pop(0)
-            sid = sch.open()
+            sid = sch.open(decoder="ctc" if ctc_only else "full")
             sid_to_seg[sid] = idx
             seg = speech[a:b]
             for pos in range(0, len(seg), chunk_length):
@@ -640,6 +781,9 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
                 else:
                     out[idx] = {"text": "", "tokens": [], "token_ids": [], "token_timestamps": [],
                                 "score": 0.0, "start": start_s}
+                if sch.ctc_beam is not None:   # (a list of one n-best per segment: paragraphs append them)
+                    out[idx]["ctc_nbest"] = [[{"text": e["text"], "score": e["score"], "conf": e["conf"]}
+                                              for e in (getattr(res, "ctc_nbest", None) or [])]]
                 if token_alignment:
                     al = getattr(res, "alignment", None) if res else None
                     n = len(out[idx]["tokens"])

@@ -212,7 +212,8 @@ def interpolate_repeating_positions(positions: List[float]) -> List[float]:
 
 
 # --token-alignment, and with --token-alternates the per-token records (recognize_segments)
-ALIGNMENT_KEYS = ("token_start", "token_end", "token_conf", "token_alternates")
+# ... and with --ctc-beam / --ctc-only the n-best list of every segment
+ALIGNMENT_KEYS = ("token_start", "token_end", "token_conf", "token_alternates", "ctc_nbest")
 
 
 def merge_paragraphs(segments: List[dict]) -> Tuple[str, List[dict]]:
@@ -244,7 +245,8 @@ def merge_paragraphs(segments: List[dict]) -> Tuple[str, List[dict]]:
 def recognize_recording_segments(batch, raw_speech_data: np.ndarray, rate: int = 16000, chunk_length: int = 8192,
                                  token_list: Optional[List[str]] = None, reference_finalize: bool = False,
                                  average_segment_length: float = 60.0, token_alignment: bool = False,
-                                 segmentation: str = "host", token_alternates: int = 0):
+                                 segmentation: str = "host", token_alternates: int = 0, ctc_beam=None,
+                                 ctc_only: bool = False):
     """The segment loop of ``recognize`` (speechcatcher.py:414-497): int16 recording -> chunk-aligned sample
     ranges and the raw per-segment results of ``recognize_segments`` (before paragraph merging)."""
     assert rate == 16000
@@ -256,14 +258,15 @@ def recognize_recording_segments(batch, raw_speech_data: np.ndarray, rate: int =
     ranges = plan_segments(len(speech), rate, segments, chunk_length)
     res = recognize_segments(batch, speech, ranges, chunk_length=chunk_length, token_list=token_list,
                              finalize_all_last_only=reference_finalize, token_alignment=token_alignment,
-                             token_alternates=token_alternates)
+                             token_alternates=token_alternates, ctc_beam=ctc_beam, ctc_only=ctc_only)
     return ranges, res
 
 
 def recognize_recording(batch, raw_speech_data: np.ndarray, rate: int = 16000, chunk_length: int = 8192,
                         token_list: Optional[List[str]] = None, reference_finalize: bool = False,
                         average_segment_length: float = 60.0, token_alignment: bool = False,
-                        segmentation: str = "host", token_alternates: int = 0) -> Tuple[str, List[dict]]:
+                        segmentation: str = "host", token_alternates: int = 0, ctc_beam=None,
+                        ctc_only: bool = False) -> Tuple[str, List[dict]]:
     """int16 recording -> (text, per-paragraph info).  Native-decoder input scaling
     /32768 in fp32 (speechcatcher.py:421); recordings over a minute are segmented;
     the segments run as parallel streams of ``batch`` (one slot = the reference CLI with one worker:
@@ -273,10 +276,12 @@ def recognize_recording(batch, raw_speech_data: np.ndarray, rate: int = 16000, c
     ``token_conf`` (CTC forced alignment, next to ``token_timestamps``).  ``segmentation="gpu"``: the energy curve the
     cut search reads comes from the GPU (csrc/segment.hip) instead of the host pass.  ``token_alternates`` = K > 0
     (implies ``token_alignment``): they also carry ``token_alternates``, one record per token with its K acoustic alternates
-    (speechcatcher_amd.alternates)."""
+    (speechcatcher_amd.alternates).  ``ctc_beam`` = B or (B, C): they also carry ``ctc_nbest``, per segment the n-best
+    list of the CTC prefix beam search; ``ctc_only``: the segments are decoded by that search alone (recognize_segments)."""
     ranges, res = recognize_recording_segments(batch, raw_speech_data, rate, chunk_length, token_list,
                                                reference_finalize, average_segment_length,
-                                               token_alignment or token_alternates > 0, segmentation, token_alternates)
+                                               token_alignment or token_alternates > 0, segmentation, token_alternates,
+                                               ctc_beam, ctc_only)
     segs = [{"start": lo / rate, "end": hi / rate, "text": r["text"], "tokens": r["tokens"],
              "token_timestamps": r["token_timestamps"], **{k: r[k] for k in ALIGNMENT_KEYS if k in r}}
             for (lo, hi), r in zip(ranges, res)]

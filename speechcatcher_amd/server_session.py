@@ -226,7 +226,7 @@ class ServerLoop:
                  acoustic_endpointing: Optional[EndpointRules] = None, spotting: Optional[dict] = None,
                  spotting_min_scores: Optional[dict] = None, draft_partials: bool = False, raw_input: bool = False,
                  input_level: bool = False, vosk_alternatives: int = 0, token_alternates: int = 0,
-                 stable_partials: bool = False):
+                 stable_partials: bool = False, ctc_beam=None):
         """``strict_reference``: no stream reset after a finalised utterance nor between clients, exactly like
         ``recognize_ws`` / ``process_audio_chunk`` (speechcatcher_server.py:270,359-397); the default resets.
         ``continuous`` (default: on whenever the batch has the C++ engine's submit / poll - round 4; False forces one
@@ -274,7 +274,21 @@ class ServerLoop:
         option): ``stable`` is what every live hypothesis of the beam begins with - no later chunk of the
         utterance changes it and it only grows -, ``stability`` the share of the beam's mass behind each open token.
         The session keeps the committed text and puts only the newly committed tokens into text.  Composes with
-        ``draft_partials`` (the ``ahead`` keys stay).  Finals are unchanged.  False (default): partials as they are."""
+        ``draft_partials`` (the ``ahead`` keys stay).  Finals are unchanged.  False (default): partials as they are.
+        ``ctc_beam`` = B or (B, C) (C++ engine, Vosk format): the scheduler's ``ctc_beam`` option.  A
+        connection whose Vosk ``config`` carries ``"decoder": "ctc"`` before its first audio becomes a decoder-free session:
+        its partials and finals are built from the beam's best, ``max_alternatives`` = m > 0 (at most B; no
+        ``vosk_alternatives`` needed) from the beam's n-best with confidence = each entry's share of the listed mass, word
+        times from the prefix tree's frames with ``vosk_alignment``.  The endpointing rules are unchanged and operate on that
+        text.  ``"decoder": "full"`` goes back.  Counts the frames of an utterance from the reset after a final, so not with
+        ``strict_reference``.  None (default): the key is refused."""
+        from . import ctc_beam as beam_mod
+        if beam_mod.params(ctc_beam):
+            if strict_reference:
+                raise ValueError("the CTC prefix beam search counts the frames of an utterance from the reset after a final: "
+                                 "not with strict_reference")
+            if scheduler.ctc_beam is None:
+                scheduler.enable_ctc_beam(*beam_mod.params(ctc_beam))
         self.stable_partials = bool(stable_partials) and vosk_output_format
         if self.stable_partials and not scheduler.stable_partials:
             scheduler.enable_stable_partials()
@@ -329,6 +343,8 @@ class ServerLoop:
         self.vosk_alignment = vosk_alignment and vosk_output_format
         if self.vosk_alignment:
             scheduler.align_final = True
+            if scheduler.ctc_beam is not None:   # the alternatives of a decoder-free session: every entry's tree frames
+                scheduler.align_nbest = max(scheduler.align_nbest, scheduler.ctc_beam[0])
         self.fui, self.mpi = finalize_update_iters, max_partial_iters
         self.sessions: Dict[int, _Session] = {}
 
@@ -409,13 +425,19 @@ class ServerLoop:
                     cfg = json.loads(message).get("config", {})
                     rate = cfg.get("sample_rate", ses.vosk_sample_rate)
                     wire = self._config_format(ses, cfg)
-                    max_alt = self._config_alternatives(ses, cfg)
+                    if not isinstance(cfg, dict):
+                        raise AttributeError("config")
+                    decoder = cfg.get("decoder", self.sch.decoder(ses.sid))
+                    if decoder not in ("full", "ctc"):
+                        raise ValueError(f'decoder must be "full" or "ctc", got {decoder!r}')
+                    max_alt = self._config_alternatives(ses, cfg, decoder)
                 except (AttributeError, json.JSONDecodeError):
                     return vosk_partial("")
                 # honoured for every rate the engine converts (8000..48000 Hz: speechcatcher_amd.resample) and every
                 # wire format it decodes (speechcatcher_amd.pcm), before the session's first audio; ValueError
                 # otherwise - this client's error reply (step)
                 # - and both or neither: a rate whose format is refused does not stay
+                self.sch.set_decoder(ses.sid, decoder)   # (the first of the three: a refusal leaves nothing changed)
                 old_rate = self.sch.sample_rate(ses.sid)
                 self.sch.set_sample_rate(ses.sid, rate)
                 if wire is not None:
@@ -475,15 +497,17 @@ class ServerLoop:
         pcm_mod.check_args(fmt, channels, channel, scale)
         return (fmt, channels, channel, scale)
 
-    def _config_alternatives(self, ses: _Session, cfg: dict) -> int:
-        """the ``max_alternatives`` a Vosk ``config`` asks for, at most ``vosk_alternatives`` (the session's own when the
-        message names none; 0 with the option off); ValueError for anything but a non-negative integer"""
-        if "max_alternatives" not in cfg or not self.vosk_alternatives:
-            return ses.max_alternatives
+    def _config_alternatives(self, ses: _Session, cfg: dict, decoder: str = "full") -> int:
+        """the ``max_alternatives`` a Vosk ``config`` asks for, at most ``vosk_alternatives`` - for a decoder-free session
+        at most the beam's B - (the session's own when the message names none; 0 with the option off); ValueError for
+        anything but a non-negative integer"""
+        cap = self.sch.ctc_beam[0] if decoder == "ctc" and self.sch.ctc_beam else self.vosk_alternatives
+        if "max_alternatives" not in cfg or not cap:
+            return min(ses.max_alternatives, cap)
         m = cfg["max_alternatives"]
         if isinstance(m, bool) or not isinstance(m, int) or m < 0:
             raise ValueError(f"max_alternatives must be a non-negative integer, got {m!r}")
-        return min(m, self.vosk_alternatives)
+        return min(m, cap)
 
     def _final_message(self, ses: _Session, results: list) -> dict:
         """the Vosk final of a reply with results: the classic {"result", "text"}, or {"alternatives": [...]} for a
@@ -493,14 +517,16 @@ class ServerLoop:
         records = al.get("alternates") if self.token_alternates and al is not None else None
         if records is not None and len(records) != len(tokens):
             records = None
-        aligned = self.vosk_alignment or (ses.max_alternatives > 0 and self.vosk_alternatives > 0)
-        if ses.max_alternatives > 0 and self.vosk_alternatives > 0:
+        free = self.sch.decoder(ses.sid) == "ctc"   # its results are the beam's entries, its alignment the tree's frames
+        alts = ses.max_alternatives > 0 and (self.vosk_alternatives > 0 or free)
+        aligned = self.vosk_alignment or (alts and not free)
+        if alts:
             res = list(results[:ses.max_alternatives])
             nbest = (al or {}).get("nbest") or [al]
             texts, words = [], []
             for r, (_t, toks, _i, p, _h) in enumerate(res):
                 texts.append("".join(toks).replace("▁", " ").strip())
-                words.append(vosk_words(toks, p, nbest[r] if r < len(nbest) else None, True, records if r == 0 else None))
+                words.append(vosk_words(toks, p, nbest[r] if r < len(nbest) else None, aligned, records if r == 0 else None))
             return alternates_mod.vosk_alternatives(texts, [r[4]["score"] for r in res], words)
         if records is None:   # today's message
             if self.vosk_alignment and al is not None and any(a is not None for a in al["start_s"]):
