@@ -16,7 +16,7 @@
 //   top-K      K rounds of a block arg-max under (S descending, v ascending): thread-local over the entries not yet
 //              taken, wave butterfly, four pairs in LDS, every thread reads the winner.  own_rank is a block count.
 // No atomics; every output has one writer (thread 0); plain vector stores.  Table, labels and spans are only read.
-#include "common.h"
+#include "ctc_row.h"
 
 namespace {
 
@@ -94,7 +94,7 @@ __device__ __forceinline__ void alt_span(const sc_ctc_alt_job &j, int k, int K, 
 #pragma unroll
       for (int i = 0; i < NV; ++i) {
         if (i < nv) {
-          bad |= (x[i] != x[i]) || x[i] == INFINITY;
+          bad |= ctc_bad_value(x[i]);
           S[i] += (double)x[i];
           m = fmaxf(m, x[i]);
         }

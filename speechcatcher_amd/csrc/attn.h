@@ -1,4 +1,24 @@
-// Device helpers shared by the decoder attention kernels (search.hip, decoder_layer.hip):
+// Device helpers shared by the decoder kernels (search.hip, decoder_layer.hip, decoder_stream.hip):
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// 8 k-steps of one 32-wide k block for NA independent accumulators (per accumulator the steps run j = 0..7),
+// interleaved: consecutive MFMAs never share an accumulator (v_mfma_f32_16x16x4_f32 issues every 32 cycles per SIMD
+// but a dependent accumulate waits 40: with one wave per SIMD - small buckets - eight back-to-back steps on one
+// accumulator run at 80 % of the matrix rate)
+template <int NA>
+__device__ __forceinline__ void mfma8_il(f32x4 (&acc)[NA], const float4 &a0, const float4 &a1, const float4 (&b0)[NA],
+                                         const float4 (&b1)[NA]) {
+  const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+#pragma unroll
+    for (int t = 0; t < NA; ++t) {
+      const float4 &bb = j < 4 ? b0[t] : b1[t];
+      const float bj = (j & 3) == 0 ? bb.x : (j & 3) == 1 ? bb.y : (j & 3) == 2 ? bb.z : bb.w;
+      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], bj, acc[t], 0, 0, 0);
+    }
+}
+
 struct AttnState {
   float m, l;
   float4 a;
@@ -51,22 +71,20 @@ __device__ __forceinline__ void kv_store1(float *base, long elem, float v) {
 // A wave walks the tiles wave, wave+4, ... NT tiles at a time (two passes per batch: scores and their maximum,
 // then exponentials and P.V), so the online-softmax rescale happens once per batch.  Masked keys (not an
 // ancestor of the hypothesis / beyond the end) get probability 0.
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 template <int DK>
 struct MAttn {
-  f32x4v o[DK / 16];   // O^T: o[dt][jj] = dim (4*kg + jj) * NDT + dt of hypothesis n
+  f32x4 o[DK / 16];   // O^T: o[dt][jj] = dim (4*kg + jj) * NDT + dt of hypothesis n
   float m, l;          // running maximum (same in the 4 lanes of a hypothesis), this lane's share of the sum
 };
 template <int DK>
 __device__ __forceinline__ void mattn_init(MAttn<DK> &a) {
 #pragma unroll
-  for (int t = 0; t < DK / 16; ++t) a.o[t] = f32x4v{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < DK / 16; ++t) a.o[t] = f32x4{0.f, 0.f, 0.f, 0.f};
   a.m = -INFINITY;
   a.l = 0.f;
 }
 
 typedef _Float16 sc_half2 __attribute__((ext_vector_type(2)));
-typedef float sc_f32x4 __attribute__((ext_vector_type(4)));
 typedef float sc_f32x2 __attribute__((ext_vector_type(2)));
 template <int N, bool KVH>
 __device__ __forceinline__ void kv_loadn(const float *base, long elem, float *out) {
@@ -84,7 +102,7 @@ __device__ __forceinline__ void kv_loadn(const float *base, long elem, float *ou
     }
   } else {
     if (N == 4) {
-      const sc_f32x4 v = *reinterpret_cast<const sc_f32x4 *>(base + elem);
+      const f32x4 v = *reinterpret_cast<const f32x4 *>(base + elem);
       out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
     } else if (N == 2) {
       const sc_f32x2 v = *reinterpret_cast<const sc_f32x2 *>(base + elem);
@@ -138,10 +156,10 @@ __device__ __forceinline__ void mattn_batch(MAttn<DK> &st, const MBatch<DK, NT> 
   const int n = lane & 15;
 #pragma unroll
   for (int b0 = 0; b0 < NT; b0 += 2) {
-    f32x4v s[2];
+    f32x4 s[2];
     float mloc = -INFINITY;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) s[i] = f32x4v{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < 2; ++i) s[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     // k-steps outermost: consecutive MFMAs go to different tiles' accumulators (a dependent accumulate waits 40
     // cycles, the pipe issues every 32)
 #pragma unroll

@@ -58,6 +58,11 @@ struct ProfScope {
 ProfScope sc_prof_begin(hipStream_t st);
 void sc_prof_end(ProfScope &p, int kind, double flops, double bytes);
 
+// with an sc_search `sb` in scope: field f of stream s's ctrl row (scasr.h), and the per-index views of the ping-pong buffers
+#define CTRL(s, f) sb.ctrl[(s) * 8 + (f)]
+#define YSEQ(pp, s, h) (sb.yseq + (((long)(pp) * sb.S + (s)) * sb.W + (h)) * sb.LCAP)
+#define ANC(pp, s) (sb.anc + ((long)(pp) * sb.S + (s)) * sb.LCAP * sb.W)
+
 // search.hip: form of the decoder layers sc_decode_step picks for sb->n_rows (0 six-launch, 1 head-parallel, 2 stream-resident)
 int sc_decode_step_form(const sc_search *sb);
 // N / ncb products that share A in one launch, block j of the columns stored at C + j * cb_stride (gemm.hip)

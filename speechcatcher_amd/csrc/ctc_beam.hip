@@ -3,12 +3,12 @@
 // contract.
 //
 // One launch per call, one workgroup of BM_WAVES = 16 wave64 per job, the job's span [t0, t1) in tiles of BM_TILE frames:
-//   row pass   the waves take the tile's rows in turn.  Lanes stride over V with an online (max, sum of exp(x - max)) in
-//              float64, combined by an xor butterfly: lse.  The C candidates come in C rounds: every lane's best entry
-//              that lies BEHIND the previous round's winner in the order (x descending, index ascending), the wave's best
-//              of those by a butterfly whose merge prefers the lower index on equal values - exact in any order, ties
-//              included.  A lane keeps its first BM_CACHE entries in registers (V <= 1024: the whole row), the rounds
-//              read the rest again.  Lane 0 writes the candidate ids, their lp and lp(blank) to LDS; BM_BAD for a bad row.
+//   row pass   the waves take the tile's rows in turn: lse by the row pass of ctc_row.h, whose first batches also fill a
+//              lane's cache.  The C candidates come in C rounds: every lane's best entry that lies BEHIND the previous
+//              round's winner in the order (x descending, index ascending), the wave's best of those by a butterfly
+//              whose merge prefers the lower index on equal values - exact in any order, ties included.  A lane keeps
+//              its first BM_CACHE entries in registers (V <= 1024: the whole row), the rounds read the rest again.
+//              Lane 0 writes the candidate ids, their lp and lp(blank) to LDS; BM_BAD for a bad row.
 //   beam pass  wave 0 walks the tile frame by frame, the beam in LDS (two buffers).  Lane j holds entry j for the stay
 //              and looks its parent up among the <= 16 entries: the extension that merges into it is added to its pnb'
 //              and stamped in a (parent, candidate) table.  The lanes then hold the ne (nc + 1) items (entry, stay or
@@ -16,7 +16,7 @@
 //              all items (broadcast reads).  The items of rank < B are written to the other buffer at their rank; a
 //              __ballot over the new prefixes numbers their nodes, one lane each stores its record.
 // No atomics; every output has one writer; plain vector stores.  The table is only read.
-#include "common.h"
+#include "ctc_row.h"
 
 namespace {
 
@@ -46,49 +46,26 @@ __device__ __forceinline__ double lae(double a, double b) {
 // ids[0..count), lp[0..count) and *lp_blank
 __device__ __forceinline__ int row_candidates(const float *__restrict__ row, int V, int blank, int C, int lane, int *ids,
                                               double *lp, double *lp_blank) {
-  double m = -INFINITY, s = 0.0;
-  bool bad = false;
+  CtcRowAcc a;
   float xv[BM_CACHE];
 #pragma unroll
   for (int k = 0; k < BM_CACHE; ++k) xv[k] = -INFINITY;
-  // BM_UNROLL values per lane at a time: their loads are in flight together, the running sum is rescaled at most once
-  // per batch (to the batch's maximum)
+  // the row pass of ctc_row.h; the first BM_CACHE / BM_UNROLL batches also fill the cache.  (One lambda for both call
+  // sites: with the batch step written out at each the launch measured 3 % slower)
   auto batch = [&](int v0, float *keep) {
-    float xf[BM_UNROLL];
-    double x[BM_UNROLL];
+    ctc_row_batch<BM_UNROLL>(a, row, V, v0, [&](const float (&xf)[BM_UNROLL], int, bool) {
 #pragma unroll
-    for (int k = 0; k < BM_UNROLL; ++k) {
-      const int v = v0 + 64 * k;
-      xf[k] = v < V ? row[v] : -INFINITY;
-      x[k] = (double)xf[k];
-      if (keep) keep[k] = v == blank ? -INFINITY : xf[k];   // (the blank is no candidate: -inf in the cache)
-    }
-    double cm = x[0];
-#pragma unroll
-    for (int k = 0; k < BM_UNROLL; ++k) {
-      bad |= (x[k] != x[k]) || x[k] == INFINITY;
-      if (x[k] > cm) cm = x[k];
-    }
-    if (cm > m) {
-      s = m == -INFINITY ? 0.0 : s * exp(m - cm);
-      m = cm;
-    }
-    if (m > -INFINITY) {   // (a -inf entry adds exp(-inf) = 0; a bad row's sum is never used)
-#pragma unroll
-      for (int k = 0; k < BM_UNROLL; ++k) s += exp(x[k] - m);
-    }
+      for (int k = 0; k < BM_UNROLL; ++k)
+        if (keep) keep[k] = v0 + 64 * k == blank ? -INFINITY : xf[k];   // (the blank is no candidate: -inf in the cache)
+    });
   };
 #pragma unroll
   for (int b = 0; b < BM_CACHE / BM_UNROLL; ++b)
     if (lane + 64 * BM_UNROLL * b < V) batch(lane + 64 * BM_UNROLL * b, xv + BM_UNROLL * b);
   for (int v0 = lane + 64 * BM_CACHE; v0 < V; v0 += 64 * BM_UNROLL) batch(v0, nullptr);
-  const bool any_bad = __any(bad);
-  double M = m;
-  for (int o = 32; o > 0; o >>= 1) M = fmax(M, __shfl_xor(M, o));
-  if (any_bad || M == -INFINITY) return BM_BAD;   // (wave-uniform)
-  double sum = m == -INFINITY ? 0.0 : s * exp(m - M);
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-  const double lse = M + log(sum);
+  const CtcRowLse rl = ctc_row_combine(a);
+  if (rl.bad) return BM_BAD;   // (wave-uniform)
+  const double lse = rl.lse;
   if (lane == 0) *lp_blank = (double)row[blank] - lse;
   // round r: the best entry behind (pv, pi), the winner of round r - 1, in the order (x descending, index ascending)
   float pv = INFINITY;
@@ -142,10 +119,9 @@ __global__ __launch_bounds__(BM_WAVES * 64) void ctc_beam_kernel(const sc_ctc_be
   __shared__ int mrg[BM_MAX * BM_MAX];
   const sc_ctc_beam_job j = jobs[blockIdx.x];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  // a malformed job writes nothing (the host-side entry point cannot see the device table)
-  if (!j.table || !j.state || j.V < 1 || j.blank < 0 || j.blank >= j.V || j.t0 < 0 || j.t1 < j.t0 || j.stride < j.V ||
-      j.capacity < 0 || (j.capacity > 0 && !j.nodes) || j.B < 1 || j.B > BM_MAX || j.C < 1 || j.C > BM_MAX)
-    return;
+  if (!ctc_job_ok(j) || !j.state || j.stride < j.V || j.capacity < 0 || (j.capacity > 0 && !j.nodes) || j.B < 1 ||
+      j.B > BM_MAX || j.C < 1 || j.C > BM_MAX)
+    return;   // (a malformed job writes nothing)
   int stored = 1;
   if (!j.restart) {
     stored = j.state->n_entries;   // (every thread reads it: the decision is uniform over the workgroup)
@@ -355,21 +331,12 @@ __global__ __launch_bounds__(PK_THREADS) void ctc_beam_pack_kernel(const sc_ctc_
 }  // namespace
 
 extern "C" int sc_ctc_beam(const sc_ctc_beam_job *jobs, int n_jobs, void *stream) {
-  SC_CHECK_ARG(n_jobs >= 0, "negative job count");
-  SC_CHECK_ARG(n_jobs == 0 || jobs, "null job table");
-  SC_CHECK_ARG(n_jobs <= SC_BEAM_MAX_JOBS, "more than SC_BEAM_MAX_JOBS jobs");
-  if (n_jobs == 0) return SC_OK;
-  ctc_beam_kernel<<<n_jobs, BM_WAVES * 64, 0, (hipStream_t)stream>>>(jobs);
-  SC_CHECK_LAUNCH();
-  return SC_OK;
+  return ctc_launch_jobs(__func__, jobs, n_jobs, SC_BEAM_MAX_JOBS, "more than SC_BEAM_MAX_JOBS jobs",
+                         [&] { ctc_beam_kernel<<<n_jobs, BM_WAVES * 64, 0, (hipStream_t)stream>>>(jobs); });
 }
 
 extern "C" int sc_ctc_beam_pack(const sc_ctc_beam_pack_job *jobs, int n_jobs, void *stream) {
-  SC_CHECK_ARG(n_jobs >= 0, "negative job count");
-  SC_CHECK_ARG(n_jobs == 0 || jobs, "null job table");
-  SC_CHECK_ARG(n_jobs <= SC_BEAM_MAX_JOBS, "more than SC_BEAM_MAX_JOBS jobs");
-  if (n_jobs == 0) return SC_OK;
-  ctc_beam_pack_kernel<<<cdiv(n_jobs, PK_THREADS), PK_THREADS, 0, (hipStream_t)stream>>>(jobs, n_jobs);
-  SC_CHECK_LAUNCH();
-  return SC_OK;
+  return ctc_launch_jobs(__func__, jobs, n_jobs, SC_BEAM_MAX_JOBS, "more than SC_BEAM_MAX_JOBS jobs", [&] {
+    ctc_beam_pack_kernel<<<cdiv(n_jobs, PK_THREADS), PK_THREADS, 0, (hipStream_t)stream>>>(jobs, n_jobs);
+  });
 }

@@ -39,17 +39,12 @@
 #include "attn.h"
 #include <type_traits>
 
-#define CTRL(s, f) sb.ctrl[(s) * 8 + (f)]
-#define YSEQ(pp, s, h) (sb.yseq + (((long)(pp) * sb.S + (s)) * sb.W + (h)) * sb.LCAP)
-#define ANC(pp, s) (sb.anc + ((long)(pp) * sb.S + (s)) * sb.LCAP * sb.W)
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 dl_h4 __attribute__((ext_vector_type(4)));
 
 // fp16 decoder mode (WH; BASELINE configs[4], scasr.h: sc_dec_layer.wqkv_pph ...): the weight fragments are the fp16
 // copies (same fragment order, 8 bytes per lane and half k-block instead of 16), the A operands are rounded to fp16 on
 // their way from LDS, two v_mfma_f32_16x16x16_f16 cover the 8 k values a lane holds per 32-wide k block (fp32
-// accumulation).  The same 8 k-steps for NA independent accumulators, as dl_mfma8_il below.
+// accumulation).  The same 8 k-steps for NA independent accumulators, as mfma8_il of attn.h.
 template <int NA>
 __device__ __forceinline__ void dl_mfma8_il_h(f32x4 (&acc)[NA], const float4 &a0, const float4 &a1, const dl_h4 (&b0)[NA],
                                               const dl_h4 (&b1)[NA]) {
@@ -88,23 +83,6 @@ __device__ __forceinline__ f32x4 dl_mfma8(f32x4 acc, const float4 &a0, const flo
   acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, b1.z, acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, b1.w, acc, 0, 0, 0);
   return acc;
-}
-
-// the same 8 k-steps for NA independent accumulators, interleaved: consecutive MFMAs never share an accumulator
-// (v_mfma_f32_16x16x4_f32 issues every 32 cycles per SIMD but a dependent accumulate waits 40: with one wave per
-// SIMD - small buckets - eight back-to-back steps on one accumulator run at 80 % of the matrix rate)
-template <int NA>
-__device__ __forceinline__ void dl_mfma8_il(f32x4 (&acc)[NA], const float4 &a0, const float4 &a1, const float4 (&b0)[NA],
-                                            const float4 (&b1)[NA]) {
-  const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-#pragma unroll
-  for (int j = 0; j < 8; ++j)
-#pragma unroll
-    for (int t = 0; t < NA; ++t) {
-      const float4 &bb = j < 4 ? b0[t] : b1[t];
-      const float bj = (j & 3) == 0 ? bb.x : (j & 3) == 1 ? bb.y : (j & 3) == 2 ? bb.z : bb.w;
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], bj, acc[t], 0, 0, 0);
-    }
 }
 
 struct DecLayerArgs {
@@ -481,7 +459,7 @@ __global__ __launch_bounds__(256 * HPW, (UNR <= 4 && WM <= 10) ? (DK > 32 ? 2 : 
         BF n0[NTP], n1[NTP];
         if (kq + 1 < KPW) load_b(ki + 1, n0, n1);   // in flight during this k-block's MFMAs
         if constexpr (WH) dl_mfma8_il_h<NTP>(accp, a0, a1, b0, b1);
-        else dl_mfma8_il<NTP>(accp, a0, a1, b0, b1);
+        else mfma8_il<NTP>(accp, a0, a1, b0, b1);
 #if defined(SC_PROJ_STAMPS) && SC_PROJ_STAMPS == 2   // (9 / 10: thread 0's / the youngest wave's FIRST MFMA of the phase has its result - its fragments have arrived)
         if (ps == 0 && kq == 0) {
           asm volatile("s_nop 0" : "+v"(accp[0]));
@@ -682,7 +660,7 @@ __global__ __launch_bounds__(256 * HPW, (UNR <= 4 && WM <= 10) ? (DK > 32 ? 2 : 
       const float *ab = As + r * LDA + 32 * kb2 + 8 * kk;
       const float4 a0 = *reinterpret_cast<const float4 *>(ab), a1 = *reinterpret_cast<const float4 *>(ab + 4);
       if constexpr (WH) dl_mfma8_il_h<TW>(oacc, a0, a1, b0[kb2], b1[kb2]);
-      else dl_mfma8_il<TW>(oacc, a0, a1, b0[kb2], b1[kb2]);
+      else mfma8_il<TW>(oacc, a0, a1, b0[kb2], b1[kb2]);
     }
 #pragma unroll
     for (int t = 0; t < TW; ++t)

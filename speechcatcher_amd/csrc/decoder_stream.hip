@@ -33,30 +33,9 @@
 #include "attn.h"
 #include <type_traits>
 
-#define CTRL(s, f) sb.ctrl[(s) * 8 + (f)]
-#define YSEQ(pp, s, h) (sb.yseq + (((long)(pp) * sb.S + (s)) * sb.W + (h)) * sb.LCAP)
-#define ANC(pp, s) (sb.anc + ((long)(pp) * sb.S + (s)) * sb.LCAP * sb.W)
-
-typedef float ds_f32x4 __attribute__((ext_vector_type(4)));
-
-// 8 k-steps of one 32-wide k block for NA independent accumulators, interleaved (consecutive MFMAs never share an
-// accumulator); per accumulator the steps run j = 0..7 - the chain decoder_layer.hip's dl_mfma8_il builds
+// (mfma8_il of attn.h) with one A tile PER accumulator (the output projection: one accumulator per head)
 template <int NA>
-__device__ __forceinline__ void ds_mfma8_il(ds_f32x4 (&acc)[NA], const float4 &a0, const float4 &a1, const float4 (&b0)[NA],
-                                            const float4 (&b1)[NA]) {
-  const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-#pragma unroll
-  for (int j = 0; j < 8; ++j)
-#pragma unroll
-    for (int t = 0; t < NA; ++t) {
-      const float4 &bb = j < 4 ? b0[t] : b1[t];
-      const float bj = (j & 3) == 0 ? bb.x : (j & 3) == 1 ? bb.y : (j & 3) == 2 ? bb.z : bb.w;
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], bj, acc[t], 0, 0, 0);
-    }
-}
-// ... with one A tile PER accumulator (the output projection: one accumulator per head)
-template <int NA>
-__device__ __forceinline__ void ds_mfma8_heads(ds_f32x4 (&acc)[NA], const float4 (&a0)[NA], const float4 (&a1)[NA],
+__device__ __forceinline__ void ds_mfma8_heads(f32x4 (&acc)[NA], const float4 (&a0)[NA], const float4 (&a1)[NA],
                                                const float4 (&b0)[NA], const float4 (&b1)[NA]) {
 #pragma unroll
   for (int j = 0; j < 8; ++j)
@@ -184,16 +163,16 @@ __device__ __forceinline__ void ds_load2(DsTiles &b, const float *kv, int t0, in
 // (the matrix pipe works through them while the VALU does the masks, maxima and exponentials of batch k - with one monolithic
 // routine per batch a wave's matrix work stops for every softmax, and two waves per SIMD do not fill the holes by themselves:
 // 29 us for 21 us of matrix work in a probe whose loads all hit the L1).  Same instructions per accumulator, same order.
-__device__ __forceinline__ void ds_scores(f32x4v (&s)[2], const DsTiles &b, const float (&qb)[8]) {
+__device__ __forceinline__ void ds_scores(f32x4 (&s)[2], const DsTiles &b, const float (&qb)[8]) {
 #pragma unroll
-  for (int i = 0; i < 2; ++i) s[i] = f32x4v{0.f, 0.f, 0.f, 0.f};
+  for (int i = 0; i < 2; ++i) s[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int q = 0; q < 8; ++q)
 #pragma unroll
     for (int i = 0; i < 2; ++i) s[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(b.kr[i][q], qb[q], s[i], 0, 0, 0);
 }
 template <class RowFn>
-__device__ __forceinline__ void ds_finish(MAttn<32> &st, const DsTiles &b, f32x4v (&s)[2], int t0, int ntiles, int lane, RowFn rowfn) {
+__device__ __forceinline__ void ds_finish(MAttn<32> &st, const DsTiles &b, f32x4 (&s)[2], int t0, int ntiles, int lane, RowFn rowfn) {
   const int n = lane & 15, kg = lane >> 4;
   float mloc = -INFINITY;
 #pragma unroll
@@ -291,18 +270,18 @@ __global__ __launch_bounds__(512, 2) void dec_layer_stream_kernel(DecStreamArgs 
   // PRE: the fragments of k blocks 0 and 1 are in (b0, b1), (c0, c1) already
   auto proj_pass = [&](const float *wp, auto tile_of, auto &sum, auto &b0, auto &b1, auto &c0, auto &c1) {
     constexpr int NTP = sizeof(sum) / sizeof(sum[0]);
-    ds_f32x4 acc[NTP];
+    f32x4 acc[NTP];
 #pragma unroll
     for (int ki = 0; ki < KI; ++ki) {
       if ((ki & 1) == 0) {
 #pragma unroll
-        for (int t = 0; t < NTP; ++t) acc[t] = ds_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < NTP; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
       const float *ab = Xn + r * LDX + ki * 32 + 8 * kk;
       const float4 a0 = *reinterpret_cast<const float4 *>(ab), a1 = *reinterpret_cast<const float4 *>(ab + 4);
       float4 n0[NTP], n1[NTP];
       if (ki + 2 < KI) load_b(wp, tile_of, ki + 2, n0, n1);   // in flight during two k blocks of MFMAs
-      ds_mfma8_il<NTP>(acc, a0, a1, b0, b1);
+      mfma8_il<NTP>(acc, a0, a1, b0, b1);
 #pragma unroll
       for (int t = 0; t < NTP; ++t) {
         b0[t] = c0[t];
@@ -434,7 +413,7 @@ __global__ __launch_bounds__(512, 2) void dec_layer_stream_kernel(DecStreamArgs 
 
   // ------------------------------------------------------------------ q|k|v of this head: two passes of three column tiles
   {
-    ds_f32x4 s0[3], s1[3];
+    f32x4 s0[3], s1[3];
     proj_pass(p.wqkv, tile_qkv0, s0, qb0, qb1, qc0, qc1);
     load_b(p.wqkv, tile_qkv1, 0, qb0, qb1);
     load_b(p.wqkv, tile_qkv1, 1, qc0, qc1);
@@ -480,13 +459,13 @@ __global__ __launch_bounds__(512, 2) void dec_layer_stream_kernel(DecStreamArgs 
     auto ld = [&](DsTiles &b, int i) {
       if (i < nb) ds_load2<KVH>(b, kv, 8 * (i >> 2) + (i & 3), lane, rowfn);
     };
-    auto sc = [&](f32x4v (&sv)[2], const DsTiles &b, int i) {
+    auto sc = [&](f32x4 (&sv)[2], const DsTiles &b, int i) {
       if (i < nb) ds_scores(sv, b, qb);
     };
-    auto fin = [&](MAttn<DK> &stw, const DsTiles &b, f32x4v (&sv)[2], int i) {
+    auto fin = [&](MAttn<DK> &stw, const DsTiles &b, f32x4 (&sv)[2], int i) {
       if (i < nb) ds_finish(stw, b, sv, 8 * (i >> 2) + (i & 3), ntiles, lane, rowfn);
     };
-    f32x4v sA[2], sB[2];
+    f32x4 sA[2], sB[2];
     ld(B0, 0);
     ld(B1, 1);
     sc(sA, B0, 0);
@@ -543,7 +522,7 @@ __global__ __launch_bounds__(512, 2) void dec_layer_stream_kernel(DecStreamArgs 
     SC_STAMP(1, NP == 5 ? 3 : 7);
   };
   auto out_proj = [&](const float *wop, const float4 bv) {
-    ds_f32x4 y[2];
+    f32x4 y[2];
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       float4 a0[4], a1[4];
@@ -553,16 +532,16 @@ __global__ __launch_bounds__(512, 2) void dec_layer_stream_kernel(DecStreamArgs 
         a0[hh] = *reinterpret_cast<const float4 *>(ab);
         a1[hh] = *reinterpret_cast<const float4 *>(ab + 4);
       }
-      ds_f32x4 acc0[4], acc1[4];
+      f32x4 acc0[4], acc1[4];
 #pragma unroll
       for (int hh = 0; hh < 4; ++hh) {
-        acc0[hh] = ds_f32x4{0.f, 0.f, 0.f, 0.f};
-        acc1[hh] = ds_f32x4{0.f, 0.f, 0.f, 0.f};
+        acc0[hh] = f32x4{0.f, 0.f, 0.f, 0.f};
+        acc1[hh] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
       ds_mfma8_heads<4>(acc0, a0, a1, ob0[0], ob1[0]);
       ds_mfma8_heads<4>(acc1, a0, a1, ob0[1], ob1[1]);
       if (half == 0) out_fetch(wop, 1);   // (behind the MFMAs that read the registers)
-      ds_f32x4 g0 = acc0[0], g1 = acc1[0];
+      f32x4 g0 = acc0[0], g1 = acc1[0];
       g0 += acc0[1]; g0 += acc0[2]; g0 += acc0[3];
       g1 += acc1[1]; g1 += acc1[2]; g1 += acc1[3];
       if (half == 0) { y[0] = g0; y[1] = g1; }
@@ -643,7 +622,7 @@ __global__ __launch_bounds__(512, 2) void dec_layer_stream_kernel(DecStreamArgs 
 
   // ------------------------------------------------------------------ cross-attention: q of this head (two column tiles)
   {
-    ds_f32x4 sq[2];
+    f32x4 sq[2];
     proj_pass(p.wq, tile_q, sq, xb0, xb1, xc0, xc1);
     const float scale = sqrtf((float)DK);
 #pragma unroll

@@ -3,17 +3,17 @@
 // (DESIGN.md 8f).
 //
 // One launch per call, one workgroup of DR_WAVES = 16 wave64 per job, the job's span [t0, t1) in tiles of DR_TILE frames:
-//   row pass   the waves take the tile's rows in turn.  Lanes stride over V with an online (max, lowest arg-max index,
-//              sum of exp(x - max) in float64); the wave combines them by an xor butterfly whose arg-max merge prefers
-//              the lower index on equal maxima, so the label is exact in any order.  Lane 0 writes the label (DR_BAD for
-//              a bad row: a NaN, a +inf, or nothing but -inf) and p = exp(x[k] - lse) to LDS.
+//   row pass   the waves take the tile's rows in turn, each by the row pass of ctc_row.h with the lane's lowest arg-max
+//              index kept beside it; the wave's maximum comes from an xor butterfly whose arg-max merge prefers the
+//              lower index on equal maxima, so the label is exact in any order.  Lane 0 writes the label (DR_BAD for
+//              a bad row) and p = exp(x[k] - lse) to LDS.
 //   scan pass  wave 0 walks the tile 64 frames at a time, lane = frame.  The previous frame's label comes from __shfl_up
 //              (lane 0: the carried open token); __ballot of "opens a token" and "continues the previous frame's token"
 //              gives every run's slot (popcount), start and end (first unset continue bit above it); a segmented max
 //              over the run gives its conf.  A run that ends inside the batch is stored by its first lane, the carried
 //              token by lane 0; the run that reaches the last frame stays open in registers across batches and tiles.
 // No atomics; every output has one writer; plain vector stores.  The table is only read.
-#include "common.h"
+#include "ctc_row.h"
 
 namespace {
 
@@ -24,51 +24,19 @@ constexpr int DR_BAD = -2;     // label of a bad row (-1: a blank or bad frame a
 
 // label and posterior of one row, computed by one wave (every lane returns them); label DR_BAD: a bad row
 __device__ __forceinline__ int row_best(const float *__restrict__ row, int V, int lane, double *p_out) {
-  double m = -INFINITY, s = 0.0;
-  int idx = 0x7fffffff;
-  bool bad = false;
-  // DR_UNROLL values per lane at a time: their loads are in flight together, the running sum is rescaled at most once
-  // per batch (to the batch's maximum).  A lane sees its v ascending, so "strictly greater" keeps the lowest index
-  for (int v0 = lane; v0 < V; v0 += 64 * DR_UNROLL) {
-    double x[DR_UNROLL];
-#pragma unroll
-    for (int k = 0; k < DR_UNROLL; ++k) {
-      const int v = v0 + 64 * k;
-      x[k] = v < V ? (double)row[v] : -INFINITY;
-    }
-    double cm = x[0];
-    int ck = 0;
-#pragma unroll
-    for (int k = 0; k < DR_UNROLL; ++k) {
-      bad |= (x[k] != x[k]) || x[k] == INFINITY;
-      if (x[k] > cm) { cm = x[k]; ck = k; }
-    }
-    if (cm > m) {
-      s = m == -INFINITY ? 0.0 : s * exp(m - cm);
-      m = cm;
-      idx = v0 + 64 * ck;
-    }
-    if (m > -INFINITY) {   // (a -inf entry adds exp(-inf) = 0; a bad row's sum is never used)
-#pragma unroll
-      for (int k = 0; k < DR_UNROLL; ++k) s += exp(x[k] - m);
-    }
-  }
-  const bool any_bad = __any(bad);
-  double M = m;
-  int K = idx;
+  int K = 0x7fffffff;   // the lane's lowest arg-max index
+  const CtcRowAcc a = ctc_row_pass<DR_UNROLL>(row, V, lane, [&](const float (&)[DR_UNROLL], int vmax, bool rose) {
+    if (rose) K = vmax;
+  });
+  double M = a.m;
   for (int o = 32; o > 0; o >>= 1) {
     const double om = __shfl_xor(M, o);
     const int ok = __shfl_xor(K, o);
     if (om > M || (om == M && ok < K)) { M = om; K = ok; }
   }
-  if (any_bad || M == -INFINITY) {   // (wave-uniform)
-    *p_out = NAN;
-    return DR_BAD;
-  }
-  double sum = m == -INFINITY ? 0.0 : s * exp(m - M);
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-  *p_out = exp(M - (M + log(sum)));   // x[K] == M
-  return K;
+  const CtcRowLse r = ctc_row_combine(a, M);
+  *p_out = r.bad ? NAN : exp(M - r.lse);   // x[K] == M
+  return r.bad ? DR_BAD : K;
 }
 
 __device__ __forceinline__ void put_token(sc_draft_token *t, int id, int start, int end, double conf) {
@@ -80,10 +48,8 @@ __global__ __launch_bounds__(DR_WAVES * 64) void ctc_draft_kernel(const sc_ctc_d
   __shared__ int lab[DR_TILE];
   const sc_ctc_draft_job j = jobs[blockIdx.x];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  // a malformed job writes nothing (the host-side entry point cannot see the device table)
-  if (!j.table || !j.state || j.V < 1 || j.blank < 0 || j.blank >= j.V || j.t0 < 0 || j.t1 < j.t0 || j.stride < j.V ||
-      j.capacity < 0 || (j.capacity > 0 && !j.tokens))
-    return;
+  if (!ctc_job_ok(j) || !j.state || j.stride < j.V || j.capacity < 0 || (j.capacity > 0 && !j.tokens))
+    return;   // (a malformed job writes nothing)
 
   // the state, wave-uniform in wave 0's registers
   int n = 0, n_closed = 0, n_bad = 0, oid = -1, ost = -1, oen = -1;
@@ -178,11 +144,6 @@ __global__ __launch_bounds__(DR_WAVES * 64) void ctc_draft_kernel(const sc_ctc_d
 }  // namespace
 
 extern "C" int sc_ctc_draft(const sc_ctc_draft_job *jobs, int n_jobs, void *stream) {
-  SC_CHECK_ARG(n_jobs >= 0, "negative job count");
-  SC_CHECK_ARG(n_jobs == 0 || jobs, "null job table");
-  SC_CHECK_ARG(n_jobs <= SC_DRAFT_MAX_JOBS, "more than SC_DRAFT_MAX_JOBS jobs");
-  if (n_jobs == 0) return SC_OK;
-  ctc_draft_kernel<<<n_jobs, DR_WAVES * 64, 0, (hipStream_t)stream>>>(jobs);
-  SC_CHECK_LAUNCH();
-  return SC_OK;
+  return ctc_launch_jobs(__func__, jobs, n_jobs, SC_DRAFT_MAX_JOBS, "more than SC_DRAFT_MAX_JOBS jobs",
+                         [&] { ctc_draft_kernel<<<n_jobs, DR_WAVES * 64, 0, (hipStream_t)stream>>>(jobs); });
 }

@@ -7,14 +7,11 @@
 #include <mutex>
 #include <unordered_map>
 
-#define CTRL(s, f) sb.ctrl[(s) * 8 + (f)]
 // rows of the CTC table / forward variables seen by a decode step (scasr.h: SC_C_TCTC)
 #define SC_CTC_T(s) (CTRL(s, SC_C_TCTC) > 0 ? CTRL(s, SC_C_TCTC) : CTRL(s, SC_C_T))
 
 // per-index helpers for the ping-pong buffers
-#define YSEQ(pp, s, h) (sb.yseq + (((long)(pp) * sb.S + (s)) * sb.W + (h)) * sb.LCAP)
 #define XPOS(pp, s, h) (sb.xpos + (((long)(pp) * sb.S + (s)) * sb.W + (h)) * sb.LCAP)
-#define ANC(pp, s) (sb.anc + ((long)(pp) * sb.S + (s)) * sb.LCAP * sb.W)
 #define CTCR(pp, s) (sb.ctc_r + ((long)(pp) * sb.S + (s)) * sb.TCAP * 2 * sb.W)
 #define CTCRS(pp, s) (sb.ctc_rs + ((long)(pp) * sb.S + (s)) * sb.TCAP * sb.W)   // log(exp r^n + exp r^b) per frame (scasr.h)
 

@@ -5,7 +5,7 @@
 // and subtractions of promoted fp32 values, comparisons.
 //
 // One launch per call, one workgroup of SPOT_WAVES = 16 wave64 per job, the job's span [t0, t1) in tiles of SPOT_TILE frames:
-//   pass 1  the waves take the tile's rows in turn: fp32 row maximum and bad flag (a NaN, a +inf, or nothing but -inf) -> LDS
+//   pass 1  the waves take the tile's rows in turn: fp32 row maximum and bad flag (the rule of ctc_row.h) -> LDS
 //   pass 2  wave w takes the enabled phrases w, w + 16, ...; lane = state.  SPOT_BATCH frames at a time: every lane
 //           first issues the emission gathers x[t][label(lane)] of the batch (in flight together), then the serial frame
 //           loop with shuffles from lanes - 1 and - 2; the fire decision is broadcast from the end state's lane.  A fire
@@ -13,7 +13,7 @@
 //   pass 3  wave 0, lane = phrase, merges the tile's fires frame by frame: a ballot and a prefix popcount give every
 //           firing lane its own event slot - events ordered by (end, phrase).
 // No atomics; every output has one writer; plain vector stores.  The table is only read.
-#include "common.h"
+#include "ctc_row.h"
 
 namespace {
 
@@ -22,9 +22,9 @@ constexpr int SPOT_TILE = 64;    // frames per tile: one bit each in a phrase's 
 constexpr int SPOT_BATCH = 16;   // frames whose emission gathers are in flight together (a group's jobs hold about 16 rows)
 constexpr int SPOT_P = SC_SPOT_MAX_PHRASES, SPOT_L = SC_SPOT_MAX_LEN, SPOT_S = SC_SPOT_STATES;
 
-__device__ __forceinline__ bool job_ok(const sc_ctc_spot_job &j) {
-  return j.table && j.labels && j.lens && j.floors && j.counters && j.values && j.starts && j.events && j.V >= 1 &&
-         j.blank >= 0 && j.blank < j.V && j.t0 >= 0 && j.t1 >= j.t0 && j.P >= 1 && j.P <= SPOT_P && j.stride >= j.V;
+__device__ __forceinline__ bool spot_job_ok(const sc_ctc_spot_job &j) {
+  return ctc_job_ok(j) && j.labels && j.lens && j.floors && j.counters && j.values && j.starts && j.events && j.P >= 1 &&
+         j.P <= SPOT_P && j.stride >= j.V;
 }
 
 __global__ __launch_bounds__(SPOT_WAVES * 64) void ctc_spot_kernel(const sc_ctc_spot_job *__restrict__ jobs) {
@@ -37,7 +37,7 @@ __global__ __launch_bounds__(SPOT_WAVES * 64) void ctc_spot_kernel(const sc_ctc_
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   // a malformed job writes nothing (the host-side entry point cannot see the device table); the phrase set belongs to
   // the job: a length outside [1, 32] or a label outside the vocabulary or equal to the blank makes it malformed
-  if (!job_ok(j)) return;   // (uniform)
+  if (!spot_job_ok(j)) return;   // (uniform)
   int wrong = 0;
   for (int i = tid; i < j.P * SPOT_L; i += SPOT_WAVES * 64) {
     const int L = j.lens[i / SPOT_L];
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(SPOT_WAVES * 64) void ctc_spot_kernel(const sc_ctc_
       bool bad = false;
       for (int v = lane; v < j.V; v += 64) {
         const float x = row[v];
-        bad |= (x != x) || x == INFINITY;
+        bad |= ctc_bad_value(x);
         m = fmaxf(m, x);   // (a NaN is skipped here and caught by the flag)
       }
       for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
@@ -179,11 +179,6 @@ __global__ __launch_bounds__(SPOT_WAVES * 64) void ctc_spot_kernel(const sc_ctc_
 }  // namespace
 
 extern "C" int sc_ctc_spot(const sc_ctc_spot_job *jobs, int n_jobs, void *stream) {
-  SC_CHECK_ARG(n_jobs >= 0, "negative job count");
-  SC_CHECK_ARG(n_jobs == 0 || jobs, "null job table");
-  SC_CHECK_ARG(n_jobs <= SC_SPOT_MAX_JOBS, "more than SC_SPOT_MAX_JOBS jobs");
-  if (n_jobs == 0) return SC_OK;
-  ctc_spot_kernel<<<n_jobs, SPOT_WAVES * 64, 0, (hipStream_t)stream>>>(jobs);
-  SC_CHECK_LAUNCH();
-  return SC_OK;
+  return ctc_launch_jobs(__func__, jobs, n_jobs, SC_SPOT_MAX_JOBS, "more than SC_SPOT_MAX_JOBS jobs",
+                         [&] { ctc_spot_kernel<<<n_jobs, SPOT_WAVES * 64, 0, (hipStream_t)stream>>>(jobs); });
 }

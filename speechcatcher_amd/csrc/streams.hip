@@ -1057,8 +1057,19 @@ int wait_group(sc_streams *b, long gen) {
   return retire_groups(b);
 }
 
+// what the jobs of every side-state option share: the stream's CTC table and the span of its rows
+template <typename J>
+void span_job(const sc_streams *b, J &j, const EncGroup::Span &sp, int opt) {
+  const int V = b->cfg.vocab_size;
+  j.table = b->sb.ctcx + (size_t)sp.s * b->TCAP * V;
+  j.stride = V;
+  j.V = V; j.blank = b->cfg.blank_id; j.t0 = sp.t0; j.t1 = sp.t1;
+  j.restart = sp.opt[opt].restart ? 1 : 0;
+}
+
 // The launch of one side-state option over the spans of a group: job i of slot g.slot's table is filled from span i (at: its
-// index in the [N_ARENA][S] tables, where its state-after slot is too), the n jobs go to the device, one launch reads them.
+// index in the [N_ARENA][S] tables, where its state-after slot is too) - span_job, then `fill` for the option's own fields -,
+// the n jobs go to the device, one launch reads them.
 template <typename J, typename Fill>
 int launch_spans(sc_streams *b, const EncGroup &g, int opt, const char *name, J *jobs_host, J *jobs_dev,
                  int (*launch)(const J *, int, void *), Fill fill) {
@@ -1069,7 +1080,10 @@ int launch_spans(sc_streams *b, const EncGroup &g, int opt, const char *name, J 
     return SC_ERR_ARG;
   }
   const size_t o = (size_t)g.slot * b->S;
-  for (int i = 0; i < n; ++i) fill(jobs_host[o + i], g.spans[i], o + i);
+  for (int i = 0; i < n; ++i) {
+    span_job(b, jobs_host[o + i], g.spans[i], opt);
+    fill(jobs_host[o + i], g.spans[i], o + i);
+  }
   HIP_TRY(hipMemcpyAsync(jobs_dev + o, jobs_host + o, (size_t)n * sizeof(J), hipMemcpyHostToDevice, b->es));
   return launch(jobs_dev + o, n, b->es);
 }
@@ -1089,54 +1103,37 @@ int project_rows(sc_streams *b, EncGroup &g) {
                    V, d, b->gemm_flags, 0, b->es));
     // side states: ONE launch per option for the group, behind the projection of the rows it reads (raw logits: the
     // in-place log-softmax of a first block runs on the decode stream behind this group's event)
-    const int blank = c.blank_id;
     RC_TRY(launch_spans(b, g, OPT_ACT, "activity", b->act_jobs_host, b->act_jobs_dev, sc_ctc_activity,
                         [=](sc_ctc_activity_job &j, const EncGroup::Span &sp, size_t at) {
-                          j.table = b->sb.ctcx + (size_t)sp.s * b->TCAP * V;
                           j.state = b->act_state + (size_t)sp.s * 6;
                           j.track = b->act_track + (size_t)sp.s * b->TCAP;
                           j.state_after = b->act_out_dev + at * 6;
-                          j.stride = V;
                           j.thr = b->act_thr;
-                          j.V = V; j.blank = blank; j.t0 = sp.t0; j.t1 = sp.t1;
-                          j.restart = sp.opt[OPT_ACT].restart ? 1 : 0;
                           j.reserved = 0;
                         }));
     RC_TRY(launch_spans(b, g, OPT_SPOT, "spotting", b->spot_jobs_host, b->spot_jobs_dev, sc_ctc_spot,
                         [=](sc_ctc_spot_job &j, const EncGroup::Span &sp, size_t at) {
-                          j.table = b->sb.ctcx + (size_t)sp.s * b->TCAP * V;
                           j.labels = b->spot_labels; j.lens = b->spot_lens; j.floors = b->spot_floors;
                           j.counters = b->spot_counters + (size_t)sp.s * 2;
                           j.values = b->spot_values + (size_t)sp.s * SC_SPOT_MAX_PHRASES * SC_SPOT_STATES;
                           j.starts = b->spot_starts + (size_t)sp.s * SC_SPOT_MAX_PHRASES * SC_SPOT_STATES;
                           j.events = b->spot_events + (size_t)sp.s * SC_SPOT_MAX_EVENTS;
                           j.state_after = b->spot_out_dev + at * 2;
-                          j.stride = V;
                           j.mask = sp.mask;
-                          j.V = V; j.blank = blank; j.t0 = sp.t0; j.t1 = sp.t1;
-                          j.restart = sp.opt[OPT_SPOT].restart ? 1 : 0;
                           j.P = b->spot_P;
                         }));
     RC_TRY(launch_spans(b, g, OPT_DRAFT, "draft", b->draft_jobs_host, b->draft_jobs_dev, sc_ctc_draft,
                         [=](sc_ctc_draft_job &j, const EncGroup::Span &sp, size_t at) {
-                          j.table = b->sb.ctcx + (size_t)sp.s * b->TCAP * V;
                           j.state = b->draft_state + sp.s;
                           j.tokens = b->draft_tokens + (size_t)sp.s * b->TCAP;
                           j.state_after = b->draft_out_dev + at;
-                          j.stride = V;
-                          j.V = V; j.blank = blank; j.t0 = sp.t0; j.t1 = sp.t1;
-                          j.restart = sp.opt[OPT_DRAFT].restart ? 1 : 0;
                           j.capacity = b->TCAP;
                         }));
     RC_TRY(launch_spans(b, g, OPT_BEAM, "beam", b->beam_jobs_host, b->beam_jobs_dev, sc_ctc_beam,
                         [=](sc_ctc_beam_job &j, const EncGroup::Span &sp, size_t at) {
-                          j.table = b->sb.ctcx + (size_t)sp.s * b->TCAP * V;
                           j.state = b->beam_state + sp.s;
                           j.nodes = b->beam_nodes + (size_t)sp.s * b->beam_ncap();
                           j.state_after = b->beam_out_dev + at;
-                          j.stride = V;
-                          j.V = V; j.blank = blank; j.t0 = sp.t0; j.t1 = sp.t1;
-                          j.restart = sp.opt[OPT_BEAM].restart ? 1 : 0;
                           j.capacity = (int32_t)b->beam_ncap();
                           j.B = b->beam_B; j.C = b->beam_C;
                         }));

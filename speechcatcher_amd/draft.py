@@ -11,6 +11,8 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
+from . import ctc_rows
+
 FIELDS = ("n_frames", "n_closed", "n_bad", "open_id", "open_start", "open_end", "open_conf")
 TOKEN_FIELDS = ("id", "start", "end", "conf")
 INITIAL = (0, 0, 0, -1, -1, -1, 0.0)
@@ -31,7 +33,7 @@ def advance(state: dict, rows, blank: int, capacity: Optional[int] = None) -> di
     toks = state["tokens"]
     for t in range(x32.shape[0]):
         r32 = x32[t]
-        bad = r32.size == 0 or bool(np.isnan(r32).any() or (r32 == np.inf).any() or r32.max() == -np.inf)
+        bad = ctc_rows.is_bad(r32)
         k = -1 if bad else int(np.argmax(r32))   # the lowest index among ties
         if bad or k == blank or k != oid:
             if oid >= 0:                          # the open token closes
@@ -42,9 +44,7 @@ def advance(state: dict, rows, blank: int, capacity: Optional[int] = None) -> di
         if bad:
             nbad += 1
         elif k != blank:
-            row = r32.astype(np.float64)
-            m = row.max()
-            p = float(np.exp(row[k] - (m + np.log(np.cumsum(np.exp(row - m))[-1]))))
+            p = float(np.exp(np.float64(r32[k]) - ctc_rows.lse(r32)))
             if k == oid:
                 oen, ocf = n, max(ocf, p)
             else:

@@ -9,6 +9,8 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
+from . import ctc_rows
+
 MAX_PHRASES = 64
 MAX_LEN = 32
 N_STATES = 64
@@ -97,7 +99,7 @@ def advance(state: dict, rows, blank: int, ps: PhraseSet, mask: int = ALL) -> di
     for t in range(x.shape[0]):
         row, n = x[t], state["n_frames"]
         state["n_frames"] = n + 1
-        if np.isnan(row).any() or (row == np.inf).any() or row.max() == NEG:
+        if ctc_rows.is_bad(row):
             Vv[used], St[used] = NEG, -1
             continue
         e = row[lab] - row.max()

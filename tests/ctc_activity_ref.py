@@ -14,6 +14,8 @@ spans (empty ones included) gives the states of the one-span scan.
 """
 import numpy as np
 
+import ctc_row_ref as row_ref
+
 FIELDS = ("n_frames", "n_speech", "n_bad", "first_speech", "last_speech", "trail_silence")
 INITIAL = (0, 0, 0, -1, -1, 0)
 
@@ -25,13 +27,8 @@ def p_blank(table, blank: int) -> np.ndarray:
     out = np.full(T, np.nan)
     for t in range(T):
         row = x[t]
-        if np.isnan(row).any() or (row == np.inf).any():
-            continue
-        m = row.max() if row.size else -np.inf
-        if m == -np.inf:
-            continue
-        s = np.cumsum(np.exp(row - m))[-1]   # cumsum adds one element after the other: v ascending
-        out[t] = np.exp(row[blank] - (m + np.log(s)))
+        if not row_ref.is_bad(row):
+            out[t] = np.exp(row[blank] - row_ref.lse(row))
     return out
 
 

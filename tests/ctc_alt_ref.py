@@ -22,21 +22,10 @@ rounding creates ties.
 """
 import numpy as np
 
+from ctc_row_ref import is_bad as row_is_bad, lse as row_lse   # (fp32 rows)
+
 OK, NO_SPAN, BAD_ROW = 0, 1, 2
 MAX_K = 8
-
-
-def row_is_bad(r32) -> bool:
-    return bool(r32.size == 0 or np.isnan(r32).any() or (r32 == np.inf).any() or r32.max() == -np.inf)
-
-
-def row_lse(r32) -> float:
-    """m + log(sum_v exp(x[v] - m)) of a good fp32 row, in float64, v ascending"""
-    row = r32.astype(np.float64)
-    m = row.max()
-    with np.errstate(under="ignore"):
-        s = np.cumsum(np.exp(row - m))[-1]   # cumsum adds one element after the other: v ascending
-    return float(m + np.log(s))
 
 
 def span_sums(x32, start: int, end: int) -> np.ndarray:

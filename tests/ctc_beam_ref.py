@@ -32,6 +32,8 @@ one-span scan: the per-frame operations are the same.
 """
 import numpy as np
 
+import ctc_row_ref as row_ref
+
 MAX_B = MAX_C = 16
 NEG = -np.inf
 ENTRY_FIELDS = ("node", "last", "len", "parent", "pb", "pnb")
@@ -58,12 +60,11 @@ def rows(table, blank: int, C: int):
     x32 = np.asarray(table, np.float32)
     out = []
     for r32 in x32:
-        if r32.size == 0 or np.isnan(r32).any() or (r32 == np.inf).any() or r32.max() == NEG:
+        if row_ref.is_bad(r32):
             out.append(None)
             continue
         row = r32.astype(np.float64)
-        m = row.max()
-        lse = m + np.log(np.cumsum(np.exp(row - m))[-1])   # v ascending
+        lse = row_ref.lse(r32)
         order = np.argsort(-r32, kind="stable")            # descending, the lowest index first among equals
         cand = [int(v) for v in order if v != blank and r32[v] > NEG][:C]
         out.append((cand, [float(row[v] - lse) for v in cand], float(row[blank] - lse)))

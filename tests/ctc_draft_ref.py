@@ -20,6 +20,8 @@ table into consecutive spans (empty ones included) gives the state and store of 
 """
 import numpy as np
 
+import ctc_row_ref as row_ref
+
 FIELDS = ("n_frames", "n_closed", "n_bad", "open_id", "open_start", "open_end", "open_conf")
 INITIAL = (0, 0, 0, -1, -1, -1, 0.0)
 BAD = -2   # label of a bad row
@@ -33,14 +35,11 @@ def rows(table, blank: int = 0):
     lab, p = np.full(T, BAD, np.int32), np.full(T, np.nan)
     for t in range(T):
         r32 = x32[t]
-        if r32.size == 0 or np.isnan(r32).any() or (r32 == np.inf).any() or r32.max() == -np.inf:
+        if row_ref.is_bad(r32):
             continue
         k = int(np.argmax(r32))   # the first of equal maxima
-        row = r32.astype(np.float64)
-        m = row.max()
-        s = np.cumsum(np.exp(row - m))[-1]   # v ascending
         lab[t] = k
-        p[t] = np.exp(row[k] - (m + np.log(s)))
+        p[t] = np.exp(np.float64(r32[k]) - row_ref.lse(r32))
     return lab, p
 
 

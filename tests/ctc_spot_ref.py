@@ -22,6 +22,8 @@ events of the one-span scan.
 """
 import numpy as np
 
+from ctc_row_ref import is_bad
+
 MAX_EVENTS = 64
 MAX_PHRASES = 64
 MAX_LEN = 32
@@ -44,10 +46,6 @@ def check_phrases(phrases, floors, V: int, blank: int):
     for y, f in zip(phrases, floors):
         assert 1 <= len(y) <= MAX_LEN and all(0 <= int(t) < V and int(t) != blank for t in y)
         assert f <= 0
-
-
-def is_bad(row) -> bool:
-    return bool(np.isnan(row).any() or (row == np.inf).any() or row.size == 0 or row.max() == -np.inf)
 
 
 def scan(state, table, blank: int, phrases, floors, mask: int = ALL):
