@@ -595,6 +595,80 @@ typedef struct sc_ctc_beam_pack_job {
  * null ids / frames with max_len > 0, a null store with capacity > 0, capacity < 0, max_len < 0) writes nothing. */
 int sc_ctc_beam_pack(const sc_ctc_beam_pack_job *jobs, int n_jobs, void *stream);
 
+/* ---- n-gram language model fused into the CTC prefix beam (lm_blob.h, ctc_beam.hip) ---------------
+ * The model is a backoff n-gram over the token ids [0, V), order 1..SC_LM_MAX_ORDER, held as a backoff automaton:
+ *   state   a context the model holds; state 0 is the empty context.  Per state backoff (float64, natural log) and
+ *           bo_state, the state of the longest proper suffix of the context that the model holds (the context without its
+ *           oldest token when the model is closed under suffixes).  Following bo_state reaches 0 in at most
+ *           SC_LM_MAX_ORDER - 1 steps.
+ *   arc     (state, token) -> (logp float64, next): next = the state of the longest suffix of context + token that the
+ *           model holds.  State 0's arcs are the dense arrays root_logp[V] / root_next[V], never searched; the arcs of all
+ *           other states are the slots of ONE open-addressing hash table: key = ((uint64)state << 32) | token, home slot
+ *           (key * SC_LM_HASH_MUL mod 2^64) >> (64 - log2 n_slots), linear probing (slot + 1 mod n_slots); an unused slot has
+ *           the key SC_LM_EMPTY.  n_slots is a power of two >= 2 and every probe run ends at an unused slot.
+ *   score(s, c):  acc = 0.0;  while s != 0 and (s, c) has no arc: acc = acc + backoff[s], s = bo_state[s];
+ *                 -> (acc + logp[s, c], next[s, c])       float64 additions in exactly this order; all values finite
+ * The blob (little endian; speechcatcher_amd/ngram.py packs it): sc_lm_header; double backoff[n_states]; int32 bo_state
+ * [n_states]; double root_logp[V]; int32 root_next[V]; sc_lm_slot slots[n_slots] - every int32 array padded to a multiple of
+ * 8 bytes.  sc_lm_create validates all of it on the host (sizes against the header, every bo_state / next in range, the
+ * bo_state chains, finite values, no key twice, an unused slot in every probe run, every key's state and token in range and
+ * the key reachable from its home slot) BEFORE a byte reaches the device: SC_ERR_ARG and nothing allocated otherwise.  The
+ * model is uploaded once and read-only afterwards; it must outlive every launch and every sc_streams that uses it. */
+#define SC_LM_MAX_ORDER 5
+#define SC_LM_MAGIC 0x4D4C4353 /* "SCLM" */
+#define SC_LM_VERSION 1
+#define SC_LM_EMPTY 0xFFFFFFFFFFFFFFFFull
+#define SC_LM_HASH_MUL 0x9E3779B97F4A7C15ull
+typedef struct sc_lm_header {
+  int32_t magic, version, V, order, n_states, n_arcs /* used slots */, n_slots, start_state;
+} sc_lm_header;
+typedef struct sc_lm_slot {
+  uint64_t key;
+  double logp;
+  int32_t next, reserved; /* reserved = 0 */
+} sc_lm_slot;
+typedef struct sc_lm_view { /* the automaton as the kernel reads it (device pointers) */
+  const double *backoff;
+  const int32_t *bo_state;
+  const double *root_logp;
+  const int32_t *root_next;
+  const sc_lm_slot *slots;
+  int32_t V, order, n_states, n_slots, start_state, shift; /* shift = 64 - log2 n_slots */
+} sc_lm_view;
+typedef struct sc_lm sc_lm;
+int sc_lm_create(const void *blob /*HOST*/, size_t bytes, sc_lm **out);
+void sc_lm_destroy(sc_lm *lm);
+/* *device: the view in device memory (what sc_ctc_beam_lm_job.lm takes); *host: a host copy of it.  Either may be NULL.
+ * SC_ERR_ARG for a null model. */
+int sc_lm_device_view(const sc_lm *lm, const sc_lm_view **device, sc_lm_view *host);
+
+/* The beam search of sc_ctc_beam with the model fused in (tests/ctc_beam_lm_ref.py is the contract, built on
+ * tests/ctc_beam_ref.py; nothing of that contract's row pass, candidates, stays, extensions or merges changes, pb / pnb
+ * stay the pure CTC prefix probabilities).  Entry i carries besides them lm_i, the raw sum of the score() values along its
+ * prefix, and ctx_i, the automaton's state after its prefix; the initial entry has (0.0, start_state), unused slots hold
+ * (0.0, 0).  A new prefix made from entry i by candidate c gets (l, s') = score(ctx_i, c): lm = lm_i + l, ctx = s'.  A stay
+ * keeps both; an extension that merges into an entry of the beam leaves that entry's alone (the same prefix has the same
+ * values).  The B best are kept by fused = total + w, w = alpha * lm + beta * len, each product and each sum rounded on its
+ * own (no fused multiply-add), ties as in sc_ctc_beam.  The candidates are still the C best by their fp32 acoustic values.
+ * lm == NULL: the job runs unfused, lm_state / lm_state_after are neither read nor written; that, and alpha = beta = 0
+ * with a model, give every bit of sc_ctc_beam on the same inputs.  Bars: every int32 and ctx equal wherever no cut between
+ * fused totals is a near-tie, lm bit-equal, pb / pnb as for sc_ctc_beam. */
+typedef struct sc_beam_lm_t {
+  double lm[SC_BEAM_MAX];
+  int32_t ctx[SC_BEAM_MAX];
+} sc_beam_lm_t;
+typedef struct sc_ctc_beam_lm_job {
+  sc_ctc_beam_job beam;
+  const sc_lm_view *lm;          /* device view; NULL: the job runs unfused */
+  sc_beam_lm_t *lm_state;        /* beside beam.state: read (unless restart), written back (device) */
+  sc_beam_lm_t *lm_state_after;  /* second copy, beside beam.state_after (NULL: none) */
+  double alpha, beta;            /* weight of the model's log probability, bonus per token; finite */
+} sc_ctc_beam_lm_job;
+/* As sc_ctc_beam (same limits, same errors before a launch).  Malformed besides what is malformed there, and writing
+ * nothing: with a model, a null lm_state, a model whose V differs from beam.V, an alpha or beta that is not finite, a stored
+ * ctx outside [0, n_states) without restart. */
+int sc_ctc_beam_lm(const sc_ctc_beam_lm_job *jobs, int n_jobs, void *stream);
+
 /* ---- CTC token alternates (alternates.hip) -----------------------------------------------------
  * "What else could this token have been": for each of L token spans [start[k], end[k]) over the T rows of an fp32 CTC
  * table, the K acoustically best tokens of those frames and the rank of the span's own label y[k] among them.  Per span,
@@ -1236,6 +1310,24 @@ int sc_stream_ctc_beam(sc_streams *streams, int stream, sc_beam_t *out /*HOST*/)
  * written), scores [n][nbest][2] (pb, pnb).  ids, frames and scores may be NULL. */
 int sc_ctc_beam_hyps(sc_streams *streams, const int *stream_ids, int n, int nbest, int max_len, int32_t *header /*HOST*/,
                      int32_t *ids /*HOST*/, int32_t *frames /*HOST*/, double *scores /*HOST*/);
+/* An n-gram model fused into the beam of every stream (off by default).  Needs the beam option on.  With a
+ * model attached the group launches sc_ctc_beam_lm in the place of sc_ctc_beam (the same launch slot, the same hand-over;
+ * the state grows by a sc_beam_lm_t per stream, S x 192 bytes, allocated when a model is first attached); with lm == NULL
+ * it launches sc_ctc_beam as before and nothing new.  One model serves all streams of the handle; the model's V must be the
+ * batch's vocabulary size, alpha and beta finite.  SC_ERR_ARG while any chunk is outstanding; attaching, replacing or
+ * detaching restarts every stream's beam (waiting for a group in flight first: the model may be destroyed once it is
+ * detached, and switching the beam option off detaches it).  sc_reset and strict_reference: as sc_streams_set_ctc_beam.
+ * Hypotheses of FULL streams do not depend on it.  Not in this revision: a model per stream, an end-of-sentence term at
+ * finals, fusion into the blockwise search of FULL streams. */
+int sc_streams_set_ctc_beam_lm(sc_streams *streams, const sc_lm *lm, double alpha, double beta);
+/* beside sc_stream_ctc_beam: the model's side of the same state ((0.0, start_state) in entry 0 before the first frame).
+ * SC_ERR_ARG when no model is attached. */
+int sc_stream_ctc_beam_lm(sc_streams *streams, int stream, sc_beam_lm_t *out /*HOST*/);
+/* beside sc_ctc_beam_hyps' scores: lm [n][nbest] and fused [n][nbest] = lae(pb, pnb) + (alpha * lm + beta * len) of the
+ * same entries, NaN where a state has no such entry; computed on the host from the reported states, no launch.  Either
+ * may be NULL.  SC_ERR_ARG when no model is attached. */
+int sc_ctc_beam_hyps_lm(sc_streams *streams, const int *stream_ids, int n, int nbest, double *lm /*HOST*/,
+                        double *fused /*HOST*/);
 /* Decoder-free streams.  SC_DECODER_NONE: the stream is served from its CTC rows alone.  Admission queues
  * no decode block for it and lists no cross-attention K|V rows for its frames; the front end, the encoder, the CTC rows,
  * every side option and the reply status are those of any stream, a chunk is complete at once (the side-state readers

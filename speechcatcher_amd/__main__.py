@@ -73,7 +73,7 @@ def to_16k(raw, rate, device="cuda:0"):
 
 def recognize_file(speech2text, media_path, output_file="", quiet=True, progress=True, num_slots=1, chunk_length=8192,
                    token_alignment=False, segmentation="host", channel=None, token_alternates=0, ctc_beam=0,
-                   ctc_only=False):
+                   ctc_only=False, ctc_lm=None, lm_weight=0.5, word_bonus=0.0):
     """speechcatcher.py:358-400: recording -> text + paragraphs JSON next to the input.  ``token_alignment``: the
     paragraphs also get token_start / token_end (seconds) and token_conf from a CTC forced alignment of each segment.
     ``segmentation``: "host" or "gpu" - where the energy curve for the cut points of a recording over 60 s is computed.
@@ -81,7 +81,13 @@ def recognize_file(speech2text, media_path, output_file="", quiet=True, progress
     ``token_alternates`` = K > 0 (implies ``token_alignment``): the paragraphs also get token_alternates, one record per
     token with its K acoustic alternates over the token's frames.  ``ctc_beam`` = B > 0: the paragraphs also get ctc_nbest,
     per segment the n-best list of the CTC prefix beam search; ``ctc_only``: the segments are decoded by that search alone,
-    with no attention decoder step (B = 8 unless ``ctc_beam`` says otherwise; not with ``token_alternates``)."""
+    with no attention decoder step (B = 8 unless ``ctc_beam`` says otherwise; not with ``token_alternates``).  ``ctc_lm``:
+    the path of a packed n-gram model (python -m speechcatcher_amd.ngram) fused into that search with ``lm_weight`` and
+    ``word_bonus`` (needs ``ctc_beam`` or ``ctc_only``)."""
+    if ctc_lm and not (ctc_only or int(ctc_beam)):
+        raise SystemExit("Error: --ctc-lm is fused into the CTC prefix beam search: it needs --ctc-beam or --ctc-only")
+    if ctc_lm and not os.path.isfile(ctc_lm):
+        raise SystemExit(f"Error: --ctc-lm: '{ctc_lm}' does not exist or is not a file")
     if ctc_only and token_alternates:
         raise SystemExit("Error: --ctc-only has no forced alignment to rank token alternates in: not with --token-alternates")
     if not 0 <= int(ctc_beam) <= 16:
@@ -104,7 +110,8 @@ def recognize_file(speech2text, media_path, output_file="", quiet=True, progress
     text, info = recognize_recording(batch, raw, rate, chunk_length=chunk_length, token_list=speech2text.token_list,
                                      reference_finalize=True, token_alignment=token_alignment,
                                      segmentation=segmentation, token_alternates=token_alternates,
-                                     ctc_beam=int(ctc_beam) or None, ctc_only=ctc_only)
+                                     ctc_beam=int(ctc_beam) or None, ctc_only=ctc_only, ctc_lm=ctc_lm or None,
+                                     lm_weight=float(lm_weight), word_bonus=float(word_bonus))
     out_txt, out_json = (output_file or media_path) + ".txt", (output_file or media_path) + ".json"
     with open(out_txt, "w") as f:
         f.write(text)
@@ -153,6 +160,13 @@ def make_parser():
     p.add_argument("--ctc-only", dest="ctc_only", action="store_true",
                    help="decode with the CTC prefix beam search alone: no attention decoder step, the transcript is the beam's "
                         "best (B = 8 unless --ctc-beam says otherwise; not with --token-alternates)")
+    p.add_argument("--ctc-lm", dest="ctc_lm", default="", metavar="FILE",
+                   help="fuse a backoff n-gram language model into the CTC prefix beam search (needs --ctc-beam or --ctc-only): "
+                        "a file packed by `python -m speechcatcher_amd.ngram in.arpa tokens.txt out.sclm`")
+    p.add_argument("--lm-weight", dest="lm_weight", type=float, default=0.5, metavar="A",
+                   help="weight of the model's log probability in the beam's ranking (default 0.5; a parameter, not tuned)")
+    p.add_argument("--word-bonus", dest="word_bonus", type=float, default=0.0, metavar="B",
+                   help="bonus per token of a prefix in the beam's ranking (default 0)")
     p.add_argument("--segmentation", dest="segmentation", choices=["host", "gpu"], default="host",
                    help="where the energy curve for the cut points of a recording over 60 s is computed: 'host' (numpy, the "
                         "default) or 'gpu' (float64 kernels; the same cuts, without the host pass over the whole recording)")
@@ -188,7 +202,7 @@ def main(argv=None):
                    num_slots=1 if args.num_processes < 1 else args.num_processes, chunk_length=args.chunk_length,
                    token_alignment=args.token_alignment or args.token_alternates > 0, segmentation=args.segmentation,
                    channel=args.channel, token_alternates=args.token_alternates, ctc_beam=args.ctc_beam,
-                   ctc_only=args.ctc_only)
+                   ctc_only=args.ctc_only, ctc_lm=args.ctc_lm or None, lm_weight=args.lm_weight, word_bonus=args.word_bonus)
     return 0
 
 

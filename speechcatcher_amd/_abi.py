@@ -163,6 +163,37 @@ class BeamJob(C.Structure):
                 + [(n, C.c_int32) for n in ("V", "blank", "t0", "t1", "restart", "capacity", "B", "C")])
 
 
+class BeamLm(C.Structure):
+    """sc_beam_lm_t (include/scasr.h): beside the entries of a sc_beam_t, the model's sum along each prefix and the
+    automaton's state after it"""
+    _fields_ = [("lm", C.c_double * BEAM_MAX), ("ctx", C.c_int32 * BEAM_MAX)]
+
+
+class BeamLmJob(C.Structure):
+    """sc_ctc_beam_lm_job (include/scasr.h): a sc_ctc_beam_job with a language model fused in"""
+    _fields_ = [("beam", BeamJob), ("lm", vp), ("lm_state", vp), ("lm_state_after", vp), ("alpha", C.c_double),
+                ("beta", C.c_double)]
+
+
+class LmHeader(C.Structure):
+    """sc_lm_header (include/scasr.h): the first bytes of a language model blob (speechcatcher_amd/ngram.py packs it)"""
+    _fields_ = [(n, C.c_int32) for n in ("magic", "version", "V", "order", "n_states", "n_arcs", "n_slots", "start_state")]
+
+
+class LmSlot(C.Structure):
+    """sc_lm_slot (include/scasr.h): one slot of the arc hash table"""
+    _fields_ = [("key", C.c_uint64), ("logp", C.c_double), ("next", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LmView(C.Structure):
+    """sc_lm_view (include/scasr.h): the automaton as the kernel reads it"""
+    _fields_ = ([(n, vp) for n in ("backoff", "bo_state", "root_logp", "root_next", "slots")]
+                + [(n, C.c_int32) for n in ("V", "order", "n_states", "n_slots", "start_state", "shift")])
+
+
+LM_MAX_ORDER, LM_MAGIC, LM_VERSION = 5, 0x4D4C4353, 1
+
+
 class BeamPackJob(C.Structure):
     """sc_ctc_beam_pack_job (include/scasr.h): one entry of a beam state walked up its parent chain"""
     _fields_ = ([(n, vp) for n in ("state", "nodes", "ids", "frames", "header", "scores")]
@@ -371,9 +402,16 @@ _SIGS = {
     # CTC prefix beam search (ctc_beam.hip, streams.hip)
     "sc_ctc_beam": (C.c_int, [vp, C.c_int, vp]),
     "sc_ctc_beam_pack": (C.c_int, [vp, C.c_int, vp]),
+    "sc_ctc_beam_lm": (C.c_int, [vp, C.c_int, vp]),
+    "sc_lm_create": (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),
+    "sc_lm_destroy": (None, [vp]),
+    "sc_lm_device_view": (C.c_int, [vp, C.POINTER(vp), C.POINTER(LmView)]),
     "sc_streams_set_ctc_beam": (C.c_int, [vp, C.c_int, C.c_int]),
     "sc_stream_ctc_beam": (C.c_int, [vp, C.c_int, C.POINTER(Beam)]),
     "sc_ctc_beam_hyps": (C.c_int, [vp, c_int_p, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "sc_streams_set_ctc_beam_lm": (C.c_int, [vp, vp, C.c_double, C.c_double]),
+    "sc_stream_ctc_beam_lm": (C.c_int, [vp, C.c_int, C.POINTER(BeamLm)]),
+    "sc_ctc_beam_hyps_lm": (C.c_int, [vp, c_int_p, C.c_int, C.c_int, vp, vp]),
     "sc_stream_set_decoder": (C.c_int, [vp, C.c_int, C.c_int]),
     "sc_stream_decoder": (C.c_int, [vp, C.c_int]),
     "sc_streams_read_ctc_projected": (C.c_int, [vp, C.c_int, vp, C.c_int]),

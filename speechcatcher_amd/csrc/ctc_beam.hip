@@ -16,7 +16,15 @@
 //              all items (broadcast reads).  The items of rank < B are written to the other buffer at their rank; a
 //              __ballot over the new prefixes numbers their nodes, one lane each stores its record.
 // No atomics; every output has one writer; plain vector stores.  The table is only read.
+//
+// sc_ctc_beam_lm is the same kernel body with an n-gram model fused in (template <bool LM>; DESIGN.md 8k,
+// tests/ctc_beam_lm_ref.py): beside the entries the beam carries (lm, ctx) in LDS; the lanes that hold the extension
+// items look their arcs up in the backoff automaton - one round per backoff level, the first probes of a lane's items
+// issued together so that their loads overlap -, and the items are ranked by total + (alpha * lm + beta * len).  The
+// LM = false instantiation is the kernel without any of it.  sc_lm_create validates a model on the host (lm_blob.h)
+// and uploads it once.
 #include "ctc_row.h"
+#include "lm_blob.h"
 
 namespace {
 
@@ -107,7 +115,13 @@ __device__ __forceinline__ sc_beam_entry empty_entry() {
   return e;
 }
 
-__global__ __launch_bounds__(BM_WAVES * 64) void ctc_beam_kernel(const sc_ctc_beam_job *__restrict__ jobs) {
+template <bool LM> struct BeamJobOf { using type = sc_ctc_beam_job; };
+template <> struct BeamJobOf<true> { using type = sc_ctc_beam_lm_job; };
+__device__ __forceinline__ const sc_ctc_beam_job &beam_of(const sc_ctc_beam_job &j) { return j; }
+__device__ __forceinline__ const sc_ctc_beam_job &beam_of(const sc_ctc_beam_lm_job &j) { return j.beam; }
+
+template <bool LM>
+__global__ __launch_bounds__(BM_WAVES * 64) void ctc_beam_kernel(const typename BeamJobOf<LM>::type *__restrict__ jobs) {
   __shared__ double clp[BM_TILE][BM_MAX];
   __shared__ int cid[BM_TILE][BM_MAX];
   __shared__ double blp[BM_TILE];
@@ -117,7 +131,9 @@ __global__ __launch_bounds__(BM_WAVES * 64) void ctc_beam_kernel(const sc_ctc_be
   __shared__ double it_tot[BM_MAX * (BM_MAX + 1)];
   __shared__ unsigned long long it_key[BM_MAX * (BM_MAX + 1)];
   __shared__ int mrg[BM_MAX * BM_MAX];
-  const sc_ctc_beam_job j = jobs[blockIdx.x];
+  __shared__ double e_lm[LM ? 2 : 1][LM ? BM_MAX : 1];   // (LM) beside ent[p][i]: the model's sum along the prefix ...
+  __shared__ int e_ctx[LM ? 2 : 1][LM ? BM_MAX : 1];     // ... and the automaton's state after it
+  const sc_ctc_beam_job j = beam_of(jobs[blockIdx.x]);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (!ctc_job_ok(j) || !j.state || j.stride < j.V || j.capacity < 0 || (j.capacity > 0 && !j.nodes) || j.B < 1 ||
       j.B > BM_MAX || j.C < 1 || j.C > BM_MAX)
@@ -127,6 +143,23 @@ __global__ __launch_bounds__(BM_WAVES * 64) void ctc_beam_kernel(const sc_ctc_be
     stored = j.state->n_entries;   // (every thread reads it: the decision is uniform over the workgroup)
     if (stored < 0 || stored > BM_MAX) return;
   }
+  // (LM) the model's side of the job; fuse: a model is attached (uniform over the workgroup)
+  sc_lm_view lv{};
+  sc_beam_lm_t *lm_state = nullptr, *lm_state_after = nullptr;
+  double alpha = 0.0, beta = 0.0;
+  bool fuse = false;
+  if constexpr (LM) {
+    const sc_ctc_beam_lm_job &jl = jobs[blockIdx.x];
+    if (jl.lm) {
+      lv = *jl.lm;
+      lm_state = jl.lm_state; lm_state_after = jl.lm_state_after; alpha = jl.alpha; beta = jl.beta;
+      fuse = true;
+      if (!lm_state || lv.V != j.V || !(fabs(alpha) < INFINITY) || !(fabs(beta) < INFINITY)) return;
+      if (!j.restart)
+        for (int k = 0; k < min(stored, j.B); ++k)
+          if (lm_state->ctx[k] < 0 || lm_state->ctx[k] >= lv.n_states) return;
+    }
+  }
   __syncthreads();   // every wave has read the count before wave 0 may rewrite it (an empty span has no other barrier)
 
   // the state: counters wave-uniform in wave 0's registers, the entries in ent[p]
@@ -135,6 +168,8 @@ __global__ __launch_bounds__(BM_WAVES * 64) void ctc_beam_kernel(const sc_ctc_be
     if (!j.restart) {
       n = j.state->n_frames; n_bad = j.state->n_bad; n_nodes = j.state->n_nodes;
       if (lane < ne) ent[0][lane] = j.state->e[lane];
+      if constexpr (LM)
+        if (fuse && lane < ne) { e_lm[0][lane] = lm_state->lm[lane]; e_ctx[0][lane] = lm_state->ctx[lane]; }
     } else {
       if (lane == 0) {
         sc_beam_entry e = empty_entry();
@@ -145,6 +180,8 @@ __global__ __launch_bounds__(BM_WAVES * 64) void ctc_beam_kernel(const sc_ctc_be
           r.parent = -1; r.token = -1; r.frame = -1; r.reserved = 0;
           j.nodes[0] = r;
         }
+        if constexpr (LM)
+          if (fuse) { e_lm[0][0] = 0.0; e_ctx[0][0] = lv.start_state; }
       }
     }
     for (int k = lane; k < BM_MAX * BM_MAX; k += 64) mrg[k] = 0;
@@ -202,6 +239,8 @@ __global__ __launch_bounds__(BM_WAVES * 64) void ctc_beam_kernel(const sc_ctc_be
         double my_t[BM_ITEMS];
         unsigned long long my_k[BM_ITEMS];
         int cnt[BM_ITEMS];
+        double my_raw[LM ? BM_ITEMS : 1], my_lm[LM ? BM_ITEMS : 1];   // (LM) the item's pure total, its lm and ctx
+        int my_ctx[LM ? BM_ITEMS : 1];
 #pragma unroll
         for (int q = 0; q < BM_ITEMS; ++q) {
           const int s = lane + 64 * q;
@@ -218,8 +257,85 @@ __global__ __launch_bounds__(BM_WAVES * 64) void ctc_beam_kernel(const sc_ctc_be
               if (mrg[ii * BM_MAX + k - 1] != f) my_t[q] = (c == ent[p][ii].last ? ent[p][ii].pb : s_tot[ii]) + clp[i][k - 1];
               my_k[q] = ((unsigned long long)(BM_MAX + ii) << 32) | (unsigned)c;
             }
-            it_tot[s] = my_t[q];
+            if (!LM || !fuse) it_tot[s] = my_t[q];
             it_key[s] = my_k[q];
+          }
+        }
+        if constexpr (LM) {
+#pragma unroll
+          for (int q = 0; q < BM_ITEMS; ++q) my_raw[q] = my_t[q];
+          if (fuse) {
+            // ---- the arcs of the new prefixes: score(ctx of the entry, candidate), every item of the lane at once
+            int st[BM_ITEMS], tk[BM_ITEMS], len[BM_ITEMS];
+            double acc[BM_ITEMS];
+            bool todo[BM_ITEMS];
+#pragma unroll
+            for (int q = 0; q < BM_ITEMS; ++q) {
+              const int s = lane + 64 * q;
+              st[q] = 0; tk[q] = 0; len[q] = 0; acc[q] = 0.0; todo[q] = false; my_lm[q] = 0.0; my_ctx[q] = 0;
+              if (s < M) {
+                const int ii = s / per, k = s - ii * per;
+                my_lm[q] = e_lm[p][ii];
+                my_ctx[q] = e_ctx[p][ii];
+                len[q] = ent[p][ii].len + (k > 0 ? 1 : 0);
+                if (k > 0 && my_raw[q] > -INFINITY) {
+                  todo[q] = true;
+                  st[q] = my_ctx[q];
+                  tk[q] = cid[i][k - 1];
+                }
+              }
+            }
+            const unsigned mask = (unsigned)lv.n_slots - 1u;
+            for (int lvl = 0; lvl < SC_LM_MAX_ORDER; ++lvl) {   // (a validated model backs off SC_LM_MAX_ORDER - 1 times at most)
+              bool any = false;
+#pragma unroll
+              for (int q = 0; q < BM_ITEMS; ++q) any = any || todo[q];
+              if (!__ballot(any)) break;   // (wave-uniform)
+              unsigned long long key[BM_ITEMS];
+              unsigned at[BM_ITEMS];
+              sc_lm_slot sl[BM_ITEMS];
+#pragma unroll
+              for (int q = 0; q < BM_ITEMS; ++q) {   // the first probe of every item: independent loads
+                key[q] = ((unsigned long long)(unsigned)st[q] << 32) | (unsigned)tk[q];
+                at[q] = todo[q] && st[q] != 0 ? (unsigned)((key[q] * SC_LM_HASH_MUL) >> lv.shift) & mask : 0u;
+                sl[q] = lv.slots[at[q]];
+              }
+#pragma unroll
+              for (int q = 0; q < BM_ITEMS; ++q) {
+                if (!todo[q]) continue;
+                double l;
+                int nx;
+                if (st[q] == 0) {
+                  l = acc[q] + lv.root_logp[tk[q]];
+                  nx = lv.root_next[tk[q]];
+                } else {
+                  for (int n = 0; sl[q].key != key[q] && sl[q].key != SC_LM_EMPTY && n < lv.n_slots; ++n) {
+                    at[q] = (at[q] + 1u) & mask;
+                    sl[q] = lv.slots[at[q]];
+                  }
+                  if (sl[q].key != key[q]) {   // no arc: back off
+                    acc[q] = acc[q] + lv.backoff[st[q]];
+                    st[q] = lv.bo_state[st[q]];
+                    continue;
+                  }
+                  l = acc[q] + sl[q].logp;
+                  nx = sl[q].next;
+                }
+                my_lm[q] = my_lm[q] + l;
+                my_ctx[q] = nx;
+                todo[q] = false;
+              }
+            }
+            // ---- fused = total + (alpha * lm + beta * len): every product and sum rounded on its own
+#pragma unroll
+            for (int q = 0; q < BM_ITEMS; ++q) {
+              const int s = lane + 64 * q;
+              if (s < M) {
+                const double w = __dadd_rn(__dmul_rn(alpha, my_lm[q]), __dmul_rn(beta, (double)len[q]));
+                my_t[q] = __dadd_rn(my_raw[q], w);
+                it_tot[s] = my_t[q];
+              }
+            }
           }
         }
         wave_sync();
@@ -233,7 +349,7 @@ __global__ __launch_bounds__(BM_WAVES * 64) void ctc_beam_kernel(const sc_ctc_be
         int finite = 0;
 #pragma unroll
         for (int q = 0; q < BM_ITEMS; ++q) {
-          const bool live = my_t[q] > -INFINITY;
+          const bool live = (LM ? my_raw[q] : my_t[q]) > -INFINITY;
           finite += __popcll(__ballot(live));
           if (live && cnt[q] < j.B) {
             const int s = lane + 64 * q, ii = s / per, k = s - ii * per;
@@ -249,9 +365,11 @@ __global__ __launch_bounds__(BM_WAVES * 64) void ctc_beam_kernel(const sc_ctc_be
               e.len = src.len + 1;
               e.parent = src.node;
               e.pb = -INFINITY;
-              e.pnb = my_t[q];
+              e.pnb = LM ? my_raw[q] : my_t[q];
             }
             ent[p ^ 1][cnt[q]] = e;
+            if constexpr (LM)
+              if (fuse) { e_lm[p ^ 1][cnt[q]] = my_lm[q]; e_ctx[p ^ 1][cnt[q]] = my_ctx[q]; }
           }
         }
         wave_sync();
@@ -280,6 +398,13 @@ __global__ __launch_bounds__(BM_WAVES * 64) void ctc_beam_kernel(const sc_ctc_be
       const sc_beam_entry e = lane < ne ? ent[p][lane] : empty_entry();
       j.state->e[lane] = e;
       if (j.state_after) j.state_after->e[lane] = e;
+      if constexpr (LM)
+        if (fuse) {
+          const double l = lane < ne ? e_lm[p][lane] : 0.0;
+          const int c = lane < ne ? e_ctx[p][lane] : 0;
+          lm_state->lm[lane] = l; lm_state->ctx[lane] = c;
+          if (lm_state_after) { lm_state_after->lm[lane] = l; lm_state_after->ctx[lane] = c; }
+        }
     }
     if (lane == 0) {
       j.state->n_frames = n; j.state->n_bad = n_bad; j.state->n_nodes = n_nodes; j.state->n_entries = ne;
@@ -332,7 +457,66 @@ __global__ __launch_bounds__(PK_THREADS) void ctc_beam_pack_kernel(const sc_ctc_
 
 extern "C" int sc_ctc_beam(const sc_ctc_beam_job *jobs, int n_jobs, void *stream) {
   return ctc_launch_jobs(__func__, jobs, n_jobs, SC_BEAM_MAX_JOBS, "more than SC_BEAM_MAX_JOBS jobs",
-                         [&] { ctc_beam_kernel<<<n_jobs, BM_WAVES * 64, 0, (hipStream_t)stream>>>(jobs); });
+                         [&] { ctc_beam_kernel<false><<<n_jobs, BM_WAVES * 64, 0, (hipStream_t)stream>>>(jobs); });
+}
+
+extern "C" int sc_ctc_beam_lm(const sc_ctc_beam_lm_job *jobs, int n_jobs, void *stream) {
+  return ctc_launch_jobs(__func__, jobs, n_jobs, SC_BEAM_MAX_JOBS, "more than SC_BEAM_MAX_JOBS jobs",
+                         [&] { ctc_beam_kernel<true><<<n_jobs, BM_WAVES * 64, 0, (hipStream_t)stream>>>(jobs); });
+}
+
+// the model on the device: the blob as it was packed, and the view whose pointers lead into it
+struct sc_lm {
+  unsigned char *blob = nullptr;
+  sc_lm_view *view = nullptr;
+  sc_lm_view host{};   // (the same device pointers)
+};
+
+extern "C" int sc_lm_create(const void *blob, size_t bytes, sc_lm **out) {
+  SC_CHECK_ARG(out, "null out");
+  *out = nullptr;
+  lm_blob::Layout L;
+  const char *wrong = lm_blob::validate(blob, bytes, &L);
+  if (wrong) {
+    sc_set_error("%s: not a sound language model blob: %s", __func__, wrong);
+    return SC_ERR_ARG;
+  }
+  sc_lm *lm = new sc_lm();
+  if (hipMalloc((void **)&lm->blob, bytes) != hipSuccess || hipMalloc((void **)&lm->view, sizeof(sc_lm_view)) != hipSuccess) {
+    sc_set_error("%s: out of device memory (%zu bytes)", __func__, bytes);
+    sc_lm_destroy(lm);
+    return SC_ERR_LAUNCH;
+  }
+  sc_lm_view &v = lm->host;
+  v.backoff = (const double *)(lm->blob + L.backoff);
+  v.bo_state = (const int32_t *)(lm->blob + L.bo_state);
+  v.root_logp = (const double *)(lm->blob + L.root_logp);
+  v.root_next = (const int32_t *)(lm->blob + L.root_next);
+  v.slots = (const sc_lm_slot *)(lm->blob + L.slots);
+  v.V = L.h.V; v.order = L.h.order; v.n_states = L.h.n_states; v.n_slots = L.h.n_slots; v.start_state = L.h.start_state;
+  v.shift = L.shift;
+  if (hipMemcpy(lm->blob, blob, bytes, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(lm->view, &v, sizeof v, hipMemcpyHostToDevice) != hipSuccess) {
+    sc_set_error("%s: upload failed", __func__);
+    sc_lm_destroy(lm);
+    return SC_ERR_LAUNCH;
+  }
+  *out = lm;
+  return SC_OK;
+}
+
+extern "C" void sc_lm_destroy(sc_lm *lm) {
+  if (!lm) return;
+  if (lm->blob) (void)hipFree(lm->blob);
+  if (lm->view) (void)hipFree(lm->view);
+  delete lm;
+}
+
+extern "C" int sc_lm_device_view(const sc_lm *lm, const sc_lm_view **device, sc_lm_view *host) {
+  SC_CHECK_ARG(lm, "null model");
+  if (device) *device = lm->view;
+  if (host) *host = lm->host;
+  return SC_OK;
 }
 
 extern "C" int sc_ctc_beam_pack(const sc_ctc_beam_pack_job *jobs, int n_jobs, void *stream) {

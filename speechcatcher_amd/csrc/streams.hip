@@ -165,14 +165,18 @@ struct DraftState {
 // CTC prefix beam search (sc_streams_set_ctc_beam; ctc_beam.hip): the beam - counters and entries.  The prefix tree stays
 // on the device: the utterance's node k is at slot k and is never touched once stored, so the chains of a reported state's
 // entries are final whatever later groups append.
+// With a language model attached (sc_streams_set_ctc_beam_lm) the model's side of the entries travels with them: all
+// zero without one, and before the first group of an utterance (the readers put the model's start state there).
 struct BeamState {
   sc_beam_t d;
+  sc_beam_lm_t lm{};
   BeamState() {
     d.n_frames = 0; d.n_bad = 0; d.n_nodes = 1; d.n_entries = 1;
     for (sc_beam_entry &e : d.e) e = sc_beam_entry{-1, -1, 0, -1, -INFINITY, -INFINITY};
     d.e[0] = sc_beam_entry{0, -1, 0, -1, 0.0, -INFINITY};
   }
   explicit BeamState(const sc_beam_t &v) : d(v) {}
+  BeamState(const sc_beam_t &v, const sc_beam_lm_t &l) : d(v), lm(l) {}
 };
 // Input level (sc_stream_set_input_format; pcm.hip): the cumulative level, all zero at first.  Its launch belongs to a
 // STAGING slot (it runs in the admission's staging step, not in an encoder group), so its key is a ticket that names the
@@ -402,6 +406,14 @@ struct sc_streams {
   sc_ctc_beam_job *beam_jobs_host = nullptr, *beam_jobs_dev = nullptr;   // [N_ARENA][S]: the job table of a group's launch
   sc_beam_t *beam_out_host = nullptr, *beam_out_dev = nullptr;           // [N_ARENA][S] host-mapped: the jobs' states-after
   handover::Track<BeamState> beam;          // keyed by encoder group, as act
+  // language model fused into the beam (sc_streams_set_ctc_beam_lm): allocated when a model is first attached
+  const sc_lm *beam_lm = nullptr;           // the caller's model (NULL: none - the group launches sc_ctc_beam as before)
+  const sc_lm_view *beam_lm_view = nullptr; // its device view
+  sc_lm_view beam_lm_info{};                // ... and a host copy of it
+  double beam_alpha = 0.0, beam_beta = 0.0;
+  sc_beam_lm_t *beam_lm_state = nullptr;    // device [S], beside beam_state
+  sc_ctc_beam_lm_job *beam_lm_jobs_host = nullptr, *beam_lm_jobs_dev = nullptr;   // [N_ARENA][S]
+  sc_beam_lm_t *beam_lm_out_host = nullptr, *beam_lm_out_dev = nullptr;           // [N_ARENA][S] host-mapped, beside beam_out
   char *bh_dev = nullptr, *bh_host = nullptr;   // sc_ctc_beam_hyps: states, pack jobs and packed outputs; grown geometrically
   size_t bh_cap = 0;
   size_t beam_ncap() const { return 1 + (size_t)beam_nodes_B * TCAP; }
@@ -1037,7 +1049,9 @@ int retire_groups(sc_streams *b) {
       if (sp.opt[OPT_DRAFT].on)
         b->draft.deliver(s, g->gen, sp.opt[OPT_DRAFT].epoch, DraftState{b->draft_out_host[o]}, b->job[s], b->ahead[s], &Job::draft);
       if (sp.opt[OPT_BEAM].on)
-        b->beam.deliver(s, g->gen, sp.opt[OPT_BEAM].epoch, BeamState(b->beam_out_host[o]), b->job[s], b->ahead[s], &Job::beam);
+        b->beam.deliver(s, g->gen, sp.opt[OPT_BEAM].epoch,
+                        b->beam_lm ? BeamState(b->beam_out_host[o], b->beam_lm_out_host[o]) : BeamState(b->beam_out_host[o]),
+                        b->job[s], b->ahead[s], &Job::beam);
     }
     b->gen_done = g->gen;
     b->slot_gen[g->slot] = 0;
@@ -1066,6 +1080,8 @@ void span_job(const sc_streams *b, J &j, const EncGroup::Span &sp, int opt) {
   j.V = V; j.blank = b->cfg.blank_id; j.t0 = sp.t0; j.t1 = sp.t1;
   j.restart = sp.opt[opt].restart ? 1 : 0;
 }
+
+void span_job(const sc_streams *b, sc_ctc_beam_lm_job &j, const EncGroup::Span &sp, int opt) { span_job(b, j.beam, sp, opt); }
 
 // The launch of one side-state option over the spans of a group: job i of slot g.slot's table is filled from span i (at: its
 // index in the [N_ARENA][S] tables, where its state-after slot is too) - span_job, then `fill` for the option's own fields -,
@@ -1129,14 +1145,24 @@ int project_rows(sc_streams *b, EncGroup &g) {
                           j.state_after = b->draft_out_dev + at;
                           j.capacity = b->TCAP;
                         }));
-    RC_TRY(launch_spans(b, g, OPT_BEAM, "beam", b->beam_jobs_host, b->beam_jobs_dev, sc_ctc_beam,
-                        [=](sc_ctc_beam_job &j, const EncGroup::Span &sp, size_t at) {
-                          j.state = b->beam_state + sp.s;
-                          j.nodes = b->beam_nodes + (size_t)sp.s * b->beam_ncap();
-                          j.state_after = b->beam_out_dev + at;
-                          j.capacity = (int32_t)b->beam_ncap();
-                          j.B = b->beam_B; j.C = b->beam_C;
-                        }));
+    const auto beam_fill = [=](sc_ctc_beam_job &j, const EncGroup::Span &sp, size_t at) {
+      j.state = b->beam_state + sp.s;
+      j.nodes = b->beam_nodes + (size_t)sp.s * b->beam_ncap();
+      j.state_after = b->beam_out_dev + at;
+      j.capacity = (int32_t)b->beam_ncap();
+      j.B = b->beam_B; j.C = b->beam_C;
+    };
+    if (!b->beam_lm)
+      RC_TRY(launch_spans(b, g, OPT_BEAM, "beam", b->beam_jobs_host, b->beam_jobs_dev, sc_ctc_beam, beam_fill));
+    else   // the same slot, the fused launch in its place
+      RC_TRY(launch_spans(b, g, OPT_BEAM, "beam", b->beam_lm_jobs_host, b->beam_lm_jobs_dev, sc_ctc_beam_lm,
+                          [=](sc_ctc_beam_lm_job &j, const EncGroup::Span &sp, size_t at) {
+                            beam_fill(j.beam, sp, at);
+                            j.lm = b->beam_lm_view;
+                            j.lm_state = b->beam_lm_state + sp.s;
+                            j.lm_state_after = b->beam_lm_out_dev + at;
+                            j.alpha = b->beam_alpha; j.beta = b->beam_beta;
+                          }));
   }
   if (!g.kv_dst.empty()) {
     if (!g.same_rows || !ar) RC_TRY(b->itensor(g.kv_src, &ar));
@@ -3644,6 +3670,12 @@ extern "C" int sc_streams_set_ctc_beam(sc_streams *b, int beam, int candidates) 
   SC_CHECK_ARG(b->n_open == 0, "chunks are outstanding");
   if (!beam) {
     b->beam_on = false;
+    if (b->beam_lm) {   // the model goes with the option (a group may still be in flight: it reads the model)
+      HIP_TRY(hipSetDevice(b->eng->device));
+      HIP_TRY(hipStreamSynchronize(b->es));
+      b->beam_lm = nullptr;
+      b->beam_lm_view = nullptr;
+    }
     return SC_OK;
   }
   SC_CHECK_ARG(beam >= 1 && beam <= SC_BEAM_MAX && candidates >= 1 && candidates <= SC_BEAM_MAX,
@@ -3670,6 +3702,90 @@ extern "C" int sc_streams_set_ctc_beam(sc_streams *b, int beam, int candidates) 
   b->beam_B = beam;
   b->beam_C = candidates;
   b->beam_on = true;
+  return SC_OK;
+  SC_API_END
+}
+
+extern "C" int sc_streams_set_ctc_beam_lm(sc_streams *b, const sc_lm *lm, double alpha, double beta) {
+  SC_CHECK_ARG(b, "null");
+  SC_API_BEGIN
+  SC_CHECK_ARG(b->n_open == 0, "chunks are outstanding");
+  HIP_TRY(hipSetDevice(b->eng->device));
+  if (!lm) {
+    if (!b->beam_lm) return SC_OK;
+    HIP_TRY(hipStreamSynchronize(b->es));   // a group may still be in flight: it reads the model
+    b->beam_lm = nullptr;
+    b->beam_lm_view = nullptr;
+    b->beam.restart_all();
+    return SC_OK;
+  }
+  SC_CHECK_ARG(b->beam_on, "the beam option is off (sc_streams_set_ctc_beam)");
+  SC_CHECK_ARG(std::isfinite(alpha) && std::isfinite(beta), "alpha and beta must be finite");
+  sc_lm_view info;
+  const sc_lm_view *view = nullptr;
+  RC_TRY(sc_lm_device_view(lm, &view, &info));
+  SC_CHECK_ARG(view && info.V == b->cfg.vocab_size, "the model's vocabulary size is not the batch's");
+  if (!b->beam_lm_state) {
+    const size_t S = (size_t)b->S;
+    RC_TRY(b->alloc(&b->beam_lm_state, S));
+    RC_TRY(b->alloc(&b->beam_lm_jobs_dev, S * N_ARENA));
+    RC_TRY(b->halloc(&b->beam_lm_jobs_host, S * N_ARENA));
+    RC_TRY(b->halloc_mapped(&b->beam_lm_out_host, &b->beam_lm_out_dev, S * N_ARENA, __func__, "state slots"));
+  }
+  HIP_TRY(hipStreamSynchronize(b->es));     // (a group in flight may read the model that is being replaced)
+  b->beam.restart_all();   // every stream starts over: a stream in mid-utterance is searched from its next frame on
+  b->beam_lm = lm;
+  b->beam_lm_view = view;
+  b->beam_lm_info = info;
+  b->beam_alpha = alpha;
+  b->beam_beta = beta;
+  return SC_OK;
+  SC_API_END
+}
+
+// the model's side of the state sc_stream_ctc_beam returns: before the first frames of an utterance (0.0, start_state)
+extern "C" int sc_stream_ctc_beam_lm(sc_streams *b, int stream, sc_beam_lm_t *out) {
+  SC_CHECK_ARG(b && out && stream >= 0 && stream < b->S, "bad arguments");
+  SC_API_BEGIN
+  SC_CHECK_ARG(b->beam_on && b->beam_lm, "no language model is attached (sc_streams_set_ctc_beam_lm)");
+  HIP_TRY(hipSetDevice(b->eng->device));
+  RC_TRY(beam_ready(b, stream));
+  const BeamState &v = b->beam.rep[stream].v;
+  *out = v.lm;
+  if (v.d.n_frames == 0) out->ctx[0] = b->beam_lm_info.start_state;
+  return SC_OK;
+  SC_API_END
+}
+
+// beside sc_ctc_beam_hyps' scores: lm [n][nbest] and fused [n][nbest] = lae(pb, pnb) + (alpha * lm + beta * len) of the
+// same entries (NaN where the state has no such entry); host arithmetic on the reported states, no launch.  Either may
+// be NULL.
+extern "C" int sc_ctc_beam_hyps_lm(sc_streams *b, const int *stream_ids, int n, int nbest, double *lm, double *fused) {
+  SC_CHECK_ARG(b && stream_ids && n >= 0 && nbest >= 0 && nbest <= SC_BEAM_MAX, "bad arguments");
+  SC_API_BEGIN
+  SC_CHECK_ARG(b->beam_on && b->beam_lm, "no language model is attached (sc_streams_set_ctc_beam_lm)");
+  SC_CHECK_ARG(n <= b->S, "more streams listed than the batch has");
+  HIP_TRY(hipSetDevice(b->eng->device));
+  for (int i = 0; i < n; ++i) {
+    const int s = stream_ids[i];
+    SC_CHECK_ARG(s >= 0 && s < b->S, "stream out of range");
+    RC_TRY(beam_ready(b, s));
+    const BeamState &v = b->beam.rep[s].v;
+    for (int r = 0; r < nbest; ++r) {
+      const size_t k = (size_t)i * nbest + r;
+      double l = NAN, f = NAN;
+      if (r < v.d.n_entries) {
+        const sc_beam_entry &e = v.d.e[r];
+        const double hi = std::max(e.pb, e.pnb), lo = std::min(e.pb, e.pnb);
+        const double total = lo == -INFINITY ? hi : hi + log1p(exp(lo - hi));
+        l = v.lm.lm[r];
+        const double wa = b->beam_alpha * l, wb = b->beam_beta * (double)e.len;
+        f = total + (wa + wb);
+      }
+      if (lm) lm[k] = l;
+      if (fused) fused[k] = f;
+    }
+  }
   return SC_OK;
   SC_API_END
 }

@@ -109,10 +109,19 @@ def words_of(hyp: dict, names: Sequence, clock=None, subsample: int = 4, sample_
 
 
 def nbest(hyps: Sequence[dict], names: Optional[Sequence] = None, clock=None, subsample: int = 4,
-          sample_rate: int = 16000) -> List[dict]:
+          sample_rate: int = 16000, side: Optional[dict] = None) -> List[dict]:
     """hypotheses (best first) -> the n-best list of a reply: {"text", "ids", "score" (the prefix's log probability),
-    "conf" (its share of the listed mass, alternates.nbest_posterior of the totals), "tokens"}"""
+    "conf" (its share of the listed mass, alternates.nbest_posterior of the totals), "tokens"}.  ``side`` (a language
+    model is fused in, DESIGN.md 8k: {"lm", "fused"} of the same entries, NativeStreamBatch.ctc_beam_lm): every entry
+    also carries "lm", the model's log probability of its tokens, "score" is the FUSED total the beam ranks by
+    ("ctc_score": the prefix's own log probability), and "conf" comes from the fused totals."""
     totals = [total(h["pb"], h["pnb"]) for h in hyps]
-    confs = nbest_posterior(totals)
-    return [{"text": text_of(h["ids"], names), "ids": list(h["ids"]), "score": t, "conf": c,
-             "tokens": token_dicts(h, clock, subsample, sample_rate, names)} for h, t, c in zip(hyps, totals, confs)]
+    if side is None:
+        confs = nbest_posterior(totals)
+        return [{"text": text_of(h["ids"], names), "ids": list(h["ids"]), "score": t, "conf": c,
+                 "tokens": token_dicts(h, clock, subsample, sample_rate, names)} for h, t, c in zip(hyps, totals, confs)]
+    fused = [float(f) for f in side["fused"][:len(hyps)]]
+    confs = nbest_posterior(fused)
+    return [{"text": text_of(h["ids"], names), "ids": list(h["ids"]), "score": f, "ctc_score": t, "lm": float(l), "conf": c,
+             "tokens": token_dicts(h, clock, subsample, sample_rate, names)}
+            for h, t, f, l, c in zip(hyps, totals, fused, side["lm"], confs)]

@@ -570,6 +570,13 @@ class StreamBatch:
         self._beam = {"B": int(beam), "C": int(candidates), "state": [None] * self.S,
                       "proj": np.asarray([x.T_ctc for x in self.st], np.int64)}
 
+    def set_ctc_beam_lm(self, model=None, alpha: float = 0.5, beta: float = 0.0):
+        """n-gram fusion into the CTC beam is an option of the native engine: this one refuses it."""
+        if model is not None:
+            raise EngineError("set_ctc_beam_lm: language model fusion needs the native engine "
+                              "(NativeStreamBatch.set_ctc_beam_lm, sc_streams_set_ctc_beam_lm); the Python engine runs "
+                              "the CTC beam unfused only")
+
     def _beam_state(self, s: int) -> dict:
         if self._beam is None:
             raise EngineError("the beam option is off (set_ctc_beam)")

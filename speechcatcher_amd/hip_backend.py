@@ -110,6 +110,32 @@ def decode_recording(buf, fmt, channels=1, channel=-1, scale=0, device="cuda:0",
     return out, total
 
 
+class DeviceLm:
+    """an n-gram model on the device (sc_lm_create / sc_lm_destroy): ``view`` is the device address of its sc_lm_view,
+    ``info`` a host copy of it"""
+
+    def __init__(self, lib, blob: bytes):
+        self._lib, self.handle = lib, C.c_void_p()
+        buf = (C.c_char * max(len(blob), 1)).from_buffer_copy(bytes(blob) or b"\0")
+        rc = lib.sc_lm_create(buf, len(blob), C.byref(self.handle))
+        if rc != 0:
+            self.handle = None
+            _abi.check(rc, "sc_lm_create")
+        self.info = _abi.LmView()
+        view = C.c_void_p()
+        _abi.check(lib.sc_lm_device_view(self.handle, C.byref(view), C.byref(self.info)), "sc_lm_device_view")
+        self.view = view.value
+        self.bytes = len(blob)
+
+    def close(self):
+        if self.handle:
+            self._lib.sc_lm_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        self.close()
+
+
 class HipBackend:
     name = "hip"
 
@@ -515,7 +541,20 @@ class HipBackend:
             rec["e"][r]["i"] = e[:4]
             rec["e"][r]["p"] = e[4:]
 
-    def ctc_beam(self, jobs, tweak=None, guard: int = 2):
+    _BEAM_LM = [("lm", "<f8", 16), ("ctx", "<i4", 16)]   # sc_beam_lm_t
+
+    def language_model(self, blob: bytes):
+        """a packed n-gram model (speechcatcher_amd.ngram.pack) validated and uploaded once (sc_lm_create)"""
+        return DeviceLm(self.lib, blob)
+
+    def ctc_beam_lm(self, jobs, model, alpha: float, beta: float, tweak=None, guard: int = 2):
+        """ctc_beam through sc_ctc_beam_lm: ``model`` (language_model(), or None: the jobs run unfused) fused in with
+        the weights alpha / beta.  A job's state dict may carry "side": [(lm, ctx)] beside its entries; the returned
+        states do, with "raw_lm": the sc_beam_lm_t as a numpy record; the second copies are (sc_beam_t, sc_beam_lm_t)
+        records.  The job handed to ``tweak`` is the sc_ctc_beam_lm_job (the plain job in its ``beam``)."""
+        return self.ctc_beam(jobs, tweak, guard, fused=(model, float(alpha), float(beta)))
+
+    def ctc_beam(self, jobs, tweak=None, guard: int = 2, fused=None):
         """Batched CTC prefix beam search (sc_ctc_beam) on the caller's tables, one launch for all jobs.  jobs: list of
         (table [T, V] fp32 tensor, rows may be strided; blank; t0; t1; state: a dict as returned here or None = the span
         starts an utterance; capacity of the node store; B; C).  Returns (states: list of {n_frames, n_bad, n_nodes,
@@ -544,19 +583,39 @@ class HipBackend:
                 for i, rec in enumerate(st["nodes"]):
                     store[off[k] + i] = tuple(rec) + (0,)
         state_d, after_d, store_d = (torch.as_tensor(a.view(np.uint8).copy()).to(dev) for a in (state, after, store))
-        tab = (_abi.BeamJob * max(1, n))()
+        if fused is not None:
+            lm_dt = np.dtype(self._BEAM_LM)
+            assert lm_dt.itemsize == C.sizeof(_abi.BeamLm) == 192
+            lms = np.zeros(max(n, 1), lm_dt)
+            lms.view(np.int32)[:] = -7
+            lms_after = lms.copy()
+            for k, job in enumerate(jobs):
+                if job[4] is not None:
+                    lms[k]["lm"], lms[k]["ctx"] = 0.0, 0
+                    for r, (l, c) in enumerate(job[4].get("side", [])):
+                        lms[k]["lm"][r], lms[k]["ctx"][r] = l, c
+            lms_d, lms_after_d = (torch.as_tensor(a.view(np.uint8).copy()).to(dev) for a in (lms, lms_after))
+        tab = ((_abi.BeamJob if fused is None else _abi.BeamLmJob) * max(1, n))()
         for k, (table, blank, t0, t1, st, cap, B, Cn) in enumerate(jobs):
             assert table.dtype == torch.float32 and table.dim() == 2 and table.stride(1) == 1
             assert 0 <= t0 <= t1 <= table.shape[0]
-            j = tab[k]
+            j = tab[k] if fused is None else tab[k].beam
             j.table, j.state, j.state_after = table.data_ptr(), state_d.data_ptr() + 528 * k, after_d.data_ptr() + 528 * k
             j.nodes = store_d.data_ptr() + 16 * int(off[k])
             j.stride, j.V, j.blank, j.t0, j.t1 = table.stride(0), table.shape[1], int(blank), int(t0), int(t1)
             j.restart, j.capacity, j.B, j.C = 1 if st is None else 0, int(cap), int(B), int(Cn)
+            if fused is not None:
+                jl = tab[k]
+                jl.lm = fused[0].view if fused[0] is not None else None
+                jl.lm_state, jl.lm_state_after = lms_d.data_ptr() + 192 * k, lms_after_d.data_ptr() + 192 * k
+                jl.alpha, jl.beta = fused[1], fused[2]
             if tweak is not None:
-                tweak(k, j)
+                tweak(k, tab[k])
         tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
-        self._chk(self.lib.sc_ctc_beam(tab_dev.data_ptr(), n, self._stream()), "sc_ctc_beam")
+        if fused is None:
+            self._chk(self.lib.sc_ctc_beam(tab_dev.data_ptr(), n, self._stream()), "sc_ctc_beam")
+        else:
+            self._chk(self.lib.sc_ctc_beam_lm(tab_dev.data_ptr(), n, self._stream()), "sc_ctc_beam_lm")
         torch.cuda.synchronize(dev)
         state, after = (a.cpu().numpy().view(st_dt) for a in (state_d, after_d))
         store = store_d.cpu().numpy().view(np.int32).reshape(-1, 4)
@@ -569,6 +628,12 @@ class HipBackend:
                  "raw_state": r.copy(), "raw_nodes": store[off[k]:off[k + 1]].copy()}
             d["nodes"] = [tuple(int(v) for v in rec[:3]) for rec in d["raw_nodes"][:max(0, min(d["n_nodes"], caps[k]))]]
             out.append(d)
+        if fused is not None:
+            lms, lms_after = (a.cpu().numpy().view(lm_dt) for a in (lms_d, lms_after_d))
+            for k, d in enumerate(out):
+                d["raw_lm"] = lms[k].copy()
+                d["side"] = [(float(lms[k]["lm"][r]), int(lms[k]["ctx"][r])) for r in range(len(d["entries"]))]
+            return out, [(after[k].copy(), lms_after[k].copy()) for k in range(n)]
         return out, [after[k].copy() for k in range(n)]
 
     def ctc_beam_pack(self, jobs, tweak=None, guard: int = 2):

@@ -666,6 +666,45 @@ class NativeStreamBatch:
             out[int(s)] = hy
         return out
 
+    # ---- n-gram model fused into the CTC beam (sc_streams_set_ctc_beam_lm) ----------------------
+    def set_ctc_beam_lm(self, model=None, alpha: float = 0.5, beta: float = 0.0):
+        """Fuse a backoff n-gram model into the CTC prefix beam of every stream: ``model`` is a packed blob
+        (speechcatcher_amd.ngram.pack, or the bytes of a .sclm file), a hip_backend.DeviceLm, or None to detach.  The
+        beam then keeps its entries by total + alpha * lm + beta * len.  Needs set_ctc_beam; only while no chunk is
+        outstanding; every stream's beam starts over.  ``alpha`` / ``beta`` are parameters, not tuned."""
+        from .hip_backend import DeviceLm
+        lm = None
+        if model is not None:
+            try:
+                lm = model if isinstance(model, DeviceLm) else DeviceLm(self.lib, bytes(model))
+            except _abi.ScasrError as e:
+                raise EngineError(str(e)) from e
+        try:
+            _abi.check(self.lib.sc_streams_set_ctc_beam_lm(self.handle, lm.handle if lm is not None else None,
+                                                           float(alpha), float(beta)), "sc_streams_set_ctc_beam_lm")
+        except _abi.ScasrError as e:
+            raise EngineError(str(e)) from e
+        self._ctc_lm = lm   # (the engine reads the model on the device: it lives as long as it is attached)
+
+    def ctc_beam_lm(self, streams: Sequence[int], nbest: int = _abi.BEAM_MAX):
+        """[{"lm": [...], "ctx": [...], "fused": [...]}] beside ``ctc_beam``'s entries of the listed streams: the model's
+        sum along each entry's prefix, the automaton's state after it, and the fused score the beam ranks by."""
+        n, nbest = len(streams), min(int(nbest), _abi.BEAM_MAX)
+        ids_in = np.asarray(list(streams), np.int32)
+        fused = np.zeros((n, nbest), np.float64)
+        out = []
+        a = _abi.BeamLm()
+        try:
+            _abi.check(self.lib.sc_ctc_beam_hyps_lm(self.handle, ids_in.ctypes.data_as(_abi.c_int_p), n, nbest, None,
+                                                    fused.ctypes.data), "sc_ctc_beam_hyps_lm")
+            for i, s in enumerate(streams):
+                _abi.check(self.lib.sc_stream_ctc_beam_lm(self.handle, int(s), C.byref(a)), "sc_stream_ctc_beam_lm")
+                k = int(np.sum(~np.isnan(fused[i])))
+                out.append({"lm": list(a.lm[:k]), "ctx": list(a.ctx[:k]), "fused": fused[i, :k].tolist()})
+        except _abi.ScasrError as e:
+            raise EngineError(str(e)) from e
+        return out
+
     def hypotheses_batch(self, streams: Sequence[int], nbest: Optional[int] = None):
         """{stream: [hypothesis dicts, best first]} for the listed streams, one device round trip for all."""
         a = self.hypotheses_arrays(streams, nbest)

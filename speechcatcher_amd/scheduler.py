@@ -110,7 +110,8 @@ class StreamScheduler:
                  result_format: str = "native", reset_after_final: bool = True, reset_on_open: bool = True,
                  queue_depth: int = 1, align_final: bool = False, activity: bool = False, blank_threshold: float = 0.8,
                  phrases=None, min_scores=None, draft: bool = False, input_level: bool = False, alternates: int = 0,
-                 align_nbest: int = 1, stable_partials: bool = False, ctc_beam=None):
+                 align_nbest: int = 1, stable_partials: bool = False, ctc_beam=None, ctc_lm=None,
+                 lm_weight: float = 0.5, word_bonus: float = 0.0):
         """``queue_depth`` > 1 (C++ engine, ``pump``): up to that many queued chunks of a session are handed to the engine
         at a time (sc_streams_set_queue_depth) - for sessions whose audio is already there (files): the encoder stage of
         the next chunk runs beside the decoding of the current one.  Replies and their order per session do not change.
@@ -143,6 +144,10 @@ class StreamScheduler:
         # ``ctc_beam``: (B, C) when on - every reply (an exception aside) is a ``CtcBeamResults`` (batch.set_ctc_beam),
         # read before the stream is reset after a final; sessions opened with decoder="ctc" are served from it alone
         self.ctc_beam = None
+        # ``ctc_lm`` (needs ``ctc_beam``; C++ engine): the path of a packed n-gram model (speechcatcher_amd.ngram) or its
+        # bytes - the beam keeps its entries by total + lm_weight * lm + word_bonus * len, the entries of
+        # ``ctc_nbest`` gain "lm" and their "score" is that fused total.  (lm_weight, word_bonus) when on.
+        self.ctc_lm = None
         self._ctc_sessions = set()
         self._slot_dec: Dict[int, str] = {}
         # ``stable_partials``: every reply (an exception aside) is a ``StableResults``.  The scheduler owns one
@@ -184,6 +189,8 @@ class StreamScheduler:
             self.enable_draft()
         if beam_mod.params(ctc_beam):
             self.enable_ctc_beam(*beam_mod.params(ctc_beam))
+        if ctc_lm is not None:
+            self.enable_ctc_lm(ctc_lm, lm_weight, word_bonus)
         if alternates:
             self.enable_alternates(alternates)
         if stable_partials:
@@ -211,6 +218,21 @@ class StreamScheduler:
             raise NotImplementedError("this batch has no CTC prefix beam search (set_ctc_beam)")
         self.batch.set_ctc_beam(int(beam), int(candidates))
         self.ctc_beam = (int(beam), int(candidates))
+
+    def enable_ctc_lm(self, source, lm_weight: float = 0.5, word_bonus: float = 0.0):
+        """fuse an n-gram model into the CTC beam (only while no chunk is at the engine; every stream's beam starts
+        over).  ``source``: the path of a packed model or its bytes; None detaches it."""
+        if self.ctc_beam is None:
+            raise ValueError("ctc_lm needs the ctc_beam option (StreamScheduler(ctc_beam=...))")
+        if not hasattr(self.batch, "set_ctc_beam_lm"):
+            raise NotImplementedError("this batch has no language model fusion (set_ctc_beam_lm)")
+        if source is None:
+            self.batch.set_ctc_beam_lm(None)
+            self.ctc_lm = None
+            return
+        from . import ngram
+        self.batch.set_ctc_beam_lm(ngram.load(source), float(lm_weight), float(word_bonus))
+        self.ctc_lm = (float(lm_weight), float(word_bonus))
 
     def enable_stable_partials(self):
         """switch the ``stable_partials`` option on (every session's tracker starts over)"""
@@ -461,10 +483,12 @@ class StreamScheduler:
                 held = [self._stable.setdefault(sid, commit_mod.StablePrefix()).next_from for sid, _ in ask]
                 delta = self.batch.hyps_delta([slot for _, slot in ask], held,
                                               final=[slot for sid, slot in ask if meta[sid][1]])
-        beams = None
+        beams, sides = None, {}
         if self.ctc_beam is not None:   # ONE launch and one copy back for the round (sc_ctc_beam_hyps)
             ask = [slot for (slot, _, _) in meta.values() if not isinstance(has[slot], Exception)]
             beams = self.batch.ctc_beam_hyps(ask, self.ctc_beam[0]) if ask else {}
+            if self.ctc_lm is not None and ask:   # the model's side of the same entries (host arithmetic, no launch)
+                sides = dict(zip(ask, self.batch.ctc_beam_lm(ask, self.ctc_beam[0])))
         for sid, (slot, fin, fa) in meta.items():
             if self._clocked and self._fed.get(sid):   # the stream's clock advances by the reported chunk
                 n, f = self._fed[sid].popleft()
@@ -517,7 +541,7 @@ class StreamScheduler:
                 res.stable = self._stable[sid].update(delta[slot], final=fin).state()   # (a final starts the tracker over)
                 out[sid] = res
             if beams is not None:
-                nbest = self._ctc_nbest(sid, beams[slot])
+                nbest = self._ctc_nbest(sid, beams[slot], sides.get(slot))
                 # a decoder-free session: its results are the beam's entries, best first (a chunk the engine answers with
                 # nothing stays [])
                 free = sid in self._ctc_sessions
@@ -534,11 +558,11 @@ class StreamScheduler:
                 self._spot_seen.pop(sid, None)
         return out
 
-    def _ctc_nbest(self, sid: int, hyps: list) -> list:
-        """the n-best list of the session's beam (``hyps``: its entries as batch.ctc_beam_hyps gives them): frames, and
-        seconds by the session's feature clock"""
+    def _ctc_nbest(self, sid: int, hyps: list, side: Optional[dict] = None) -> list:
+        """the n-best list of the session's beam (``hyps``: its entries as batch.ctc_beam_hyps gives them; ``side``: the
+        language model's side of them when one is attached): frames, and seconds by the session's feature clock"""
         cfg = self.batch.cfg
-        out = beam_mod.nbest(hyps, names=self.token_list)
+        out = beam_mod.nbest(hyps, names=self.token_list, side=side)
         clock = self._clock.get(sid) or FeatureClock(cfg.win_length, cfg.hop_length)
         for entry, h in zip(out, hyps):
             secs = beam_mod.token_dicts(h, clock, cfg.subsample, cfg.sample_rate)
@@ -723,7 +747,8 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
                        chunk_length: int = 8192, token_list: Optional[List[str]] = None,
                        frames_per_second: float = 24.0, finalize_all_last_only: bool = False,
                        queue_depth: int = 1, token_alignment: bool = False, token_alternates: int = 0,
-                       ctc_beam=None, ctc_only: bool = False) -> List[dict]:
+                       ctc_beam=None, ctc_only: bool = False, ctc_lm=None, lm_weight: float = 0.5,
+                       word_bonus: float = 0.0) -> List[dict]:
     """Decode the (start, end) sample ranges of one recording as PARALLEL streams
     of one batch instead of the reference's process pool over segments
     (speechcatcher/speechcatcher.py:474-497, chunk loop :574-592; SURVEY 8(f)
@@ -737,8 +762,12 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
     segment also gets ``ctc_nbest``, the n-best list of the CTC prefix beam search over it ({"text", "score", "conf"} per
     entry, best first).  ``ctc_only`` (implies ``ctc_beam``, default (8, 8)): the segments are decoder-free
     streams - text, tokens and token_timestamps are the beam's best, token_start / token_end the prefix tree's frames; not
-    with ``token_alternates``."""
+    with ``token_alternates``.  ``ctc_lm`` (needs ``ctc_beam`` or ``ctc_only``): a packed n-gram model fused into that
+    search with ``lm_weight`` / ``word_bonus``; the entries of ``ctc_nbest`` then carry "lm" too and their
+    "score" is the fused total."""
     token_alignment = token_alignment or token_alternates > 0
+    if ctc_lm is not None and not (ctc_only or beam_mod.params(ctc_beam)):
+        raise ValueError("ctc_lm: the model is fused into the CTC prefix beam search - it needs ctc_beam or ctc_only")
     if ctc_only and token_alternates:
         raise ValueError("ctc_only: token alternates rank the frames of a forced alignment against a decode block's rows, "
                          "which a decoder-free stream does not have")
@@ -748,7 +777,8 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
     # +6..12 % when the search is decode-heavy (no block-boundary detection, <= 32 segments), nothing to -8 % with
     # detection on (the CLI's default), hence off by default
     sch = StreamScheduler(batch, token_list, result_format="espnet", queue_depth=queue_depth, align_final=token_alignment,
-                          alternates=token_alternates, ctc_beam=ctc_beam)
+                          alternates=token_alternates, ctc_beam=ctc_beam, ctc_lm=ctc_lm, lm_weight=lm_weight,
+                          word_bonus=word_bonus)
     out: List[Optional[dict]] = [None] * len(segments)
     todo = list(enumerate(segments))
     sid_to_seg: Dict[int, int] = {}
@@ -782,7 +812,7 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
                     out[idx] = {"text": "", "tokens": [], "token_ids": [], "token_timestamps": [],
                                 "score": 0.0, "start": start_s}
                 if sch.ctc_beam is not None:   # (a list of one n-best per segment: paragraphs append them)
-                    out[idx]["ctc_nbest"] = [[{"text": e["text"], "score": e["score"], "conf": e["conf"]}
+                    out[idx]["ctc_nbest"] = [[{k: e[k] for k in ("text", "score", "conf", "lm", "ctc_score") if k in e}
                                               for e in (getattr(res, "ctc_nbest", None) or [])]]
                 if token_alignment:
                     al = getattr(res, "alignment", None) if res else None

@@ -226,7 +226,8 @@ class ServerLoop:
                  acoustic_endpointing: Optional[EndpointRules] = None, spotting: Optional[dict] = None,
                  spotting_min_scores: Optional[dict] = None, draft_partials: bool = False, raw_input: bool = False,
                  input_level: bool = False, vosk_alternatives: int = 0, token_alternates: int = 0,
-                 stable_partials: bool = False, ctc_beam=None):
+                 stable_partials: bool = False, ctc_beam=None, ctc_lm=None, lm_weight: float = 0.5,
+                 word_bonus: float = 0.0):
         """``strict_reference``: no stream reset after a finalised utterance nor between clients, exactly like
         ``recognize_ws`` / ``process_audio_chunk`` (speechcatcher_server.py:270,359-397); the default resets.
         ``continuous`` (default: on whenever the batch has the C++ engine's submit / poll - round 4; False forces one
@@ -281,14 +282,22 @@ class ServerLoop:
         ``vosk_alternatives`` needed) from the beam's n-best with confidence = each entry's share of the listed mass, word
         times from the prefix tree's frames with ``vosk_alignment``.  The endpointing rules are unchanged and operate on that
         text.  ``"decoder": "full"`` goes back.  Counts the frames of an utterance from the reset after a final, so not with
-        ``strict_reference``.  None (default): the key is refused."""
+        ``strict_reference``.  None (default): the key is refused.
+        ``ctc_lm`` (needs ``ctc_beam``): the path of a packed n-gram model (speechcatcher_amd.ngram) or its bytes, fused
+        into that search with ``lm_weight`` / ``word_bonus`` (the scheduler's ``ctc_lm`` option): the
+        beam's best and its n-best are ranked by the fused totals, and the ``max_alternatives`` confidences of a
+        decoder-free session are the entries' shares of the listed FUSED mass."""
         from . import ctc_beam as beam_mod
+        if ctc_lm is not None and not (beam_mod.params(ctc_beam) or scheduler.ctc_beam is not None):
+            raise ValueError("ctc_lm needs the ctc_beam option")
         if beam_mod.params(ctc_beam):
             if strict_reference:
                 raise ValueError("the CTC prefix beam search counts the frames of an utterance from the reset after a final: "
                                  "not with strict_reference")
             if scheduler.ctc_beam is None:
                 scheduler.enable_ctc_beam(*beam_mod.params(ctc_beam))
+        if ctc_lm is not None:
+            scheduler.enable_ctc_lm(ctc_lm, lm_weight, word_bonus)
         self.stable_partials = bool(stable_partials) and vosk_output_format
         if self.stable_partials and not scheduler.stable_partials:
             scheduler.enable_stable_partials()
