@@ -669,6 +669,58 @@ typedef struct sc_ctc_beam_lm_job {
  * ctx outside [0, n_states) without restart. */
 int sc_ctc_beam_lm(const sc_ctc_beam_lm_job *jobs, int n_jobs, void *stream);
 
+/* ---- n-gram rescoring of n-best lists, with an </s> term (lm_rescore.hip, lm_score.h) ---------------
+ * A job is one list: n_hyp <= SC_RESCORE_MAX_HYPS rows of token ids, row h at yseq + h * row_stride with lens[h] tokens
+ * (lens == NULL: L tokens each; a lens[h] outside [0, L] makes the row a bad one, below), their totals at
+ * score[h * score_stride].  The LABELS of a row are its tokens without the first `skip` (1 for <sos>) and without ONE
+ * trailing token equal to `strip` (-1: none is dropped; as sc_align_hyps drops a trailing <eos>): y_0 .. y_{m-1}.  With
+ * score() of the model above:
+ *   s_0 = state0 (-1: the model's start_state);  (l_t, s_{t+1}) = score(s_t, y_t);  tok_lm[h * tok_stride + t] = l_t
+ *   lm[h]        ((0.0 + l_0) + l_1) + ..., ascending t - what an entry of sc_ctc_beam_lm carries for the same prefix
+ *   end_state[h] s_m
+ *   eos_lm[h]    score(s_m, lm_eos) when lm_eos >= 0 (the id that stands for </s> in the model), else 0.0
+ *   fused[h]     score[h] + (alpha * (lm[h] + eos_lm[h]) + beta * m), every product and sum rounded on its own; a NaN is
+ *                stored as the quiet NaN 0x7FF8000000000000
+ *   order[r]     the row at rank r: fused descending, ties to the lower row
+ * status[h]: SC_RESCORE_NONFINITE when score[h] or fused[h] is not finite; SC_RESCORE_BAD_TOKEN for a label outside
+ * [0, V) (or a bad lens[h]): lm = eos_lm = 0.0, every tok_lm of the row 0.0, end_state -1, fused NaN.  Rows of both kinds
+ * rank behind all others, in row order among themselves.  SC_RESCORE_SERIAL: the row was walked label by label by one
+ * lane and not by the speculate-and-verify form (a row on which a guessed state did not hold, or every row of a job with
+ * SC_RESCORE_FORCE_SERIAL) - both forms give the same bits.  tests/lm_rescore_ref.py is the contract: every output bit
+ * for bit. */
+#define SC_RESCORE_MAX_HYPS 16
+#define SC_RESCORE_FORCE_SERIAL 1 /* flags */
+#define SC_RESCORE_NONFINITE 1    /* status bits */
+#define SC_RESCORE_BAD_TOKEN 2
+#define SC_RESCORE_SERIAL 4
+typedef struct sc_lm_rescore_job {
+  const sc_lm_view *model;  /* device view (sc_lm_device_view) */
+  const int32_t *yseq;      /* row h at yseq + h * row_stride (device) */
+  const double *score;      /* total of row h at score[h * score_stride] (device) */
+  const int32_t *lens;      /* [n_hyp] tokens per row, or NULL: L each (device) */
+  double *lm;               /* [n_hyp] (device) */
+  double *eos_lm;           /* [n_hyp] (device) */
+  double *fused;            /* [n_hyp] (device) */
+  int32_t *end_state;       /* [n_hyp] (device) */
+  int32_t *order;           /* [n_hyp] (device) */
+  int32_t *status;          /* [n_hyp] SC_RESCORE_* (device) */
+  double *tok_lm;           /* row h at tok_lm + h * tok_stride, m values; NULL: not wanted (device) */
+  int64_t row_stride;       /* int32 elements between two rows, >= L */
+  int64_t score_stride;     /* doubles between two rows' scores, >= 1 */
+  int64_t tok_stride;       /* doubles between two rows of tok_lm, >= max(0, L - skip) when tok_lm is given */
+  double alpha, beta;       /* weight of the model's log probability, bonus per label; finite */
+  int32_t n_hyp, L, skip, strip, state0, lm_eos, V, flags;
+} sc_lm_rescore_job;
+#define SC_RESCORE_MAX_JOBS 65535
+/* jobs: device table of n_jobs entries.  ONE launch on `stream`, one workgroup per job: no atomics, one writer per
+ * output, plain stores; the model, the rows and the scores are only read, nothing outside the sizes above is written.
+ * SC_ERR_ARG before anything is launched for n_jobs outside [0, SC_RESCORE_MAX_JOBS] or a null table with n_jobs > 0.  A
+ * job whose own fields are malformed (a null pointer other than lens / tok_lm, n_hyp outside [1, SC_RESCORE_MAX_HYPS],
+ * L < 0, row_stride < L, score_stride < 1, tok_stride < max(0, L - skip) with tok_lm, skip < 0, strip < -1, a model whose
+ * V differs from the job's, state0 outside [-1, n_states), lm_eos outside [-1, V), an alpha or beta that is not finite,
+ * unknown flags) writes nothing.  Two jobs of one call must not share outputs. */
+int sc_lm_rescore(const sc_lm_rescore_job *jobs, int n_jobs, void *stream);
+
 /* ---- CTC token alternates (alternates.hip) -----------------------------------------------------
  * "What else could this token have been": for each of L token spans [start[k], end[k]) over the T rows of an fp32 CTC
  * table, the K acoustically best tokens of those frames and the rank of the span's own label y[k] among them.  Per span,
@@ -1132,6 +1184,26 @@ int sc_get_hyps_batch(sc_streams *streams, const int *stream_ids, int n, int nbe
 int sc_get_hyps_delta(sc_streams *streams, const int *stream_ids, int n, const int *from, const int *final,
                       int max_tail, int32_t *L, int32_t *commit, int32_t *n_hyps, int32_t *ids, int32_t *xpos,
                       double *stability, double *scores, int32_t *status);
+/* N-gram rescoring of the hypotheses sc_get_hyps_batch would return (sc_lm_rescore above; same rules: the
+ * snapshot with a queue depth > 1, an error for a stream inside a decode block or listed twice): per stream its first
+ * n_hyps[i] = min(nbest, live hypotheses) rows, labels without <sos> and without a trailing <eos>, from the model's
+ * start_state; the </s> term (lm_eos >= 0: the id that stands for </s> in the model, -1: none) only where final[i] != 0
+ * (final may be NULL).  order / fused / lm_sum / eos_lm / status [n][nbest] (any may be NULL; entries behind n_hyps[i] are
+ * left as they are); order[i][r] indexes the rows of sc_get_hyps_batch.  lm: any sc_lm whose V is the model's vocabulary
+ * size; it is not bound to the handle, and the call has synchronised before it returns.  nbest <= SC_RESCORE_MAX_HYPS.
+ * The buffers are allocated by the first call; ONE job-table upload, ONE launch and ONE copy back into pinned memory,
+ * all on the read-back stream.  Reads the engine's state, changes none, keeps none of its own. */
+int sc_rescore_hyps(sc_streams *streams, const int *stream_ids, int n, int nbest, const sc_lm *lm, double alpha,
+                    double beta, int lm_eos, const int *final, int32_t *order, double *fused, double *lm_sum,
+                    double *eos_lm, int32_t *status, int *n_hyps);
+/* The same launch for caller-given lists (all arrays HOST): list i has list_sizes[i] <= nbest rows, row r the LABELS
+ * ids[i][r][0 .. lens[i][r]) - nothing skipped, nothing stripped - and the total scores[i][r]; state0[i] is the
+ * automaton's state before the first label (-1, or state0 == NULL: the model's start_state).  Outputs [n][nbest] as above,
+ * and end_state.  How the final of a decoder-free stream gets its </s> term (the ids and totals of sc_ctc_beam_hyps). */
+int sc_lm_rescore_lists(sc_streams *streams, const sc_lm *lm, const int32_t *ids, const int32_t *lens,
+                        const double *scores, const int *list_sizes, int n, int nbest, int max_len,
+                        const int32_t *state0, double alpha, double beta, int lm_eos, int32_t *order, double *fused,
+                        double *lm_sum, double *eos_lm, int32_t *status, int32_t *end_state);
 /* CTC forced alignment of the hypotheses sc_get_hyps_batch would return (same rules: the snapshot with a queue depth
  * > 1, an error for a stream inside a decode block), best first, against the stream's own CTC rows: the T frames of
  * the decode block the hypotheses come from.  Labels: yseq without <sos> and without a trailing <eos>.  Outputs

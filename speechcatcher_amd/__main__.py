@@ -73,7 +73,8 @@ def to_16k(raw, rate, device="cuda:0"):
 
 def recognize_file(speech2text, media_path, output_file="", quiet=True, progress=True, num_slots=1, chunk_length=8192,
                    token_alignment=False, segmentation="host", channel=None, token_alternates=0, ctc_beam=0,
-                   ctc_only=False, ctc_lm=None, lm_weight=0.5, word_bonus=0.0):
+                   ctc_only=False, ctc_lm=None, lm_weight=0.5, word_bonus=0.0, rescore_lm=None, rescore_weight=0.5,
+                   rescore_bonus=0.0):
     """speechcatcher.py:358-400: recording -> text + paragraphs JSON next to the input.  ``token_alignment``: the
     paragraphs also get token_start / token_end (seconds) and token_conf from a CTC forced alignment of each segment.
     ``segmentation``: "host" or "gpu" - where the energy curve for the cut points of a recording over 60 s is computed.
@@ -83,7 +84,13 @@ def recognize_file(speech2text, media_path, output_file="", quiet=True, progress
     per segment the n-best list of the CTC prefix beam search; ``ctc_only``: the segments are decoded by that search alone,
     with no attention decoder step (B = 8 unless ``ctc_beam`` says otherwise; not with ``token_alternates``).  ``ctc_lm``:
     the path of a packed n-gram model (python -m speechcatcher_amd.ngram) fused into that search with ``lm_weight`` and
-    ``word_bonus`` (needs ``ctc_beam`` or ``ctc_only``)."""
+    ``word_bonus`` (needs ``ctc_beam`` or ``ctc_only``).  ``rescore_lm``: the path of a packed n-gram model the final
+    n-best list of every segment is rescored with and re-ranked by, at ``rescore_weight`` / ``rescore_bonus`` (not with
+    ``ctc_only``)."""
+    if rescore_lm and ctc_only:
+        raise SystemExit("Error: --rescore-lm re-ranks the n-best list of the attention decoder's search: not with --ctc-only")
+    if rescore_lm and not os.path.isfile(rescore_lm):
+        raise SystemExit(f"Error: --rescore-lm: '{rescore_lm}' does not exist or is not a file")
     if ctc_lm and not (ctc_only or int(ctc_beam)):
         raise SystemExit("Error: --ctc-lm is fused into the CTC prefix beam search: it needs --ctc-beam or --ctc-only")
     if ctc_lm and not os.path.isfile(ctc_lm):
@@ -111,7 +118,9 @@ def recognize_file(speech2text, media_path, output_file="", quiet=True, progress
                                      reference_finalize=True, token_alignment=token_alignment,
                                      segmentation=segmentation, token_alternates=token_alternates,
                                      ctc_beam=int(ctc_beam) or None, ctc_only=ctc_only, ctc_lm=ctc_lm or None,
-                                     lm_weight=float(lm_weight), word_bonus=float(word_bonus))
+                                     lm_weight=float(lm_weight), word_bonus=float(word_bonus),
+                                     rescore_lm=rescore_lm or None, rescore_weight=float(rescore_weight),
+                                     rescore_bonus=float(rescore_bonus))
     out_txt, out_json = (output_file or media_path) + ".txt", (output_file or media_path) + ".json"
     with open(out_txt, "w") as f:
         f.write(text)
@@ -167,6 +176,14 @@ def make_parser():
                    help="weight of the model's log probability in the beam's ranking (default 0.5; a parameter, not tuned)")
     p.add_argument("--word-bonus", dest="word_bonus", type=float, default=0.0, metavar="B",
                    help="bonus per token of a prefix in the beam's ranking (default 0)")
+    p.add_argument("--rescore-lm", dest="rescore_lm", default="", metavar="FILE",
+                   help="rescore the final n-best list of every segment with a backoff n-gram language model on the GPU and "
+                        "report the fused best (a file packed by `python -m speechcatcher_amd.ngram`; not with --ctc-only)")
+    p.add_argument("--rescore-weight", dest="rescore_weight", type=float, default=0.5, metavar="A",
+                   help="weight of the model's log probability, </s> included, in the re-ranking (default 0.5; a parameter, "
+                        "not tuned)")
+    p.add_argument("--rescore-bonus", dest="rescore_bonus", type=float, default=0.0, metavar="B",
+                   help="bonus per token of a hypothesis in the re-ranking (default 0)")
     p.add_argument("--segmentation", dest="segmentation", choices=["host", "gpu"], default="host",
                    help="where the energy curve for the cut points of a recording over 60 s is computed: 'host' (numpy, the "
                         "default) or 'gpu' (float64 kernels; the same cuts, without the host pass over the whole recording)")
@@ -202,7 +219,8 @@ def main(argv=None):
                    num_slots=1 if args.num_processes < 1 else args.num_processes, chunk_length=args.chunk_length,
                    token_alignment=args.token_alignment or args.token_alternates > 0, segmentation=args.segmentation,
                    channel=args.channel, token_alternates=args.token_alternates, ctc_beam=args.ctc_beam,
-                   ctc_only=args.ctc_only, ctc_lm=args.ctc_lm or None, lm_weight=args.lm_weight, word_bonus=args.word_bonus)
+                   ctc_only=args.ctc_only, ctc_lm=args.ctc_lm or None, lm_weight=args.lm_weight, word_bonus=args.word_bonus,
+                   rescore_lm=args.rescore_lm or None, rescore_weight=args.rescore_weight, rescore_bonus=args.rescore_bonus)
     return 0
 
 

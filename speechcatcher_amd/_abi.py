@@ -194,6 +194,20 @@ class LmView(C.Structure):
 LM_MAX_ORDER, LM_MAGIC, LM_VERSION = 5, 0x4D4C4353, 1
 
 
+class RescoreJob(C.Structure):
+    """sc_lm_rescore_job (include/scasr.h): one n-best list rescored by sc_lm_rescore"""
+    _fields_ = ([(n, vp) for n in ("model", "yseq", "score", "lens", "lm", "eos_lm", "fused", "end_state", "order",
+                                   "status", "tok_lm")]
+                + [(n, C.c_int64) for n in ("row_stride", "score_stride", "tok_stride")]
+                + [("alpha", C.c_double), ("beta", C.c_double)]
+                + [(n, C.c_int32) for n in ("n_hyp", "L", "skip", "strip", "state0", "lm_eos", "V", "flags")])
+
+
+# SC_RESCORE_* of include/scasr.h
+RESCORE_MAX_HYPS, RESCORE_MAX_JOBS, RESCORE_FORCE_SERIAL = 16, 65535, 1
+RESCORE_NONFINITE, RESCORE_BAD_TOKEN, RESCORE_SERIAL = 1, 2, 4
+
+
 class BeamPackJob(C.Structure):
     """sc_ctc_beam_pack_job (include/scasr.h): one entry of a beam state walked up its parent chain"""
     _fields_ = ([(n, vp) for n in ("state", "nodes", "ids", "frames", "header", "scores")]
@@ -412,6 +426,12 @@ _SIGS = {
     "sc_streams_set_ctc_beam_lm": (C.c_int, [vp, vp, C.c_double, C.c_double]),
     "sc_stream_ctc_beam_lm": (C.c_int, [vp, C.c_int, C.POINTER(BeamLm)]),
     "sc_ctc_beam_hyps_lm": (C.c_int, [vp, c_int_p, C.c_int, C.c_int, vp, vp]),
+    # n-gram rescoring of n-best lists (lm_rescore.hip, streams.hip)
+    "sc_lm_rescore": (C.c_int, [vp, C.c_int, vp]),
+    "sc_rescore_hyps": (C.c_int, [vp, c_int_p, C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_int, c_int_p, vp, vp,
+                                  vp, vp, vp, c_int_p]),
+    "sc_lm_rescore_lists": (C.c_int, [vp, vp, vp, vp, vp, c_int_p, C.c_int, C.c_int, C.c_int, vp, C.c_double,
+                                      C.c_double, C.c_int, vp, vp, vp, vp, vp, vp]),
     "sc_stream_set_decoder": (C.c_int, [vp, C.c_int, C.c_int]),
     "sc_stream_decoder": (C.c_int, [vp, C.c_int]),
     "sc_streams_read_ctc_projected": (C.c_int, [vp, C.c_int, vp, C.c_int]),

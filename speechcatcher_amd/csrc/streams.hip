@@ -416,6 +416,8 @@ struct sc_streams {
   sc_beam_lm_t *beam_lm_out_host = nullptr, *beam_lm_out_dev = nullptr;           // [N_ARENA][S] host-mapped, beside beam_out
   char *bh_dev = nullptr, *bh_host = nullptr;   // sc_ctc_beam_hyps: states, pack jobs and packed outputs; grown geometrically
   size_t bh_cap = 0;
+  char *rs_dev = nullptr, *rs_host = nullptr;   // sc_rescore_hyps / sc_lm_rescore_lists: job table, inputs, outputs; grown geometrically
+  size_t rs_cap = 0;
   size_t beam_ncap() const { return 1 + (size_t)beam_nodes_B * TCAP; }
   // ---- tick engine -----------------------------------------------------------------------------------------------------
   std::vector<St> st;
@@ -481,6 +483,8 @@ struct sc_streams {
     if (beam_nodes) (void)hipFree(beam_nodes);
     if (bh_dev) (void)hipFree(bh_dev);
     if (bh_host) (void)hipHostFree(bh_host);
+    if (rs_dev) (void)hipFree(rs_dev);
+    if (rs_host) (void)hipHostFree(rs_host);
   }
 
   template <typename T>
@@ -3123,6 +3127,196 @@ extern "C" int sc_get_hyps_delta(sc_streams *b, const int *stream_ids, int n, co
     if (ids) memcpy(ids + (size_t)i * max_tail, src + CM_FIXED + 2 * t, t * 4);
     if (xpos) memcpy(xpos + (size_t)i * max_tail, src + CM_FIXED + 3 * t, t * 4);
   }
+  return SC_OK;
+  SC_API_END
+}
+
+// ---- n-gram rescoring of n-best lists ---------------------------------------------------------------
+// rs_dev / rs_host hold [job table][inputs of caller-given lists][outputs]: what lies before the outputs goes up in ONE
+// copy, ONE sc_lm_rescore launch, the outputs come back in ONE copy, all on the read-back stream.  A job's outputs:
+// fused, lm, eos_lm [16] doubles, then end_state, order, status [16] int32.
+namespace {
+constexpr size_t RS_OUT = (size_t)SC_RESCORE_MAX_HYPS * (3 * sizeof(double) + 3 * sizeof(int32_t));
+
+int rs_reserve(sc_streams *b, size_t need) {
+  if (need <= b->rs_cap) return SC_OK;
+  HIP_TRY(hipStreamSynchronize(b->stream_rb));
+  if (b->rs_dev) (void)hipFree(b->rs_dev);
+  if (b->rs_host) (void)hipHostFree(b->rs_host);
+  const size_t cap = std::max(need, 2 * b->rs_cap);
+  b->rs_dev = b->rs_host = nullptr;
+  b->rs_cap = 0;
+  HIP_TRY(hipMalloc((void **)&b->rs_dev, cap));
+  HIP_TRY(hipHostMalloc((void **)&b->rs_host, cap));
+  b->rs_cap = cap;
+  return SC_OK;
+}
+
+void rs_outputs(sc_lm_rescore_job &j, char *out) {
+  j.fused = (double *)out;
+  j.lm = j.fused + SC_RESCORE_MAX_HYPS;
+  j.eos_lm = j.lm + SC_RESCORE_MAX_HYPS;
+  j.end_state = (int32_t *)(j.eos_lm + SC_RESCORE_MAX_HYPS);
+  j.order = j.end_state + SC_RESCORE_MAX_HYPS;
+  j.status = j.order + SC_RESCORE_MAX_HYPS;
+  j.tok_lm = nullptr;
+  j.tok_stride = 0;
+}
+
+// the m jobs at the head of rs_host, with whatever else lies before o_out, go up; the outputs [o_out, o_out + m RS_OUT) come back
+int rs_run(sc_streams *b, size_t o_out, int m, bool from_snapshot) {
+  const int rc = [&]() -> int {
+    HIP_TRY(hipMemcpyAsync(b->rs_dev, b->rs_host, o_out, hipMemcpyHostToDevice, b->stream_rb));
+    if (from_snapshot) HIP_TRY(hipStreamWaitEvent(b->stream_rb, b->ev_snap, 0));   // the copies are written on the batch's stream
+    RC_TRY(sc_lm_rescore((const sc_lm_rescore_job *)b->rs_dev, m, b->stream_rb));
+    HIP_TRY(hipMemcpyAsync(b->rs_host + o_out, b->rs_dev + o_out, (size_t)m * RS_OUT, hipMemcpyDeviceToHost, b->stream_rb));
+    HIP_TRY(hipStreamSynchronize(b->stream_rb));
+    return SC_OK;
+  }();
+  if (rc != SC_OK) (void)hipStreamSynchronize(b->stream_rb);   // nothing of this call may still read the pinned table
+  return rc;
+}
+
+// the outputs of job k -> row i of the caller's [n][nbest] arrays (nh entries each)
+void rs_copy_out(const char *out, size_t i, int nbest, int nh, int32_t *order, double *fused, double *lm_sum, double *eos_lm,
+                 int32_t *status, int32_t *end_state) {
+  const double *d = (const double *)out;
+  const int32_t *q = (const int32_t *)(d + 3 * SC_RESCORE_MAX_HYPS);
+  const size_t o = i * (size_t)nbest;
+  if (fused) memcpy(fused + o, d, nh * sizeof(double));
+  if (lm_sum) memcpy(lm_sum + o, d + SC_RESCORE_MAX_HYPS, nh * sizeof(double));
+  if (eos_lm) memcpy(eos_lm + o, d + 2 * SC_RESCORE_MAX_HYPS, nh * sizeof(double));
+  if (end_state) memcpy(end_state + o, q, nh * sizeof(int32_t));
+  if (order) memcpy(order + o, q + SC_RESCORE_MAX_HYPS, nh * sizeof(int32_t));
+  if (status) memcpy(status + o, q + 2 * SC_RESCORE_MAX_HYPS, nh * sizeof(int32_t));
+}
+
+int rs_model(const sc_lm *lm, double alpha, double beta, int lm_eos, const sc_lm_view **view, sc_lm_view *info) {
+  SC_CHECK_ARG(std::isfinite(alpha) && std::isfinite(beta), "alpha and beta must be finite");
+  RC_TRY(sc_lm_device_view(lm, view, info));
+  SC_CHECK_ARG(*view, "the model has no device view");
+  SC_CHECK_ARG(lm_eos >= -1 && lm_eos < info->V, "lm_eos is outside the model's vocabulary");
+  return SC_OK;
+}
+}  // namespace
+
+// The hypotheses sc_get_hyps_batch would return (same rules: the snapshot with a queue depth > 1, an error for a stream
+// inside a decode block or listed twice), rescored: labels without <sos> and without a trailing <eos>.  Reads the
+// engine's state, changes none, keeps none of its own; synchronised before it returns.
+extern "C" int sc_rescore_hyps(sc_streams *b, const int *stream_ids, int n, int nbest, const sc_lm *lm, double alpha,
+                               double beta, int lm_eos, const int *final, int32_t *order, double *fused, double *lm_sum,
+                               double *eos_lm, int32_t *status, int *n_hyps) {
+  SC_CHECK_ARG(b && stream_ids && lm && n_hyps && n >= 0 && nbest >= 0 && nbest <= SC_RESCORE_MAX_HYPS, "bad arguments");
+  SC_API_BEGIN
+  HIP_TRY(hipSetDevice(b->eng->device));
+  SC_CHECK_ARG(n <= b->S, "more streams listed than the batch has");
+  sc_lm_view info;
+  const sc_lm_view *view = nullptr;
+  RC_TRY(rs_model(lm, alpha, beta, lm_eos, &view, &info));
+  SC_CHECK_ARG(info.V == b->cfg.vocab_size, "the model's vocabulary size is not the batch's");
+  const size_t o_out = (size_t)std::max(n, 1) * sizeof(sc_lm_rescore_job);
+  RC_TRY(rs_reserve(b, o_out + (size_t)std::max(n, 1) * RS_OUT));
+  sc_lm_rescore_job *jobs = (sc_lm_rescore_job *)b->rs_host;
+  std::vector<char> listed(b->S, 0);
+  std::vector<int> job_of(n, -1);
+  int m = 0;
+  bool from_snapshot = false;
+  for (int i = 0; i < n; ++i) {
+    const int s = stream_ids[i];
+    SC_CHECK_ARG(s >= 0 && s < b->S, "stream out of range");
+    SC_CHECK_ARG(!listed[s], "a stream is listed twice");
+    listed[s] = 1;
+    const Snap &sn = b->snap[s];
+    int nh, L;
+    sc_lm_rescore_job j{};
+    if (sn.valid) {   // queue depth > 1: the copy taken when the stream's last reported chunk completed
+      const size_t row = (size_t)s * b->W;
+      nh = std::min(nbest, sn.nhyp); L = sn.L;
+      j.yseq = b->snap_yseq + row * b->LCAP;
+      j.score = b->snap_score + row * 3;
+      j.score_stride = 3;
+      from_snapshot = from_snapshot || nh > 0;
+    } else {
+      SC_CHECK_ARG(!b->run[s].inblk && b->bq[s].empty(), "stream is inside a decode block (its chunk has not been reported yet)");
+      const St &st = b->st[s];
+      const size_t row = ((size_t)st.cur * b->S + s) * b->W;
+      nh = st.started ? std::min(nbest, st.nhyp) : 0; L = st.L;
+      j.yseq = b->sb.yseq + row * b->LCAP;
+      j.score = b->sb.score + row;
+      j.score_stride = 1;
+    }
+    n_hyps[i] = nh;
+    if (nh == 0) continue;
+    j.model = view;
+    j.lens = nullptr;
+    rs_outputs(j, b->rs_dev + o_out + (size_t)m * RS_OUT);
+    j.row_stride = b->LCAP;
+    j.alpha = alpha; j.beta = beta;
+    j.n_hyp = nh; j.L = L; j.skip = 1; j.strip = b->cfg.eos_id; j.state0 = -1;
+    j.lm_eos = (final && final[i]) ? lm_eos : -1;
+    j.V = info.V; j.flags = 0;
+    jobs[m] = j;
+    job_of[i] = m++;
+  }
+  if (m > 0) RC_TRY(rs_run(b, o_out, m, from_snapshot));
+  for (int i = 0; i < n; ++i)
+    if (job_of[i] >= 0)
+      rs_copy_out(b->rs_host + o_out + (size_t)job_of[i] * RS_OUT, (size_t)i, nbest, n_hyps[i], order, fused, lm_sum, eos_lm,
+                  status, nullptr);
+  return SC_OK;
+  SC_API_END
+}
+
+// The same launch for caller-given lists: list i has list_sizes[i] <= nbest rows, row r its lens[i][r] LABELS
+// ids[i][r][0 .. lens) (nothing skipped, nothing stripped) and its total scores[i][r]; state0[i] is the automaton's state
+// before the first label (-1, or state0 == NULL: the model's start_state).  How a decoder-free stream's final gets its
+// </s> term (the ids and totals of sc_ctc_beam_hyps), and how any list from elsewhere is rescored.
+extern "C" int sc_lm_rescore_lists(sc_streams *b, const sc_lm *lm, const int32_t *ids, const int32_t *lens,
+                                   const double *scores, const int *list_sizes, int n, int nbest, int max_len,
+                                   const int32_t *state0, double alpha, double beta, int lm_eos, int32_t *order,
+                                   double *fused, double *lm_sum, double *eos_lm, int32_t *status, int32_t *end_state) {
+  SC_CHECK_ARG(b && lm && lens && scores && list_sizes && n >= 0 && n <= SC_RESCORE_MAX_JOBS && nbest >= 0 &&
+               nbest <= SC_RESCORE_MAX_HYPS && max_len >= 0 && (ids || max_len == 0), "bad arguments");
+  SC_API_BEGIN
+  HIP_TRY(hipSetDevice(b->eng->device));
+  sc_lm_view info;
+  const sc_lm_view *view = nullptr;
+  RC_TRY(rs_model(lm, alpha, beta, lm_eos, &view, &info));
+  const size_t rows = (size_t)n * nbest;
+  const size_t o_sc = (size_t)std::max(n, 1) * sizeof(sc_lm_rescore_job), o_len = o_sc + rows * sizeof(double),
+               o_ids = o_len + ((rows * sizeof(int32_t) + 7) & ~(size_t)7),
+               o_out = o_ids + ((rows * max_len * sizeof(int32_t) + 7) & ~(size_t)7);
+  for (int i = 0; i < n; ++i) {
+    SC_CHECK_ARG(list_sizes[i] >= 0 && list_sizes[i] <= nbest, "a list size outside [0, nbest]");
+    SC_CHECK_ARG(!state0 || (state0[i] >= -1 && state0[i] < info.n_states), "a state0 outside the model's states");
+  }
+  RC_TRY(rs_reserve(b, o_out + (size_t)std::max(n, 1) * RS_OUT));
+  sc_lm_rescore_job *jobs = (sc_lm_rescore_job *)b->rs_host;
+  memcpy(b->rs_host + o_sc, scores, rows * sizeof(double));
+  memcpy(b->rs_host + o_len, lens, rows * sizeof(int32_t));
+  if (rows * max_len) memcpy(b->rs_host + o_ids, ids, rows * max_len * sizeof(int32_t));
+  std::vector<int> job_of(n, -1);
+  int m = 0;
+  for (int i = 0; i < n; ++i) {
+    if (list_sizes[i] == 0) continue;
+    sc_lm_rescore_job j{};
+    j.model = view;
+    j.yseq = (const int32_t *)(b->rs_dev + o_ids) + (size_t)i * nbest * max_len;
+    j.score = (const double *)(b->rs_dev + o_sc) + (size_t)i * nbest;
+    j.lens = (const int32_t *)(b->rs_dev + o_len) + (size_t)i * nbest;
+    rs_outputs(j, b->rs_dev + o_out + (size_t)m * RS_OUT);
+    j.row_stride = max_len; j.score_stride = 1;
+    j.alpha = alpha; j.beta = beta;
+    j.n_hyp = list_sizes[i]; j.L = max_len; j.skip = 0; j.strip = -1; j.state0 = state0 ? state0[i] : -1;
+    j.lm_eos = lm_eos; j.V = info.V; j.flags = 0;
+    jobs[m] = j;
+    job_of[i] = m++;
+  }
+  if (m > 0) RC_TRY(rs_run(b, o_out, m, false));
+  for (int i = 0; i < n; ++i)
+    if (job_of[i] >= 0)
+      rs_copy_out(b->rs_host + o_out + (size_t)job_of[i] * RS_OUT, (size_t)i, nbest, list_sizes[i], order, fused, lm_sum,
+                  eos_lm, status, end_state);
   return SC_OK;
   SC_API_END
 }

@@ -577,6 +577,11 @@ class StreamBatch:
                               "(NativeStreamBatch.set_ctc_beam_lm, sc_streams_set_ctc_beam_lm); the Python engine runs "
                               "the CTC beam unfused only")
 
+    def language_model(self, model):
+        """n-gram rescoring of final n-best lists is an option of the native engine: this one refuses it."""
+        raise EngineError("language_model: n-gram rescoring of finals needs the native engine (NativeStreamBatch."
+                          "rescore_hyps / rescore_lists, sc_rescore_hyps / sc_lm_rescore_lists); the Python engine has none")
+
     def _beam_state(self, s: int) -> dict:
         if self._beam is None:
             raise EngineError("the beam option is off (set_ctc_beam)")

@@ -784,6 +784,64 @@ class HipBackend:
                                 "pos": pos[a:b].copy(), "stability": stab[a:b].copy(), "totals": tot[k].copy()}})
         return out
 
+    def lm_rescore(self, jobs, model, tweak=None, guard: int = 2):
+        """N-gram rescoring of n-best lists (sc_lm_rescore) on the caller's device arrays, one launch for
+        all jobs.  ``model``: language_model().  jobs: list of dicts - "rows": int32 device tensor [n, >= L], rows may be
+        strided; "scores": float64 device tensor [n]; "L"; optional "lens" (a sequence of n ints; default: L each),
+        "skip" (1), "strip" (-1), "state0" (-1), "lm_eos" (-1), "alpha" (0), "beta" (0), "flags" (0), "tok" (True: the
+        per-label values are wanted).  Returns one dict per job: "lm", "eos_lm", "fused" (float64 [n]), "end_state",
+        "order", "status" (int32 [n]), "tok_lm" ([n, width] or None) and "raw": the output buffers whole, every one
+        handed over filled with -7 and ``guard`` words longer than the kernel may write.  ``tweak(k, job)``: test aid,
+        edits the sc_lm_rescore_job of job k before the launch."""
+        import numpy as np
+        n = len(jobs)
+        dev = self.device
+        H = _abi.RESCORE_MAX_HYPS
+        f64 = torch.full((max(n, 1), 3, H + guard), -7.0, dtype=torch.float64, device=dev)
+        i32 = torch.full((max(n, 1), 3, H + guard), -7, dtype=torch.int32, device=dev)
+        widths = [max(0, int(j["L"]) - int(j.get("skip", 1))) if j.get("tok", True) else 0 for j in jobs]
+        ti = np.concatenate([[0], np.cumsum([int(j["rows"].shape[0]) * w + guard for j, w in zip(jobs, widths)])])
+        tok = torch.full((max(int(ti[-1]), 1),), -7.0, dtype=torch.float64, device=dev)
+        keep = []
+        tab = (_abi.RescoreJob * max(1, n))()
+        for k, job in enumerate(jobs):
+            rows, sc = job["rows"], job["scores"]
+            assert rows.dtype == torch.int32 and rows.dim() == 2 and (rows.shape[1] == 0 or rows.stride(1) == 1)
+            assert sc.dtype == torch.float64 and sc.dim() == 1 and sc.shape[0] == rows.shape[0]
+            assert int(job["L"]) <= rows.shape[1]
+            j = tab[k]
+            j.model = model.view
+            j.yseq, j.row_stride = rows.data_ptr(), rows.stride(0) if rows.shape[0] > 1 else max(rows.shape[1], 1)
+            j.score, j.score_stride = sc.data_ptr(), sc.stride(0) if sc.shape[0] > 1 else 1
+            if job.get("lens") is not None:
+                lens = torch.tensor([int(v) for v in job["lens"]], dtype=torch.int32, device=dev)
+                keep.append(lens)
+                j.lens = lens.data_ptr()
+            j.fused, j.lm, j.eos_lm = (f64[k, c].data_ptr() for c in range(3))
+            j.end_state, j.order, j.status = (i32[k, c].data_ptr() for c in range(3))
+            if job.get("tok", True):
+                j.tok_lm, j.tok_stride = tok.data_ptr() + 8 * int(ti[k]), widths[k]
+            j.alpha, j.beta = float(job.get("alpha", 0.0)), float(job.get("beta", 0.0))
+            j.n_hyp, j.L, j.skip, j.strip = rows.shape[0], int(job["L"]), int(job.get("skip", 1)), int(job.get("strip", -1))
+            j.state0, j.lm_eos, j.V, j.flags = (int(job.get("state0", -1)), int(job.get("lm_eos", -1)), model.info.V,
+                                                int(job.get("flags", 0)))
+            if tweak is not None:
+                tweak(k, j)
+        tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+        self._chk(self.lib.sc_lm_rescore(tab_dev.data_ptr(), n, self._stream()), "sc_lm_rescore")
+        torch.cuda.synchronize(dev)
+        f64, i32, tok = f64.cpu().numpy(), i32.cpu().numpy(), tok.cpu().numpy()
+        out = []
+        for k, job in enumerate(jobs):
+            nh, w = int(job["rows"].shape[0]), widths[k]
+            a, b = int(ti[k]), int(ti[k + 1])
+            out.append({"fused": f64[k, 0, :nh].copy(), "lm": f64[k, 1, :nh].copy(), "eos_lm": f64[k, 2, :nh].copy(),
+                        "end_state": i32[k, 0, :nh].copy(), "order": i32[k, 1, :nh].copy(),
+                        "status": i32[k, 2, :nh].copy(),
+                        "tok_lm": tok[a:a + nh * w].reshape(nh, w).copy() if job.get("tok", True) else None,
+                        "raw": {"f64": f64[k].copy(), "i32": i32[k].copy(), "tok": tok[a:b].copy()}})
+        return out
+
     def decode_pcm(self, jobs, tweak=None, guard: int = 4):
         """Batched decode of coded audio (sc_pcm_decode) on the caller's buffers, one launch for all jobs.  jobs: list of
         (src: a bytes-like object, a numpy array or a uint8 device tensor; byte offset; format; channels; channel; scale;

@@ -767,6 +767,74 @@ class NativeStreamBatch:
                            "status": int(a["status"][i])}
         return out
 
+    # ---- n-gram rescoring of final n-best lists (sc_rescore_hyps, sc_lm_rescore_lists) -----------
+    def language_model(self, model):
+        """``model`` (a packed blob, the bytes of a .sclm file or a hip_backend.DeviceLm) as a DeviceLm"""
+        from .hip_backend import DeviceLm
+        try:
+            return model if isinstance(model, DeviceLm) else DeviceLm(self.lib, bytes(model))
+        except _abi.ScasrError as e:
+            raise EngineError(str(e)) from e
+
+    def rescore_hyps(self, streams: Sequence[int], model, alpha: float = 0.5, beta: float = 0.0, lm_eos: int = -1,
+                     final: Sequence[int] = (), nbest: Optional[int] = None):
+        """{stream: {"order", "fused", "lm", "eos_lm", "status"}} for the hypotheses ``hypotheses_batch`` would return
+        (numpy arrays over those rows; order[r] is the row at rank r by fused = score + alpha * (lm + eos_lm) +
+        beta * labels): one launch and one copy back for all listed streams, nothing of the engine changes.  ``model``:
+        language_model(); ``lm_eos``: the id that stands for </s> in the model, applied to the streams in ``final``."""
+        sid = np.ascontiguousarray(streams, dtype=np.int32)
+        n = len(sid)
+        nb = min(int(self.W if nbest is None else nbest), _abi.RESCORE_MAX_HYPS)
+        fin = np.zeros(n, np.int32)
+        if len(final):
+            fin[np.isin(sid, np.asarray(list(final), np.int32))] = 1
+        order, status, nh = np.zeros((n, nb), np.int32), np.zeros((n, nb), np.int32), np.zeros(n, np.int32)
+        fused, lm, eos = np.zeros((n, nb)), np.zeros((n, nb)), np.zeros((n, nb))
+        ip = _abi.c_int_p
+        try:
+            _abi.check(self.lib.sc_rescore_hyps(self.handle, sid.ctypes.data_as(ip), n, nb, model.handle, float(alpha),
+                                                float(beta), int(lm_eos), fin.ctypes.data_as(ip), order.ctypes.data,
+                                                fused.ctypes.data, lm.ctypes.data, eos.ctypes.data, status.ctypes.data,
+                                                nh.ctypes.data_as(ip)), "sc_rescore_hyps")
+        except _abi.ScasrError as e:
+            raise EngineError(str(e)) from e
+        return {int(s): {"order": order[i, :nh[i]], "fused": fused[i, :nh[i]], "lm": lm[i, :nh[i]],
+                         "eos_lm": eos[i, :nh[i]], "status": status[i, :nh[i]]} for i, s in enumerate(sid)}
+
+    def rescore_lists(self, lists, scores, model, alpha: float = 0.5, beta: float = 0.0, lm_eos: int = -1, state0=None):
+        """The same for caller-given lists: ``lists[i]`` is a list of label sequences (at most 16), ``scores[i]`` their
+        totals, ``state0[i]`` the automaton's state before the first label (default: the model's start).  Returns one
+        dict per list: "order", "fused", "lm", "eos_lm", "status", "end_state"."""
+        n = len(lists)
+        nb = max([len(li) for li in lists] + [1])
+        if nb > _abi.RESCORE_MAX_HYPS:
+            raise ValueError(f"a list holds more than {_abi.RESCORE_MAX_HYPS} rows")
+        ml = max([len(y) for li in lists for y in li] + [1])
+        ids, lens = np.zeros((n, nb, ml), np.int32), np.zeros((n, nb), np.int32)
+        sc, sizes = np.zeros((n, nb)), np.zeros(n, np.int32)
+        for i, (li, ss) in enumerate(zip(lists, scores)):
+            if len(li) != len(ss):
+                raise ValueError("one score per row")
+            sizes[i] = len(li)
+            for r, y in enumerate(li):
+                ids[i, r, :len(y)], lens[i, r], sc[i, r] = y, len(y), ss[r]
+        st = None if state0 is None else np.ascontiguousarray(state0, dtype=np.int32)
+        if st is not None and st.shape != (n,):
+            raise ValueError("one state0 per list")
+        order, status, end = (np.zeros((n, nb), np.int32) for _ in range(3))
+        fused, lm, eos = np.zeros((n, nb)), np.zeros((n, nb)), np.zeros((n, nb))
+        try:
+            _abi.check(self.lib.sc_lm_rescore_lists(self.handle, model.handle, ids.ctypes.data, lens.ctypes.data,
+                                                    sc.ctypes.data, sizes.ctypes.data_as(_abi.c_int_p), n, nb, ml,
+                                                    None if st is None else st.ctypes.data, float(alpha), float(beta),
+                                                    int(lm_eos), order.ctypes.data, fused.ctypes.data, lm.ctypes.data,
+                                                    eos.ctypes.data, status.ctypes.data, end.ctypes.data),
+                       "sc_lm_rescore_lists")
+        except _abi.ScasrError as e:
+            raise EngineError(str(e)) from e
+        return [{"order": order[i, :k], "fused": fused[i, :k], "lm": lm[i, :k], "eos_lm": eos[i, :k],
+                 "status": status[i, :k], "end_state": end[i, :k]} for i, k in enumerate(sizes)]
+
     def hypotheses(self, s: int):
         """Live hypotheses of stream s: list of dicts (yseq, score, score_dec, score_ctc, xpos), best first."""
         return self.hypotheses_batch([int(s)])[int(s)]

@@ -19,7 +19,12 @@ root_logp[V]; int32 root_next[V] (padded); n_slots slots of 24 bytes (uint64 key
 n_slots a power of two >= 2, an unused slot has the key EMPTY and is otherwise zero.  The home slot of a key is
 (key * HASH_MUL mod 2^64) >> (64 - log2 n_slots).
 
-    python -m speechcatcher_amd.ngram in.arpa tokens.txt out.sclm
+    python -m speechcatcher_amd.ngram [--alias WORD=TOKEN ...] in.arpa tokens.txt out.sclm
+
+``--alias WORD=TOKEN`` (may be repeated): the ARPA word WORD stands for the entry TOKEN of the token list.  ESPnet token
+lists have ONE <sos/eos> entry where ARPA files have <s> and </s>: ``--alias "<s>=<sos/eos>" --alias "</s>=<sos/eos>"``.
+When two ARPA words map to one id, the id's unigram takes its logp from </s> and its backoff from <s>: the id is predicted
+only as an end and conditions only as a start.  The start state (``bos``) and the id printed as "eos" follow the aliases.
 """
 import math
 import struct
@@ -165,12 +170,25 @@ class Blob:
         return float(acc + float(self.root_logp[c])), int(self.root_next[c])
 
 
-def parse_arpa(text: str, tokens: Sequence[str]) -> Tuple[Model, int]:
+def word_ids(tokens: Sequence[str], alias: Optional[Dict[str, str]] = None) -> Dict[str, int]:
+    """ARPA word -> token id: the token list's entries, and every alias WORD -> the id of its TOKEN"""
+    ids = {t: i for i, t in enumerate(tokens)}
+    for word, tok in (alias or {}).items():
+        if tok not in ids:
+            raise ValueError(f"alias {word}={tok}: '{tok}' is not in the token list")
+        ids[word] = ids[tok]
+    return ids
+
+
+def parse_arpa(text: str, tokens: Sequence[str], alias: Optional[Dict[str, str]] = None) -> Tuple[Model, int]:
     """ARPA text -> (model, order): log10 -> ln, words -> ids through ``tokens`` (an n-gram with a word that is not
     among them is left out - with it every n-gram that extends it, so the model stays closed under prefixes); "-99"
-    becomes FLOOR; an n-gram without a backoff column has backoff 0."""
-    ids = {t: i for i, t in enumerate(tokens)}
+    becomes FLOOR; an n-gram without a backoff column has backoff 0.  ``alias``: {ARPA word: entry of ``tokens``} (the
+    module's doc).  Two unigrams on one id merge when one of them is <s>: logp from the other word (</s>), backoff from
+    <s>; any other pair of words on one id is an error.  Of two longer n-grams on the same ids the first is kept."""
+    ids = word_ids(tokens, alias)
     model: Model = {}
+    first: Dict[int, str] = {}   # id -> the word of its first unigram
     n, order = 0, 0
     for line in text.splitlines():
         line = line.strip()
@@ -196,6 +214,17 @@ def parse_arpa(text: str, tokens: Sequence[str]) -> Tuple[Model, int]:
         g = tuple(ids[w] for w in words)
         if len(g) > 1 and g[:-1] not in model:
             continue
+        if g in model:
+            if n > 1:
+                continue
+            a, b = first[g[0]], words[0]
+            if "<s>" not in (a, b) or a == b:
+                raise ValueError(f"ARPA: the words {a!r} and {b!r} map to one token id and neither is <s>")
+            other, start = (model[g], (lp10 * LN10, bo10 * LN10)) if b == "<s>" else ((lp10 * LN10, bo10 * LN10), model[g])
+            model[g] = (other[0], start[1])   # predicted as an end, conditions as a start
+            continue
+        if n == 1:
+            first[g[0]] = words[0]
         model[g] = (lp10 * LN10, bo10 * LN10)
     if order == 0:
         raise ValueError("ARPA: no n-gram section")
@@ -227,21 +256,31 @@ def load(source) -> bytes:
 
 
 def main(argv=None) -> int:
-    argv = sys.argv[1:] if argv is None else argv
+    argv = list(sys.argv[1:] if argv is None else argv)
+    alias: Dict[str, str] = {}
+    while "--alias" in argv:
+        k = argv.index("--alias")
+        word, sep, tok = (argv[k + 1] if k + 1 < len(argv) else "").partition("=")
+        if not (word and sep and tok):
+            print("--alias takes WORD=TOKEN", file=sys.stderr)
+            return 2
+        alias[word] = tok
+        del argv[k:k + 2]
     if len(argv) != 3:
-        print("usage: python -m speechcatcher_amd.ngram in.arpa tokens.txt out.sclm", file=sys.stderr)
+        print("usage: python -m speechcatcher_amd.ngram [--alias WORD=TOKEN ...] in.arpa tokens.txt out.sclm", file=sys.stderr)
         return 2
     with open(argv[1], encoding="utf-8") as fh:
         tokens = [line.rstrip("\n").split(" ")[0] for line in fh if line.strip()]
     with open(argv[0], encoding="utf-8") as fh:
-        model, order = parse_arpa(fh.read(), tokens)
-    bos = tokens.index("<s>") if "<s>" in tokens else None
+        model, order = parse_arpa(fh.read(), tokens, alias)
+    ids = word_ids(tokens, alias)
+    bos = ids.get("<s>")
     blob = pack(model, len(tokens), order, bos=bos)
     with open(argv[2], "wb") as fh:
         fh.write(blob)
     b = Blob(blob)
     print(f"{argv[2]}: order {b.order}, V {b.V}, {b.n_states} states, {b.n_arcs} arcs in {b.n_slots} slots, "
-          f"{len(blob)} bytes")
+          f"{len(blob)} bytes" + (f", bos {bos}, eos {ids.get('</s>')}" if alias else ""))
     return 0
 
 

@@ -13,6 +13,7 @@ Parity note: the reference's output depends on the chunking of each stream, so
 the scheduler never re-chunks: one chunk fed by a session is one engine call
 for that stream, exactly as if the session owned a private Speech2TextStreaming.
 """
+import math
 from collections import deque
 from typing import Deque, Dict, List, Optional, Tuple
 
@@ -24,6 +25,7 @@ from . import draft as draft_mod
 from . import ctc_beam as beam_mod
 from . import alternates as alternates_mod
 from . import commit as commit_mod
+from . import rescore as rescore_mod
 from .activity import of_stream as activity_of_stream
 from .align import FeatureClock
 from . import pcm as pcm_mod
@@ -47,6 +49,8 @@ class AlignedResults(list):
     "alternates": the records of those tokens (speechcatcher_amd.alternates.result_token_alternates); with
     ``align_nbest`` > 1 also "nbest": result_token_alignment of each of the reply's first ``align_nbest`` results."""
     alignment: Optional[dict] = None
+    # StreamScheduler(final_lm=...): per result of a re-ranked final {"score", "lm", "fused", "am_rank"} (DESIGN.md 8l)
+    rescored: Optional[list] = None
 
 
 class ActivityResults(AlignedResults):
@@ -111,7 +115,8 @@ class StreamScheduler:
                  queue_depth: int = 1, align_final: bool = False, activity: bool = False, blank_threshold: float = 0.8,
                  phrases=None, min_scores=None, draft: bool = False, input_level: bool = False, alternates: int = 0,
                  align_nbest: int = 1, stable_partials: bool = False, ctc_beam=None, ctc_lm=None,
-                 lm_weight: float = 0.5, word_bonus: float = 0.0):
+                 lm_weight: float = 0.5, word_bonus: float = 0.0, final_lm=None, final_lm_weight: float = 0.5,
+                 final_word_bonus: float = 0.0, final_lm_eos: bool = False):
         """``queue_depth`` > 1 (C++ engine, ``pump``): up to that many queued chunks of a session are handed to the engine
         at a time (sc_streams_set_queue_depth) - for sessions whose audio is already there (files): the encoder stage of
         the next chunk runs beside the decoding of the current one.  Replies and their order per session do not change.
@@ -148,6 +153,17 @@ class StreamScheduler:
         # bytes - the beam keeps its entries by total + lm_weight * lm + word_bonus * len, the entries of
         # ``ctc_nbest`` gain "lm" and their "score" is that fused total.  (lm_weight, word_bonus) when on.
         self.ctc_lm = None
+        # ``final_lm`` (C++ engine): the path of a packed n-gram model or its bytes - at a final of a FULL session the
+        # n-best list is rescored on the GPU and re-ranked by fused = score + final_lm_weight * (lm + the </s> term with
+        # ``final_lm_eos``) + final_word_bonus * labels (NativeStreamBatch.rescore_hyps): the reply's results
+        # come in that order, its ``rescored`` holds {"score", "lm", "fused", "am_rank"} per result (result_format
+        # "espnet": the hypothesis dicts carry them too), and the alignment / alternates belong to the results reported.
+        # Partials are untouched; no hypothesis or score of the search changes.  (weight, bonus, eos) when on.
+        # ``final_lm_eos`` with ``ctc_lm``: the final ``ctc_nbest`` of a decoder-free session is re-ranked with the </s>
+        # term of the SAME model at the beam's weights (NativeStreamBatch.rescore_lists).
+        self.final_lm = None
+        self.final_lm_eos = bool(final_lm_eos)
+        self._final_dev = self._ctc_blob = self._ctc_dev = None
         self._ctc_sessions = set()
         self._slot_dec: Dict[int, str] = {}
         # ``stable_partials``: every reply (an exception aside) is a ``StableResults``.  The scheduler owns one
@@ -191,6 +207,11 @@ class StreamScheduler:
             self.enable_ctc_beam(*beam_mod.params(ctc_beam))
         if ctc_lm is not None:
             self.enable_ctc_lm(ctc_lm, lm_weight, word_bonus)
+        if final_lm is not None:
+            self.enable_final_lm(final_lm, final_lm_weight, final_word_bonus, final_lm_eos)
+        elif self.final_lm_eos and not hasattr(batch, "rescore_lists"):
+            raise NotImplementedError("the </s> term of finals is computed by the C++ engine (NativeStreamBatch."
+                                      "rescore_lists); the Python lock-step engine has none")
         if alternates:
             self.enable_alternates(alternates)
         if stable_partials:
@@ -228,11 +249,36 @@ class StreamScheduler:
             raise NotImplementedError("this batch has no language model fusion (set_ctc_beam_lm)")
         if source is None:
             self.batch.set_ctc_beam_lm(None)
-            self.ctc_lm = None
+            self.ctc_lm = self._ctc_blob = self._ctc_dev = None
             return
         from . import ngram
-        self.batch.set_ctc_beam_lm(ngram.load(source), float(lm_weight), float(word_bonus))
+        blob = ngram.load(source)
+        self.batch.set_ctc_beam_lm(blob, float(lm_weight), float(word_bonus))
         self.ctc_lm = (float(lm_weight), float(word_bonus))
+        self._ctc_blob, self._ctc_dev = blob, None
+
+    def enable_final_lm(self, source, lm_weight: float = 0.5, word_bonus: float = 0.0, eos: bool = False):
+        """switch the ``final_lm`` option on: ``source`` is the path of a packed model or its bytes; None switches it
+        off.  ``lm_weight`` / ``word_bonus`` are parameters, not tuned."""
+        if source is None:
+            self.final_lm = self._final_dev = None
+            return
+        if not hasattr(self.batch, "rescore_hyps"):
+            raise NotImplementedError("n-gram rescoring of finals runs in the C++ engine (NativeStreamBatch.rescore_hyps); "
+                                      "the Python lock-step engine has none")
+        if self.batch.W > rescore_mod.MAX_HYPS:
+            raise ValueError(f"final_lm rescores a list of at most {rescore_mod.MAX_HYPS} hypotheses "
+                             f"(this batch has beam {self.batch.W})")
+        if not (math.isfinite(lm_weight) and math.isfinite(word_bonus)):
+            raise ValueError("final_lm_weight and final_word_bonus must be finite")
+        from . import ngram
+        self._final_dev = self.batch.language_model(ngram.load(source))
+        self.final_lm = (float(lm_weight), float(word_bonus), bool(eos))
+        self.final_lm_eos = bool(eos)
+
+    @property
+    def _eos_id(self) -> int:
+        return int(getattr(self.batch.cfg, "eos_id", EOS_ID))
 
     def enable_stable_partials(self):
         """switch the ``stable_partials`` option on (every session's tracker starts over)"""
@@ -471,6 +517,16 @@ class StreamScheduler:
                 row = {slot: i for i, slot in enumerate(want)}
             else:
                 hyps = {slot: self.batch.hypotheses(slot) for slot in want}
+        perm = {}
+        if self.final_lm is not None and arrays is not None:   # ONE launch and one copy back for the round's finals
+            fins = [slot for sid, (slot, fin, _) in meta.items()
+                    if fin and has[slot] is True and sid not in self._ctc_sessions]
+            if fins:
+                a, b, eos = self.final_lm
+                got = self.batch.rescore_hyps(fins, self._final_dev, a, b, lm_eos=self._eos_id if eos else -1, final=fins,
+                                              nbest=arrays["ids"].shape[1])
+                for slot in fins:
+                    perm[slot] = rescore_mod.rerank_arrays(arrays, row[slot], got[slot])
         act = act_row = None
         if self.activity:
             act_slots = [slot for (slot, _, _) in meta.values() if not isinstance(has[slot], Exception)]
@@ -500,29 +556,37 @@ class StreamScheduler:
                 self._spot_seen.pop(sid, None)
                 self._stable.pop(sid, None)
                 continue
+            rescored = None
             if not has[slot]:
                 out[sid] = []
             elif arrays is not None:
-                out[sid] = hyps_to_results(_select_hyps(arrays, row[slot], fin, fa), fin, fa, self.token_list, self.result_format)
+                kept = _select_hyps(arrays, row[slot], fin, fa)
+                out[sid] = hyps_to_results(kept, fin, fa, self.token_list, self.result_format)
+                if slot in perm:
+                    rescored = [{k: h[k] for k in ("score", "lm", "fused", "am_rank")} for h in kept]
             else:
                 out[sid] = hyps_to_results(hyps[slot], fin, fa, self.token_list, self.result_format)
             if fin and self.align_final and not isinstance(out[sid], Exception) and sid not in self._ctc_sessions:
                 out[sid] = self._aligned(out[sid], arrays, row[slot] if arrays is not None and has[slot] is True else None,
-                                         slot, fin, fa, self._clock.get(sid))
+                                         slot, fin, fa, self._clock.get(sid), perm.get(slot))
+            if rescored is not None:
+                if not isinstance(out[sid], AlignedResults):
+                    out[sid] = AlignedResults(out[sid])
+                out[sid].rescored = rescored
             if act is not None:
                 res = ActivityResults(out[sid])
-                res.alignment = getattr(out[sid], "alignment", None)
+                res.alignment, res.rescored = getattr(out[sid], "alignment", None), getattr(out[sid], "rescored", None)
                 res.activity = activity_of_stream(act, act_row[slot])
                 out[sid] = res
             if self.spotting:
                 res = SpottingResults(out[sid])
-                res.alignment = getattr(out[sid], "alignment", None)
+                res.alignment, res.rescored = getattr(out[sid], "alignment", None), getattr(out[sid], "rescored", None)
                 res.activity = getattr(out[sid], "activity", None)
                 res.detections = self._detections(sid, slot)
                 out[sid] = res
             if self.draft:
                 res = DraftResults(out[sid])
-                for k in ("alignment", "activity", "detections"):
+                for k in ("alignment", "activity", "detections", "rescored"):
                     setattr(res, k, getattr(out[sid], k, None))
                 res.draft = self._draft_tokens(sid, slot)
                 pos = out[sid][0][3] if out[sid] and len(out[sid][0]) > 3 else None
@@ -530,23 +594,25 @@ class StreamScheduler:
                 out[sid] = res
             if self.input_level:
                 res = LevelResults(out[sid])
-                for k in ("alignment", "activity", "detections", "draft", "ahead"):
+                for k in ("alignment", "activity", "detections", "draft", "ahead", "rescored"):
                     setattr(res, k, getattr(out[sid], k, None))
                 res.level = self.batch.input_level(slot) if hasattr(self.batch, "input_level") else pcm_mod.zero_level()
                 out[sid] = res
             if delta is not None:
                 res = StableResults(out[sid])
-                for k in ("alignment", "activity", "detections", "draft", "ahead", "level"):
+                for k in ("alignment", "activity", "detections", "draft", "ahead", "level", "rescored"):
                     setattr(res, k, getattr(out[sid], k, None))
                 res.stable = self._stable[sid].update(delta[slot], final=fin).state()   # (a final starts the tracker over)
                 out[sid] = res
             if beams is not None:
                 nbest = self._ctc_nbest(sid, beams[slot], sides.get(slot))
+                if fin and self.final_lm_eos and self.ctc_lm is not None and sid in self._ctc_sessions and nbest:
+                    nbest = self._ctc_end_term(nbest)
                 # a decoder-free session: its results are the beam's entries, best first (a chunk the engine answers with
                 # nothing stays [])
                 free = sid in self._ctc_sessions
                 res = CtcBeamResults(self._ctc_results(nbest) if free and has[slot] else out[sid])
-                for k in ("alignment", "activity", "detections", "draft", "ahead", "level", "stable"):
+                for k in ("alignment", "activity", "detections", "draft", "ahead", "level", "stable", "rescored"):
                     setattr(res, k, getattr(out[sid], k, None))
                 res.ctc_nbest = nbest
                 if free and fin and self.align_final and len(res):
@@ -568,6 +634,24 @@ class StreamScheduler:
             secs = beam_mod.token_dicts(h, clock, cfg.subsample, cfg.sample_rate)
             for d, t in zip(entry["tokens"], secs):
                 d["start_s"], d["end_s"] = t["start"], t["end"]
+        return out
+
+    def _ctc_end_term(self, nbest: list) -> list:
+        """the final n-best list of a decoder-free session with the </s> term of the fused model: rescored as a
+        caller-given list at the beam's weights (one launch), re-ranked; "score" is the fused total with the term,
+        "eos_lm" the term, "am_rank" the entry's rank in the beam, "conf" from the new totals"""
+        if self._ctc_dev is None:
+            self._ctc_dev = self.batch.language_model(self._ctc_blob)
+        a, b = self.ctc_lm
+        got = self.batch.rescore_lists([[e["ids"] for e in nbest]], [[e["ctc_score"] for e in nbest]], self._ctc_dev, a, b,
+                                       lm_eos=self._eos_id)[0]
+        out = []
+        for r in got["order"]:
+            e = dict(nbest[int(r)])
+            e["score"], e["eos_lm"], e["am_rank"] = float(got["fused"][r]), float(got["eos_lm"][r]), int(r)
+            out.append(e)
+        for e, c in zip(out, alternates_mod.nbest_posterior([e["score"] for e in out])):
+            e["conf"] = c
         return out
 
     def _ctc_results(self, nbest: list) -> list:
@@ -629,7 +713,9 @@ class StreamScheduler:
             d["start_s"], d["end_s"] = t["start"], t["end"]
         return out
 
-    def _aligned(self, res: list, arrays, i, slot: int, fin: bool, fa: bool, clock) -> "AlignedResults":
+    def _aligned(self, res: list, arrays, i, slot: int, fin: bool, fa: bool, clock, perm=None) -> "AlignedResults":
+        """``perm`` (a re-ranked final): row q of ``arrays`` is the engine's row perm[q] - the alignment is asked for a list
+        wide enough to hold the rows reported and read at THEIR rows"""
         out = AlignedResults(res)
         if not res or arrays is None:
             return out
@@ -637,12 +723,14 @@ class StreamScheduler:
         # (with align_nbest > 1: the hypotheses behind res[:align_nbest], in the order _select_hyps keeps them)
         js = [j for j in range(int(arrays["n_hyps"][i]))
               if (fin and fa) or int(arrays["ids"][i, j, int(arrays["lens"][i, j]) - 1]) == EOS_ID][:self.align_nbest]
+        ys = [arrays["ids"][i, q, :int(arrays["lens"][i, q])].tolist() for q in js]
+        if perm is not None:
+            js = [int(perm[q]) for q in js]
         j = js[0]
         if self.alternates:
-            al = self.batch.alternates([slot], js[-1] + 1, self.alternates)
+            al = self.batch.alternates([slot], max(js) + 1, self.alternates)
         else:
-            al = self.batch.align([slot], js[-1] + 1)
-        ys = [arrays["ids"][i, q, :int(arrays["lens"][i, q])].tolist() for q in js]
+            al = self.batch.align([slot], max(js) + 1)
         out.alignment = result_token_alignment(ys[0], fin, al, 0, j, self.batch.cfg, clock)
         if self.alternates:
             out.alignment["alternates"] = alternates_mod.result_token_alternates(ys[0], fin, al, 0, j, self.batch.cfg,
@@ -729,6 +817,18 @@ class StreamScheduler:
 
 
 def _select_hyps(a: dict, i: int, is_final: bool, finalize_all: bool) -> List[dict]:
+    out = _select_plain(a, i, is_final, finalize_all)
+    if "am_rank" in a and int(a["am_rank"][i, 0]) >= 0:   # a re-ranked final (rescore.rerank_arrays)
+        for h in out:
+            j = h.pop("_row")
+            h["lm"], h["fused"], h["am_rank"] = float(a["lm"][i, j]), float(a["fused"][i, j]), int(a["am_rank"][i, j])
+    else:
+        for h in out:
+            del h["_row"]
+    return out
+
+
+def _select_plain(a: dict, i: int, is_final: bool, finalize_all: bool) -> List[dict]:
     """hypothesis dicts of row i of ``hypotheses_arrays`` - only those the reference's result assembly looks at
     (speech2text_streaming.py:469-476: without finalize_all only hypotheses that end in <eos>), so that a partial
     reply does not turn W x L token ids into Python lists"""
@@ -739,7 +839,7 @@ def _select_hyps(a: dict, i: int, is_final: bool, finalize_all: bool) -> List[di
             continue
         out.append({"yseq": a["ids"][i, j, :L].tolist(), "score": float(a["score"][i, j]),
                     "score_dec": float(a["score_dec"][i, j]), "score_ctc": float(a["score_ctc"][i, j]),
-                    "xpos": a["xpos"][i, j, :L].tolist()})
+                    "xpos": a["xpos"][i, j, :L].tolist(), "_row": j})
     return out
 
 
@@ -748,7 +848,8 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
                        frames_per_second: float = 24.0, finalize_all_last_only: bool = False,
                        queue_depth: int = 1, token_alignment: bool = False, token_alternates: int = 0,
                        ctc_beam=None, ctc_only: bool = False, ctc_lm=None, lm_weight: float = 0.5,
-                       word_bonus: float = 0.0) -> List[dict]:
+                       word_bonus: float = 0.0, rescore_lm=None, rescore_weight: float = 0.5,
+                       rescore_bonus: float = 0.0) -> List[dict]:
     """Decode the (start, end) sample ranges of one recording as PARALLEL streams
     of one batch instead of the reference's process pool over segments
     (speechcatcher/speechcatcher.py:474-497, chunk loop :574-592; SURVEY 8(f)
@@ -764,8 +865,14 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
     streams - text, tokens and token_timestamps are the beam's best, token_start / token_end the prefix tree's frames; not
     with ``token_alternates``.  ``ctc_lm`` (needs ``ctc_beam`` or ``ctc_only``): a packed n-gram model fused into that
     search with ``lm_weight`` / ``word_bonus``; the entries of ``ctc_nbest`` then carry "lm" too and their
-    "score" is the fused total."""
+    "score" is the fused total.  ``rescore_lm`` (C++ engine; not with ``ctc_only``): a packed n-gram model the final n-best
+    list of every segment is rescored with and re-ranked by, </s> term included, at ``rescore_weight`` / ``rescore_bonus``
+    (the scheduler's ``final_lm`` option): the segment's text is the fused best, "score" stays its search
+    score, "lm_score" / "fused_score" / "am_rank" say what the model added and which row of the search's list it was."""
     token_alignment = token_alignment or token_alternates > 0
+    if rescore_lm is not None and ctc_only:
+        raise ValueError("rescore_lm re-ranks the n-best list of the attention decoder's search: not with ctc_only "
+                         "(fuse the model into the CTC beam with ctc_lm)")
     if ctc_lm is not None and not (ctc_only or beam_mod.params(ctc_beam)):
         raise ValueError("ctc_lm: the model is fused into the CTC prefix beam search - it needs ctc_beam or ctc_only")
     if ctc_only and token_alternates:
@@ -778,7 +885,8 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
     # detection on (the CLI's default), hence off by default
     sch = StreamScheduler(batch, token_list, result_format="espnet", queue_depth=queue_depth, align_final=token_alignment,
                           alternates=token_alternates, ctc_beam=ctc_beam, ctc_lm=ctc_lm, lm_weight=lm_weight,
-                          word_bonus=word_bonus)
+                          word_bonus=word_bonus, final_lm=rescore_lm, final_lm_weight=rescore_weight,
+                          final_word_bonus=rescore_bonus, final_lm_eos=rescore_lm is not None)
     out: List[Optional[dict]] = [None] * len(segments)
     todo = list(enumerate(segments))
     sid_to_seg: Dict[int, int] = {}
@@ -808,6 +916,8 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
                     out[idx] = {"text": text, "tokens": toks, "token_ids": ids,
                                 "token_timestamps": [start_s + p / frames_per_second for p in pos],
                                 "score": hyp["score"], "start": start_s}
+                    if "fused" in hyp:
+                        out[idx].update(lm_score=hyp["lm"], fused_score=hyp["fused"], am_rank=hyp["am_rank"])
                 else:
                     out[idx] = {"text": "", "tokens": [], "token_ids": [], "token_timestamps": [],
                                 "score": 0.0, "start": start_s}

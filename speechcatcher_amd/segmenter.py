@@ -246,7 +246,8 @@ def recognize_recording_segments(batch, raw_speech_data: np.ndarray, rate: int =
                                  token_list: Optional[List[str]] = None, reference_finalize: bool = False,
                                  average_segment_length: float = 60.0, token_alignment: bool = False,
                                  segmentation: str = "host", token_alternates: int = 0, ctc_beam=None,
-                                 ctc_only: bool = False, ctc_lm=None, lm_weight: float = 0.5, word_bonus: float = 0.0):
+                                 ctc_only: bool = False, ctc_lm=None, lm_weight: float = 0.5, word_bonus: float = 0.0,
+                                 rescore_lm=None, rescore_weight: float = 0.5, rescore_bonus: float = 0.0):
     """The segment loop of ``recognize`` (speechcatcher.py:414-497): int16 recording -> chunk-aligned sample
     ranges and the raw per-segment results of ``recognize_segments`` (before paragraph merging)."""
     assert rate == 16000
@@ -259,7 +260,8 @@ def recognize_recording_segments(batch, raw_speech_data: np.ndarray, rate: int =
     res = recognize_segments(batch, speech, ranges, chunk_length=chunk_length, token_list=token_list,
                              finalize_all_last_only=reference_finalize, token_alignment=token_alignment,
                              token_alternates=token_alternates, ctc_beam=ctc_beam, ctc_only=ctc_only,
-                             ctc_lm=ctc_lm, lm_weight=lm_weight, word_bonus=word_bonus)
+                             ctc_lm=ctc_lm, lm_weight=lm_weight, word_bonus=word_bonus, rescore_lm=rescore_lm,
+                             rescore_weight=rescore_weight, rescore_bonus=rescore_bonus)
     return ranges, res
 
 
@@ -268,7 +270,8 @@ def recognize_recording(batch, raw_speech_data: np.ndarray, rate: int = 16000, c
                         average_segment_length: float = 60.0, token_alignment: bool = False,
                         segmentation: str = "host", token_alternates: int = 0, ctc_beam=None,
                         ctc_only: bool = False, ctc_lm=None, lm_weight: float = 0.5,
-                        word_bonus: float = 0.0) -> Tuple[str, List[dict]]:
+                        word_bonus: float = 0.0, rescore_lm=None, rescore_weight: float = 0.5,
+                        rescore_bonus: float = 0.0) -> Tuple[str, List[dict]]:
     """int16 recording -> (text, per-paragraph info).  Native-decoder input scaling
     /32768 in fp32 (speechcatcher.py:421); recordings over a minute are segmented;
     the segments run as parallel streams of ``batch`` (one slot = the reference CLI with one worker:
@@ -280,11 +283,14 @@ def recognize_recording(batch, raw_speech_data: np.ndarray, rate: int = 16000, c
     (implies ``token_alignment``): they also carry ``token_alternates``, one record per token with its K acoustic alternates
     (speechcatcher_amd.alternates).  ``ctc_beam`` = B or (B, C): they also carry ``ctc_nbest``, per segment the n-best
     list of the CTC prefix beam search; ``ctc_only``: the segments are decoded by that search alone (recognize_segments);
-    ``ctc_lm`` / ``lm_weight`` / ``word_bonus``: a packed n-gram model fused into it."""
+    ``ctc_lm`` / ``lm_weight`` / ``word_bonus``: a packed n-gram model fused into it.
+    ``rescore_lm`` / ``rescore_weight`` / ``rescore_bonus``: a packed n-gram model every segment's final n-best list is
+    rescored with and re-ranked by (recognize_segments)."""
     ranges, res = recognize_recording_segments(batch, raw_speech_data, rate, chunk_length, token_list,
                                                reference_finalize, average_segment_length,
                                                token_alignment or token_alternates > 0, segmentation, token_alternates,
-                                               ctc_beam, ctc_only, ctc_lm, lm_weight, word_bonus)
+                                               ctc_beam, ctc_only, ctc_lm, lm_weight, word_bonus, rescore_lm,
+                                               rescore_weight, rescore_bonus)
     segs = [{"start": lo / rate, "end": hi / rate, "text": r["text"], "tokens": r["tokens"],
              "token_timestamps": r["token_timestamps"], **{k: r[k] for k in ALIGNMENT_KEYS if k in r}}
             for (lo, hi), r in zip(ranges, res)]

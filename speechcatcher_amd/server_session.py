@@ -227,7 +227,7 @@ class ServerLoop:
                  spotting_min_scores: Optional[dict] = None, draft_partials: bool = False, raw_input: bool = False,
                  input_level: bool = False, vosk_alternatives: int = 0, token_alternates: int = 0,
                  stable_partials: bool = False, ctc_beam=None, ctc_lm=None, lm_weight: float = 0.5,
-                 word_bonus: float = 0.0):
+                 word_bonus: float = 0.0, rescore_lm=None, rescore_weight: float = 0.5, rescore_bonus: float = 0.0):
         """``strict_reference``: no stream reset after a finalised utterance nor between clients, exactly like
         ``recognize_ws`` / ``process_audio_chunk`` (speechcatcher_server.py:270,359-397); the default resets.
         ``continuous`` (default: on whenever the batch has the C++ engine's submit / poll - round 4; False forces one
@@ -286,7 +286,14 @@ class ServerLoop:
         ``ctc_lm`` (needs ``ctc_beam``): the path of a packed n-gram model (speechcatcher_amd.ngram) or its bytes, fused
         into that search with ``lm_weight`` / ``word_bonus`` (the scheduler's ``ctc_lm`` option): the
         beam's best and its n-best are ranked by the fused totals, and the ``max_alternatives`` confidences of a
-        decoder-free session are the entries' shares of the listed FUSED mass."""
+        decoder-free session are the entries' shares of the listed FUSED mass.
+        ``rescore_lm`` (C++ engine): the path of a packed n-gram model or its bytes - the final n-best list of a FULL
+        session is rescored on the GPU, </s> term included, and re-ranked by score + ``rescore_weight`` * lm +
+        ``rescore_bonus`` * tokens (the scheduler's ``final_lm`` option): the final's text and the order of
+        its ``alternatives`` come from that ranking, their confidences are nbest_posterior of the FUSED totals, and the
+        word times belong to the hypotheses reported.  Partials are unchanged."""
+        if rescore_lm is not None:
+            scheduler.enable_final_lm(rescore_lm, rescore_weight, rescore_bonus, eos=True)
         from . import ctc_beam as beam_mod
         if ctc_lm is not None and not (beam_mod.params(ctc_beam) or scheduler.ctc_beam is not None):
             raise ValueError("ctc_lm needs the ctc_beam option")
@@ -536,7 +543,8 @@ class ServerLoop:
             for r, (_t, toks, _i, p, _h) in enumerate(res):
                 texts.append("".join(toks).replace("▁", " ").strip())
                 words.append(vosk_words(toks, p, nbest[r] if r < len(nbest) else None, aligned, records if r == 0 else None))
-            return alternates_mod.vosk_alternatives(texts, [r[4]["score"] for r in res], words)
+            # (a re-ranked final: the fused totals rank the list, so the confidences come from them)
+            return alternates_mod.vosk_alternatives(texts, [r[4].get("fused", r[4]["score"]) for r in res], words)
         if records is None:   # today's message
             if self.vosk_alignment and al is not None and any(a is not None for a in al["start_s"]):
                 return vosk_result_aligned(tokens, al)
