@@ -669,6 +669,77 @@ typedef struct sc_ctc_beam_lm_job {
  * ctx outside [0, n_states) without restart. */
 int sc_ctc_beam_lm(const sc_ctc_beam_lm_job *jobs, int n_jobs, void *stream);
 
+/* ---- grammar-constrained CTC prefix beam (grammar_blob.h, ctc_beam_grammar.hip) ----------------------
+ * "Answer only from this list": a grammar is a deterministic finite automaton over the token ids [0, V); the blank is
+ * never a label.  State g has the out-arcs arc_tok / arc_next [arc_off[g], arc_off[g + 1]), strictly ascending by token,
+ * and an accept flag; there is one start state.
+ * The blob (little endian; speechcatcher_amd/grammar.py compiles it from phrases): sc_grammar_header; int32 arc_off
+ * [n_states + 1]; int32 arc_tok[n_arcs]; int32 arc_next[n_arcs]; int32 accept[n_states] - every array padded to a
+ * multiple of 8 bytes.  sc_grammar_create validates all of it on the host (the size against the header; V >= 1, blank in
+ * [0, V), 1 <= n_states <= SC_GRAMMAR_MAX_STATES, 0 <= n_arcs <= SC_GRAMMAR_MAX_ARCS, reserved == 0; arc_off monotone from
+ * 0 to n_arcs; the tokens of a state strictly ascending, in [0, V) and not the blank; every next and the start state in
+ * [0, n_states); accept flags 0 or 1) BEFORE a byte reaches the device: SC_ERR_ARG and nothing allocated otherwise.  The
+ * grammar is uploaded once and read-only afterwards; the handle keeps a host copy of the arrays.  It must outlive every
+ * launch that reads it. */
+#define SC_GRAMMAR_MAGIC 0x52474353 /* "SCGR" */
+#define SC_GRAMMAR_VERSION 1
+#define SC_GRAMMAR_MAX_STATES (1 << 20)
+#define SC_GRAMMAR_MAX_ARCS (1 << 24)
+typedef struct sc_grammar_header {
+  int32_t magic, version, V, blank, n_states, n_arcs, start_state, reserved /* 0 */;
+} sc_grammar_header;
+typedef struct sc_grammar_view { /* the automaton as the kernel reads it (device pointers) */
+  const int32_t *arc_off;  /* [n_states + 1] */
+  const int32_t *arc_tok;  /* [n_arcs] */
+  const int32_t *arc_next; /* [n_arcs] */
+  const int32_t *accept;   /* [n_states] */
+  int32_t V, blank, n_states, n_arcs, start_state, reserved;
+} sc_grammar_view;
+typedef struct sc_grammar sc_grammar;
+int sc_grammar_create(const void *blob /*HOST*/, size_t bytes, sc_grammar **out);
+/* SC_ERR_ARG (and nothing freed) while the grammar's use count is not 0; a null grammar is SC_OK. */
+int sc_grammar_destroy(sc_grammar *g);
+/* *device: the view in device memory (what sc_ctc_beam_gr_job.grammar takes); *host: a host copy of it (device pointers).
+ * Either may be NULL.  SC_ERR_ARG for a null grammar. */
+int sc_grammar_device_view(const sc_grammar *g, const sc_grammar_view **device, sc_grammar_view *host);
+/* The use count destroy looks at: whoever names the grammar beyond a launch takes a use (+1) and drops it (-1).  Returns
+ * the new count; SC_ERR_ARG for a null grammar or a count that would fall below 0. */
+int sc_grammar_use(sc_grammar *g, int delta);
+/* the handle's host copy: next state of (state, token) or -1 (no such arc, or an argument out of range) / the accept
+ * flag (0 or 1; -1 for a state out of range).  Host arithmetic, no launch. */
+int sc_grammar_step(const sc_grammar *g, int state, int token);
+int sc_grammar_accepts(const sc_grammar *g, int state);
+
+/* The beam search of sc_ctc_beam with the grammar choosing the candidates (tests/ctc_beam_grammar_ref.py is the
+ * contract, built on tests/ctc_beam_ref.py).  Unchanged from sc_ctc_beam: the row rule (bad rows, lse, lp), lae, the merge
+ * rule, the prune order and its ties, the node records, chained spans.  Entry i carries besides them g_i, the automaton's
+ * state after its prefix; the initial entry has start_state, unused slots hold 0.  Three things differ:
+ *   candidates   are per entry: the C out-arc tokens of g_i with the largest x, compared as fp32, the lowest token among
+ *                ties, none at -inf; fewer than C when the state has fewer arcs - a state without arcs only stays.  Two
+ *                entries in one state have the same candidates.
+ *   stay         the repeat term is unconditional: pnb'_i = pnb_i + lp(last_i), lp(v) = (double)x[v] - lse for any v
+ *                (-inf when x[last_i] is -inf or the entry is the empty prefix).  (With per-entry candidates the rule of
+ *                sc_ctc_beam would end every accepted phrase: its last token is seldom an out-arc of the state it led to.)
+ *   extension    a new prefix made from entry i by c gets g = next(g_i, c); a stay keeps g; an extension that merges
+ *                leaves the target's g alone (the automaton is deterministic: the same prefix has the same state).
+ * The free grammar (one state, a self-loop on every non-blank token) with V - 1 <= C gives every byte of sc_ctc_beam on
+ * the same inputs.  Bars: every int32 and g equal wherever no prune decision is a near-tie, pb / pnb as for sc_ctc_beam.
+ * Not in this revision: weighted arcs, a grammar together with an n-gram model. */
+typedef struct sc_beam_gr_t {
+  int32_t g[SC_BEAM_MAX];
+} sc_beam_gr_t;
+typedef struct sc_ctc_beam_gr_job {
+  sc_ctc_beam_job beam;
+  const sc_grammar_view *grammar; /* device view */
+  sc_beam_gr_t *gr_state;         /* beside beam.state: read (unless restart), written back (device) */
+  sc_beam_gr_t *gr_state_after;   /* second copy, beside beam.state_after (NULL: none) */
+} sc_ctc_beam_gr_job;
+/* As sc_ctc_beam (ONE launch, one workgroup per job, same limits, same errors before a launch; no atomics, one writer
+ * per output, the table and the grammar only read).  Malformed besides what is malformed there, and writing nothing: a
+ * null grammar or gr_state, a grammar whose V or blank differs from the job's, a stored g outside [0, n_states) without
+ * restart. */
+int sc_ctc_beam_grammar(const sc_ctc_beam_gr_job *jobs, int n_jobs, void *stream);
+
 /* ---- n-gram rescoring of n-best lists, with an </s> term (lm_rescore.hip, lm_score.h) ---------------
  * A job is one list: n_hyp <= SC_RESCORE_MAX_HYPS rows of token ids, row h at yseq + h * row_stride with lens[h] tokens
  * (lens == NULL: L tokens each; a lens[h] outside [0, L] makes the row a bad one, below), their totals at
@@ -1389,7 +1460,8 @@ int sc_ctc_beam_hyps(sc_streams *streams, const int *stream_ids, int n, int nbes
  * batch's vocabulary size, alpha and beta finite.  SC_ERR_ARG while any chunk is outstanding; attaching, replacing or
  * detaching restarts every stream's beam (waiting for a group in flight first: the model may be destroyed once it is
  * detached, and switching the beam option off detaches it).  sc_reset and strict_reference: as sc_streams_set_ctc_beam.
- * Hypotheses of FULL streams do not depend on it.  Not in this revision: a model per stream, an end-of-sentence term at
+ * Hypotheses of FULL streams do not depend on it.  SC_ERR_ARG while any stream has a grammar (sc_stream_set_grammar): grammar
+ * and model together are not served.  Not in this revision: a model per stream, an end-of-sentence term at
  * finals, fusion into the blockwise search of FULL streams. */
 int sc_streams_set_ctc_beam_lm(sc_streams *streams, const sc_lm *lm, double alpha, double beta);
 /* beside sc_stream_ctc_beam: the model's side of the same state ((0.0, start_state) in entry 0 before the first frame).
@@ -1400,6 +1472,29 @@ int sc_stream_ctc_beam_lm(sc_streams *streams, int stream, sc_beam_lm_t *out /*H
  * may be NULL.  SC_ERR_ARG when no model is attached. */
 int sc_ctc_beam_hyps_lm(sc_streams *streams, const int *stream_ids, int n, int nbest, double *lm /*HOST*/,
                         double *fused /*HOST*/);
+/* A grammar per stream (sc_ctc_beam_grammar above): the stream's beam answers only from the grammar.  Needs
+ * the beam option on; NULL: none.  A menu belongs to a stream, not to the handle: streams of one handle may name different
+ * grammars, the same one, or none.  A group lists the jobs of its streams without a grammar in its sc_ctc_beam launch, as
+ * always, and those of its streams with one in ONE sc_ctc_beam_grammar launch behind it (the same hand-over; the state
+ * grows by a sc_beam_gr_t per stream, S x 64 bytes, allocated when a grammar is first set on the handle); either launch is
+ * skipped when its list is empty, and a handle on which no stream has a grammar issues the launches it always did.  The
+ * rule of sc_stream_set_decoder: SC_ERR_ARG unless the stream is idle and has taken nothing of its utterance.  The setting
+ * outlives sc_reset; switching the beam option off drops every stream's grammar.  The handle holds one use of the grammar
+ * while a stream names it: sc_grammar_destroy returns SC_ERR_ARG meanwhile.  It works for SC_DECODER_FULL and
+ * SC_DECODER_NONE streams alike; for a FULL stream the beam is a side result and its hypotheses do not depend on it.
+ * Grammar and n-gram model together are not served in this revision: SC_ERR_ARG here while a model is attached to the
+ * handle, and from sc_streams_set_ctc_beam_lm while any stream has a grammar.  The grammar's V and blank must be the
+ * batch's. */
+int sc_stream_set_grammar(sc_streams *streams, int stream, sc_grammar *grammar /*NULL: none*/);
+/* beside sc_stream_ctc_beam: the grammar's side of the same state (start_state in entry 0 before the first frame), with
+ * the same waiting rule.  SC_ERR_ARG when the stream has no grammar. */
+int sc_stream_ctc_beam_grammar(sc_streams *streams, int stream, sc_beam_gr_t *out /*HOST*/);
+/* beside sc_ctc_beam_hyps: g [n][nbest], the grammar's state after each of the same entries, and accept [n][nbest], its
+ * accept flag (1: the entry is a complete phrase, or a sequence of them under a looped grammar); -1 where a state has no
+ * such entry or the stream has no grammar.  Computed on the host from the reported states and the grammar's host copy, no
+ * launch.  Either may be NULL. */
+int sc_ctc_beam_hyps_grammar(sc_streams *streams, const int *stream_ids, int n, int nbest, int32_t *g /*HOST*/,
+                             int32_t *accept /*HOST*/);
 /* Decoder-free streams.  SC_DECODER_NONE: the stream is served from its CTC rows alone.  Admission queues
  * no decode block for it and lists no cross-attention K|V rows for its frames; the front end, the encoder, the CTC rows,
  * every side option and the reply status are those of any stream, a chunk is complete at once (the side-state readers

@@ -74,7 +74,7 @@ def to_16k(raw, rate, device="cuda:0"):
 def recognize_file(speech2text, media_path, output_file="", quiet=True, progress=True, num_slots=1, chunk_length=8192,
                    token_alignment=False, segmentation="host", channel=None, token_alternates=0, ctc_beam=0,
                    ctc_only=False, ctc_lm=None, lm_weight=0.5, word_bonus=0.0, rescore_lm=None, rescore_weight=0.5,
-                   rescore_bonus=0.0):
+                   rescore_bonus=0.0, ctc_grammar=None):
     """speechcatcher.py:358-400: recording -> text + paragraphs JSON next to the input.  ``token_alignment``: the
     paragraphs also get token_start / token_end (seconds) and token_conf from a CTC forced alignment of each segment.
     ``segmentation``: "host" or "gpu" - where the energy curve for the cut points of a recording over 60 s is computed.
@@ -86,7 +86,14 @@ def recognize_file(speech2text, media_path, output_file="", quiet=True, progress
     the path of a packed n-gram model (python -m speechcatcher_amd.ngram) fused into that search with ``lm_weight`` and
     ``word_bonus`` (needs ``ctc_beam`` or ``ctc_only``).  ``rescore_lm``: the path of a packed n-gram model the final
     n-best list of every segment is rescored with and re-ranked by, at ``rescore_weight`` / ``rescore_bonus`` (not with
-    ``ctc_only``)."""
+    ``ctc_only``).  ``ctc_grammar``: the path of a compiled grammar (python -m speechcatcher_amd.grammar) or of a text file
+    with one phrase per line - the CTC beam answers only from it (needs ``ctc_beam`` or ``ctc_only``; not with ``ctc_lm``)."""
+    if ctc_grammar and not (ctc_only or int(ctc_beam)):
+        raise SystemExit("Error: --ctc-grammar constrains the CTC prefix beam search: it needs --ctc-beam or --ctc-only")
+    if ctc_grammar and ctc_lm:
+        raise SystemExit("Error: --ctc-grammar and --ctc-lm together are not served")
+    if ctc_grammar and not os.path.isfile(ctc_grammar):
+        raise SystemExit(f"Error: --ctc-grammar: '{ctc_grammar}' does not exist or is not a file")
     if rescore_lm and ctc_only:
         raise SystemExit("Error: --rescore-lm re-ranks the n-best list of the attention decoder's search: not with --ctc-only")
     if rescore_lm and not os.path.isfile(rescore_lm):
@@ -120,7 +127,8 @@ def recognize_file(speech2text, media_path, output_file="", quiet=True, progress
                                      ctc_beam=int(ctc_beam) or None, ctc_only=ctc_only, ctc_lm=ctc_lm or None,
                                      lm_weight=float(lm_weight), word_bonus=float(word_bonus),
                                      rescore_lm=rescore_lm or None, rescore_weight=float(rescore_weight),
-                                     rescore_bonus=float(rescore_bonus))
+                                     rescore_bonus=float(rescore_bonus),
+                                     **({"ctc_grammar": ctc_grammar} if ctc_grammar else {}))
     out_txt, out_json = (output_file or media_path) + ".txt", (output_file or media_path) + ".json"
     with open(out_txt, "w") as f:
         f.write(text)
@@ -172,6 +180,10 @@ def make_parser():
     p.add_argument("--ctc-lm", dest="ctc_lm", default="", metavar="FILE",
                    help="fuse a backoff n-gram language model into the CTC prefix beam search (needs --ctc-beam or --ctc-only): "
                         "a file packed by `python -m speechcatcher_amd.ngram in.arpa tokens.txt out.sclm`")
+    p.add_argument("--ctc-grammar", dest="ctc_grammar", default="", metavar="FILE",
+                   help="answer only from a list: the CTC prefix beam search is constrained to the phrases of FILE and their "
+                        "concatenations (needs --ctc-beam or --ctc-only; not with --ctc-lm): a grammar compiled by `python -m "
+                        "speechcatcher_amd.grammar phrases.txt tokens.txt out.scgr`, or a text file with one phrase per line")
     p.add_argument("--lm-weight", dest="lm_weight", type=float, default=0.5, metavar="A",
                    help="weight of the model's log probability in the beam's ranking (default 0.5; a parameter, not tuned)")
     p.add_argument("--word-bonus", dest="word_bonus", type=float, default=0.0, metavar="B",
@@ -220,7 +232,8 @@ def main(argv=None):
                    token_alignment=args.token_alignment or args.token_alternates > 0, segmentation=args.segmentation,
                    channel=args.channel, token_alternates=args.token_alternates, ctc_beam=args.ctc_beam,
                    ctc_only=args.ctc_only, ctc_lm=args.ctc_lm or None, lm_weight=args.lm_weight, word_bonus=args.word_bonus,
-                   rescore_lm=args.rescore_lm or None, rescore_weight=args.rescore_weight, rescore_bonus=args.rescore_bonus)
+                   rescore_lm=args.rescore_lm or None, rescore_weight=args.rescore_weight, rescore_bonus=args.rescore_bonus,
+                   **({"ctc_grammar": args.ctc_grammar} if args.ctc_grammar else {}))
     return 0
 
 

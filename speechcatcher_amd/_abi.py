@@ -194,6 +194,30 @@ class LmView(C.Structure):
 LM_MAX_ORDER, LM_MAGIC, LM_VERSION = 5, 0x4D4C4353, 1
 
 
+class GrammarHeader(C.Structure):
+    """sc_grammar_header (include/scasr.h): the first bytes of a grammar blob (speechcatcher_amd/grammar.py compiles it)"""
+    _fields_ = [(n, C.c_int32) for n in ("magic", "version", "V", "blank", "n_states", "n_arcs", "start_state", "reserved")]
+
+
+class GrammarView(C.Structure):
+    """sc_grammar_view (include/scasr.h): the automaton as the kernel reads it"""
+    _fields_ = ([(n, vp) for n in ("arc_off", "arc_tok", "arc_next", "accept")]
+                + [(n, C.c_int32) for n in ("V", "blank", "n_states", "n_arcs", "start_state", "reserved")])
+
+
+class BeamGr(C.Structure):
+    """sc_beam_gr_t (include/scasr.h): beside the entries of a sc_beam_t, the grammar's state after each prefix"""
+    _fields_ = [("g", C.c_int32 * BEAM_MAX)]
+
+
+class BeamGrJob(C.Structure):
+    """sc_ctc_beam_gr_job (include/scasr.h): a sc_ctc_beam_job whose candidates a grammar chooses"""
+    _fields_ = [("beam", BeamJob), ("grammar", vp), ("gr_state", vp), ("gr_state_after", vp)]
+
+
+GRAMMAR_MAGIC, GRAMMAR_VERSION, GRAMMAR_MAX_STATES, GRAMMAR_MAX_ARCS = 0x52474353, 1, 1 << 20, 1 << 24
+
+
 class RescoreJob(C.Structure):
     """sc_lm_rescore_job (include/scasr.h): one n-best list rescored by sc_lm_rescore"""
     _fields_ = ([(n, vp) for n in ("model", "yseq", "score", "lens", "lm", "eos_lm", "fused", "end_state", "order",
@@ -426,6 +450,17 @@ _SIGS = {
     "sc_streams_set_ctc_beam_lm": (C.c_int, [vp, vp, C.c_double, C.c_double]),
     "sc_stream_ctc_beam_lm": (C.c_int, [vp, C.c_int, C.POINTER(BeamLm)]),
     "sc_ctc_beam_hyps_lm": (C.c_int, [vp, c_int_p, C.c_int, C.c_int, vp, vp]),
+    # grammar-constrained CTC prefix beam (ctc_beam_grammar.hip)
+    "sc_ctc_beam_grammar": (C.c_int, [vp, C.c_int, vp]),
+    "sc_grammar_create": (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),
+    "sc_grammar_destroy": (C.c_int, [vp]),
+    "sc_grammar_device_view": (C.c_int, [vp, C.POINTER(vp), C.POINTER(GrammarView)]),
+    "sc_grammar_use": (C.c_int, [vp, C.c_int]),
+    "sc_grammar_step": (C.c_int, [vp, C.c_int, C.c_int]),
+    "sc_grammar_accepts": (C.c_int, [vp, C.c_int]),
+    "sc_stream_set_grammar": (C.c_int, [vp, C.c_int, vp]),
+    "sc_stream_ctc_beam_grammar": (C.c_int, [vp, C.c_int, C.POINTER(BeamGr)]),
+    "sc_ctc_beam_hyps_grammar": (C.c_int, [vp, c_int_p, C.c_int, C.c_int, c_int_p, c_int_p]),
     # n-gram rescoring of n-best lists (lm_rescore.hip, streams.hip)
     "sc_lm_rescore": (C.c_int, [vp, C.c_int, vp]),
     "sc_rescore_hyps": (C.c_int, [vp, c_int_p, C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_int, c_int_p, vp, vp,

@@ -23,6 +23,10 @@
 // issued together so that their loads overlap -, and the items are ranked by total + (alpha * lm + beta * len).  The
 // LM = false instantiation is the kernel without any of it.  sc_lm_create validates a model on the host (lm_blob.h)
 // and uploads it once.
+//
+// ctc_beam_grammar.hip (sc_ctc_beam_grammar) writes lae, the entry constructors and the beam step a second
+// time instead of sharing them with this file through a header: the register allocation of ctc_beam_kernel follows the
+// shape of its source (8j, 8k), and this file stays as it is.
 #include "ctc_row.h"
 #include "lm_blob.h"
 

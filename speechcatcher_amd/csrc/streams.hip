@@ -167,9 +167,11 @@ struct DraftState {
 // entries are final whatever later groups append.
 // With a language model attached (sc_streams_set_ctc_beam_lm) the model's side of the entries travels with them: all
 // zero without one, and before the first group of an utterance (the readers put the model's start state there).
+// A stream with a grammar (sc_stream_set_grammar) carries the automaton's states beside its entries in the same way.
 struct BeamState {
   sc_beam_t d;
   sc_beam_lm_t lm{};
+  sc_beam_gr_t gr{};
   BeamState() {
     d.n_frames = 0; d.n_bad = 0; d.n_nodes = 1; d.n_entries = 1;
     for (sc_beam_entry &e : d.e) e = sc_beam_entry{-1, -1, 0, -1, -INFINITY, -INFINITY};
@@ -177,6 +179,7 @@ struct BeamState {
   }
   explicit BeamState(const sc_beam_t &v) : d(v) {}
   BeamState(const sc_beam_t &v, const sc_beam_lm_t &l) : d(v), lm(l) {}
+  BeamState(const sc_beam_t &v, const sc_beam_gr_t &g) : d(v), gr(g) {}
 };
 // Input level (sc_stream_set_input_format; pcm.hip): the cumulative level, all zero at first.  Its launch belongs to a
 // STAGING slot (it runs in the admission's staging step, not in an encoder group), so its key is a ticket that names the
@@ -263,6 +266,7 @@ struct EncGroup {
   struct Span {
     int s = 0, t0 = 0, t1 = 0;
     uint64_t mask = 0;
+    const sc_grammar_view *grammar = nullptr;   // (beam) the device view of the stream's grammar when the span was planned
     handover::Plan opt[N_OPT];
   };
   std::vector<Span> spans;
@@ -414,6 +418,12 @@ struct sc_streams {
   sc_beam_lm_t *beam_lm_state = nullptr;    // device [S], beside beam_state
   sc_ctc_beam_lm_job *beam_lm_jobs_host = nullptr, *beam_lm_jobs_dev = nullptr;   // [N_ARENA][S]
   sc_beam_lm_t *beam_lm_out_host = nullptr, *beam_lm_out_dev = nullptr;           // [N_ARENA][S] host-mapped, beside beam_out
+  // grammars (sc_stream_set_grammar): a menu belongs to a stream.  Allocated when a grammar is first set on the handle.
+  std::vector<sc_grammar *> beam_gr;         // [S] the stream's grammar (NULL: none); the handle holds one use of each
+  int beam_gr_n = 0;                         // streams with a grammar
+  sc_beam_gr_t *beam_gr_state = nullptr;    // device [S], beside beam_state
+  sc_ctc_beam_gr_job *beam_gr_jobs_host = nullptr, *beam_gr_jobs_dev = nullptr;   // [N_ARENA][S]
+  sc_beam_gr_t *beam_gr_out_host = nullptr, *beam_gr_out_dev = nullptr;           // [N_ARENA][S] host-mapped, beside beam_out
   char *bh_dev = nullptr, *bh_host = nullptr;   // sc_ctc_beam_hyps: states, pack jobs and packed outputs; grown geometrically
   size_t bh_cap = 0;
   char *rs_dev = nullptr, *rs_host = nullptr;   // sc_rescore_hyps / sc_lm_rescore_lists: job table, inputs, outputs; grown geometrically
@@ -481,6 +491,8 @@ struct sc_streams {
     if (stream) (void)hipStreamDestroy(stream);
     if (al_dev) (void)hipFree(al_dev);
     if (beam_nodes) (void)hipFree(beam_nodes);
+    for (sc_grammar *g : beam_gr)   // (the streams are synchronised: nothing reads a grammar any more)
+      if (g) (void)sc_grammar_use(g, -1);
     if (bh_dev) (void)hipFree(bh_dev);
     if (bh_host) (void)hipHostFree(bh_host);
     if (rs_dev) (void)hipFree(rs_dev);
@@ -1054,7 +1066,9 @@ int retire_groups(sc_streams *b) {
         b->draft.deliver(s, g->gen, sp.opt[OPT_DRAFT].epoch, DraftState{b->draft_out_host[o]}, b->job[s], b->ahead[s], &Job::draft);
       if (sp.opt[OPT_BEAM].on)
         b->beam.deliver(s, g->gen, sp.opt[OPT_BEAM].epoch,
-                        b->beam_lm ? BeamState(b->beam_out_host[o], b->beam_lm_out_host[o]) : BeamState(b->beam_out_host[o]),
+                        b->beam_lm      ? BeamState(b->beam_out_host[o], b->beam_lm_out_host[o])
+                        : sp.grammar ? BeamState(b->beam_out_host[o], b->beam_gr_out_host[o])
+                                     : BeamState(b->beam_out_host[o]),
                         b->job[s], b->ahead[s], &Job::beam);
     }
     b->gen_done = g->gen;
@@ -1108,6 +1122,47 @@ int launch_spans(sc_streams *b, const EncGroup &g, int opt, const char *name, J 
   return launch(jobs_dev + o, n, b->es);
 }
 
+// The beam launches of a group in which a stream has a grammar: the jobs of the streams without one are listed in the
+// sc_ctc_beam launch, as in every other group, those of the streams with one in ONE sc_ctc_beam_grammar launch behind it;
+// either launch is skipped when its list is empty.  A job's state-after slot is its span's (at), wherever it is listed.
+template <typename Fill>
+int launch_beam_grammars(sc_streams *b, const EncGroup &g, Fill beam_fill) {
+  if (g.spans.empty() || !g.spans[0].opt[OPT_BEAM].on) return SC_OK;
+  const int n = (int)g.spans.size();
+  if (n > b->S) {
+    sc_set_error("beam: %d spans in a group of a batch of %d streams (internal error)", n, b->S);
+    return SC_ERR_ARG;
+  }
+  const size_t o = (size_t)g.slot * b->S;
+  int n_plain = 0, n_gr = 0;
+  for (int i = 0; i < n; ++i) {
+    const EncGroup::Span &sp = g.spans[i];
+    if (!sp.grammar) {
+      sc_ctc_beam_job &j = b->beam_jobs_host[o + n_plain++];
+      span_job(b, j, sp, OPT_BEAM);
+      beam_fill(j, sp, o + i);
+    } else {
+      sc_ctc_beam_gr_job &j = b->beam_gr_jobs_host[o + n_gr++];
+      span_job(b, j.beam, sp, OPT_BEAM);
+      beam_fill(j.beam, sp, o + i);
+      j.grammar = sp.grammar;
+      j.gr_state = b->beam_gr_state + sp.s;
+      j.gr_state_after = b->beam_gr_out_dev + o + i;
+    }
+  }
+  if (n_plain) {
+    HIP_TRY(hipMemcpyAsync(b->beam_jobs_dev + o, b->beam_jobs_host + o, (size_t)n_plain * sizeof(sc_ctc_beam_job),
+                           hipMemcpyHostToDevice, b->es));
+    RC_TRY(sc_ctc_beam(b->beam_jobs_dev + o, n_plain, b->es));
+  }
+  if (n_gr) {
+    HIP_TRY(hipMemcpyAsync(b->beam_gr_jobs_dev + o, b->beam_gr_jobs_host + o, (size_t)n_gr * sizeof(sc_ctc_beam_gr_job),
+                           hipMemcpyHostToDevice, b->es));
+    RC_TRY(sc_ctc_beam_grammar(b->beam_gr_jobs_dev + o, n_gr, b->es));
+  }
+  return SC_OK;
+}
+
 // CTC rows and cross-attention K|V rows of the frames a group emits (extend_scorers' encoder-side half,
 // beam_search.py:403-464; scorers.py:342-350 stores RAW logits - the log-softmax of a stream's first block, quirk
 // A1, is applied when that block starts).  They depend on the encoder output only, so they belong to the encoder
@@ -1156,7 +1211,11 @@ int project_rows(sc_streams *b, EncGroup &g) {
       j.capacity = (int32_t)b->beam_ncap();
       j.B = b->beam_B; j.C = b->beam_C;
     };
-    if (!b->beam_lm)
+    bool any_grammar = false;
+    for (const EncGroup::Span &sp : g.spans) any_grammar = any_grammar || sp.grammar;
+    if (any_grammar)   // (no model is attached then: sc_stream_set_grammar)
+      RC_TRY(launch_beam_grammars(b, g, beam_fill));
+    else if (!b->beam_lm)
       RC_TRY(launch_spans(b, g, OPT_BEAM, "beam", b->beam_jobs_host, b->beam_jobs_dev, sc_ctc_beam, beam_fill));
     else   // the same slot, the fused launch in its place
       RC_TRY(launch_spans(b, g, OPT_BEAM, "beam", b->beam_lm_jobs_host, b->beam_lm_jobs_dev, sc_ctc_beam_lm,
@@ -1847,7 +1906,10 @@ int admit(sc_streams *b, std::vector<Chunk> chunks, bool features, bool defer, s
         sp.mask = b->spot_mask[ch.s];
       }
       if (b->draft_on) sp.opt[OPT_DRAFT] = b->draft.plan(ch.s);
-      if (b->beam_on) sp.opt[OPT_BEAM] = b->beam.plan(ch.s);
+      if (b->beam_on) {
+        sp.opt[OPT_BEAM] = b->beam.plan(ch.s);
+        if (b->beam_gr_n && b->beam_gr[ch.s]) RC_TRY(sc_grammar_device_view(b->beam_gr[ch.s], &sp.grammar, nullptr));
+      }
       g->spans.push_back(sp);
       act_new.push_back(ch.s);
     }
@@ -3864,6 +3926,16 @@ extern "C" int sc_streams_set_ctc_beam(sc_streams *b, int beam, int candidates) 
   SC_CHECK_ARG(b->n_open == 0, "chunks are outstanding");
   if (!beam) {
     b->beam_on = false;
+    if (b->beam_gr_n) {   // every stream's grammar goes with the option (a group may still be held back or in flight: it reads them)
+      HIP_TRY(hipSetDevice(b->eng->device));
+      RC_TRY(launch_pending_groups(b));
+      HIP_TRY(hipStreamSynchronize(b->es));
+      for (sc_grammar *&g : b->beam_gr) {
+        if (g) (void)sc_grammar_use(g, -1);
+        g = nullptr;
+      }
+      b->beam_gr_n = 0;
+    }
     if (b->beam_lm) {   // the model goes with the option (a group may still be in flight: it reads the model)
       HIP_TRY(hipSetDevice(b->eng->device));
       HIP_TRY(hipStreamSynchronize(b->es));
@@ -3914,6 +3986,7 @@ extern "C" int sc_streams_set_ctc_beam_lm(sc_streams *b, const sc_lm *lm, double
     return SC_OK;
   }
   SC_CHECK_ARG(b->beam_on, "the beam option is off (sc_streams_set_ctc_beam)");
+  SC_CHECK_ARG(b->beam_gr_n == 0, "a stream has a grammar (sc_stream_set_grammar): grammar and model together are not served");
   SC_CHECK_ARG(std::isfinite(alpha) && std::isfinite(beta), "alpha and beta must be finite");
   sc_lm_view info;
   const sc_lm_view *view = nullptr;
@@ -3978,6 +4051,99 @@ extern "C" int sc_ctc_beam_hyps_lm(sc_streams *b, const int *stream_ids, int n, 
       }
       if (lm) lm[k] = l;
       if (fused) fused[k] = f;
+    }
+  }
+  return SC_OK;
+  SC_API_END
+}
+
+// ---- grammars: a menu per stream ------------------------------------------------------------------------------------------
+// The rule of sc_stream_set_decoder: only while the stream is idle and has taken nothing of its utterance.  The handle
+// holds one use of every grammar a stream names (sc_grammar_destroy refuses meanwhile); a grammar that is replaced or
+// dropped is let go only when no group that may read it is held back or in flight.
+extern "C" int sc_stream_set_grammar(sc_streams *b, int stream, sc_grammar *grammar) {
+  SC_CHECK_ARG(b && stream >= 0 && stream < b->S, "stream out of range");
+  SC_API_BEGIN
+  const St &cur = b->st[stream];
+  SC_CHECK_ARG(!b->job[stream].open && b->ahead[stream].empty(), "the stream has a chunk outstanding (sc_poll reports it first)");
+  SC_CHECK_ARG(cur.pcm_end == 0 && !cur.fe_started && !cur.enc_started && !cur.started && cur.rs_in == 0,
+               "the stream has buffered audio since its last reset (sc_reset first)");
+  sc_grammar *old = b->beam_gr_n ? b->beam_gr[stream] : nullptr;
+  if (grammar == old) return SC_OK;
+  HIP_TRY(hipSetDevice(b->eng->device));
+  if (grammar) {
+    SC_CHECK_ARG(b->beam_on, "the beam option is off (sc_streams_set_ctc_beam)");
+    SC_CHECK_ARG(!b->beam_lm, "a language model is attached (sc_streams_set_ctc_beam_lm): grammar and model together are not served");
+    sc_grammar_view info;
+    RC_TRY(sc_grammar_device_view(grammar, nullptr, &info));
+    SC_CHECK_ARG(info.V == b->cfg.vocab_size && info.blank == b->cfg.blank_id,
+                 "the grammar's vocabulary size or blank is not the batch's");
+    if (!b->beam_gr_state) {
+      const size_t S = (size_t)b->S;
+      RC_TRY(b->alloc(&b->beam_gr_state, S));
+      RC_TRY(b->alloc(&b->beam_gr_jobs_dev, S * N_ARENA));
+      RC_TRY(b->halloc(&b->beam_gr_jobs_host, S * N_ARENA));
+      RC_TRY(b->halloc_mapped(&b->beam_gr_out_host, &b->beam_gr_out_dev, S * N_ARENA, __func__, "state slots"));
+    }
+    if (b->beam_gr.empty()) b->beam_gr.assign((size_t)b->S, nullptr);
+  }
+  if (old) {   // a group of the stream's last utterance may still be held back or in flight: it reads the old grammar
+    RC_TRY(launch_pending_groups(b));
+    HIP_TRY(hipStreamSynchronize(b->es));
+    (void)sc_grammar_use(old, -1);
+    b->beam_gr_n--;
+  }
+  if (grammar) {
+    RC_TRY(sc_grammar_use(grammar, 1) > 0 ? SC_OK : SC_ERR_ARG);
+    b->beam_gr_n++;
+  }
+  b->beam_gr[stream] = grammar;
+  b->beam.restart(stream);   // the stream's next span starts its utterance, in the new grammar's start state
+  return SC_OK;
+  SC_API_END
+}
+
+// the grammar's side of the state sc_stream_ctc_beam returns: before the first frames of an utterance the start state
+extern "C" int sc_stream_ctc_beam_grammar(sc_streams *b, int stream, sc_beam_gr_t *out) {
+  SC_CHECK_ARG(b && out && stream >= 0 && stream < b->S, "bad arguments");
+  SC_API_BEGIN
+  SC_CHECK_ARG(b->beam_on && b->beam_gr_n && b->beam_gr[stream], "the stream has no grammar (sc_stream_set_grammar)");
+  HIP_TRY(hipSetDevice(b->eng->device));
+  RC_TRY(beam_ready(b, stream));
+  const BeamState &v = b->beam.rep[stream].v;
+  *out = v.gr;
+  if (v.d.n_frames == 0) {
+    sc_grammar_view info;
+    RC_TRY(sc_grammar_device_view(b->beam_gr[stream], nullptr, &info));
+    out->g[0] = info.start_state;
+  }
+  return SC_OK;
+  SC_API_END
+}
+
+// beside sc_ctc_beam_hyps: g [n][nbest], the grammar's state after each entry's prefix, and accept [n][nbest], its accept
+// flag; -1 where the state has no such entry or the stream has no grammar.  Host arithmetic on the reported states and the
+// grammars' host copies, no launch.  Either may be NULL.
+extern "C" int sc_ctc_beam_hyps_grammar(sc_streams *b, const int *stream_ids, int n, int nbest, int32_t *g, int32_t *accept) {
+  SC_CHECK_ARG(b && stream_ids && n >= 0 && nbest >= 0 && nbest <= SC_BEAM_MAX, "bad arguments");
+  SC_API_BEGIN
+  SC_CHECK_ARG(b->beam_on, "the beam option is off (sc_streams_set_ctc_beam)");
+  SC_CHECK_ARG(n <= b->S, "more streams listed than the batch has");
+  HIP_TRY(hipSetDevice(b->eng->device));
+  for (int i = 0; i < n; ++i) {
+    const int s = stream_ids[i];
+    SC_CHECK_ARG(s >= 0 && s < b->S, "stream out of range");
+    RC_TRY(beam_ready(b, s));
+    const BeamState &v = b->beam.rep[s].v;
+    const sc_grammar *gr = b->beam_gr_n ? b->beam_gr[s] : nullptr;
+    sc_grammar_view info{};
+    if (gr) RC_TRY(sc_grammar_device_view(gr, nullptr, &info));
+    for (int r = 0; r < nbest; ++r) {
+      const size_t k = (size_t)i * nbest + r;
+      int32_t st = -1;
+      if (gr && r < v.d.n_entries) st = v.d.n_frames == 0 ? info.start_state : v.gr.g[r];
+      if (g) g[k] = st;
+      if (accept) accept[k] = st < 0 ? -1 : sc_grammar_accepts(gr, st);
     }
   }
   return SC_OK;

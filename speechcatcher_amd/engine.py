@@ -577,6 +577,16 @@ class StreamBatch:
                               "(NativeStreamBatch.set_ctc_beam_lm, sc_streams_set_ctc_beam_lm); the Python engine runs "
                               "the CTC beam unfused only")
 
+    def grammar(self, blob):
+        """a grammar per stream is an option of the native engine: this one refuses it."""
+        raise EngineError("grammar: the grammar-constrained CTC beam needs the native engine (NativeStreamBatch.grammar / "
+                          "set_stream_grammar, sc_stream_set_grammar); the Python engine runs the CTC beam unconstrained only")
+
+    def set_stream_grammar(self, s: int, handle=None):
+        """see ``grammar``: refused, unless it asks for none"""
+        if handle is not None:
+            self.grammar(None)
+
     def language_model(self, model):
         """n-gram rescoring of final n-best lists is an option of the native engine: this one refuses it."""
         raise EngineError("language_model: n-gram rescoring of finals needs the native engine (NativeStreamBatch."

@@ -136,6 +136,41 @@ class DeviceLm:
         self.close()
 
 
+class DeviceGrammar:
+    """a grammar on the device (sc_grammar_create / sc_grammar_destroy): ``view`` is the device address of its
+    sc_grammar_view, ``info`` a host copy of it; step / accepts walk the handle's host copy"""
+
+    def __init__(self, lib, blob: bytes):
+        self._lib, self.handle = lib, C.c_void_p()
+        buf = (C.c_char * max(len(blob), 1)).from_buffer_copy(bytes(blob) or b"\0")
+        rc = lib.sc_grammar_create(buf, len(blob), C.byref(self.handle))
+        if rc != 0:
+            self.handle = None
+            _abi.check(rc, "sc_grammar_create")
+        self.info = _abi.GrammarView()
+        view = C.c_void_p()
+        _abi.check(lib.sc_grammar_device_view(self.handle, C.byref(view), C.byref(self.info)), "sc_grammar_device_view")
+        self.view = view.value
+        self.bytes = len(blob)
+
+    def step(self, state: int, token: int) -> int:
+        return self._lib.sc_grammar_step(self.handle, int(state), int(token))
+
+    def accepts(self, state: int) -> bool:
+        return self._lib.sc_grammar_accepts(self.handle, int(state)) == 1
+
+    def close(self):
+        if self.handle:
+            _abi.check(self._lib.sc_grammar_destroy(self.handle), "sc_grammar_destroy")
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # (still in use: whoever holds the use lets go of it first; or the interpreter is shutting down)
+            pass
+
+
 class HipBackend:
     name = "hip"
 
@@ -554,7 +589,23 @@ class HipBackend:
         records.  The job handed to ``tweak`` is the sc_ctc_beam_lm_job (the plain job in its ``beam``)."""
         return self.ctc_beam(jobs, tweak, guard, fused=(model, float(alpha), float(beta)))
 
-    def ctc_beam(self, jobs, tweak=None, guard: int = 2, fused=None):
+    _BEAM_GR = [("g", "<i4", 16)]   # sc_beam_gr_t
+
+    def grammar(self, blob: bytes):
+        """a compiled grammar (speechcatcher_amd.grammar.compile) validated and uploaded once (sc_grammar_create)"""
+        return DeviceGrammar(self.lib, blob)
+
+    def ctc_beam_grammar(self, jobs, grammars, tweak=None, guard: int = 2):
+        """ctc_beam through sc_ctc_beam_grammar: ``grammars`` - one grammar() for all jobs or a list with one per job -
+        choose the candidates.  A job's state dict may carry "g": the grammar's state beside each entry; the returned
+        states do, with "raw_gr": the sc_beam_gr_t as a numpy record; the second copies are (sc_beam_t, sc_beam_gr_t)
+        records.  The job handed to ``tweak`` is the sc_ctc_beam_gr_job (the plain job in its ``beam``)."""
+        if not isinstance(grammars, (list, tuple)):
+            grammars = [grammars] * len(jobs)
+        assert len(grammars) == len(jobs)
+        return self.ctc_beam(jobs, tweak, guard, grammars=list(grammars))
+
+    def ctc_beam(self, jobs, tweak=None, guard: int = 2, fused=None, grammars=None):
         """Batched CTC prefix beam search (sc_ctc_beam) on the caller's tables, one launch for all jobs.  jobs: list of
         (table [T, V] fp32 tensor, rows may be strided; blank; t0; t1; state: a dict as returned here or None = the span
         starts an utterance; capacity of the node store; B; C).  Returns (states: list of {n_frames, n_bad, n_nodes,
@@ -595,11 +646,24 @@ class HipBackend:
                     for r, (l, c) in enumerate(job[4].get("side", [])):
                         lms[k]["lm"][r], lms[k]["ctx"][r] = l, c
             lms_d, lms_after_d = (torch.as_tensor(a.view(np.uint8).copy()).to(dev) for a in (lms, lms_after))
-        tab = ((_abi.BeamJob if fused is None else _abi.BeamLmJob) * max(1, n))()
+        if grammars is not None:
+            assert fused is None
+            gr_dt = np.dtype(self._BEAM_GR)
+            assert gr_dt.itemsize == C.sizeof(_abi.BeamGr) == 64
+            grs = np.zeros(max(n, 1), gr_dt)
+            grs.view(np.int32)[:] = -7
+            grs_after = grs.copy()
+            for k, job in enumerate(jobs):
+                if job[4] is not None:
+                    grs[k]["g"] = 0
+                    for r, g in enumerate(job[4].get("g", [])):
+                        grs[k]["g"][r] = g
+            grs_d, grs_after_d = (torch.as_tensor(a.view(np.uint8).copy()).to(dev) for a in (grs, grs_after))
+        tab = ((_abi.BeamGrJob if grammars is not None else _abi.BeamJob if fused is None else _abi.BeamLmJob) * max(1, n))()
         for k, (table, blank, t0, t1, st, cap, B, Cn) in enumerate(jobs):
             assert table.dtype == torch.float32 and table.dim() == 2 and table.stride(1) == 1
             assert 0 <= t0 <= t1 <= table.shape[0]
-            j = tab[k] if fused is None else tab[k].beam
+            j = tab[k] if fused is None and grammars is None else tab[k].beam
             j.table, j.state, j.state_after = table.data_ptr(), state_d.data_ptr() + 528 * k, after_d.data_ptr() + 528 * k
             j.nodes = store_d.data_ptr() + 16 * int(off[k])
             j.stride, j.V, j.blank, j.t0, j.t1 = table.stride(0), table.shape[1], int(blank), int(t0), int(t1)
@@ -609,10 +673,16 @@ class HipBackend:
                 jl.lm = fused[0].view if fused[0] is not None else None
                 jl.lm_state, jl.lm_state_after = lms_d.data_ptr() + 192 * k, lms_after_d.data_ptr() + 192 * k
                 jl.alpha, jl.beta = fused[1], fused[2]
+            if grammars is not None:
+                jg = tab[k]
+                jg.grammar = grammars[k].view if grammars[k] is not None else None
+                jg.gr_state, jg.gr_state_after = grs_d.data_ptr() + 64 * k, grs_after_d.data_ptr() + 64 * k
             if tweak is not None:
                 tweak(k, tab[k])
         tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
-        if fused is None:
+        if grammars is not None:
+            self._chk(self.lib.sc_ctc_beam_grammar(tab_dev.data_ptr(), n, self._stream()), "sc_ctc_beam_grammar")
+        elif fused is None:
             self._chk(self.lib.sc_ctc_beam(tab_dev.data_ptr(), n, self._stream()), "sc_ctc_beam")
         else:
             self._chk(self.lib.sc_ctc_beam_lm(tab_dev.data_ptr(), n, self._stream()), "sc_ctc_beam_lm")
@@ -634,6 +704,12 @@ class HipBackend:
                 d["raw_lm"] = lms[k].copy()
                 d["side"] = [(float(lms[k]["lm"][r]), int(lms[k]["ctx"][r])) for r in range(len(d["entries"]))]
             return out, [(after[k].copy(), lms_after[k].copy()) for k in range(n)]
+        if grammars is not None:
+            grs, grs_after = (a.cpu().numpy().view(gr_dt) for a in (grs_d, grs_after_d))
+            for k, d in enumerate(out):
+                d["raw_gr"] = grs[k].copy()
+                d["g"] = [int(grs[k]["g"][r]) for r in range(len(d["entries"]))]
+            return out, [(after[k].copy(), grs_after[k].copy()) for k in range(n)]
         return out, [after[k].copy() for k in range(n)]
 
     def ctc_beam_pack(self, jobs, tweak=None, guard: int = 2):

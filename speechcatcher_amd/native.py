@@ -705,6 +705,62 @@ class NativeStreamBatch:
             raise EngineError(str(e)) from e
         return out
 
+    # ---- a grammar per stream (sc_stream_set_grammar) -------------------------------------------
+    def grammar(self, blob):
+        """``blob`` (speechcatcher_amd.grammar.compile, the bytes of a .scgr file, or a hip_backend.DeviceGrammar) as a
+        DeviceGrammar: validated and uploaded once; any number of streams, of any handle, may name it."""
+        from .hip_backend import DeviceGrammar
+        try:
+            return blob if isinstance(blob, DeviceGrammar) else DeviceGrammar(self.lib, bytes(blob))
+        except _abi.ScasrError as e:
+            raise EngineError(str(e)) from e
+
+    def release_grammar(self, handle):
+        """free a grammar() - an EngineError while a stream still names it"""
+        try:
+            handle.close()
+        except _abi.ScasrError as e:
+            raise EngineError(str(e)) from e
+
+    def set_stream_grammar(self, s: int, handle=None):
+        """The grammar of stream s (a grammar(), or None: none): its CTC beam then answers only from it.  Needs
+        set_ctc_beam and no model attached; only on an idle stream that has taken nothing of its utterance; the setting
+        outlives ``reset``."""
+        try:
+            _abi.check(self.lib.sc_stream_set_grammar(self.handle, int(s), handle.handle if handle is not None else None),
+                       "sc_stream_set_grammar")
+        except _abi.ScasrError as e:
+            raise EngineError(str(e)) from e
+        self._grammars = getattr(self, "_grammars", {})
+        self._grammars[int(s)] = handle   # (the engine reads the grammar on the device: it lives while a stream names it)
+
+    def ctc_beam_grammar(self, streams: Sequence[int]):
+        """[[g, ...]] beside ``ctc_beam``'s entries of the listed streams: the grammar's state after each entry's prefix"""
+        out = []
+        a = _abi.BeamGr()
+        for s, st in zip(streams, self.ctc_beam(streams)):
+            try:
+                _abi.check(self.lib.sc_stream_ctc_beam_grammar(self.handle, int(s), C.byref(a)), "sc_stream_ctc_beam_grammar")
+            except _abi.ScasrError as e:
+                raise EngineError(str(e)) from e
+            out.append(list(a.g[:len(st["entries"])]))
+        return out
+
+    def ctc_beam_hyps_grammar(self, streams: Sequence[int], nbest: int = 1):
+        """{stream: [(g, complete), best first]} beside ``ctc_beam_hyps``: the grammar's state after each entry and
+        whether it accepts; (-1, None) for a stream without a grammar.  Host arithmetic, no launch."""
+        n, nbest = len(streams), min(int(nbest), _abi.BEAM_MAX)
+        ids_in = np.asarray(list(streams), np.int32)
+        g, acc = np.zeros((n, nbest), np.int32), np.zeros((n, nbest), np.int32)
+        try:
+            _abi.check(self.lib.sc_ctc_beam_hyps_grammar(self.handle, ids_in.ctypes.data_as(_abi.c_int_p), n, nbest,
+                                                         g.ctypes.data_as(_abi.c_int_p), acc.ctypes.data_as(_abi.c_int_p)),
+                       "sc_ctc_beam_hyps_grammar")
+        except _abi.ScasrError as e:
+            raise EngineError(str(e)) from e
+        return {int(s): [(int(g[i, r]), bool(acc[i, r]) if acc[i, r] >= 0 else None) for r in range(nbest)]
+                for i, s in enumerate(streams)}
+
     def hypotheses_batch(self, streams: Sequence[int], nbest: Optional[int] = None):
         """{stream: [hypothesis dicts, best first]} for the listed streams, one device round trip for all."""
         a = self.hypotheses_arrays(streams, nbest)

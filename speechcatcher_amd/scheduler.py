@@ -13,7 +13,9 @@ Parity note: the reference's output depends on the chunking of each stream, so
 the scheduler never re-chunks: one chunk fed by a session is one engine call
 for that stream, exactly as if the session owned a private Speech2TextStreaming.
 """
+import hashlib
 import math
+import os
 from collections import deque
 from typing import Deque, Dict, List, Optional, Tuple
 
@@ -21,6 +23,8 @@ import numpy as np
 
 from .engine import StreamBatch
 from . import spotting
+from .spotting import phrase_ids
+from . import grammar as grammar_mod
 from . import draft as draft_mod
 from . import ctc_beam as beam_mod
 from . import alternates as alternates_mod
@@ -107,6 +111,10 @@ class CtcBeamResults(StableResults):
     list}]}.  For a decoder-free session (``open(decoder="ctc")``) the reply's results ARE the beam's best.  The
     attributes of the other options are carried as well when those are on."""
     ctc_nbest: Optional[list] = None
+    # a session with a grammar (open(grammar=...); DESIGN.md 8m): the entries of ``ctc_nbest`` carry "complete", the
+    # grammar's accept flag; at a final they come complete entries first (each group in beam order), and
+    # ``grammar_complete`` says whether the entry reported first is complete (None without a grammar)
+    grammar_complete: Optional[bool] = None
 
 
 class StreamScheduler:
@@ -166,6 +174,11 @@ class StreamScheduler:
         self._final_dev = self._ctc_blob = self._ctc_dev = None
         self._ctc_sessions = set()
         self._slot_dec: Dict[int, str] = {}
+        # grammars (``open(grammar=...)``, ``set_grammar``; needs ``ctc_beam``; C++ engine): compiled grammars by the
+        # SHA-256 of their blob, {"handle": the device copy, "uses": the slots that name it, "walk": its host walk} - a
+        # thousand connections with one menu share one device copy, released when the last lets go of it
+        self._gr_cache: Dict[str, dict] = {}
+        self._slot_gr: Dict[int, Optional[str]] = {}
         # ``stable_partials``: every reply (an exception aside) is a ``StableResults``.  The scheduler owns one
         # commit.StablePrefix per session and asks the engine only for the tokens behind what that holds
         # (batch.hyps_delta: one call for all sessions of a reply round)
@@ -304,10 +317,13 @@ class StreamScheduler:
 
     # ---- session lifecycle -------------------------------------------------
     def open(self, sample_rate: int = 16000, format: int = pcm_mod.F32, channels: int = 1, channel: int = pcm_mod.MIX,
-             scale: int = pcm_mod.SCALE_FULL, decoder: str = "full") -> int:
+             scale: int = pcm_mod.SCALE_FULL, decoder: str = "full", grammar=None) -> int:
         """``decoder``: "full" - the attention search (the default) - or "ctc": a decoder-free session, served from the CTC
         prefix beam search alone (needs the ``ctc_beam`` option and the C++ engine; its replies carry the beam's best as
         their result; a slot goes back to "full" for a later session that does not ask).
+        ``grammar`` (needs the ``ctc_beam`` option and the C++ engine): the session's CTC beam answers only from it - a
+        compiled blob (speechcatcher_amd.grammar), the path of a .scgr file or of a text file with one phrase per line,
+        or a list of phrases (lists of token ids, or strings tokenised by spotting.phrase_ids); see ``set_grammar``.
         ``sample_rate``: rate of the PCM this session feeds (speechcatcher_amd.resample: 8000..48000 Hz; the C++
         engine converts it to 16 kHz on the GPU).  A slot goes back to 16000 for a later session that does not ask.
         ``format`` / ``channels`` / ``channel`` / ``scale``: the wire format of what the session feeds
@@ -319,9 +335,15 @@ class StreamScheduler:
         self._check_decoder(decoder)
         if not self._free:
             raise ServerBusy("Server busy: all stream slots are in use")
+        gr_key = self._grammar_key(grammar) if grammar is not None else None
         slot = self._free[0]
         if self.reset_on_open:
             self.batch.reset(slot)
+        try:
+            self._set_slot_grammar(slot, gr_key)
+        finally:
+            if gr_key in self._gr_cache and self._gr_cache[gr_key]["uses"] == 0:   # (the set failed)
+                self.batch.release_grammar(self._gr_cache.pop(gr_key)["handle"])
         self._set_slot_decoder(slot, decoder)
         self._set_slot_rate(slot, sample_rate)
         self._set_slot_format(slot, fmt)
@@ -377,6 +399,93 @@ class StreamScheduler:
 
     def decoder(self, sid: int) -> str:
         return "ctc" if sid in self._ctc_sessions else "full"
+
+    # ---- a grammar per session ------------------------------
+    def _grammar_blob(self, source) -> bytes:
+        """``source`` as ``open(grammar=...)`` takes it -> a compiled blob: the blob itself (bytes), the path of a .scgr
+        file or of a text file with one phrase per line, or a list of phrases - each a list of token ids or a string,
+        tokenised by spotting.phrase_ids against the scheduler's token list"""
+        cfg = self.batch.cfg
+        if isinstance(source, (bytes, bytearray, memoryview)):
+            return bytes(source)
+        if isinstance(source, (str, os.PathLike)):
+            with open(source, "rb") as fh:
+                data = fh.read()
+            if data[:4] == b"SCGR":
+                return data
+            source = [ln.strip() for ln in data.decode("utf-8").splitlines() if ln.strip()]
+        phrases = []
+        for ph in source:
+            if isinstance(ph, str):
+                if self.token_list is None:
+                    raise ValueError("grammar: phrases given as text need the scheduler's token list")
+                ph = phrase_ids(ph, self.token_list)
+            phrases.append([int(t) for t in ph])
+        return grammar_mod.compile(phrases, cfg.vocab_size, cfg.blank_id)
+
+    def _set_slot_grammar(self, slot: int, key):
+        """the slot's grammar becomes the cached one ``key`` (None: none); the cache counts the slots that name an entry and
+        frees the device copy with the last"""
+        old = self._slot_gr.get(slot)
+        if old == key:
+            return
+        if key is not None and not hasattr(self.batch, "set_stream_grammar"):
+            raise NotImplementedError("grammar: this batch has no grammar-constrained CTC beam (set_stream_grammar)")
+        try:
+            self.batch.set_stream_grammar(slot, self._gr_cache[key]["handle"] if key is not None else None)
+        except RuntimeError as e:     # e.g. a slot that is never reset (strict_reference) and has audio buffered
+            raise ValueError(f"the grammar cannot be set on this stream: {e}") from e
+        if key is not None:
+            self._gr_cache[key]["uses"] += 1
+        self._slot_gr[slot] = key
+        if old is not None:
+            entry = self._gr_cache[old]
+            entry["uses"] -= 1
+            if entry["uses"] == 0:
+                self.batch.release_grammar(entry["handle"])
+                del self._gr_cache[old]
+
+    def _grammar_key(self, source):
+        """the cache entry of ``source`` (compiled and uploaded when it is new), by the blob's SHA-256"""
+        if self.ctc_beam is None:
+            raise ValueError("grammar needs the ctc_beam option (StreamScheduler(ctc_beam=...))")
+        if self.ctc_lm is not None:
+            raise ValueError("grammar: a grammar and a fused language model (ctc_lm) together are not served")
+        if not hasattr(self.batch, "grammar"):
+            raise NotImplementedError("grammar: this batch has no grammar-constrained CTC beam (set_stream_grammar)")
+        blob = self._grammar_blob(source)
+        key = hashlib.sha256(blob).hexdigest()
+        if key not in self._gr_cache:
+            try:
+                handle = self.batch.grammar(blob)
+            except NotImplementedError:
+                raise
+            except RuntimeError as e:
+                raise ValueError(f"grammar: {e}") from e
+            self._gr_cache[key] = {"handle": handle, "uses": 0, "walk": grammar_mod.Grammar(blob)}
+        return key
+
+    def set_grammar(self, sid: int, source):
+        """The grammar of a session that has not fed any audio yet (the Vosk ``config`` message arrives after the connection
+        is made): its CTC beam answers only from it; None: none.  ``source``: see ``open``.  ValueError for phrases that
+        cannot be compiled, without the ``ctc_beam`` option, with ``ctc_lm``, or once audio has been fed."""
+        if self._rate[sid].fed:
+            raise ValueError("the grammar of a session can only be set before its first audio")
+        slot = self._slot_of[sid]
+        if source is None:
+            self._set_slot_grammar(slot, None)
+            return
+        key = self._grammar_key(source)
+        try:
+            self._set_slot_grammar(slot, key)
+        finally:
+            if key in self._gr_cache and self._gr_cache[key]["uses"] == 0:   # (the set failed: nobody names the new entry)
+                self.batch.release_grammar(self._gr_cache.pop(key)["handle"])
+
+    def grammar(self, sid: int):
+        """the host walk (speechcatcher_amd.grammar.Grammar) of the session's grammar, None without one"""
+        key = self._slot_gr.get(self._slot_of[sid])
+        return self._gr_cache[key]["walk"] if key is not None else None
 
     @staticmethod
     def _check_format(format, channels, channel, scale) -> tuple:
@@ -461,6 +570,11 @@ class StreamScheduler:
         self._ctc_sessions.discard(sid)
         if self.reset_on_open:
             self.batch.reset(slot)
+        if self._slot_gr.get(slot) is not None:   # the session's grammar goes with it (the cache frees it with its last user)
+            try:
+                self._set_slot_grammar(slot, None)
+            except ValueError:                    # a slot that is never reset: it keeps the grammar until it is opened again
+                pass
         self._free.append(slot)
 
     @property
@@ -606,6 +720,13 @@ class StreamScheduler:
                 out[sid] = res
             if beams is not None:
                 nbest = self._ctc_nbest(sid, beams[slot], sides.get(slot))
+                gr_key = self._slot_gr.get(slot)
+                if gr_key is not None:   # the accept flags of the same entries (host arithmetic, no launch)
+                    flags = self.batch.ctc_beam_hyps_grammar([slot], self.ctc_beam[0])[slot]
+                    for e, (_, acc) in zip(nbest, flags):
+                        e["complete"] = bool(acc)
+                    if fin:              # a final: the complete entries first, each group in beam order
+                        nbest = [e for e in nbest if e["complete"]] + [e for e in nbest if not e["complete"]]
                 if fin and self.final_lm_eos and self.ctc_lm is not None and sid in self._ctc_sessions and nbest:
                     nbest = self._ctc_end_term(nbest)
                 # a decoder-free session: its results are the beam's entries, best first (a chunk the engine answers with
@@ -615,6 +736,8 @@ class StreamScheduler:
                 for k in ("alignment", "activity", "detections", "draft", "ahead", "level", "stable", "rescored"):
                     setattr(res, k, getattr(out[sid], k, None))
                 res.ctc_nbest = nbest
+                if gr_key is not None:
+                    res.grammar_complete = bool(nbest and nbest[0]["complete"])
                 if free and fin and self.align_final and len(res):
                     res.alignment = self._ctc_alignment(res)
                 out[sid] = res
@@ -849,7 +972,7 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
                        queue_depth: int = 1, token_alignment: bool = False, token_alternates: int = 0,
                        ctc_beam=None, ctc_only: bool = False, ctc_lm=None, lm_weight: float = 0.5,
                        word_bonus: float = 0.0, rescore_lm=None, rescore_weight: float = 0.5,
-                       rescore_bonus: float = 0.0) -> List[dict]:
+                       rescore_bonus: float = 0.0, ctc_grammar=None) -> List[dict]:
     """Decode the (start, end) sample ranges of one recording as PARALLEL streams
     of one batch instead of the reference's process pool over segments
     (speechcatcher/speechcatcher.py:474-497, chunk loop :574-592; SURVEY 8(f)
@@ -868,13 +991,19 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
     "score" is the fused total.  ``rescore_lm`` (C++ engine; not with ``ctc_only``): a packed n-gram model the final n-best
     list of every segment is rescored with and re-ranked by, </s> term included, at ``rescore_weight`` / ``rescore_bonus``
     (the scheduler's ``final_lm`` option): the segment's text is the fused best, "score" stays its search
-    score, "lm_score" / "fused_score" / "am_rank" say what the model added and which row of the search's list it was."""
+    score, "lm_score" / "fused_score" / "am_rank" say what the model added and which row of the search's list it was.
+    ``ctc_grammar`` (needs ``ctc_beam`` or ``ctc_only``; not with ``ctc_lm``): every segment's CTC beam answers only from
+    this grammar (``StreamScheduler.open(grammar=...)``); the entries of ``ctc_nbest`` carry "complete"."""
     token_alignment = token_alignment or token_alternates > 0
     if rescore_lm is not None and ctc_only:
         raise ValueError("rescore_lm re-ranks the n-best list of the attention decoder's search: not with ctc_only "
                          "(fuse the model into the CTC beam with ctc_lm)")
     if ctc_lm is not None and not (ctc_only or beam_mod.params(ctc_beam)):
         raise ValueError("ctc_lm: the model is fused into the CTC prefix beam search - it needs ctc_beam or ctc_only")
+    if ctc_grammar is not None and not (ctc_only or beam_mod.params(ctc_beam)):
+        raise ValueError("ctc_grammar: the grammar constrains the CTC prefix beam search - it needs ctc_beam or ctc_only")
+    if ctc_grammar is not None and ctc_lm is not None:
+        raise ValueError("ctc_grammar: a grammar and a fused language model (ctc_lm) together are not served")
     if ctc_only and token_alternates:
         raise ValueError("ctc_only: token alternates rank the frames of a forced alignment against a decode block's rows, "
                          "which a decoder-free stream does not have")
@@ -893,7 +1022,7 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
     while todo or sch.n_active:
         while todo and sch._free:
             idx, (a, b) = todo.pop(0)
-            sid = sch.open(decoder="ctc" if ctc_only else "full")
+            sid = sch.open(decoder="ctc" if ctc_only else "full", **({} if ctc_grammar is None else {"grammar": ctc_grammar}))
             sid_to_seg[sid] = idx
             seg = speech[a:b]
             for pos in range(0, len(seg), chunk_length):
@@ -922,7 +1051,7 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
                     out[idx] = {"text": "", "tokens": [], "token_ids": [], "token_timestamps": [],
                                 "score": 0.0, "start": start_s}
                 if sch.ctc_beam is not None:   # (a list of one n-best per segment: paragraphs append them)
-                    out[idx]["ctc_nbest"] = [[{k: e[k] for k in ("text", "score", "conf", "lm", "ctc_score") if k in e}
+                    out[idx]["ctc_nbest"] = [[{k: e[k] for k in ("text", "score", "conf", "lm", "ctc_score", "complete") if k in e}
                                               for e in (getattr(res, "ctc_nbest", None) or [])]]
                 if token_alignment:
                     al = getattr(res, "alignment", None) if res else None

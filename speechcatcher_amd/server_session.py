@@ -447,12 +447,15 @@ class ServerLoop:
                     if decoder not in ("full", "ctc"):
                         raise ValueError(f'decoder must be "full" or "ctc", got {decoder!r}')
                     max_alt = self._config_alternatives(ses, cfg, decoder)
+                    phrases, unk = self._config_phrases(cfg, decoder)
                 except (AttributeError, json.JSONDecodeError):
                     return vosk_partial("")
                 # honoured for every rate the engine converts (8000..48000 Hz: speechcatcher_amd.resample) and every
                 # wire format it decodes (speechcatcher_amd.pcm), before the session's first audio; ValueError
                 # otherwise - this client's error reply (step)
                 # - and both or neither: a rate whose format is refused does not stay
+                if phrases is not None:   # the session answers only from this list (StreamScheduler.set_grammar); it is
+                    self.sch.set_grammar(ses.sid, phrases)   # refused where the decoder would be: nothing has changed then
                 self.sch.set_decoder(ses.sid, decoder)   # (the first of the three: a refusal leaves nothing changed)
                 old_rate = self.sch.sample_rate(ses.sid)
                 self.sch.set_sample_rate(ses.sid, rate)
@@ -465,6 +468,8 @@ class ServerLoop:
                     ses.wire = wire
                 ses.vosk_sample_rate = int(rate)
                 ses.max_alternatives = max_alt
+                if unk:   # no garbage model: the entry is left out of the grammar, and the reply says so
+                    return dict(vosk_partial(""), ignored=["[unk]"])
                 return vosk_partial("")
         elif ses.wire is not None:                          # the session's bytes go to the engine as they are
             if isinstance(message, np.ndarray) and message.dtype.kind not in "iu" and not (
@@ -513,6 +518,24 @@ class ServerLoop:
         pcm_mod.check_args(fmt, channels, channel, scale)
         return (fmt, channels, channel, scale)
 
+    @staticmethod
+    def _config_phrases(cfg: dict, decoder: str):
+        """the ``phrase_list`` a Vosk ``config`` carries -> (its phrases without "[unk]" entries, whether one was left
+        out); (None, False) when the message names none.  ValueError for anything but a list of strings with a phrase
+        left, and on a connection that is not decoder-free: the grammar constrains the CTC beam, the blockwise search of
+        a FULL session has none."""
+        if "phrase_list" not in cfg:
+            return None, False
+        pl = cfg["phrase_list"]
+        if decoder != "ctc":
+            raise ValueError('phrase_list needs a decoder-free connection ("decoder": "ctc")')
+        if not isinstance(pl, list) or not all(isinstance(p, str) for p in pl):
+            raise ValueError("phrase_list must be a list of strings")
+        phrases = [p for p in pl if p.strip() != "[unk]"]
+        if not any(p.strip() for p in phrases):
+            raise ValueError("phrase_list holds no phrase")
+        return [p for p in phrases if p.strip()], len(phrases) != len(pl)
+
     def _config_alternatives(self, ses: _Session, cfg: dict, decoder: str = "full") -> int:
         """the ``max_alternatives`` a Vosk ``config`` asks for, at most ``vosk_alternatives`` - for a decoder-free session
         at most the beam's B - (the session's own when the message names none; 0 with the option off); ValueError for
@@ -527,7 +550,21 @@ class ServerLoop:
 
     def _final_message(self, ses: _Session, results: list) -> dict:
         """the Vosk final of a reply with results: the classic {"result", "text"}, or {"alternatives": [...]} for a
-        session that asked for them; with ``token_alternates`` the first hypothesis' entries carry their token records"""
+        session that asked for them; with ``token_alternates`` the first hypothesis' entries carry their token records.
+        A session with a ``phrase_list``: the text is the best COMPLETE entry's (the scheduler lists those first); when
+        none is complete the text is empty and the best entry's goes out under "incomplete"; alternatives carry
+        "complete"."""
+        msg = self._final_message_plain(ses, results)
+        complete = getattr(results, "grammar_complete", None)
+        if complete is None:
+            return msg
+        if "alternatives" in msg:
+            for a, r in zip(msg["alternatives"], results):
+                a["complete"] = bool(r[4].get("complete")) if len(r) > 4 and isinstance(r[4], dict) else bool(complete)
+            return msg
+        return msg if complete else {"result": [], "text": "", "incomplete": msg["text"]}
+
+    def _final_message_plain(self, ses: _Session, results: list) -> dict:
         _text, tokens, _ids, pos, _hyp = results[0]
         al = getattr(results, "alignment", None)
         records = al.get("alternates") if self.token_alternates and al is not None else None
