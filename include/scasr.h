@@ -1081,7 +1081,10 @@ int sc_dec_layer_self(const sc_search *sb, int layer, const float *x_in, float *
  * encoder K|V (decoder_layer.py:106-115); ph2 = per-head partial of src_attn.linear_out. */
 int sc_dec_layer_cross(const sc_search *sb, int layer, const float *x_in, float *x_out, void *stream);
 /* C: x = x_in + bo2 + sum_h ph2 -> x_out; feed-forward of norm3(x) (decoder_layer.py:117-123,
- * feed_forward.py:48-50) as partial sums ffn_part[z][row], z < *n_part (HOST out; <= max_part). */
+ * feed_forward.py:48-50) as partial sums ffn_part[z][row], z < *n_part (HOST out; <= max_part).  *n_part is F/128 or
+ * F/256 (aligned pairs of chunks; always pairs when F/128 is even and > 16): with fp32 partial sums either gives the same
+ * bits behind the consumer's tree and the row count picks; with fp16 partial sums (act_half & 2), which are rounded at the
+ * store, it is F/256 whenever F/128 is even - a function of F alone. */
 int sc_dec_layer_ffn(const sc_search *sb, int layer, const float *x_in, float *x_out, float *ffn_part,
                      int max_part, int *n_part /*HOST*/, void *stream);
 /* ---- stream-resident decoder layers: 2 launches per layer (round 6; decoder_layer.py:80-132) -------------------

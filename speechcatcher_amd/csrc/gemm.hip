@@ -1827,6 +1827,11 @@ extern "C" int sc_dec_layer_ffn(const sc_search *sbp, int layer, const float *xi
     //  the consumers' batches of 8 are a balanced tree over the chunk index for up to 16 partials only: a model with
     // linear_units > 2048 always takes aligned pairs, so that the shape - and with it the order - never depends on the row count
     if (nch > 16 && nch % 2 == 0 && cpw != 2) continue;
+    // fp16 partial sums (sc_search.act_half & 2) are rounded where they are STORED: an aligned pair summed here and rounded
+    // once is not the two rounded chunks whose sum the consumer's tree takes, so no order of summation makes cpw invisible
+    // there - the shape itself must not depend on the row count: aligned pairs whenever F/128 is even, the shape the cost
+    // model takes at the full buckets this mode is for (the mode's bits and speed there are what they were)
+    if ((sb.act_half & 2) && nch % 2 == 0 && cpw != 2) continue;
     const int ngrp = nch / cpw;
     for (int rtt = 1; rtt <= ffn_rtt_max(D, wf); ++rtt) {
       const long wgs = (long)ngrp * ((M + 16 * rtt - 1) / (16 * rtt));

@@ -19,7 +19,22 @@ feed-forward.  The error of the projected q is NOT carried into the scores: as a
 and 256-term products it is ~50 times what any fp32 evaluation shows (kv_new, the same projection, needs kappa 0.05 - 0.4), and
 amplified by max|k| it left the partial products a kappa of 1e-4 - 1e-2, where a wrong reference could hide; it is part of kappa.
 The constant kappa is NOT chosen here: the CPU test measures the kappa that the fp32 torch spec needs per family and output
-(kappa_ref), and the GPU test allows a kernel 4 x kappa_ref."""
+(kappa_ref), and the GPU test allows a kernel 4 x kappa_ref.
+
+FP16 DECODER MODE (Case(dec_half = sc_search.act_half: 1, 2 or 3; kinds "self" and "cross"; fp16 K|V caches).  Where the
+kernel (csrc/decoder_layer.hip: dec_layer_attn_kernel<.., WH>) rounds, and what E gains (r(a) = max(2^-11 |a|, 2^-25)):
+  bit 1  the *_pph weights are fp16 numbers (the reference takes them as given); the LayerNorm row is rounded to fp16 on its way
+         from LDS into the projection's MFMA, the context on its way into the output projection: sum |w| r(a) per product sum.
+         The error dq of the projected q that comes from THIS rounding (not its fp32 part, see above) is carried into the
+         scores: with Ds = max over the attended keys of sum_j (dq_j |k_j| + |q_j| dk_j) / sqrt(dk) (dk: the new token's own
+         key only, cached rows are inputs) every p moves by a factor within exp(+-2 Ds), so a context element gains
+         expm1(2 Ds) sum_i p_i |v_ic| + p_own dv_c.  q, the scores, the softmax and all accumulators stay fp32;
+  bit 2  ph1 / ph2 / ffn_part hold fp16 elements in the first half of their buffers: what the launch reads is taken as given
+         (the cases write fp16 numbers); a stored partial product is rounded once, at the store, AFTER the sum over the heads
+         of a workgroup (one head, or four): r(p) per stored partial.
+SpecBackend has no such mode: kappa_ref of these cases is the kappa a numpy TRANSCRIPTION of this arithmetic needs (fp32
+k-ordered chains over the rounded operands, an fp32 softmax, the head partials summed per workgroup and rounded at the store).
+The cases are a reduced set: families flat and dominant, cached lengths 16, 17, 128, 129, cross T 16, 17, 129."""
 import dataclasses
 import functools
 import math
@@ -109,6 +124,36 @@ def stream_plan(family, W):
         out.append(Stream(s, 1, i % 2, T, Lc + 1, nhs[i], kind, fork, variant))
     out.insert(INACTIVE, Stream(INACTIVE, 0, 0, 100, 40, W))
     return out
+
+
+HALF_LC, HALF_T = (16, 17, 128, 129), (16, 17, 129)
+HALF_FAMILIES = ("flat", "dominant")
+HALF_DOMINANT = ("first", "last", "wave1", "wave2", "own", "last", "wave3")      # by live stream; wave1.. only where they exist
+
+
+def half_stream_plan(family, W):
+    """the reduced set of the fp16 decoder mode: L - 1 over HALF_LC, T over HALF_T, the nh and ancestries of stream_plan"""
+    f = FAMILIES.index(family)
+    nhs = [W, 1, 3, W, max(W - 1, 1), 2, W]
+    out = []
+    for i, s in enumerate(LIVE):
+        Lc, T = HALF_LC[(i + f) % 4], HALF_T[(i + 2 * f) % 3]
+        variant = ""
+        if family == "dominant":
+            variant = HALF_DOMINANT[i]
+            if PLACE.get(variant, 0) >= min(Lc, T):
+                variant = "last"
+        kind = ("shared", "fork", "divergent")[(f + i) % 3]
+        fork = (max(Lc - 3, 0), (Lc // 16) * 16, min(5, Lc))[i % 3] if kind == "fork" else -1
+        out.append(Stream(s, 1, i % 2, T, Lc + 1, nhs[i], kind, fork, variant))
+    out.insert(INACTIVE, Stream(INACTIVE, 0, 0, 100, 40, W))
+    return out
+
+
+def _r16(x):
+    """r(x) = max(2^-11 |x|, 2^-25), r(0) = 0: the rounding of a value to fp16"""
+    x = np.abs(x)
+    return np.where(x == 0, 0.0, np.maximum(2.0 ** -11 * x, 2.0 ** -25))
 
 
 def build_ancestry(st, kv_rows, rng):
@@ -255,17 +300,24 @@ class Case:
     """One launch: inputs (fp32 tensors shaped like the batch's buffers), the float64 reference of every output with its A,
     and what must stay as it was.  kind: "attn" (stand-alone self + cross on one set of buffers), "self", "cross", "stream"."""
 
-    def __init__(self, geom, W, kind, family, half=False, li=1, npart=1, hpw=1, seed=0):
+    def __init__(self, geom, W, kind, family, half=False, li=1, npart=1, hpw=1, seed=0, dec_half=0):
         sc = spec_batch(geom, W)
         cfg = sc.cfg
         self.geom, self.kind, self.family, self.half, self.li, self.npart, self.hpw = geom, kind, family, half, li, npart, hpw
+        # fp16 decoder mode (sc_search.act_half): bit 1 fp16 projection weights / MFMA inputs, bit 2 fp16 partial products
+        assert not dec_half or (half and kind in ("self", "cross") and dec_half in (1, 2, 3))
+        self.dec_half, self.wh, self.part_half, self._t = dec_half, bool(dec_half & 1), bool(dec_half & 2), {}
         self.W, self.d, self.H = sc.W, cfg.d_model, cfg.dec_heads
         self.dk, self.nl, self.kv_rows = self.d // self.H, cfg.dec_layers, int(sc.kv_rows)
         self.eps, self.V = cfg.ln_eps, cfg.vocab_size
         self.w = _weights(sc)
-        rng = self.rng = np.random.default_rng([seed, FAMILIES.index(family), self.W, self.dk, int(half), li, npart])
+        if self.wh:                      # the *_pph copies: fp16 numbers, the operands of the form
+            self.w = dict(self.w, dec=[dict(lw, **{k: f16(lw[k]).astype(np.float64) for k in ("wqkv", "wq", "wo", "wo2")})
+                                       for lw in self.w["dec"]])
+        rng = self.rng = np.random.default_rng([seed, FAMILIES.index(family), self.W, self.dk, int(half), li, npart] +
+                                               ([dec_half] if dec_half else []))
         W, d, n = self.W, self.d, S * self.W
-        self.streams = stream_plan(family, W)
+        self.streams = half_stream_plan(family, W) if dec_half else stream_plan(family, W)
         f32 = np.float32
         nan = lambda *shape: np.full(shape, np.nan, f32)   # noqa: E731
         self.ctrl = np.array([[st.active, st.cur, 0, st.T, st.L, st.nh, 0, 0] for st in self.streams], np.int32)
@@ -331,15 +383,16 @@ class Case:
         if self.kind == "cross":
             self._keep(st, "xout", x, Ax)
             xn, Axn = layer_norm_ref(x, Ax, lw["ln2_g"], lw["ln2_b"], self.eps)
-            ctx2, Actx2 = self._cross_attention(st, linear_ref(xn[:nh], Axn[:nh], lw["wq"], lw["bq"])[0])
-            self._keep(st, "ph2", *head_partials_ref(ctx2, Actx2, lw["wo2"], self.H, self.hpw))
+            qc, _, Dq = self._proj(xn[:nh], Axn[:nh], lw["wq"], lw["bq"])
+            ctx2, Actx2 = self._cross_attention(st, qc, Dq)
+            self._keep(st, "ph2", *self._head_partials(ctx2, Actx2, lw["wo2"]))
             return
         xn, Axn = layer_norm_ref(x, Ax, lw["ln1_g"], lw["ln1_b"], self.eps)
-        qkv, Aqkv = linear_ref(xn[:nh], Axn[:nh], lw["wqkv"], lw["bqkv"])
-        ctx, Actx = self._self_attention(st, qkv, Aqkv)
+        qkv, Aqkv, Dqkv = self._proj(xn[:nh], Axn[:nh], lw["wqkv"], lw["bqkv"])
+        ctx, Actx = self._self_attention(st, qkv, Aqkv, Dqkv)
         if self.kind == "self":
             self._keep(st, "xout", x, Ax)
-            self._keep(st, "ph1", *head_partials_ref(ctx, Actx, lw["wo"], self.H, self.hpw))
+            self._keep(st, "ph1", *self._head_partials(ctx, Actx, lw["wo"]))
             return
         # stream-resident form: residual of the self-attention block, norm2, q, cross-attention, residual, norm3
         x1, Ax1 = self._residual(x, Ax, ctx, Actx, lw["wo"], lw["bo"], nh)
@@ -348,6 +401,41 @@ class Case:
         x2, Ax2 = self._residual(x1, Ax1, ctx2, Actx2, lw["wo2"], lw["bo2"], nh)
         self._keep(st, "xout", x2, Ax2)
         self._keep(st, "xn_out", *layer_norm_ref(x2, Ax2, lw["ln3_g"], lw["ln3_b"], self.eps))
+
+    def _proj(self, xn, Axn, W, b):
+        """LayerNorm rows . W^T + b -> (y, A, D); fp16 decoder mode: D = sum |w| r(xn), the rounding of the rows on their way
+        into the MFMA (in the units of y; also part of A), else None"""
+        y, A = linear_ref(xn, Axn, W, b)
+        if not self.wh:
+            return y, A, None
+        D = _r16(xn) @ np.abs(W).T
+        return y, A + D / EPS, D
+
+    def _head_partials(self, ctx, Actx, Wo):
+        """head_partials_ref + the fp16 mode's terms: the context rounded on its way into the output projection (bit 1), the
+        partial product of a workgroup's heads rounded once at the store (bit 2)"""
+        ph, A = head_partials_ref(ctx, Actx, Wo, self.H, self.hpw)
+        if self.wh:
+            for h in range(self.H):
+                c = slice(h * self.dk, (h + 1) * self.dk)
+                A[:, h // self.hpw] += _r16(ctx[:, c]) @ np.abs(Wo[:, c]).T / EPS
+        if self.part_half:
+            A = A + _r16(ph) / EPS
+        return ph, A
+
+    def _score_terms(self, q, K, V, Dq, dk, Dk_own=None, Dv_own=None):
+        """fp16 decoder mode: what a context element gains from the rounding error of the projected q (and of the new token's
+        own k, v), in units of 2^-24 (see the module docstring); q [nh][H][dk], K, V [nh][n][H][dk], own row last"""
+        s = np.einsum("hgd,hngd->hgn", q, K) / math.sqrt(dk)
+        p = np.exp(s - s.max(-1, keepdims=True))
+        p /= p.sum(-1, keepdims=True)
+        ds = np.einsum("hgd,hngd->hgn", Dq, np.abs(K)) / math.sqrt(dk)
+        if Dk_own is not None:
+            ds[..., -1] += np.einsum("hgd,hgd->hg", np.abs(q), Dk_own) / math.sqrt(dk)
+        extra = np.expm1(2.0 * ds.max(-1))[:, :, None] * np.einsum("hgn,hngd->hgd", p, np.abs(V))
+        if Dv_own is not None:
+            extra = extra + p[..., -1][:, :, None] * Dv_own
+        return extra.reshape(q.shape[0], -1) / EPS
 
     @staticmethod
     def _residual(x, Ax, ctx, Actx, Wo, bo, nh):
@@ -365,18 +453,24 @@ class Case:
         if self.kind != "cross" and li == 0:
             tok = self.yseq[st.cur, st.s, np.minimum(np.arange(W), st.nh - 1), st.L - 1]
             e, pe = w["embed"][tok], w["pe"][st.L - 1]
+            self._t[st.s] = dict(x=(e * math.sqrt(d) + pe).astype(np.float32))
             return e * math.sqrt(d) + pe, np.abs(e) * math.sqrt(d) + np.abs(pe)
         xin = self._r32(W, d, scale=2.0)
         self.inputs["dx"][rows] = xin
         if self.kind == "cross":         # per-head partial products of the self-attention's output projection
             nph = H // self.hpw
             part = self._r32(W, nph, d, scale=0.5)
+            if self.part_half:
+                part = f16(part)
             self.inputs["ph1"].reshape(-1)[:S * W * nph * d].reshape(S * W, nph, d)[rows] = part
             part, bias = part.transpose(1, 0, 2), w["dec"][li]["bo"]
         else:                            # split sums of the previous layer's feed-forward
             part = self._r32(self.npart, W, d, scale=0.5)
+            if self.part_half:
+                part = f16(part)
             self.inputs["ffn_part"][:self.npart, rows] = part
             bias = w["dec"][li - 1]["b2"]
+        self._t[st.s] = dict(xin=xin, part=part.copy(), bias=bias)
         part = part.astype(np.float64)
         return xin + (part.sum(0) + bias), np.abs(xin) + np.abs(part).sum(0) + np.abs(bias)
 
@@ -390,7 +484,7 @@ class Case:
         assert np.isfinite(kv).all()
         return kv
 
-    def _self_attention(self, st, qkv, Aqkv):
+    def _self_attention(self, st, qkv, Aqkv, Dqkv=None):
         """cached rows through the ancestor table + the new token's own row.  qkv [nh][3d] (float32 inputs or the float64
         projection, Aqkv its A); writes the cached rows into skv; keeps kv_new (and self_ctx, stand-alone)"""
         rng, d, H, dk, li = self.rng, self.d, self.H, self.dk, self.li
@@ -419,13 +513,16 @@ class Case:
         Kh = np.concatenate([kv[:, :, :d].transpose(1, 0, 2).reshape(nh, Lc, H, dk), kn[:, None]], 1)
         Vh = np.concatenate([kv[:, :, d:].transpose(1, 0, 2).reshape(nh, Lc, H, dk), vn[:, None]], 1)
         ctx, Actx = attention_ref(q, Kh, Vh, dk)
+        if Dqkv is not None:
+            Dq, Dk, Dv = (Dqkv[:, i * d:(i + 1) * d].reshape(nh, H, dk) for i in range(3))
+            Actx = Actx + self._score_terms(q, Kh, Vh, Dq, dk, Dk, Dv)
         knv = np.concatenate([kn.reshape(nh, d), vn.reshape(nh, d)], 1)
         self._keep(st, "kv_new", knv, np.abs(knv) if Aqkv is None else Aqkv[:, d:])
         if self.kind == "attn":
             self._keep(st, "self_ctx", ctx, Actx)
         return ctx, Actx
 
-    def _cross_attention(self, st, qc):
+    def _cross_attention(self, st, qc, Dq=None):
         """the T frames of the stream, shared by its hypotheses; qc [nh][d]; writes ckv; keeps cross_ctx (stand-alone)"""
         rng, d, H, dk, nh, T = self.rng, self.d, self.H, self.dk, st.nh, st.T
         qx = np.asarray(qc, np.float64).reshape(nh, H, dk)
@@ -440,6 +537,8 @@ class Case:
         Kx = np.broadcast_to(kv[None, :, :d].reshape(1, T, H, dk), (nh, T, H, dk))
         Vx = np.broadcast_to(kv[None, :, d:].reshape(1, T, H, dk), (nh, T, H, dk))
         ctx, Actx = attention_ref(qx, Kx, Vx, dk)
+        if Dq is not None:
+            Actx = Actx + self._score_terms(qx, Kx, Vx, Dq.reshape(nh, H, dk), dk)
         if self.kind == "attn":
             self._keep(st, "cross_ctx", ctx, Actx)
         return ctx, Actx
@@ -454,9 +553,18 @@ class Case:
         sb.skv.copy_(t(self.skv.reshape(-1, 2 * self.d)).to(sb.skv.dtype))
         sb.ckv.copy_(t(self.ckv.reshape(-1, 2 * self.d)).to(sb.ckv.dtype))
         for name, a in self.inputs.items():
+            if self.part_half and name in ("ph1", "ffn_part"):     # fp16 elements at the same element offsets; the rest NaN
+                h = np.full(2 * a.size, np.nan, np.float16)
+                h[:a.size] = a.reshape(-1).astype(np.float16)
+                a = h.view(np.float32).reshape(a.shape)
             getattr(sb, name).copy_(t(a))
         for name in self.outputs():
-            getattr(sb, name).fill_(SENTINEL)
+            self._elems(sb, name).fill_(SENTINEL)
+
+    def _elems(self, sb, name):
+        """a buffer as the flat array of its ELEMENTS: fp16 ones for the partial products of the fp16 decoder mode"""
+        buf = getattr(sb, name).view(-1)
+        return buf.view(torch.float16) if self.part_half and name in ("ph1", "ph2") else buf
 
     def outputs(self):
         """buffers the launch writes (besides the K|V append): all start as the sentinel"""
@@ -476,7 +584,7 @@ class Case:
                 out[st.s] = (sb.dxn if name == "xout" else sb.dq)[rows].cpu().double().numpy()
             elif name in ("ph1", "ph2"):
                 nph = H // self.hpw
-                buf = getattr(sb, name).view(-1)[:S * W * nph * d].view(S * W, nph, d)
+                buf = self._elems(sb, name)[:S * W * nph * d].view(S * W, nph, d)
                 out[st.s] = buf[rows][:st.nh].cpu().double().numpy()
             elif name == "kv_new":
                 pool = sb.skv.view(S, self.nl, self.kv_rows, 2 * d)[st.s, self.li]
@@ -506,8 +614,8 @@ class Case:
             ina = flat[INACTIVE * W:(INACTIVE + 1) * W]
             if name in ("ph1", "ph2"):
                 nph = H // self.hpw
-                used = buf.view(-1)[:S * W * nph * d].view(S * W, nph * d)
-                rest = buf.view(-1)[S * W * nph * d:]
+                used = self._elems(sb, name)[:S * W * nph * d].view(S * W, nph * d)
+                rest = self._elems(sb, name)[S * W * nph * d:]
                 ina = used[INACTIVE * W:(INACTIVE + 1) * W]
                 if rest.numel() and not bool((rest == SENTINEL).all()):
                     bad.append(f"{name}: more than H / {self.hpw} partial slots per row written")
@@ -534,6 +642,96 @@ class Case:
         if not torch.equal(after.view(it), before.view(it)):
             bad.append("skv: an element outside the new tokens' rows changed")
         return bad
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the fp32 transcription of a fused launch (kappa_ref of the fp16 decoder mode; it runs on an fp32 case too)
+def _chain32(a, W):
+    """[M][K] . [N][K]^T, one k-ordered fp32 chain per element (dense_ref.chain32)"""
+    a64, W64 = a.astype(np.float64), W.astype(np.float64)
+    acc = np.zeros((a.shape[0], W.shape[0]), np.float32)
+    for k in range(a.shape[1]):
+        acc = (acc + a64[:, k, None] * W64[None, :, k]).astype(np.float32)
+    return acc
+
+
+def _ln32(x, g, b, eps):
+    x = x.astype(np.float32)
+    n = np.float32(x.shape[-1])
+    xc = x - x.sum(-1, keepdims=True, dtype=np.float32) / n
+    rstd = np.float32(1.0) / np.sqrt((xc * xc).sum(-1, keepdims=True, dtype=np.float32) / n + np.float32(eps))
+    return xc * rstd * g.astype(np.float32) + b.astype(np.float32)
+
+
+def transcription(case):
+    """name -> {stream: rows} of a "self" / "cross" case in fp32 arithmetic, rounded where the form rounds"""
+    assert case.kind in ("self", "cross")
+    f32 = np.float32
+    d, H, dk, W, li = case.d, case.H, case.dk, case.W, case.li
+    lw = case.w["dec"][li]
+    rnd = f16 if case.wh else (lambda a: np.asarray(a, f32))
+    out = {}
+    for st in case.streams:
+        if not st.active:
+            continue
+        nh, t = st.nh, case._t[st.s]
+        if "x" in t:
+            x = t["x"]
+        else:
+            part = t["part"].astype(f32)
+            if case.kind == "cross" and part.shape[0] == H and H >= 4:       # one partial per head: aligned groups of four
+                y = None
+                for g in range(0, H, 4):
+                    s4 = ((part[g] + part[g + 1]) + part[g + 2]) + part[g + 3]
+                    y = s4 if y is None else y + s4
+            elif case.kind == "cross":
+                y = part[0]
+                for z in range(1, part.shape[0]):
+                    y = y + part[z]
+            else:                                                            # split sums: trees of eight, in order
+                y = None
+                for z0 in range(0, part.shape[0], 8):
+                    p8 = list(part[z0:z0 + 8]) + [np.zeros_like(part[0])] * (8 - len(part[z0:z0 + 8]))
+                    t8 = ((p8[0] + p8[1]) + (p8[2] + p8[3])) + ((p8[4] + p8[5]) + (p8[6] + p8[7]))
+                    y = t8 if y is None else y + t8
+            x = t["xin"] + (y + t["bias"].astype(f32))
+        ln = "ln2" if case.kind == "cross" else "ln1"
+        xn = _ln32(x, lw[ln + "_g"], lw[ln + "_b"], case.eps)[:nh]
+        Wp, bp = (lw["wq"], lw["bq"]) if case.kind == "cross" else (lw["wqkv"], lw["bqkv"])
+        y = _chain32(rnd(xn), Wp.astype(f32)) + bp.astype(f32)
+        q = (y[:, :d] / f32(math.sqrt(dk))).reshape(nh, H, dk)
+        if case.kind == "cross":
+            kv = case.ckv[st.s, li, :st.T].astype(f32)
+            K = np.broadcast_to(kv[None, :, :d].reshape(1, st.T, H, dk), (nh, st.T, H, dk))
+            V = np.broadcast_to(kv[None, :, d:].reshape(1, st.T, H, dk), (nh, st.T, H, dk))
+        else:
+            Lc = st.L - 1
+            kv = case.skv[st.s, li].astype(f32)[st.anc[:Lc]]                  # [Lc][nh][2d]
+            kn, vn = y[:, d:2 * d].reshape(nh, 1, H, dk), y[:, 2 * d:].reshape(nh, 1, H, dk)
+            K = np.concatenate([kv[:, :, :d].transpose(1, 0, 2).reshape(nh, Lc, H, dk), kn], 1)
+            V = np.concatenate([kv[:, :, d:].transpose(1, 0, 2).reshape(nh, Lc, H, dk), vn], 1)
+        s = np.einsum("hgd,hngd->hgn", q, K).astype(f32)
+        p = np.exp(s - s.max(-1, keepdims=True)).astype(f32)
+        ctx = (np.einsum("hgn,hngd->hgd", p, V).astype(f32) / p.sum(-1, dtype=f32)[:, :, None]).reshape(nh, d)
+        Wo = (lw["wo2"] if case.kind == "cross" else lw["wo"]).astype(f32)
+        ph = np.zeros((nh, H // case.hpw, d), f32)
+        for h in range(H):
+            c = slice(h * dk, (h + 1) * dk)
+            o = _chain32(rnd(ctx[:, c]), Wo[:, c])
+            ph[:, h // case.hpw] = o if h % case.hpw == 0 else ph[:, h // case.hpw] + o
+        if case.part_half:
+            ph = f16(ph)
+        out.setdefault("xout", {})[st.s] = x
+        out.setdefault("ph2" if case.kind == "cross" else "ph1", {})[st.s] = ph
+        if case.kind == "self":
+            out.setdefault("kv_new", {})[st.s] = y[:, d:]
+    return out
+
+
+def transcription_kappas(case):
+    """kappa_ref of an fp16-decoder-mode case: the kappa the transcription needs, per output"""
+    t = transcription(case)
+    return {name: max(kappa(rows[s], case.ref[name][s], case.A[name][s]) for s in rows) for name, rows in t.items()}
 
 
 def validity_problems(case):

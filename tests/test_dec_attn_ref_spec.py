@@ -77,6 +77,65 @@ def test_stream_resident_reference_against_the_spec(capsys):
               "; ".join(f"{f} " + " ".join(f"{n} {v:.3g}" for n, v in k.items()) for f, k in rep.items()))
 
 
+# fp16 decoder mode: (geometry, beam, act_half) - all three settings at XL beam 10, the whole mode at head dim 64 and at beam 5
+HALF_GEOMS = [("XL", 10, 1), ("XL", 10, 2), ("XL", 10, 3), ("L_LIKE", 10, 3), ("XL", 5, 3)]
+
+
+def half_cases(geom, W, kind, dec_half):
+    """the reduced case set of the fp16 decoder mode: families flat and dominant, one and (XL, beams <= 10) four heads per
+    workgroup; the layer / partial-sum variant rotates"""
+    for f, fam in enumerate(dr.HALF_FAMILIES):
+        for hpw in (1, 4) if geom == "XL" and W <= 10 else (1,):
+            li, npart = dr.layer_variant(f + hpw + dec_half)
+            yield dr.Case(geom, W, kind, fam, half=True, li=li if kind == "self" else 1, npart=npart, hpw=hpw, dec_half=dec_half)
+
+
+@pytest.mark.parametrize("kind", ["self", "cross"])
+@pytest.mark.parametrize("geom,W,dec_half", HALF_GEOMS)
+def test_fp16_decoder_mode_references_against_their_transcription(geom, W, dec_half, kind, capsys):
+    """SpecBackend has no fp16 mode: kappa_ref of these cases is the kappa the fp32 transcription of the documented arithmetic
+    needs (dec_attn_ref.transcription).  The transcription itself is held to the spec where both exist: on the same cases with
+    the mode off it needs what the spec needs, within the cap.  Then the planted mistake: fp16 partial products read as fp32"""
+    rep = {}
+    for case in half_cases(geom, W, kind, dec_half):
+        assert not dr.validity_problems(case)
+        k = dr.transcription_kappas(case)
+        for name, v in k.items():
+            assert math.isfinite(v) and 0 < v <= KAPPA_MAX, (case.family, case.hpw, name, v)
+        rep[(case.family, case.hpw)] = k
+        off = dr.Case(geom, W, kind, case.family, half=True, li=case.li, npart=case.npart, hpw=case.hpw)
+        k0, ks = dr.transcription_kappas(off), dr.spec_kappas(off)
+        for name, v in k0.items():
+            assert math.isfinite(v) and v <= KAPPA_MAX and ks[name] <= KAPPA_MAX, (case.family, case.hpw, name, v, ks[name])
+    with capsys.disabled():
+        print(f"\ntranscription kappa, dec_layer_{kind} {geom} beam {W} act_half {dec_half}: " +
+              "; ".join(f"{f} hpw{h} " + " ".join(f"{n} {v:.3g}" for n, v in k.items()) for (f, h), k in rep.items()))
+
+
+def test_fp16_decoder_mode_cases_cover_the_reduced_set():
+    Lc, T = set(), set()
+    for fam in dr.HALF_FAMILIES:
+        plan = dr.half_stream_plan(fam, 10)
+        assert not plan[dr.INACTIVE].active and {st.nh for st in plan if st.active} >= {1, 3, 10}
+        for st in plan:
+            if st.active:
+                Lc.add(st.L - 1), T.add(st.T)
+                assert dr.PLACE.get(st.variant, 0) < min(st.L - 1, st.T)
+    assert Lc == set(dr.HALF_LC) == {16, 17, 128, 129} and T == set(dr.HALF_T) == {16, 17, 129}
+    # the mode changes what is written, not only what is allowed: fp16 weights, fp16 partial inputs
+    case = next(half_cases("XL", 10, "cross", 3))
+    assert (case.inputs["ph1"][np.isfinite(case.inputs["ph1"])] == dr.f16(case.inputs["ph1"][np.isfinite(case.inputs["ph1"])])).all()
+    wq = case.w["dec"][1]["wq"]
+    assert (wq == dr.f16(wq)).all() and not (dr._weights(dr.spec_batch("XL", 10))["dec"][1]["wq"] == wq).all()
+    # a planted mistake: the head partials of a four-head launch rounded per head instead of once per workgroup is a
+    # reordering of roundings that kappa cannot see; one that drops the rounding of the context is closer to exact; what kappa
+    # does see is a partial product read in the wrong precision
+    t = dr.transcription(case)
+    s = next(iter(t["ph2"]))
+    wrong = t["ph2"][s].astype(np.float16).view(np.uint16).astype(np.float32)          # the fp16 bits taken for numbers
+    assert dr.kappa(wrong, case.ref["ph2"][s], case.A["ph2"][s]) > 4 * dr.transcription_kappas(case)["ph2"]
+
+
 def test_cases_cover_the_lengths_forms_and_patterns():
     """every length of the issue's lists, an inactive stream, nh = 1 and 1 < nh < W in every launch, the three ancestries, a fork
     on the 512 edge / a tile edge / inside a tile, and the dominant key at every place"""

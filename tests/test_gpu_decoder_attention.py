@@ -18,7 +18,7 @@ import pytest
 import torch
 
 import dec_attn_ref as dr
-from test_dec_attn_ref_spec import ATTN_GEOMS, FUSED_GEOMS
+from test_dec_attn_ref_spec import ATTN_GEOMS, FUSED_GEOMS, HALF_GEOMS, half_cases
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -30,10 +30,11 @@ def hip():
     return HipBackend(DEV)
 
 
-def _gpu_batch(hip, geom, W, half):
+def _gpu_batch(hip, geom, W, half, dec_half=False):
     from test_engine_spec import make_batch
     return make_batch(dr.cfg_name(geom), 1234, "meanstd", W, False, backend=hip, device=DEV,
-                      kv_dtype="float16" if half else "float32", **dr.batch_kwargs(W))
+                      kv_dtype="float16" if half else "float32", dec_dtype="float16" if dec_half else "float32",
+                      **dr.batch_kwargs(W))
 
 
 def _bits(sb, case):
@@ -142,6 +143,27 @@ def test_fused_layer_kernels_against_float64(hip, monkeypatch, capsys, geom, W, 
                 bad.append((fam, f"hpw{hpw}", "SC_ATTN_DEEP = 0 and 1 differ in bits"))
             rows.append((f"{fam} hpw{hpw}", kref, ks))
     _report(capsys, f"dec_layer_{kind} {geom} beam {W} {'fp16' if half else 'fp32'} K|V (kernel: deep 0 / deep 1)", rows, bad)
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("kind", ["self", "cross"])
+@pytest.mark.parametrize("geom,W,dec_half", HALF_GEOMS)
+def test_fused_layer_kernels_in_fp16_decoder_mode(hip, monkeypatch, capsys, geom, W, dec_half, kind):
+    """sc_dec_layer_self / sc_dec_layer_cross with the *_pph weights and fp16 partial products (SC_ACT_HALF = 1, 2, 3; fp16 K|V):
+    the reduced case set of dec_attn_ref against float64 at 4 x the kappa the transcription of the mode's arithmetic needs;
+    the same checks of what must stay untouched, on the fp16 elements of ph1 / ph2"""
+    sg = _gpu_batch(hip, geom, W, True, dec_half=True)
+    monkeypatch.setenv("SC_ACT_HALF", str(dec_half))
+    sg._sc_search_struct = None                      # (the search struct carries act_half)
+    assert hip.search_struct(sg).act_half == dec_half
+    monkeypatch.setenv("SC_ATTN_DEEP", "0")
+    bad, rows = [], []
+    for case in half_cases(geom, W, kind, dec_half):
+        kref = dr.transcription_kappas(case)
+        monkeypatch.setenv("SC_DEC_HPW", str(case.hpw))
+        k, _ = _run(hip, sg, case, kref, None, (case.family, f"hpw{case.hpw}", f"layer {case.li} npart {case.npart}"), bad)
+        rows.append((f"{case.family} hpw{case.hpw}", kref, [k]))
+    _report(capsys, f"dec_layer_{kind} {geom} beam {W} act_half {dec_half} (fp16 decoder mode)", rows, bad)
     assert not bad, bad
 
 
