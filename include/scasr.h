@@ -792,6 +792,98 @@ typedef struct sc_lm_rescore_job {
  * unknown flags) writes nothing.  Two jobs of one call must not share outputs. */
 int sc_lm_rescore(const sc_lm_rescore_job *jobs, int n_jobs, void *stream);
 
+/* ---- attention rescoring of n-best lists (dec_rescore.hip) --------------------------------------------
+ * Attention of whole sequences (sc_seq_attention).  A job is ONE sequence: Lq query rows against Lk key / value rows, H
+ * heads of dk columns each (head h at columns [h * dk, (h + 1) * dk) of a row of q, k, v and o), every buffer with its
+ * own row stride:
+ *   s_ij = q_i . k_j / sqrt(dk);   key j is MASKED when j >= Lk, or when the job is causal and j > i
+ *   o_i  = sum_j softmax_j(s_i)_j v_j over the keys that are not masked
+ * fp32 throughout, both products on the matrix cores (v_mfma_f32_16x16x4_f32), keys walked in tiles of 16 from key 0
+ * with an online softmax.  A mask is a select: a masked key has weight exactly 0 and neither its k nor its v row reaches
+ * an output - rows at or beyond Lk are never read, the rows j > i of a causal job are read (a later query needs them)
+ * but their products are discarded by selects.  The bits of o_i depend on q_i and on the rows k_j, v_j the mask leaves
+ * to it alone - not on Lq, on the other jobs of the launch or on the workgroup it lands in.  One workgroup of one wave
+ * per (job, head, tile of 16 queries); no atomics, one writer per output, plain stores; nothing outside
+ * [0, Lq) x [0, H * dk) of o is written, nothing outside the stated sizes is read. */
+typedef struct sc_seq_attn_job {
+  const float *q, *k, *v;  /* row i at q + i * q_stride, ... (device; 16-byte aligned) */
+  float *o;                /* row i at o + i * o_stride (device) */
+  int64_t q_stride, k_stride, v_stride, o_stride; /* floats between two rows, multiples of 4, >= H * dk */
+  int32_t Lq, Lk;          /* Lq == 0: nothing to do; else Lk >= 1 */
+  int32_t H, causal;       /* causal: 0 or 1 */
+} sc_seq_attn_job;
+#define SC_SEQ_ATTN_MAX_JOBS (1 << 24)
+/* jobs: device table of n_jobs entries.  dk: 16, 32 or 64.  max_Lq, max_H: the launch covers query rows below max_Lq and
+ * heads below max_H of every job (a job with more is malformed).  forms: bit 0 - the table holds jobs that are not
+ * causal, bit 1 - it holds causal jobs (one launch per set bit; a job of a form whose bit is not set is skipped).
+ * SC_ERR_ARG before anything is launched for a bad count, dk, max_Lq, max_H or forms; a job whose own fields are
+ * malformed (a null or misaligned pointer, a bad stride, Lq < 0, Lq > max_Lq, H outside [1, max_H], Lk < 1 with Lq > 0,
+ * causal outside {0, 1}) writes nothing. */
+int sc_seq_attention(const sc_seq_attn_job *jobs, int n_jobs, int dk, int max_Lq, int max_H, int forms, void *stream);
+
+/* One teacher-forced pass of the attention decoder over n-best lists (sc_dec_rescore).  A job is one list: n_hyp <=
+ * SC_ATT_MAX_HYPS rows of labels (no <sos>, no <eos>), row h at yseq + h * row_stride with m_h = lens[h] labels (lens ==
+ * NULL: L each), their first-pass totals at score[h * score_stride], and the T encoder rows E (row t at E + t * e_stride,
+ * d floats) the list was decoded from.  Row h is scored as the decoder scores it without a cache (decoder_layer.py:60-132,
+ * transformer_decoder.py): inputs [sos, y_0 .. y_{m-1}] at positions 0 .. m, targets [y_0 .. y_{m-1}, eos];
+ *   tok_att[h * tok_stride + t]  log-probability of target t, t in [0, m_h] (the last is the <eos> term); float64 =
+ *                (double)logit[target] - lse, lse of the fp32 logits row in float64 (csrc/ctc_row.h)
+ *   att[h]       ((0.0 + tok_att[0]) + tok_att[1]) + ..., ascending t
+ *   fused[h]     (w_ctc * score[h] + w_att * att[h]) + beta * m_h, every product and sum rounded on its own; a NaN is
+ *                stored as the quiet NaN 0x7FF8000000000000
+ *   order[r]     the row at rank r: fused descending, ties to the lower row
+ * status[h], a set of bits: SC_ATT_BAD_TOKEN - lens[h] outside [0, L] (nothing else of the row is examined) or a label
+ * outside [0, V); SC_ATT_TOO_LONG - m_h + 1 exceeds pe_rows or the model's LCAP; SC_ATT_NO_FRAMES - T == 0 (every row of
+ * the job).  A row with one of these has att = 0.0, fused = NaN and all L + 1 entries of its tok_att row 0.0.
+ * SC_ATT_NONFINITE - score[h] is not finite, or the fused total of a row without the bits above is not.  Rows with any
+ * status rank behind all others, in row order among themselves.  A label equal to sos / eos is an ordinary label.
+ * tests/dec_rescore_ref.py is the contract (float64): integers equal, att within the fp32 decoder's error.
+ * fp32 weights only: the model's sc_dec_layer entries wqkv, wo, wq, wo2, w1, w2 (w1_p / w2_p where sc_ffn_ln_supported)
+ * with their biases and norms, embed, pe, the after-norm and out_w / out_b; of sc_search nothing else but V, d, H, F,
+ * n_layers, LCAP, sos, eos and ln_eps is read.  sc_dec_layer carries no cross-attention K|V weights (the stream engine
+ * projects K|V where the encoder runs), so a job names them: wkv [n_layers * 2d][d] and bkv [n_layers * 2d], the
+ * layers' linear_k | linear_v one behind the other - the same for every job of a call. */
+#define SC_ATT_MAX_HYPS 16
+#define SC_ATT_NONFINITE 1 /* status bits */
+#define SC_ATT_BAD_TOKEN 2
+#define SC_ATT_TOO_LONG 4
+#define SC_ATT_NO_FRAMES 8
+#define SC_ERR_UNSUPPORTED (-5) /* sc_dec_rescore: the fp32 decoder weights are not resident in this handle */
+typedef struct sc_dec_rescore_job {
+  const float *E;           /* encoder rows (device); may be NULL when T == 0 */
+  const int32_t *yseq;      /* row h at yseq + h * row_stride (device) */
+  const double *score;      /* total of row h at score[h * score_stride] (device) */
+  const int32_t *lens;      /* [n_hyp] labels per row, or NULL: L each (device) */
+  const float *wkv, *bkv;   /* cross-attention K|V weights and biases of all layers (device) */
+  double *att;              /* [n_hyp] (device) */
+  double *fused;            /* [n_hyp] (device) */
+  int32_t *order;           /* [n_hyp] (device) */
+  int32_t *status;          /* [n_hyp] SC_ATT_* (device) */
+  double *tok_att;          /* row h at tok_att + h * tok_stride, m_h + 1 values; NULL: not wanted (device) */
+  int64_t e_stride;         /* floats between two rows of E, a multiple of 4, >= d */
+  int64_t row_stride;       /* int32 elements between two rows, >= L */
+  int64_t score_stride;     /* doubles between two rows' scores, >= 1 */
+  int64_t tok_stride;       /* doubles between two rows of tok_att, >= L + 1 when tok_att is given */
+  double w_att, w_ctc, beta; /* finite */
+  int32_t n_hyp, L, T, pe_rows; /* pe_rows: rows of the model's position table */
+} sc_dec_rescore_job;
+#define SC_ATT_MAX_JOBS 65535
+/* bytes of workspace a call (or one slab of a call) needs for lists of `rows` = sum n_hyp * (L + 1) token rows, `enc_rows`
+ * = sum T encoder rows, `n_seqs` = sum n_hyp and n_jobs jobs; 0 for a model the call refuses */
+size_t sc_dec_rescore_ws_bytes(const sc_search *model /*HOST*/, long rows, long enc_rows, int n_seqs, int n_jobs);
+/* jobs: HOST table.  Launches on `stream`: the dense work through sc_gemm / sc_gemm_ln / sc_gemm_colblocks / sc_ffn_ln
+ * (the feed-forward takes sc_ffn_ln where sc_ffn_ln_supported and the stream has its split-K workspace, else two sc_gemm)
+ * over the packed row table of all lists - their canonical sums keep a row's bits independent of the row count -, the
+ * two attentions of a layer through sc_seq_attention.  ws: device memory of ws_bytes, 256-byte aligned; a call whose
+ * lists need more is processed in slabs of whole jobs, with the same bits; SC_ERR_CAPACITY when one job alone does not
+ * fit.  Every error is raised before anything is launched or written: SC_ERR_ARG for a bad count, a null table, a
+ * model whose dims the kernels do not cover (d % 32, head dim not 16 / 32 / 64, V > SC_MAX_VOCAB) and for a malformed job
+ * (a null pointer other than lens / tok_att / E with T == 0, n_hyp outside [1, SC_ATT_MAX_HYPS], L outside [0, 65535), T outside [0, 65535], pe_rows < 1,
+ * a stride below its size, a misaligned E, a weight that is not finite, wkv / bkv differing between jobs);
+ * SC_ERR_UNSUPPORTED when a fp32 weight of the model is missing.  Two jobs of one call must not share outputs. */
+int sc_dec_rescore(const sc_dec_rescore_job *jobs /*HOST*/, int n_jobs, const sc_search *model /*HOST*/, void *ws,
+                   size_t ws_bytes, void *stream);
+
 /* ---- CTC token alternates (alternates.hip) -----------------------------------------------------
  * "What else could this token have been": for each of L token spans [start[k], end[k]) over the T rows of an fp32 CTC
  * table, the K acoustically best tokens of those frames and the rank of the span's own label y[k] among them.  Per span,
@@ -1278,6 +1370,34 @@ int sc_lm_rescore_lists(sc_streams *streams, const sc_lm *lm, const int32_t *ids
                         const double *scores, const int *list_sizes, int n, int nbest, int max_len,
                         const int32_t *state0, double alpha, double beta, int lm_eos, int32_t *order, double *fused,
                         double *lm_sum, double *eos_lm, int32_t *status, int32_t *end_state);
+/* Attention rescoring of n-best lists at finals (sc_dec_rescore above): ONE teacher-forced pass of the
+ * attention decoder over the rows of the lists, against the listed streams' encoder rows enc[s][0 .. T_enc) - FULL and
+ * decoder-free streams alike; a FULL stream's cross-attention cache is not reused, K|V are projected from the encoder rows
+ * on one path.  fp32 weights only (SC_ERR_UNSUPPORTED when the handle does not hold them).  A listed stream must be idle -
+ * no chunk outstanding, as for sc_reset -; its encoder group is waited for, as the beam's readers do.  Everything runs on
+ * the read-back stream with one copy back; nothing of the engine is written, and a handle that never calls these
+ * allocates nothing for them and issues the launches it issued before.  After sc_reset a stream has no frames: every
+ * row SC_ATT_NO_FRAMES.  The workspace is allocated by the first call, as large as that call needs but never beyond the
+ * limit (default SC_ATT_WS_DEFAULT_BYTES; sc_streams_set_attention_rescore_ws, at least 1 MiB); a call that needs more
+ * is processed in slabs of whole streams, with the same bits; SC_ERR_CAPACITY when one stream's list alone does not fit.
+ * sc_streams_attention_rescore_ws reports the limit and what is allocated.
+ * sc_attention_rescore_beam: the first nbest <= SC_ATT_MAX_HYPS entries of the listed streams' REPORTED CTC beam states -
+ * the entries sc_ctc_beam_hyps returns, packed on the device by sc_ctc_beam_pack -, their first-pass scores the entries'
+ * totals lae(pb, pnb), with a language model attached the fused totals of sc_ctc_beam_hyps_lm; ctc_score [n][nbest]
+ * receives them.  Outputs [n][nbest], n_hyps[i] entries each: order, fused, att, status as sc_dec_rescore defines them.
+ * sc_attention_rescore_lists: the same for caller-given lists - list i has list_sizes[i] <= nbest rows, row r its
+ * lens[i][r] labels ids[i][r][0 .. lens) and its total scores[i][r] - against the encoder rows of stream_ids[i] (a stream
+ * may be listed more than once). */
+#define SC_ATT_WS_DEFAULT_BYTES ((size_t)256 << 20)
+int sc_attention_rescore_beam(sc_streams *streams, const int *stream_ids, int n, int nbest, double w_att, double w_ctc,
+                              double beta, int32_t *order, double *fused, double *att, double *ctc_score, int32_t *status,
+                              int *n_hyps);
+int sc_attention_rescore_lists(sc_streams *streams, const int *stream_ids, int n, const int32_t *ids, const int32_t *lens,
+                               const double *scores, const int *list_sizes, int nbest, int max_len, double w_att,
+                               double w_ctc, double beta, int32_t *order, double *fused, double *att, int32_t *status);
+int sc_streams_set_attention_rescore_ws(sc_streams *streams, size_t max_bytes);
+int sc_streams_attention_rescore_ws(const sc_streams *streams, size_t *limit, size_t *allocated);
+
 /* CTC forced alignment of the hypotheses sc_get_hyps_batch would return (same rules: the snapshot with a queue depth
  * > 1, an error for a stream inside a decode block), best first, against the stream's own CTC rows: the T frames of
  * the decode block the hypotheses come from.  Labels: yseq without <sos> and without a trailing <eos>.  Outputs

@@ -74,7 +74,7 @@ def to_16k(raw, rate, device="cuda:0"):
 def recognize_file(speech2text, media_path, output_file="", quiet=True, progress=True, num_slots=1, chunk_length=8192,
                    token_alignment=False, segmentation="host", channel=None, token_alternates=0, ctc_beam=0,
                    ctc_only=False, ctc_lm=None, lm_weight=0.5, word_bonus=0.0, rescore_lm=None, rescore_weight=0.5,
-                   rescore_bonus=0.0, ctc_grammar=None):
+                   rescore_bonus=0.0, ctc_grammar=None, attention_rescore=None):
     """speechcatcher.py:358-400: recording -> text + paragraphs JSON next to the input.  ``token_alignment``: the
     paragraphs also get token_start / token_end (seconds) and token_conf from a CTC forced alignment of each segment.
     ``segmentation``: "host" or "gpu" - where the energy curve for the cut points of a recording over 60 s is computed.
@@ -94,6 +94,8 @@ def recognize_file(speech2text, media_path, output_file="", quiet=True, progress
         raise SystemExit("Error: --ctc-grammar and --ctc-lm together are not served")
     if ctc_grammar and not os.path.isfile(ctc_grammar):
         raise SystemExit(f"Error: --ctc-grammar: '{ctc_grammar}' does not exist or is not a file")
+    if attention_rescore is not None and not ctc_only:
+        raise SystemExit("Error: --attention-rescore re-ranks the n-best list of a decoder-free segment: it needs --ctc-only")
     if rescore_lm and ctc_only:
         raise SystemExit("Error: --rescore-lm re-ranks the n-best list of the attention decoder's search: not with --ctc-only")
     if rescore_lm and not os.path.isfile(rescore_lm):
@@ -128,7 +130,8 @@ def recognize_file(speech2text, media_path, output_file="", quiet=True, progress
                                      lm_weight=float(lm_weight), word_bonus=float(word_bonus),
                                      rescore_lm=rescore_lm or None, rescore_weight=float(rescore_weight),
                                      rescore_bonus=float(rescore_bonus),
-                                     **({"ctc_grammar": ctc_grammar} if ctc_grammar else {}))
+                                     **({"ctc_grammar": ctc_grammar} if ctc_grammar else {}),
+                                     **({} if attention_rescore is None else {"attention_rescore": (float(attention_rescore), 0.5)}))
     out_txt, out_json = (output_file or media_path) + ".txt", (output_file or media_path) + ".json"
     with open(out_txt, "w") as f:
         f.write(text)
@@ -196,6 +199,10 @@ def make_parser():
                         "not tuned)")
     p.add_argument("--rescore-bonus", dest="rescore_bonus", type=float, default=0.0, metavar="B",
                    help="bonus per token of a hypothesis in the re-ranking (default 0)")
+    p.add_argument("--attention-rescore", dest="attention_rescore", type=float, nargs="?", const=1.0, default=None, metavar="W_ATT",
+                   help="with --ctc-only: re-rank every segment's final n-best list by one teacher-forced pass of the attention "
+                        "decoder over the segment's encoder output, fused = 0.5 * ctc + W_ATT * att (default 1.0; parameters, not "
+                        "tuned); the segment .json carries the re-ranked ctc_nbest")
     p.add_argument("--segmentation", dest="segmentation", choices=["host", "gpu"], default="host",
                    help="where the energy curve for the cut points of a recording over 60 s is computed: 'host' (numpy, the "
                         "default) or 'gpu' (float64 kernels; the same cuts, without the host pass over the whole recording)")
@@ -233,7 +240,8 @@ def main(argv=None):
                    channel=args.channel, token_alternates=args.token_alternates, ctc_beam=args.ctc_beam,
                    ctc_only=args.ctc_only, ctc_lm=args.ctc_lm or None, lm_weight=args.lm_weight, word_bonus=args.word_bonus,
                    rescore_lm=args.rescore_lm or None, rescore_weight=args.rescore_weight, rescore_bonus=args.rescore_bonus,
-                   **({"ctc_grammar": args.ctc_grammar} if args.ctc_grammar else {}))
+                   **({"ctc_grammar": args.ctc_grammar} if args.ctc_grammar else {}),
+                   **({} if args.attention_rescore is None else {"attention_rescore": args.attention_rescore}))
     return 0
 
 

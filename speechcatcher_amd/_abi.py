@@ -232,6 +232,27 @@ RESCORE_MAX_HYPS, RESCORE_MAX_JOBS, RESCORE_FORCE_SERIAL = 16, 65535, 1
 RESCORE_NONFINITE, RESCORE_BAD_TOKEN, RESCORE_SERIAL = 1, 2, 4
 
 
+class SeqAttnJob(C.Structure):
+    """sc_seq_attn_job (include/scasr.h): the attention of one sequence in sc_seq_attention"""
+    _fields_ = ([(n, vp) for n in ("q", "k", "v", "o")]
+                + [(n, C.c_int64) for n in ("q_stride", "k_stride", "v_stride", "o_stride")]
+                + [(n, C.c_int32) for n in ("Lq", "Lk", "H", "causal")])
+
+
+class DecRescoreJob(C.Structure):
+    """sc_dec_rescore_job (include/scasr.h): one n-best list rescored by the attention decoder in sc_dec_rescore"""
+    _fields_ = ([(n, vp) for n in ("E", "yseq", "score", "lens", "wkv", "bkv", "att", "fused", "order", "status", "tok_att")]
+                + [(n, C.c_int64) for n in ("e_stride", "row_stride", "score_stride", "tok_stride")]
+                + [(n, C.c_double) for n in ("w_att", "w_ctc", "beta")]
+                + [(n, C.c_int32) for n in ("n_hyp", "L", "T", "pe_rows")])
+
+
+# SC_ATT_* / SC_SEQ_ATTN_* of include/scasr.h
+ATT_MAX_HYPS, ATT_MAX_JOBS, SEQ_ATTN_MAX_JOBS = 16, 65535, 1 << 24
+ATT_NONFINITE, ATT_BAD_TOKEN, ATT_TOO_LONG, ATT_NO_FRAMES = 1, 2, 4, 8
+ERR_CAPACITY, ERR_UNSUPPORTED = -3, -5
+
+
 class BeamPackJob(C.Structure):
     """sc_ctc_beam_pack_job (include/scasr.h): one entry of a beam state walked up its parent chain"""
     _fields_ = ([(n, vp) for n in ("state", "nodes", "ids", "frames", "header", "scores")]
@@ -467,6 +488,16 @@ _SIGS = {
                                   vp, vp, vp, c_int_p]),
     "sc_lm_rescore_lists": (C.c_int, [vp, vp, vp, vp, vp, c_int_p, C.c_int, C.c_int, C.c_int, vp, C.c_double,
                                       C.c_double, C.c_int, vp, vp, vp, vp, vp, vp]),
+    # attention rescoring of n-best lists (dec_rescore.hip)
+    "sc_seq_attention": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "sc_dec_rescore_ws_bytes": (C.c_size_t, [vp, C.c_long, C.c_long, C.c_int, C.c_int]),
+    "sc_dec_rescore": (C.c_int, [vp, C.c_int, vp, vp, C.c_size_t, vp]),
+    "sc_attention_rescore_beam": (C.c_int, [vp, c_int_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp,
+                                            vp, c_int_p]),
+    "sc_attention_rescore_lists": (C.c_int, [vp, c_int_p, C.c_int, vp, vp, vp, c_int_p, C.c_int, C.c_int, C.c_double,
+                                             C.c_double, C.c_double, vp, vp, vp, vp]),
+    "sc_streams_set_attention_rescore_ws": (C.c_int, [vp, C.c_size_t]),
+    "sc_streams_attention_rescore_ws": (C.c_int, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "sc_stream_set_decoder": (C.c_int, [vp, C.c_int, C.c_int]),
     "sc_stream_decoder": (C.c_int, [vp, C.c_int]),
     "sc_streams_read_ctc_projected": (C.c_int, [vp, C.c_int, vp, C.c_int]),

@@ -428,6 +428,12 @@ struct sc_streams {
   size_t bh_cap = 0;
   char *rs_dev = nullptr, *rs_host = nullptr;   // sc_rescore_hyps / sc_lm_rescore_lists: job table, inputs, outputs; grown geometrically
   size_t rs_cap = 0;
+  // ---- attention rescoring (sc_attention_rescore_beam / _lists): everything below is allocated by the first call ----
+  char *ar_dev = nullptr, *ar_host = nullptr;   // the lists' inputs and the outputs; grown geometrically
+  size_t ar_cap = 0;
+  char *ar_ws = nullptr;                        // workspace of sc_dec_rescore: what a call needs, at most ar_ws_limit bytes
+  size_t ar_ws_bytes = 0, ar_ws_limit = SC_ATT_WS_DEFAULT_BYTES;
+  void *ar_splitk = nullptr;                    // split-K workspace of the read-back stream (the fused feed-forward's partial sums)
   size_t beam_ncap() const { return 1 + (size_t)beam_nodes_B * TCAP; }
   // ---- tick engine -----------------------------------------------------------------------------------------------------
   std::vector<St> st;
@@ -487,8 +493,13 @@ struct sc_streams {
     for (EncGroup *g : groups) delete g;
     for (void *p : owned) (void)hipFree(p);
     for (void *p : owned_host) (void)hipHostFree(p);
+    if (stream_rb && ar_splitk) (void)sc_set_stream_workspace(stream_rb, nullptr, 0);
     if (stream_rb) (void)hipStreamDestroy(stream_rb);
     if (stream) (void)hipStreamDestroy(stream);
+    if (ar_dev) (void)hipFree(ar_dev);
+    if (ar_host) (void)hipHostFree(ar_host);
+    if (ar_ws) (void)hipFree(ar_ws);
+    if (ar_splitk) (void)hipFree(ar_splitk);
     if (al_dev) (void)hipFree(al_dev);
     if (beam_nodes) (void)hipFree(beam_nodes);
     for (sc_grammar *g : beam_gr)   // (the streams are synchronised: nothing reads a grammar any more)
@@ -4229,6 +4240,274 @@ extern "C" int sc_ctc_beam_hyps(sc_streams *b, const int *stream_ids, int n, int
     if (ids) memcpy(ids + k * max_len, (const int32_t *)(b->bh_host + o_ids) + k * max_len, L * sizeof(int32_t));
     if (frames) memcpy(frames + k * max_len, (const int32_t *)(b->bh_host + o_frames) + k * max_len, L * sizeof(int32_t));
   }
+  return SC_OK;
+  SC_API_END
+}
+
+// ---- attention rescoring of n-best lists at finals (dec_rescore.hip) ------------------------------------
+// The lists' rows are scored by ONE sc_dec_rescore call against the listed streams' encoder rows enc[s][0 .. T_enc), on
+// the read-back stream, with ONE copy back; nothing of the engine is written.  ar_dev / ar_host hold [inputs][outputs]; a
+// job's outputs: att, fused [16] doubles, then order, status [16] int32.  The workspace is allocated by the first call, as
+// large as the call needs and never beyond ar_ws_limit (sc_streams_set_attention_rescore_ws): a call that needs more
+// runs in slabs of whole streams, with the same bits.
+namespace {
+constexpr size_t AR_OUT = (size_t)SC_ATT_MAX_HYPS * (2 * sizeof(double) + 2 * sizeof(int32_t));
+constexpr size_t AR_SPLITK = (size_t)32 << 20;
+
+size_t ar_up(size_t x) { return (x + 255) & ~(size_t)255; }
+
+int ar_reserve(sc_streams *b, size_t need) {
+  if (need <= b->ar_cap) return SC_OK;
+  HIP_TRY(hipStreamSynchronize(b->stream_rb));
+  if (b->ar_dev) (void)hipFree(b->ar_dev);
+  if (b->ar_host) (void)hipHostFree(b->ar_host);
+  const size_t cap = std::max(need, 2 * b->ar_cap);
+  b->ar_dev = b->ar_host = nullptr;
+  b->ar_cap = 0;
+  HIP_TRY(hipMalloc((void **)&b->ar_dev, cap));
+  HIP_TRY(hipHostMalloc((void **)&b->ar_host, cap));
+  b->ar_cap = cap;
+  return SC_OK;
+}
+
+int ar_workspace(sc_streams *b, size_t need) {
+  if (!b->ar_splitk) {   // the read-back stream gets split-K storage of its own: the dense launchers never share partial sums
+    HIP_TRY(hipMalloc(&b->ar_splitk, AR_SPLITK));
+    RC_TRY(sc_set_stream_workspace(b->stream_rb, b->ar_splitk, AR_SPLITK));
+  }
+  const size_t want = std::min(ar_up(need), b->ar_ws_limit & ~(size_t)255);
+  if (want <= b->ar_ws_bytes) return SC_OK;
+  HIP_TRY(hipStreamSynchronize(b->stream_rb));
+  if (b->ar_ws) (void)hipFree(b->ar_ws);
+  b->ar_ws = nullptr;
+  b->ar_ws_bytes = 0;
+  HIP_TRY(hipMalloc((void **)&b->ar_ws, want));
+  b->ar_ws_bytes = want;
+  return SC_OK;
+}
+
+// the layers' cross-attention K|V weights one behind the other, as sc_dec_rescore takes them
+int ar_weights(const sc_streams *b, const float **wkv, const float **bkv) {
+  const sc_engine *e = b->eng;
+  if (e->wkv_all && e->bkv_all) { *wkv = e->wkv_all; *bkv = e->bkv_all; return SC_OK; }
+  if (b->cfg.dec_layers == 1) { *wkv = e->wkv[0]; *bkv = e->bkv[0]; return SC_OK; }
+  sc_set_error("attention rescoring: the engine holds no contiguous copy of the cross-attention K|V weights");
+  return SC_ERR_UNSUPPORTED;
+}
+
+// a listed stream: idle (its chunks reported), its encoder rows complete
+int ar_stream(sc_streams *b, int s) {
+  SC_CHECK_ARG(s >= 0 && s < b->S, "stream out of range");
+  SC_CHECK_ARG(!b->job[s].open && b->ahead[s].empty(), "the stream has a chunk outstanding (sc_poll reports it first)");
+  return wait_group(b, b->enc_gen[s]);
+}
+
+void ar_job(const sc_streams *b, sc_dec_rescore_job &j, int s, const float *wkv, const float *bkv, double w_att, double w_ctc,
+            double beta, char *out) {
+  j.E = b->enc + (size_t)s * b->TCAP * b->cfg.d_model;
+  j.e_stride = b->cfg.d_model;
+  j.T = b->st[s].T_enc;
+  j.wkv = wkv; j.bkv = bkv;
+  j.att = (double *)out;
+  j.fused = j.att + SC_ATT_MAX_HYPS;
+  j.order = (int32_t *)(j.fused + SC_ATT_MAX_HYPS);
+  j.status = j.order + SC_ATT_MAX_HYPS;
+  j.tok_att = nullptr; j.tok_stride = 0;
+  j.score_stride = 1;
+  j.w_att = w_att; j.w_ctc = w_ctc; j.beta = beta;
+  j.pe_rows = b->cfg.pe_max_len;
+}
+
+// what lies before `up` of ar_host goes up, `before` (NULL: nothing) is launched, the jobs run, their outputs come back
+template <typename Before>
+int ar_run(sc_streams *b, const std::vector<sc_dec_rescore_job> &jobs, size_t up, size_t o_out, Before before) {
+  long rows = 0, enc_rows = 0;
+  int seqs = 0;
+  for (const sc_dec_rescore_job &j : jobs) { rows += (long)j.n_hyp * (j.L + 1); enc_rows += j.T; seqs += j.n_hyp; }
+  RC_TRY(ar_workspace(b, sc_dec_rescore_ws_bytes(&b->sb, rows, enc_rows, seqs, (int)jobs.size())));
+  const int rc = [&]() -> int {
+    HIP_TRY(hipMemcpyAsync(b->ar_dev, b->ar_host, up, hipMemcpyHostToDevice, b->stream_rb));
+    RC_TRY(before());
+    RC_TRY(sc_dec_rescore(jobs.data(), (int)jobs.size(), &b->sb, b->ar_ws, b->ar_ws_bytes, b->stream_rb));
+    HIP_TRY(hipMemcpyAsync(b->ar_host + o_out, b->ar_dev + o_out, jobs.size() * AR_OUT, hipMemcpyDeviceToHost, b->stream_rb));
+    HIP_TRY(hipStreamSynchronize(b->stream_rb));
+    return SC_OK;
+  }();
+  if (rc != SC_OK) (void)hipStreamSynchronize(b->stream_rb);   // nothing of this call may still read the pinned area
+  return rc;
+}
+
+void ar_copy_out(const char *out, size_t i, int nbest, int nh, int32_t *order, double *fused, double *att, int32_t *status) {
+  const double *d = (const double *)out;
+  const int32_t *q = (const int32_t *)(d + 2 * SC_ATT_MAX_HYPS);
+  const size_t o = i * (size_t)nbest;
+  if (att) memcpy(att + o, d, nh * sizeof(double));
+  if (fused) memcpy(fused + o, d + SC_ATT_MAX_HYPS, nh * sizeof(double));
+  if (order) memcpy(order + o, q, nh * sizeof(int32_t));
+  if (status) memcpy(status + o, q + SC_ATT_MAX_HYPS, nh * sizeof(int32_t));
+}
+
+int ar_weights_ok(double w_att, double w_ctc, double beta) {
+  SC_CHECK_ARG(std::isfinite(w_att) && std::isfinite(w_ctc) && std::isfinite(beta), "w_att, w_ctc and beta must be finite");
+  return SC_OK;
+}
+}  // namespace
+
+extern "C" int sc_streams_set_attention_rescore_ws(sc_streams *b, size_t max_bytes) {
+  SC_CHECK_ARG(b && max_bytes >= ((size_t)1 << 20), "a workspace limit of at least 1 MiB");
+  SC_API_BEGIN
+  HIP_TRY(hipSetDevice(b->eng->device));
+  b->ar_ws_limit = max_bytes;
+  if (b->ar_ws_bytes > max_bytes) {   // the next call allocates within the new limit
+    HIP_TRY(hipStreamSynchronize(b->stream_rb));
+    (void)hipFree(b->ar_ws);
+    b->ar_ws = nullptr;
+    b->ar_ws_bytes = 0;
+  }
+  return SC_OK;
+  SC_API_END
+}
+
+extern "C" int sc_streams_attention_rescore_ws(const sc_streams *b, size_t *limit, size_t *allocated) {
+  SC_CHECK_ARG(b, "null");
+  if (limit) *limit = b->ar_ws_limit;
+  if (allocated) *allocated = b->ar_ws_bytes;
+  return SC_OK;
+}
+
+extern "C" int sc_attention_rescore_lists(sc_streams *b, const int *stream_ids, int n, const int32_t *ids, const int32_t *lens,
+                                          const double *scores, const int *list_sizes, int nbest, int max_len, double w_att,
+                                          double w_ctc, double beta, int32_t *order, double *fused, double *att,
+                                          int32_t *status) {
+  SC_CHECK_ARG(b && stream_ids && lens && scores && list_sizes && n >= 0 && n <= SC_ATT_MAX_JOBS && nbest >= 0 &&
+               nbest <= SC_ATT_MAX_HYPS && max_len >= 0 && max_len < 65535 && (ids || max_len == 0), "bad arguments");
+  SC_API_BEGIN
+  HIP_TRY(hipSetDevice(b->eng->device));
+  RC_TRY(ar_weights_ok(w_att, w_ctc, beta));
+  const float *wkv = nullptr, *bkv = nullptr;
+  RC_TRY(ar_weights(b, &wkv, &bkv));
+  for (int i = 0; i < n; ++i) {
+    SC_CHECK_ARG(list_sizes[i] >= 0 && list_sizes[i] <= nbest, "a list size outside [0, nbest]");
+    RC_TRY(ar_stream(b, stream_ids[i]));
+  }
+  const size_t rows = (size_t)n * nbest;
+  const size_t o_len = ar_up(rows * sizeof(double)), o_ids = o_len + ar_up(rows * sizeof(int32_t)),
+               o_out = o_ids + ar_up(rows * max_len * sizeof(int32_t));
+  RC_TRY(ar_reserve(b, o_out + (size_t)std::max(n, 1) * AR_OUT));
+  memcpy(b->ar_host, scores, rows * sizeof(double));
+  memcpy(b->ar_host + o_len, lens, rows * sizeof(int32_t));
+  if (rows * max_len) memcpy(b->ar_host + o_ids, ids, rows * max_len * sizeof(int32_t));
+  std::vector<sc_dec_rescore_job> jobs;
+  std::vector<int> job_of(n, -1);
+  for (int i = 0; i < n; ++i) {
+    if (list_sizes[i] == 0) continue;
+    sc_dec_rescore_job j{};
+    ar_job(b, j, stream_ids[i], wkv, bkv, w_att, w_ctc, beta, b->ar_dev + o_out + jobs.size() * AR_OUT);
+    j.yseq = (const int32_t *)(b->ar_dev + o_ids) + (size_t)i * nbest * max_len;
+    j.score = (const double *)b->ar_dev + (size_t)i * nbest;
+    j.lens = (const int32_t *)(b->ar_dev + o_len) + (size_t)i * nbest;
+    j.row_stride = max_len;
+    j.n_hyp = list_sizes[i]; j.L = max_len;
+    job_of[i] = (int)jobs.size();
+    jobs.push_back(j);
+  }
+  if (!jobs.empty()) RC_TRY(ar_run(b, jobs, o_out, o_out, []() { return SC_OK; }));
+  for (int i = 0; i < n; ++i)
+    if (job_of[i] >= 0)
+      ar_copy_out(b->ar_host + o_out + (size_t)job_of[i] * AR_OUT, (size_t)i, nbest, list_sizes[i], order, fused, att, status);
+  return SC_OK;
+  SC_API_END
+}
+
+// The first nbest entries of the listed streams' REPORTED beam states - the entries sc_ctc_beam_hyps returns -, packed on
+// the device by sc_ctc_beam_pack; their first-pass scores are the entries' totals lae(pb, pnb), with a language model
+// attached the fused totals sc_ctc_beam_hyps_lm reports.  ctc_score [n][nbest] receives them.
+extern "C" int sc_attention_rescore_beam(sc_streams *b, const int *stream_ids, int n, int nbest, double w_att, double w_ctc,
+                                         double beta, int32_t *order, double *fused, double *att, double *ctc_score,
+                                         int32_t *status, int *n_hyps) {
+  SC_CHECK_ARG(b && stream_ids && n_hyps && n >= 0 && nbest >= 0 && nbest <= SC_ATT_MAX_HYPS, "bad arguments");
+  SC_API_BEGIN
+  SC_CHECK_ARG(b->beam_on, "the beam option is off (sc_streams_set_ctc_beam)");
+  SC_CHECK_ARG(n <= b->S, "more streams listed than the batch has");
+  HIP_TRY(hipSetDevice(b->eng->device));
+  RC_TRY(ar_weights_ok(w_att, w_ctc, beta));
+  const float *wkv = nullptr, *bkv = nullptr;
+  RC_TRY(ar_weights(b, &wkv, &bkv));
+  std::vector<char> listed(b->S, 0);
+  int max_len = 0;
+  for (int i = 0; i < n; ++i) {
+    const int s = stream_ids[i];
+    RC_TRY(ar_stream(b, s));
+    SC_CHECK_ARG(!listed[s], "a stream is listed twice");
+    listed[s] = 1;
+    RC_TRY(beam_ready(b, s));
+    const sc_beam_t &d = b->beam.rep[s].v.d;
+    n_hyps[i] = std::max(0, std::min(nbest, d.n_entries));
+    for (int r = 0; r < n_hyps[i]; ++r) max_len = std::max(max_len, d.e[r].len);
+  }
+  SC_CHECK_ARG(max_len < 65535, "an entry too long");
+  const size_t m = (size_t)n * nbest;
+  if (m == 0) return SC_OK;
+  // [states: n][pack jobs: m][scores: m][lens: m] go up; [ids, frames: m][max_len], [pack header: m][4], [pack scores: m][2] stay on
+  // the device; [outputs] come back
+  const size_t o_pj = ar_up((size_t)n * sizeof(sc_beam_t)), o_sc = o_pj + ar_up(m * sizeof(sc_ctc_beam_pack_job)),
+               o_len = o_sc + ar_up(m * sizeof(double)), o_ids = o_len + ar_up(m * sizeof(int32_t)),
+               o_frames = o_ids + ar_up(m * max_len * sizeof(int32_t)), o_head = o_frames + ar_up(m * max_len * sizeof(int32_t)),
+               o_psc = o_head + ar_up(m * 4 * sizeof(int32_t)),
+               o_out = o_psc + ar_up(m * 2 * sizeof(double));
+  RC_TRY(ar_reserve(b, o_out + (size_t)n * AR_OUT));
+  sc_beam_t *st_host = (sc_beam_t *)b->ar_host;
+  sc_ctc_beam_pack_job *pj = (sc_ctc_beam_pack_job *)(b->ar_host + o_pj);
+  double *sc_host = (double *)(b->ar_host + o_sc);
+  int32_t *len_host = (int32_t *)(b->ar_host + o_len);
+  std::vector<sc_dec_rescore_job> jobs;
+  std::vector<int> job_of(n, -1);
+  for (int i = 0; i < n; ++i) {
+    const int s = stream_ids[i];
+    const BeamState &v = b->beam.rep[s].v;
+    st_host[i] = v.d;
+    for (int r = 0; r < nbest; ++r) {
+      const size_t k = (size_t)i * nbest + r;
+      sc_ctc_beam_pack_job &j = pj[k];
+      j.state = (const sc_beam_t *)b->ar_dev + i;
+      j.nodes = b->beam_nodes + (size_t)s * b->beam_ncap();
+      j.ids = (int32_t *)(b->ar_dev + o_ids) + k * max_len;
+      j.frames = (int32_t *)(b->ar_dev + o_frames) + k * max_len;
+      j.header = (int32_t *)(b->ar_dev + o_head) + k * 4;
+      j.scores = (double *)(b->ar_dev + o_psc) + k * 2;
+      j.capacity = (int32_t)b->beam_ncap(); j.rank = r; j.max_len = max_len; j.reserved = 0;
+      double total = NAN;
+      int len = 0;
+      if (r < n_hyps[i]) {
+        const sc_beam_entry &e = v.d.e[r];
+        const double hi = std::max(e.pb, e.pnb), lo = std::min(e.pb, e.pnb);
+        total = lo == -INFINITY ? hi : hi + log1p(exp(lo - hi));
+        if (b->beam_lm) total = total + (b->beam_alpha * v.lm.lm[r] + b->beam_beta * (double)e.len);   // (sc_ctc_beam_hyps_lm)
+        len = e.len;
+      }
+      sc_host[k] = total;
+      len_host[k] = len;
+      if (ctc_score) ctc_score[k] = total;
+    }
+    if (n_hyps[i] == 0) continue;
+    sc_dec_rescore_job j{};
+    ar_job(b, j, s, wkv, bkv, w_att, w_ctc, beta, b->ar_dev + o_out + jobs.size() * AR_OUT);
+    j.yseq = (const int32_t *)(b->ar_dev + o_ids) + (size_t)i * nbest * max_len;
+    j.score = (const double *)(b->ar_dev + o_sc) + (size_t)i * nbest;
+    j.lens = (const int32_t *)(b->ar_dev + o_len) + (size_t)i * nbest;
+    j.row_stride = max_len;
+    j.n_hyp = n_hyps[i]; j.L = max_len;
+    job_of[i] = (int)jobs.size();
+    jobs.push_back(j);
+  }
+  if (!jobs.empty())
+    RC_TRY(ar_run(b, jobs, o_ids, o_out, [&]() -> int {
+      if (max_len == 0) return SC_OK;   // every entry is the empty prefix: there is nothing to pack
+      return sc_ctc_beam_pack((const sc_ctc_beam_pack_job *)(b->ar_dev + o_pj), (int)m, b->stream_rb);
+    }));
+  for (int i = 0; i < n; ++i)
+    if (job_of[i] >= 0)
+      ar_copy_out(b->ar_host + o_out + (size_t)job_of[i] * AR_OUT, (size_t)i, nbest, n_hyps[i], order, fused, att, status);
   return SC_OK;
   SC_API_END
 }

@@ -918,6 +918,127 @@ class HipBackend:
                         "raw": {"f64": f64[k].copy(), "i32": i32[k].copy(), "tok": tok[a:b].copy()}})
         return out
 
+    # ---- attention rescoring of n-best lists (csrc/dec_rescore.hip) -------------------------------------
+    def seq_attention(self, jobs, dk: int, max_Lq=None, tweak=None):
+        """Attention of whole sequences (sc_seq_attention), one call for all jobs.  jobs: list of dicts - "q" [>= Lq,
+        >= H * dk], "k", "v" [>= Lk, >= H * dk] and "o" [>= Lq, >= H * dk]: float32 device tensors whose rows may be
+        strided, "Lq", "Lk", "H", "causal".  The outputs are written into the jobs' "o".  ``tweak(k, job)``: test aid,
+        edits the sc_seq_attn_job of job k before the launch."""
+        n = len(jobs)
+        tab = (_abi.SeqAttnJob * max(1, n))()
+        forms = 0
+        for k, job in enumerate(jobs):
+            j = tab[k]
+            for name in ("q", "k", "v", "o"):
+                t = job[name]
+                assert t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1
+                setattr(j, name, t.data_ptr())
+                setattr(j, name + "_stride", t.stride(0))
+            j.Lq, j.Lk, j.H, j.causal = int(job["Lq"]), int(job["Lk"]), int(job["H"]), int(bool(job["causal"]))
+            assert j.Lq <= job["q"].shape[0] and j.Lq <= job["o"].shape[0] and j.Lk <= min(job["k"].shape[0], job["v"].shape[0])
+            assert j.H * dk <= min(job[name].shape[1] for name in ("q", "k", "v", "o"))
+            forms |= 2 if j.causal else 1
+            if tweak is not None:
+                tweak(k, j)
+        max_Lq = max([int(j["Lq"]) for j in jobs], default=0) if max_Lq is None else max_Lq
+        max_H = max([int(j["H"]) for j in jobs], default=1)
+        tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(self.device)
+        self._chk(self.lib.sc_seq_attention(tab_dev.data_ptr(), n, dk, max_Lq, max_H, forms or 1, self._stream()),
+                  "sc_seq_attention")
+        torch.cuda.synchronize(self.device)
+
+    def decoder_model(self, w, LCAP: int):
+        """The model part of an sc_search for sc_dec_rescore from PackedWeights ``w``: dims, ids and the fp32 decoder
+        weights; no search buffers.  Returns an object that keeps everything alive: .struct (the _abi.Search), .wkv /
+        .bkv (the layers' cross-attention K|V weights and biases one behind the other), .pe_rows."""
+        cfg = w.cfg
+        layers = (_abi.DecLayer * len(w.dec))()
+        for i, lw in enumerate(w.dec):
+            for name, _ in _abi.DecLayer._fields_:
+                if name in lw and lw[name].dtype == torch.float32:
+                    setattr(layers[i], name, lw[name].data_ptr())
+        s = _abi.Search()
+        s.V, s.d, s.H, s.F, s.n_layers, s.LCAP = cfg.vocab_size, cfg.d_model, cfg.dec_heads, cfg.ffn_dim, cfg.dec_layers, LCAP
+        s.blank, s.eos, s.sos, s.ln_eps = cfg.blank_id, cfg.eos_id, cfg.sos_id, cfg.ln_eps
+        s.embed, s.pe = w.embed.data_ptr(), w.pe.data_ptr()
+        s.dec_norm_g, s.dec_norm_b = w.dec_norm_g.data_ptr(), w.dec_norm_b.data_ptr()
+        s.out_w, s.out_b = w.out_w.data_ptr(), w.out_b.data_ptr()
+        s.layers = C.cast(layers, C.c_void_p).value
+
+        class _Model:
+            pass
+        m = _Model()
+        m.struct, m.layers, m.w, m.pe_rows = s, layers, w, int(w.pe.shape[0])
+        m.wkv = torch.cat([lw["wkv"] for lw in w.dec], 0).contiguous()
+        m.bkv = torch.cat([lw["bkv"] for lw in w.dec], 0).contiguous()
+        return m
+
+    def dec_rescore(self, jobs, model, ws_bytes=None, tweak=None, guard: int = 2):
+        """Attention rescoring of n-best lists (sc_dec_rescore) on the caller's device arrays.  ``model``:
+        decoder_model().  jobs: list of dicts - "E": float32 device tensor [T, >= d] (rows may be strided) or None;
+        "rows": int32 device tensor [n, >= L]; "scores": float64 device tensor [n]; "L"; optional "lens" (n ints; default
+        L each), "w_att" (1), "w_ctc" (0.5), "beta" (0), "tok" (True), "pe_rows" (the model's).  ``ws_bytes``: size of the
+        workspace handed over (default: what all jobs need at once) - a smaller one makes the call run in slabs.
+        Returns one dict per job: "att", "fused" (float64 [n]), "order", "status" (int32 [n]), "tok_att" ([n, L + 1] or
+        None) and "raw": the output buffers whole, every one handed over filled with -7 and ``guard`` words longer than
+        the kernel may write.  ``tweak(k, job)``: test aid, edits the sc_dec_rescore_job of job k before the call."""
+        import numpy as np
+        n = len(jobs)
+        dev = self.device
+        H = _abi.ATT_MAX_HYPS
+        f64 = torch.full((max(n, 1), 2, H + guard), -7.0, dtype=torch.float64, device=dev)
+        i32 = torch.full((max(n, 1), 2, H + guard), -7, dtype=torch.int32, device=dev)
+        widths = [int(j["L"]) + 1 if j.get("tok", True) else 0 for j in jobs]
+        ti = np.concatenate([[0], np.cumsum([int(j["rows"].shape[0]) * w + guard for j, w in zip(jobs, widths)])])
+        tok = torch.full((max(int(ti[-1]), 1),), -7.0, dtype=torch.float64, device=dev)
+        keep = []
+        tab = (_abi.DecRescoreJob * max(1, n))()
+        rows_total = enc_total = seqs = 0
+        for k, job in enumerate(jobs):
+            rows, sc, E = job["rows"], job["scores"], job.get("E")
+            assert rows.dtype == torch.int32 and rows.dim() == 2 and (rows.shape[1] == 0 or rows.stride(1) == 1)
+            assert sc.dtype == torch.float64 and sc.dim() == 1 and sc.shape[0] == rows.shape[0]
+            assert int(job["L"]) <= rows.shape[1]
+            j = tab[k]
+            if E is not None and E.shape[0] > 0:
+                assert E.dtype == torch.float32 and E.dim() == 2 and E.stride(1) == 1 and E.shape[1] >= model.struct.d
+                j.E, j.e_stride, j.T = E.data_ptr(), E.stride(0), E.shape[0]
+            j.yseq, j.row_stride = rows.data_ptr(), rows.stride(0) if rows.shape[0] > 1 else max(rows.shape[1], 1)
+            j.score, j.score_stride = sc.data_ptr(), sc.stride(0) if sc.shape[0] > 1 else 1
+            if job.get("lens") is not None:
+                lens = torch.tensor([int(v) for v in job["lens"]], dtype=torch.int32, device=dev)
+                keep.append(lens)
+                j.lens = lens.data_ptr()
+            j.wkv, j.bkv = model.wkv.data_ptr(), model.bkv.data_ptr()
+            j.att, j.fused = (f64[k, c].data_ptr() for c in range(2))
+            j.order, j.status = (i32[k, c].data_ptr() for c in range(2))
+            if job.get("tok", True):
+                j.tok_att, j.tok_stride = tok.data_ptr() + 8 * int(ti[k]), widths[k]
+            j.w_att, j.w_ctc, j.beta = float(job.get("w_att", 1.0)), float(job.get("w_ctc", 0.5)), float(job.get("beta", 0.0))
+            j.n_hyp, j.L, j.pe_rows = rows.shape[0], int(job["L"]), int(job.get("pe_rows", model.pe_rows))
+            if tweak is not None:
+                tweak(k, j)
+            rows_total += max(0, j.n_hyp) * (max(0, j.L) + 1)
+            enc_total += max(0, j.T)
+            seqs += max(0, j.n_hyp)
+        need = int(self.lib.sc_dec_rescore_ws_bytes(C.addressof(model.struct), rows_total, enc_total, seqs, n))
+        # (the two-GEMM feed-forward of a stream without split-K workspace keeps its hidden rows too)
+        need += rows_total * model.struct.F * 4 + 256
+        ws = torch.empty(max(256, need if ws_bytes is None else int(ws_bytes)), dtype=torch.uint8, device=dev)
+        self._chk(self.lib.sc_dec_rescore(C.cast(tab, C.c_void_p), n, C.addressof(model.struct), ws.data_ptr(), ws.numel(),
+                                          self._stream()), "sc_dec_rescore")
+        torch.cuda.synchronize(dev)
+        f64, i32, tok = f64.cpu().numpy(), i32.cpu().numpy(), tok.cpu().numpy()
+        out = []
+        for k, job in enumerate(jobs):
+            nh, w = int(job["rows"].shape[0]), widths[k]
+            a, b = int(ti[k]), int(ti[k + 1])
+            out.append({"att": f64[k, 0, :nh].copy(), "fused": f64[k, 1, :nh].copy(),
+                        "order": i32[k, 0, :nh].copy(), "status": i32[k, 1, :nh].copy(),
+                        "tok_att": tok[a:a + nh * w].reshape(nh, w).copy() if job.get("tok", True) else None,
+                        "raw": {"f64": f64[k].copy(), "i32": i32[k].copy(), "tok": tok[a:b].copy()}})
+        return out
+
     def decode_pcm(self, jobs, tweak=None, guard: int = 4):
         """Batched decode of coded audio (sc_pcm_decode) on the caller's buffers, one launch for all jobs.  jobs: list of
         (src: a bytes-like object, a numpy array or a uint8 device tensor; byte offset; format; channels; channel; scale;

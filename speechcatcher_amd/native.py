@@ -891,6 +891,75 @@ class NativeStreamBatch:
         return [{"order": order[i, :k], "fused": fused[i, :k], "lm": lm[i, :k], "eos_lm": eos[i, :k],
                  "status": status[i, :k], "end_state": end[i, :k]} for i, k in enumerate(sizes)]
 
+    # ---- attention rescoring of n-best lists at finals (sc_attention_rescore_beam / _lists) ---------
+    def attention_rescore_beam(self, streams: Sequence[int], nbest: Optional[int] = None, w_att: float = 1.0,
+                               w_ctc: float = 0.5, beta: float = 0.0):
+        """{stream: {"order", "fused", "att", "ctc_score", "status"}} for the first ``nbest`` entries of the listed
+        streams' reported CTC beams (the entries ``ctc_beam_hyps`` returns; numpy arrays over those entries): one
+        teacher-forced pass of the attention decoder over the stream's encoder output, fused = w_ctc * ctc_score +
+        w_att * att + beta * labels, order[r] the entry at rank r.  One call and one copy back for all listed streams;
+        nothing of the engine changes.  The streams must be idle (their chunks reported)."""
+        sid = np.ascontiguousarray(streams, dtype=np.int32)
+        n = len(sid)
+        nb = min(int(_abi.ATT_MAX_HYPS if nbest is None else nbest), _abi.ATT_MAX_HYPS)
+        order, status, nh = np.zeros((n, nb), np.int32), np.zeros((n, nb), np.int32), np.zeros(n, np.int32)
+        fused, att, ctc = np.zeros((n, nb)), np.zeros((n, nb)), np.zeros((n, nb))
+        try:
+            _abi.check(self.lib.sc_attention_rescore_beam(self.handle, sid.ctypes.data_as(_abi.c_int_p), n, nb, float(w_att),
+                                                          float(w_ctc), float(beta), order.ctypes.data, fused.ctypes.data,
+                                                          att.ctypes.data, ctc.ctypes.data, status.ctypes.data,
+                                                          nh.ctypes.data_as(_abi.c_int_p)), "sc_attention_rescore_beam")
+        except _abi.ScasrError as e:
+            raise EngineError(str(e)) from e
+        return {int(s): {"order": order[i, :nh[i]], "fused": fused[i, :nh[i]], "att": att[i, :nh[i]],
+                         "ctc_score": ctc[i, :nh[i]], "status": status[i, :nh[i]]} for i, s in enumerate(sid)}
+
+    def attention_rescore_lists(self, streams: Sequence[int], lists, scores, w_att: float = 1.0, w_ctc: float = 0.5,
+                                beta: float = 0.0):
+        """The same for caller-given lists: ``lists[i]`` is a list of label sequences (at most 16, no <sos> / <eos>)
+        scored against the encoder output of ``streams[i]`` (FULL or decoder-free), ``scores[i]`` their first-pass
+        totals.  Returns one dict per list: "order", "fused", "att", "status"."""
+        sid = np.ascontiguousarray(streams, dtype=np.int32)
+        n = len(lists)
+        if len(sid) != n or len(scores) != n:
+            raise ValueError("one stream and one score list per list")
+        nb = max([len(li) for li in lists] + [1])
+        if nb > _abi.ATT_MAX_HYPS:
+            raise ValueError(f"a list holds more than {_abi.ATT_MAX_HYPS} rows")
+        ml = max([len(y) for li in lists for y in li] + [1])
+        ids, lens = np.zeros((n, nb, ml), np.int32), np.zeros((n, nb), np.int32)
+        sc, sizes = np.zeros((n, nb)), np.zeros(n, np.int32)
+        for i, (li, ss) in enumerate(zip(lists, scores)):
+            if len(li) != len(ss):
+                raise ValueError("one score per row")
+            sizes[i] = len(li)
+            for r, y in enumerate(li):
+                ids[i, r, :len(y)], lens[i, r], sc[i, r] = y, len(y), ss[r]
+        order, status = np.zeros((n, nb), np.int32), np.zeros((n, nb), np.int32)
+        fused, att = np.zeros((n, nb)), np.zeros((n, nb))
+        try:
+            _abi.check(self.lib.sc_attention_rescore_lists(self.handle, sid.ctypes.data_as(_abi.c_int_p), n, ids.ctypes.data,
+                                                           lens.ctypes.data, sc.ctypes.data,
+                                                           sizes.ctypes.data_as(_abi.c_int_p), nb, ml, float(w_att),
+                                                           float(w_ctc), float(beta), order.ctypes.data, fused.ctypes.data,
+                                                           att.ctypes.data, status.ctypes.data),
+                       "sc_attention_rescore_lists")
+        except _abi.ScasrError as e:
+            raise EngineError(str(e)) from e
+        return [{"order": order[i, :k], "fused": fused[i, :k], "att": att[i, :k], "status": status[i, :k]}
+                for i, k in enumerate(sizes)]
+
+    def set_attention_rescore_workspace(self, max_bytes: int):
+        """Upper bound of the workspace the two calls above allocate (default 256 MiB; include/scasr.h): a call that
+        needs more runs in slabs of whole streams, with the same bits."""
+        _abi.check(self.lib.sc_streams_set_attention_rescore_ws(self.handle, int(max_bytes)), "sc_streams_set_attention_rescore_ws")
+
+    def attention_rescore_workspace(self):
+        """(limit, allocated) bytes of that workspace; allocated is 0 until the first call"""
+        lim, got = C.c_size_t(0), C.c_size_t(0)
+        _abi.check(self.lib.sc_streams_attention_rescore_ws(self.handle, C.byref(lim), C.byref(got)), "sc_streams_attention_rescore_ws")
+        return int(lim.value), int(got.value)
+
     def hypotheses(self, s: int):
         """Live hypotheses of stream s: list of dicts (yseq, score, score_dec, score_ctc, xpos), best first."""
         return self.hypotheses_batch([int(s)])[int(s)]

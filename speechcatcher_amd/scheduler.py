@@ -124,7 +124,7 @@ class StreamScheduler:
                  phrases=None, min_scores=None, draft: bool = False, input_level: bool = False, alternates: int = 0,
                  align_nbest: int = 1, stable_partials: bool = False, ctc_beam=None, ctc_lm=None,
                  lm_weight: float = 0.5, word_bonus: float = 0.0, final_lm=None, final_lm_weight: float = 0.5,
-                 final_word_bonus: float = 0.0, final_lm_eos: bool = False):
+                 final_word_bonus: float = 0.0, final_lm_eos: bool = False, attention_rescore=None):
         """``queue_depth`` > 1 (C++ engine, ``pump``): up to that many queued chunks of a session are handed to the engine
         at a time (sc_streams_set_queue_depth) - for sessions whose audio is already there (files): the encoder stage of
         the next chunk runs beside the decoding of the current one.  Replies and their order per session do not change.
@@ -173,6 +173,14 @@ class StreamScheduler:
         self.final_lm_eos = bool(final_lm_eos)
         self._final_dev = self._ctc_blob = self._ctc_dev = None
         self._ctc_sessions = set()
+        # ``attention_rescore`` (needs ``ctc_beam``; C++ engine): True or (w_att, w_ctc[, beta]) - sessions
+        # opened with decoder="rescore" are decoder-free in the engine, their partials the beam's best as for "ctc"; at a
+        # final the n-best list gets one teacher-forced pass of the attention decoder over the stream's encoder output and
+        # is re-ranked by w_ctc * first pass + w_att * att + beta * labels (NativeStreamBatch.attention_rescore_beam, ONE
+        # call for all such finals of a reply round).  (w_att, w_ctc, beta) when on; the default (1.0, 0.5, 0.0) are
+        # parameters, not tuned.
+        self.attention_rescore = None
+        self._rescore_sessions = set()
         self._slot_dec: Dict[int, str] = {}
         # grammars (``open(grammar=...)``, ``set_grammar``; needs ``ctc_beam``; C++ engine): compiled grammars by the
         # SHA-256 of their blob, {"handle": the device copy, "uses": the slots that name it, "walk": its host walk} - a
@@ -225,6 +233,8 @@ class StreamScheduler:
         elif self.final_lm_eos and not hasattr(batch, "rescore_lists"):
             raise NotImplementedError("the </s> term of finals is computed by the C++ engine (NativeStreamBatch."
                                       "rescore_lists); the Python lock-step engine has none")
+        if attention_rescore is not None and attention_rescore is not False:
+            self.enable_attention_rescore(attention_rescore)
         if alternates:
             self.enable_alternates(alternates)
         if stable_partials:
@@ -289,6 +299,23 @@ class StreamScheduler:
         self.final_lm = (float(lm_weight), float(word_bonus), bool(eos))
         self.final_lm_eos = bool(eos)
 
+    def enable_attention_rescore(self, spec=True):
+        """switch the ``attention_rescore`` option on: True, or (w_att, w_ctc[, beta]); None / False switches it off"""
+        if spec is None or spec is False:
+            self.attention_rescore = None
+            return
+        if self.ctc_beam is None:
+            raise ValueError("attention_rescore needs the ctc_beam option (StreamScheduler(ctc_beam=...))")
+        if not hasattr(self.batch, "attention_rescore_beam"):
+            raise NotImplementedError("attention rescoring runs in the C++ engine (NativeStreamBatch.attention_rescore_beam, "
+                                      "sc_attention_rescore_beam); the Python lock-step engine has none")
+        w = (1.0, 0.5, 0.0) if spec is True else tuple(float(v) for v in spec)
+        if len(w) == 2:
+            w = w + (0.0,)
+        if len(w) != 3 or not all(np.isfinite(v) for v in w):
+            raise ValueError("attention_rescore is True or (w_att, w_ctc[, beta]), all finite")
+        self.attention_rescore = w
+
     @property
     def _eos_id(self) -> int:
         return int(getattr(self.batch.cfg, "eos_id", EOS_ID))
@@ -344,7 +371,7 @@ class StreamScheduler:
         finally:
             if gr_key in self._gr_cache and self._gr_cache[gr_key]["uses"] == 0:   # (the set failed)
                 self.batch.release_grammar(self._gr_cache.pop(gr_key)["handle"])
-        self._set_slot_decoder(slot, decoder)
+        self._set_slot_decoder(slot, "ctc" if decoder == "rescore" else decoder)   # (decoder-free in the engine)
         self._set_slot_rate(slot, sample_rate)
         self._set_slot_format(slot, fmt)
         self._free.popleft()
@@ -359,17 +386,21 @@ class StreamScheduler:
         self._stable.pop(sid, None)
         if fmt != _FLOAT_INPUT:
             self._fmt[sid] = fmt
-        if decoder == "ctc":
+        if decoder in ("ctc", "rescore"):
             self._ctc_sessions.add(sid)
+        if decoder == "rescore":
+            self._rescore_sessions.add(sid)
         return sid
 
     def _check_decoder(self, decoder):
-        if decoder not in ("full", "ctc"):
-            raise ValueError(f'decoder must be "full" or "ctc", got {decoder!r}')
-        if decoder == "ctc" and self.ctc_beam is None:
-            raise ValueError('decoder="ctc" needs the ctc_beam option (StreamScheduler(ctc_beam=...))')
-        if decoder == "ctc" and self.alternates:
-            raise ValueError('decoder="ctc": token alternates rank the frames of a forced alignment against a decode '
+        if decoder not in ("full", "ctc", "rescore"):
+            raise ValueError(f'decoder must be "full", "ctc" or "rescore", got {decoder!r}')
+        if decoder != "full" and self.ctc_beam is None:
+            raise ValueError(f'decoder="{decoder}" needs the ctc_beam option (StreamScheduler(ctc_beam=...))')
+        if decoder == "rescore" and self.attention_rescore is None:
+            raise ValueError('decoder="rescore" needs the attention_rescore option (StreamScheduler(attention_rescore=...))')
+        if decoder != "full" and self.alternates:
+            raise ValueError(f'decoder="{decoder}": token alternates rank the frames of a forced alignment against a decode '
                              "block's rows, which a decoder-free session does not have")
 
     def set_decoder(self, sid: int, decoder: str):
@@ -380,11 +411,16 @@ class StreamScheduler:
             return
         if self._rate[sid].fed:
             raise ValueError("the decoder of a session can only be set before its first audio")
-        self._set_slot_decoder(self._slot_of[sid], decoder)
-        if decoder == "ctc":
+        self._set_slot_decoder(self._slot_of[sid], "ctc" if decoder == "rescore" else decoder)
+        if decoder in ("ctc", "rescore"):
             self._ctc_sessions.add(sid)
         else:
             self._ctc_sessions.discard(sid)
+        self._rescore_sessions.discard(sid)
+        if decoder == "rescore":
+            self._rescore_sessions.add(sid)
+        else:
+            self._rescore_sessions.discard(sid)
 
     def _set_slot_decoder(self, slot: int, decoder: str):
         if self._slot_dec.get(slot, "full") == decoder:
@@ -398,7 +434,7 @@ class StreamScheduler:
         self._slot_dec[slot] = decoder
 
     def decoder(self, sid: int) -> str:
-        return "ctc" if sid in self._ctc_sessions else "full"
+        return "rescore" if sid in self._rescore_sessions else "ctc" if sid in self._ctc_sessions else "full"
 
     # ---- a grammar per session ------------------------------
     def _grammar_blob(self, source) -> bytes:
@@ -659,6 +695,12 @@ class StreamScheduler:
             beams = self.batch.ctc_beam_hyps(ask, self.ctc_beam[0]) if ask else {}
             if self.ctc_lm is not None and ask:   # the model's side of the same entries (host arithmetic, no launch)
                 sides = dict(zip(ask, self.batch.ctc_beam_lm(ask, self.ctc_beam[0])))
+        att = {}
+        if self.attention_rescore is not None and beams is not None:   # ONE call and one copy back for the round's finals
+            fins = [slot for sid, (slot, fin, _) in meta.items()
+                    if fin and has[slot] is True and sid in self._rescore_sessions and beams.get(slot)]
+            if fins:
+                att = self.batch.attention_rescore_beam(fins, self.ctc_beam[0], *self.attention_rescore)
         for sid, (slot, fin, fa) in meta.items():
             if self._clocked and self._fed.get(sid):   # the stream's clock advances by the reported chunk
                 n, f = self._fed[sid].popleft()
@@ -721,14 +763,17 @@ class StreamScheduler:
             if beams is not None:
                 nbest = self._ctc_nbest(sid, beams[slot], sides.get(slot))
                 gr_key = self._slot_gr.get(slot)
-                if gr_key is not None:   # the accept flags of the same entries (host arithmetic, no launch)
+                if gr_key is not None:   # the accept flags of the same entries (host arithmetic, no launch), read before
+                    # the list is re-ordered
                     flags = self.batch.ctc_beam_hyps_grammar([slot], self.ctc_beam[0])[slot]
                     for e, (_, acc) in zip(nbest, flags):
                         e["complete"] = bool(acc)
-                    if fin:              # a final: the complete entries first, each group in beam order
-                        nbest = [e for e in nbest if e["complete"]] + [e for e in nbest if not e["complete"]]
+                if slot in att and nbest:
+                    nbest = self._attention_reranked(nbest, att[slot])
+                if gr_key is not None and fin:   # a final: the complete entries first, each group in its order
+                    nbest = [e for e in nbest if e["complete"]] + [e for e in nbest if not e["complete"]]
                 if fin and self.final_lm_eos and self.ctc_lm is not None and sid in self._ctc_sessions and nbest:
-                    nbest = self._ctc_end_term(nbest)
+                    nbest = self._ctc_end_term(nbest, after_attention=slot in att)
                 # a decoder-free session: its results are the beam's entries, best first (a chunk the engine answers with
                 # nothing stays [])
                 free = sid in self._ctc_sessions
@@ -759,7 +804,26 @@ class StreamScheduler:
                 d["start_s"], d["end_s"] = t["start"], t["end"]
         return out
 
-    def _ctc_end_term(self, nbest: list) -> list:
+    def _attention_reranked(self, nbest: list, got: dict) -> list:
+        """the final n-best list of a "rescore" session after the attention pass (``got``: its entry of
+        batch.attention_rescore_beam): re-ordered; "att" the decoder's log probability of the entry's labels and <eos>,
+        "ctc_score" its first-pass total, "am_rank" its rank in the beam, "score" the fused total, "conf" from the new
+        totals"""
+        out = []
+        for r in got["order"][:len(nbest)]:
+            r = int(r)
+            if r >= len(nbest):
+                continue
+            e = dict(nbest[r])
+            e.setdefault("ctc_score", e["score"])
+            e["first_pass"], e["att"], e["am_rank"] = float(got["ctc_score"][r]), float(got["att"][r]), r
+            e["score"] = float(got["fused"][r])
+            out.append(e)
+        for e, c in zip(out, alternates_mod.nbest_posterior([e["score"] for e in out])):
+            e["conf"] = c
+        return out
+
+    def _ctc_end_term(self, nbest: list, after_attention: bool = False) -> list:
         """the final n-best list of a decoder-free session with the </s> term of the fused model: rescored as a
         caller-given list at the beam's weights (one launch), re-ranked; "score" is the fused total with the term,
         "eos_lm" the term, "am_rank" the entry's rank in the beam, "conf" from the new totals"""
@@ -769,7 +833,12 @@ class StreamScheduler:
         got = self.batch.rescore_lists([[e["ids"] for e in nbest]], [[e["ctc_score"] for e in nbest]], self._ctc_dev, a, b,
                                        lm_eos=self._eos_id)[0]
         out = []
-        for r in got["order"]:
+        if after_attention:   # the term is added to the attention-fused totals; ties keep the attention pass's order
+            rows = [dict(e, score=float(e["score"] + a * float(got["eos_lm"][r])), eos_lm=float(got["eos_lm"][r]))
+                    for r, e in enumerate(nbest)]
+            finite = [e for e in rows if np.isfinite(e["score"])]
+            out = sorted(finite, key=lambda e: -e["score"]) + [e for e in rows if not np.isfinite(e["score"])]
+        for r in ([] if after_attention else got["order"]):
             e = dict(nbest[int(r)])
             e["score"], e["eos_lm"], e["am_rank"] = float(got["fused"][r]), float(got["eos_lm"][r]), int(r)
             out.append(e)
@@ -972,7 +1041,7 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
                        queue_depth: int = 1, token_alignment: bool = False, token_alternates: int = 0,
                        ctc_beam=None, ctc_only: bool = False, ctc_lm=None, lm_weight: float = 0.5,
                        word_bonus: float = 0.0, rescore_lm=None, rescore_weight: float = 0.5,
-                       rescore_bonus: float = 0.0, ctc_grammar=None) -> List[dict]:
+                       rescore_bonus: float = 0.0, ctc_grammar=None, attention_rescore=None) -> List[dict]:
     """Decode the (start, end) sample ranges of one recording as PARALLEL streams
     of one batch instead of the reference's process pool over segments
     (speechcatcher/speechcatcher.py:474-497, chunk loop :574-592; SURVEY 8(f)
@@ -1007,6 +1076,10 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
     if ctc_only and token_alternates:
         raise ValueError("ctc_only: token alternates rank the frames of a forced alignment against a decode block's rows, "
                          "which a decoder-free stream does not have")
+    # ``attention_rescore`` (only with ``ctc_only``): True or (w_att, w_ctc[, beta]) - every segment is a "rescore" session,
+    # its final ``ctc_nbest`` re-ranked by one pass of the attention decoder (the scheduler's option)
+    if attention_rescore is not None and attention_rescore is not False and not ctc_only:
+        raise ValueError("attention_rescore re-ranks the n-best list of a decoder-free segment: it needs ctc_only")
     if ctc_only and not beam_mod.params(ctc_beam):
         ctc_beam = beam_mod.DEFAULT
     # queue_depth > 1 (C++ engine): that many chunks of a segment at the engine - the audio is all there.  Measured: worth
@@ -1015,14 +1088,16 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
     sch = StreamScheduler(batch, token_list, result_format="espnet", queue_depth=queue_depth, align_final=token_alignment,
                           alternates=token_alternates, ctc_beam=ctc_beam, ctc_lm=ctc_lm, lm_weight=lm_weight,
                           word_bonus=word_bonus, final_lm=rescore_lm, final_lm_weight=rescore_weight,
-                          final_word_bonus=rescore_bonus, final_lm_eos=rescore_lm is not None)
+                          final_word_bonus=rescore_bonus, final_lm_eos=rescore_lm is not None,
+                          attention_rescore=attention_rescore)
+    free = "rescore" if sch.attention_rescore is not None else "ctc"
     out: List[Optional[dict]] = [None] * len(segments)
     todo = list(enumerate(segments))
     sid_to_seg: Dict[int, int] = {}
     while todo or sch.n_active:
         while todo and sch._free:
             idx, (a, b) = todo.pop(0)
-            sid = sch.open(decoder="ctc" if ctc_only else "full", **({} if ctc_grammar is None else {"grammar": ctc_grammar}))
+            sid = sch.open(decoder=free if ctc_only else "full", **({} if ctc_grammar is None else {"grammar": ctc_grammar}))
             sid_to_seg[sid] = idx
             seg = speech[a:b]
             for pos in range(0, len(seg), chunk_length):

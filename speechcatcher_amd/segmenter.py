@@ -248,7 +248,7 @@ def recognize_recording_segments(batch, raw_speech_data: np.ndarray, rate: int =
                                  segmentation: str = "host", token_alternates: int = 0, ctc_beam=None,
                                  ctc_only: bool = False, ctc_lm=None, lm_weight: float = 0.5, word_bonus: float = 0.0,
                                  rescore_lm=None, rescore_weight: float = 0.5, rescore_bonus: float = 0.0,
-                                 ctc_grammar=None):
+                                 ctc_grammar=None, attention_rescore=None):
     """The segment loop of ``recognize`` (speechcatcher.py:414-497): int16 recording -> chunk-aligned sample
     ranges and the raw per-segment results of ``recognize_segments`` (before paragraph merging)."""
     assert rate == 16000
@@ -263,7 +263,7 @@ def recognize_recording_segments(batch, raw_speech_data: np.ndarray, rate: int =
                              token_alternates=token_alternates, ctc_beam=ctc_beam, ctc_only=ctc_only,
                              ctc_lm=ctc_lm, lm_weight=lm_weight, word_bonus=word_bonus, rescore_lm=rescore_lm,
                              rescore_weight=rescore_weight, rescore_bonus=rescore_bonus,
-                             **({} if ctc_grammar is None else {"ctc_grammar": ctc_grammar}))
+                             **({} if ctc_grammar is None else {"ctc_grammar": ctc_grammar}), **({} if attention_rescore is None else {"attention_rescore": attention_rescore}))
     return ranges, res
 
 
@@ -273,7 +273,7 @@ def recognize_recording(batch, raw_speech_data: np.ndarray, rate: int = 16000, c
                         segmentation: str = "host", token_alternates: int = 0, ctc_beam=None,
                         ctc_only: bool = False, ctc_lm=None, lm_weight: float = 0.5,
                         word_bonus: float = 0.0, rescore_lm=None, rescore_weight: float = 0.5,
-                        rescore_bonus: float = 0.0, ctc_grammar=None) -> Tuple[str, List[dict]]:
+                        rescore_bonus: float = 0.0, ctc_grammar=None, attention_rescore=None) -> Tuple[str, List[dict]]:
     """int16 recording -> (text, per-paragraph info).  Native-decoder input scaling
     /32768 in fp32 (speechcatcher.py:421); recordings over a minute are segmented;
     the segments run as parallel streams of ``batch`` (one slot = the reference CLI with one worker:
@@ -288,13 +288,14 @@ def recognize_recording(batch, raw_speech_data: np.ndarray, rate: int = 16000, c
     ``ctc_lm`` / ``lm_weight`` / ``word_bonus``: a packed n-gram model fused into it.
     ``rescore_lm`` / ``rescore_weight`` / ``rescore_bonus``: a packed n-gram model every segment's final n-best list is
     rescored with and re-ranked by (recognize_segments).  ``ctc_grammar``: a grammar every segment's CTC
-    beam answers only from (recognize_segments)."""
+    beam answers only from (recognize_segments).  ``attention_rescore`` (with ``ctc_only``): every segment's
+    final ``ctc_nbest`` is re-ranked by one pass of the attention decoder (recognize_segments)."""
     ranges, res = recognize_recording_segments(batch, raw_speech_data, rate, chunk_length, token_list,
                                                reference_finalize, average_segment_length,
                                                token_alignment or token_alternates > 0, segmentation, token_alternates,
                                                ctc_beam, ctc_only, ctc_lm, lm_weight, word_bonus, rescore_lm,
                                                rescore_weight, rescore_bonus,
-                                               **({} if ctc_grammar is None else {"ctc_grammar": ctc_grammar}))
+                                               **({} if ctc_grammar is None else {"ctc_grammar": ctc_grammar}), **({} if attention_rescore is None else {"attention_rescore": attention_rescore}))
     segs = [{"start": lo / rate, "end": hi / rate, "text": r["text"], "tokens": r["tokens"],
              "token_timestamps": r["token_timestamps"], **{k: r[k] for k in ALIGNMENT_KEYS if k in r}}
             for (lo, hi), r in zip(ranges, res)]

@@ -227,7 +227,8 @@ class ServerLoop:
                  spotting_min_scores: Optional[dict] = None, draft_partials: bool = False, raw_input: bool = False,
                  input_level: bool = False, vosk_alternatives: int = 0, token_alternates: int = 0,
                  stable_partials: bool = False, ctc_beam=None, ctc_lm=None, lm_weight: float = 0.5,
-                 word_bonus: float = 0.0, rescore_lm=None, rescore_weight: float = 0.5, rescore_bonus: float = 0.0):
+                 word_bonus: float = 0.0, rescore_lm=None, rescore_weight: float = 0.5, rescore_bonus: float = 0.0,
+                 attention_rescore=None):
         """``strict_reference``: no stream reset after a finalised utterance nor between clients, exactly like
         ``recognize_ws`` / ``process_audio_chunk`` (speechcatcher_server.py:270,359-397); the default resets.
         ``continuous`` (default: on whenever the batch has the C++ engine's submit / poll - round 4; False forces one
@@ -305,6 +306,12 @@ class ServerLoop:
                 scheduler.enable_ctc_beam(*beam_mod.params(ctc_beam))
         if ctc_lm is not None:
             scheduler.enable_ctc_lm(ctc_lm, lm_weight, word_bonus)
+        # ``attention_rescore`` = True or (w_att, w_ctc[, beta]) (needs ``ctc_beam``): the scheduler's option of that name
+        #  - a connection whose Vosk ``config`` carries ``"decoder": "rescore"`` before its first audio is
+        # decoder-free until its final, whose n-best list the attention decoder re-ranks; ``max_alternatives`` come from
+        # the re-ranked list
+        if attention_rescore is not None and attention_rescore is not False:
+            scheduler.enable_attention_rescore(attention_rescore)
         self.stable_partials = bool(stable_partials) and vosk_output_format
         if self.stable_partials and not scheduler.stable_partials:
             scheduler.enable_stable_partials()
@@ -444,8 +451,8 @@ class ServerLoop:
                     if not isinstance(cfg, dict):
                         raise AttributeError("config")
                     decoder = cfg.get("decoder", self.sch.decoder(ses.sid))
-                    if decoder not in ("full", "ctc"):
-                        raise ValueError(f'decoder must be "full" or "ctc", got {decoder!r}')
+                    if decoder not in ("full", "ctc", "rescore"):
+                        raise ValueError(f'decoder must be "full", "ctc" or "rescore", got {decoder!r}')
                     max_alt = self._config_alternatives(ses, cfg, decoder)
                     phrases, unk = self._config_phrases(cfg, decoder)
                 except (AttributeError, json.JSONDecodeError):
@@ -527,7 +534,7 @@ class ServerLoop:
         if "phrase_list" not in cfg:
             return None, False
         pl = cfg["phrase_list"]
-        if decoder != "ctc":
+        if decoder not in ("ctc", "rescore"):
             raise ValueError('phrase_list needs a decoder-free connection ("decoder": "ctc")')
         if not isinstance(pl, list) or not all(isinstance(p, str) for p in pl):
             raise ValueError("phrase_list must be a list of strings")
@@ -540,7 +547,7 @@ class ServerLoop:
         """the ``max_alternatives`` a Vosk ``config`` asks for, at most ``vosk_alternatives`` - for a decoder-free session
         at most the beam's B - (the session's own when the message names none; 0 with the option off); ValueError for
         anything but a non-negative integer"""
-        cap = self.sch.ctc_beam[0] if decoder == "ctc" and self.sch.ctc_beam else self.vosk_alternatives
+        cap = self.sch.ctc_beam[0] if decoder in ("ctc", "rescore") and self.sch.ctc_beam else self.vosk_alternatives
         if "max_alternatives" not in cfg or not cap:
             return min(ses.max_alternatives, cap)
         m = cfg["max_alternatives"]
@@ -570,7 +577,7 @@ class ServerLoop:
         records = al.get("alternates") if self.token_alternates and al is not None else None
         if records is not None and len(records) != len(tokens):
             records = None
-        free = self.sch.decoder(ses.sid) == "ctc"   # its results are the beam's entries, its alignment the tree's frames
+        free = self.sch.decoder(ses.sid) in ("ctc", "rescore")   # its results are the beam's entries, its alignment the tree's frames
         alts = ses.max_alternatives > 0 and (self.vosk_alternatives > 0 or free)
         aligned = self.vosk_alignment or (alts and not free)
         if alts:
