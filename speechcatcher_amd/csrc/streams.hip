@@ -24,537 +24,8 @@
 //                        stragglers of the previous one are still decoding (the reference's concurrency unit is an
 //                        independent stream: speechcatcher_server.py:331-371).
 // Per stream both give the same blocks, the same steps, the same results.
-#include <algorithm>
-#include <array>
-#include <chrono>
-#include <cmath>
-#include <cstdarg>
-#include <cstring>
-#include <deque>
-#include <map>
-#include <memory>
-#include <new>
-#include <string>
-#include <vector>
+#include "streams_state.h"
 
-#include "common.h"
-#include "handover.h"
-#include "resample.h"
-
-namespace {
-
-#define HIP_TRY(call)                                                              \
-  do {                                                                             \
-    hipError_t e__ = (call);                                                       \
-    if (e__ != hipSuccess) {                                                       \
-      sc_set_error("%s: %s failed: %s", __func__, #call, hipGetErrorString(e__));  \
-      return SC_ERR_LAUNCH;                                                        \
-    }                                                                              \
-  } while (0)
-#define RC_TRY(call)                 \
-  do {                               \
-    int rc__ = (call);               \
-    if (rc__ != SC_OK) return rc__;  \
-  } while (0)
-
-struct Tensor {
-  void *ptr = nullptr;
-  int64_t numel = 0;
-  int dtype = 0;  // 0 f32, 1 f64, 2 f16
-  bool owned = false;
-};
-
-struct StreamFault {
-  int stream;
-  int code;  // SC_ERR_CAPACITY / SC_ERR_INPUT
-  std::string msg;
-};
-
-}  // namespace
-
-struct sc_engine {
-  sc_config cfg{};
-  int device = 0;
-  std::map<std::string, Tensor> t;
-  std::vector<sc_enc_layer> enc;
-  std::vector<sc_dec_layer> dec;
-  std::vector<const float *> wkv, bkv;
-  float *wkv_all = nullptr, *bkv_all = nullptr;   // the layers' K|V weights [Ld * 2d][d] and biases one behind the other (project_rows)
-
-  const float *f(const std::string &name, bool required = true) const {
-    auto it = t.find(name);
-    if (it == t.end()) {
-      if (required) sc_set_error("sc_engine: tensor '%s' is missing", name.c_str());
-      return nullptr;
-    }
-    return (const float *)it->second.ptr;
-  }
-  ~sc_engine() {
-    for (auto &kv : t)
-      if (kv.second.owned && kv.second.ptr) (void)hipFree(kv.second.ptr);
-    if (wkv_all) (void)hipFree(wkv_all);
-    if (bkv_all) (void)hipFree(bkv_all);
-  }
-};
-
-namespace {
-
-// host mirror of one stream's scalar state (engine.py: StreamState)
-struct St {
-  bool fe_started = false;
-  long pcm_start = 0, pcm_end = 0;
-  bool enc_started = false;
-  int fpp = 0, nfeat = 0, upp = 0, nsub = 0;
-  bool has_sub = false;
-  int n_blocks = 0;
-  bool has_addin = false, has_ctx = false;
-  int short_pos = 0;
-  int T_enc = 0, processed_block = 0, process_idx = 0;
-  bool prev_valid = false, started = false;
-  int cur = 0, L = 1, nhyp = 1;
-  bool has_ctc = false;
-  int T_ctc = 0, T_kv = 0, output_index = 0;
-  // encoder frames whose CTC rows / cross-attention K|V rows have been projected (by the encoder stage that
-  // emitted them); after a strict reset() T_proj restarts at the stale table's extent (scorers.py:342-350)
-  int T_proj = 0, T_projkv = 0;
-  long n_steps_total = 0;
-  int T_hyp = 0;   // frames [0, T_hyp) of the decode block the live hypotheses come from (sc_align_hyps)
-  // sample-rate conversion (resample.hip): coefficient table of the stream's input rate (-1: 16 kHz, no conversion), input
-  // samples taken and 16 kHz samples produced in this utterance, history row the next launch reads (it writes the other)
-  int rs_tab = -1, rs_par = 0;
-  long rs_in = 0, rs_out = 0;
-  // wire format of the stream's input (pcm.hip): SC_PCM_F32 with one channel is the float path - no decode launch
-  int in_fmt = SC_PCM_F32, in_ch = 1, in_sel = 0, in_scale = SC_PCM_SCALE_FULL;
-  bool coded() const { return in_fmt != SC_PCM_F32 || in_ch != 1; }
-  // SC_DECODER_NONE (sc_stream_set_decoder): admission queues no decode block and lists no cross-attention K|V rows
-  bool no_dec = false;
-};
-
-// a decode block of the schedule (beam_search.py:590-634): the T frames [0, T) it presents to the scorers, whether
-// it is the final block, and the encoder group whose frames it sees (0: only frames that were there before)
-// ... and the chunk (Job::seq of its stream) that queued it
-struct Blk { int T; bool fin; long gen; long job; };
-
-// the block a stream is inside (the loop state of _decode_one_block, beam_search.py:655-838)
-struct Run {
-  bool inblk = false, live = false, took = false, pvalid = false, has = false, hasp = false, fin = false;
-  int cur = 0, L = 1, nhyp = 1, nhp = 1, pidx = 0, T = 0, Tc = 0, out = 0;
-  long nsteps = 0;
-  long job = 0;   // Job::seq of the chunk the block belongs to
-};
-
-// The side states (handover.h; DESIGN.md section 5, "Side states"): the payload each option hands over with a chunk, with
-// its value before anything of the utterance has been scanned.  A Job carries a handover::Pending of each.
-// Acoustic activity (sc_streams_set_activity; activity.hip): the state over every frame the encoder had emitted for the
-// utterance when the chunk was admitted.  T: rows of the CTC table the state covers (the track's extent).
-struct ActState {
-  int32_t v[6] = {0, 0, 0, -1, -1, 0};
-  int T = 0;
-};
-// Phrase spotting (sc_streams_set_phrases; spot.hip): the counters (n_frames, n_events).  The events themselves stay on the
-// device: the utterance's event k is at slot k, so the first n_events of them are final whatever later groups append.
-struct SpotState {
-  int32_t v[2] = {0, 0};
-};
-// Draft transcript (sc_streams_set_draft; draft.hip): the greedy state.  The tokens stay on the device: the utterance's
-// token k is at slot k and is never touched once stored, so the first n_closed of them are final whatever later groups
-// append; the open token travels in the state.
-struct DraftState {
-  sc_draft_t d = {0, 0, 0, -1, -1, -1, 0.0};
-};
-// CTC prefix beam search (sc_streams_set_ctc_beam; ctc_beam.hip): the beam - counters and entries.  The prefix tree stays
-// on the device: the utterance's node k is at slot k and is never touched once stored, so the chains of a reported state's
-// entries are final whatever later groups append.
-// With a language model attached (sc_streams_set_ctc_beam_lm) the model's side of the entries travels with them: all
-// zero without one, and before the first group of an utterance (the readers put the model's start state there).
-// A stream with a grammar (sc_stream_set_grammar) carries the automaton's states beside its entries in the same way.
-struct BeamState {
-  sc_beam_t d;
-  sc_beam_lm_t lm{};
-  sc_beam_gr_t gr{};
-  BeamState() {
-    d.n_frames = 0; d.n_bad = 0; d.n_nodes = 1; d.n_entries = 1;
-    for (sc_beam_entry &e : d.e) e = sc_beam_entry{-1, -1, 0, -1, -INFINITY, -INFINITY};
-    d.e[0] = sc_beam_entry{0, -1, 0, -1, 0.0, -INFINITY};
-  }
-  explicit BeamState(const sc_beam_t &v) : d(v) {}
-  BeamState(const sc_beam_t &v, const sc_beam_lm_t &l) : d(v), lm(l) {}
-  BeamState(const sc_beam_t &v, const sc_beam_gr_t &g) : d(v), gr(g) {}
-};
-// Input level (sc_stream_set_input_format; pcm.hip): the cumulative level, all zero at first.  Its launch belongs to a
-// STAGING slot (it runs in the admission's staging step, not in an encoder group), so its key is a ticket that names the
-// decode job, and slots are collected in any order.
-using LevelState = sc_input_level_t;
-
-// the options that scan the CTC rows of an encoder group, in launch order (EncGroup::Span::opt)
-enum { OPT_ACT, OPT_SPOT, OPT_DRAFT, OPT_BEAM, N_OPT };
-
-// a stream's outstanding chunk (sc_push / sc_submit): open until it has been reported.  With a queue depth > 1
-// (sc_streams_set_queue_depth) further chunks of the stream wait behind it (sc_streams::ahead), in order.
-struct Job {
-  bool open = false;
-  int has_out = 0;   // 1: the call produced output, 0: the reference's early `return []`
-  int fault = 0;     // SC_ERR_*: the chunk failed, the stream is reset when it is reported
-  long seq = 0;      // per-stream sequence number of the chunk (tags its decode blocks)
-  bool fin = false;  // is_final chunk: nothing may be queued behind it
-  bool dropped = false;   // failed only because an EARLIER chunk of the stream failed (the reset has happened by then)
-  bool started = false;   // St::started right after THIS chunk's admission (a later admission may set it before this one is reported)
-  handover::Pending<ActState> act;       // sc_streams_set_activity: the activity state that belongs to this chunk
-  handover::Pending<SpotState> spot;     // sc_streams_set_phrases: the spotting counters that belong to this chunk
-  handover::Pending<DraftState> draft;   // sc_streams_set_draft: the draft state that belongs to this chunk
-  handover::Pending<BeamState> beam;     // sc_streams_set_ctc_beam: the beam that belongs to this chunk
-  handover::Pending<LevelState> level;   // sc_stream_set_input_format: the input level up to and including this chunk
-};
-
-// hypotheses of a stream's last complete chunk, copied aside when later chunks of the stream may go on decoding
-// (queue depth > 1): what sc_get_hyps_batch returns for the stream until the next sc_poll call
-struct Snap {
-  bool valid = false, reported = false;
-  long seq = 0;
-  int L = 1, nhyp = 0;
-  int T = 0;   // St::T_hyp of the copied hypotheses
-};
-
-template <typename T>
-int dalloc(T **p, size_t n) {
-  const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-  HIP_TRY(hipMalloc((void **)p, bytes));
-  HIP_TRY(hipMemset(*p, 0, bytes));
-  // (a fill of device memory may return before it has run, and the engine's streams are not ordered behind the null
-  // stream: without the wait the zeros can land on what a first launch has already written there)
-  HIP_TRY(hipStreamSynchronize(nullptr));
-  return SC_OK;
-}
-
-}  // namespace
-
-struct EncPlan {
-  std::vector<int32_t> conv_jobs, a_rows, lin_dst, feat_src, feat_dst, blk_jobs, sjobs, emit_src, emit_dst, sub_src,
-      sub_dst;
-  struct Short { int s, ubase, U, pe_pos, dst_T; };
-  std::vector<Short> shorts;
-  int n_conv = 0, max_t1 = 0;
-};
-
-// One admission group: the frontend + encoder launches of the chunks admitted together, planned (host state already
-// advanced) and issued on the encoder stream either at once (sc_submit) or when the decode loop has thinned out
-// (sc_push).  `ev` completes when the group's encoder output, CTC rows and cross-attention K|V rows are in place.
-struct EncGroup {
-  long gen = 0;
-  bool launched = false, features = false;
-  bool open = false;                         // sc_submit: later admissions may still be merged into this (unlaunched) group
-  bool deferred = false;                     // sc_submit: issued when it is full or when a decode block needs its frames
-  int slot = 0;                              // job-table arena slot
-  int stage_slot = -1;                       // pinned staging slot holding the admission's host input (-1: none)
-  std::vector<long long> copy_jobs;          // [n][3] staging offset, destination offset, count (floats)
-  std::vector<sc_rs_job> rs_jobs;            // chunks of the streams whose input rate is not 16000: converted, not copied
-  size_t stage_floats = 0;
-  // coded chunks (streams with an input format): their bytes go to the slot's byte region, ONE sc_pcm_decode launch writes
-  // the float spans reserved for them before the scatter / conversion launch reads those; pcm_spans[i] belongs to pcm_jobs[i]
-  struct PcmSpan { int s; bool fin; };
-  std::vector<sc_pcm_job> pcm_jobs;
-  std::vector<PcmSpan> pcm_spans;
-  size_t stage_bytes = 0;
-  bool stage_filled = false;                 // the host wrote floats into the slot (false: the float copy is skipped)
-  std::vector<int32_t> fe_jobs;
-  int n_fe = 0, max_keep = 0;
-  EncPlan P;
-  std::vector<int32_t> ctc_rows, kv_src, kv_dst;   // eager projections of the frames the group emits
-  // side-state options (activity, spotting, draft, beam): per stream the span [t0, t1) of ctc_rows that every option which is on
-  // scans, one job each and in this order in every option's launch; mask: the stream's enabled phrases (spotting);
-  // opt[o]: the span as option o planned it (every span of a group carries the same options)
-  struct Span {
-    int s = 0, t0 = 0, t1 = 0;
-    uint64_t mask = 0;
-    const sc_grammar_view *grammar = nullptr;   // (beam) the device view of the stream's grammar when the span was planned
-    handover::Plan opt[N_OPT];
-  };
-  std::vector<Span> spans;
-  bool same_rows = true;
-  std::vector<int> streams;                  // streams with work in this group (each at most once)
-  bool empty() const { return !n_fe && !P.n_conv; }
-};
-
-constexpr int N_ARENA = 8;   // job-table arena slots = encoder groups that can be in flight
-constexpr int N_STAGE = 4;   // pinned staging slots for host input (a slot is free again when its H2D copy is done)
-constexpr int N_RING = 4;    // block-start tables (ctrl rows, log-softmax row lists): pinned ring
-constexpr int CM_FIXED = 4 + SC_COMMIT_MAX_HYPS + 6;   // sc_get_hyps_delta, int32 per job: header, agree, three float64 totals
-
-struct sc_streams {
-  sc_engine *eng = nullptr;
-  sc_config cfg{};
-  int S = 0, W = 0, K = 0, TCAP = 0, LCAP = 0, FCAP = 0, UCAP = 0, max_feat_new = 0, max_t1 = 0, max_t2 = 0,
-      max_blocks = 0, max_chunk = 0, max_length = 500;
-  long PCAP = 0;
-  bool use_bbd = false, strict = true;
-  hipStream_t stream = nullptr;
-  // Encoder side on its OWN HIP stream: frontend + encoder of a chunk do not feed the decode blocks whose frames
-  // were already there before the chunk (the block schedule runs one hop behind the encoder), so both
-  // are in flight together: the encoder's kernels run in the gaps of the decode chain (between a step's last kernel
-  // and the next step's first - the host reads the stop flags there) and behind its thin iterations.  Kernel traces
-  // (tools/rocpd_busy.py) show the kernels of the two streams ALTERNATING, not sharing CUs: 1.5 % of the wall time
-  // has both running - every kernel of the path fills the registers or the LDS of the CUs it occupies.
-  // `es` is the stream the current phase launches into.
-  hipStream_t stream_enc = nullptr, es = nullptr;
-  hipEvent_t ev_iter[2] = {nullptr, nullptr};   // end of decode iteration k (k & 1)
-  int32_t *ring_dev = nullptr;                  // device view of flags_host [S]: the prune kernel stores the stop flags there
-  int32_t *rm_host[2] = {nullptr, nullptr};     // pinned rowmap images (double-buffered: one may still be in a copy queue)
-  int rm_idx = 0;
-  bool rm_dirty = false;                        // rm_host[rm_idx] differs from the device rowmap
-  // T-parallel CTC scan: frames to walk >= scan_split_min (tools: and bucket streams <= scan_split_streams, 0 = any).  1024
-  // (round 5; 256 with a 48-stream bucket limit until round 4): WHICH form a stream's scan takes must depend on that
-  // stream alone (bit-reproducible serving), and with every stream of a full bucket in it the T-parallel form costs more
-  // than the sequential walk (3181 against 3258 audio-s/s at 390 frames to walk, profiles/r05_ab_scan_logits.txt) - it is
-  // for the long tables of CLI segments (T = 4500: 61 against 588 us per step)
-  int scan_split_min = 1024, scan_split_streams = 0;
-  bool scan_long = false;                       // this step: a live stream has >= scan_split_min frames to walk
-  // (round 5) the T-parallel kernel is part of a step whenever ONE live stream has a table long enough for it - whatever the
-  // size of the bucket: which form a stream's scan takes must depend on that stream alone (bit-reproducible serving);
-  // scan_split_streams (tools) restores the old bucket limit for A/B runs
-  int step_split_min() const { return (scan_long && (scan_split_streams <= 0 || n_rows_step <= scan_split_streams * W)) ? scan_split_min : 0; }
-  int graph_key() const { return n_rows_step * 2 + (step_split_min() > 0 ? 1 : 0); }
-  int enc_start_thr = 0;         // sc_push: launch the planned encoder group when at most this many streams are still decoding
-  int enc_batch_min = 0;         // sc_submit: launch the open encoder group when it holds this many streams (sc_streams_set_encoder_batch)
-  int gemm_flags = 0;            // SC_GEMM_SPLIT16 when the engine carries split-precision copies of the PROJECTIONS (wqkv_s): the tiled
-                                 // GEMMs of the encoder stage (conv2, subsampling Linear, CTC / cross-K|V projections) in the same form
-                                 // (weights.py checks the range of their operands at load time)
-  void *ws = nullptr, *ws_enc = nullptr;
-  std::vector<void *> owned, owned_host;
-  // device buffers
-  float *pcm = nullptr, *featbuf = nullptr, *subbuf = nullptr, *prev_addin = nullptr, *past_ctx = nullptr, *enc = nullptr,
-        *c1 = nullptr, *c2 = nullptr, *xblk = nullptr, *ws_xn = nullptr, *ws_qkv = nullptr, *ws_att = nullptr,
-        *ws_ffh = nullptr;
-  int32_t *jobs_ctx = nullptr, *ctrlmap = nullptr;
-  float *kv_stage = nullptr;   // kv_half: fp32 staging [dec_layers][kv_stage_rows][2d] of the K|V projections
-  int kv_stage_rows = 0;
-  sc_search sb{};
-  // pinned host
-  int32_t *ctrlmap_host = nullptr, *flags_host = nullptr;
-  // ---- job tables of the encoder groups: N_ARENA slots of one pinned / one device arena --------------------------
-  int32_t *arena_host = nullptr, *arena_dev = nullptr;
-  size_t slot_cap = 0, arena_off = 0;
-  int cur_slot = 0;
-  hipEvent_t ev_group[N_ARENA] = {nullptr};
-  long slot_gen[N_ARENA] = {0};   // group that owns the slot (0: free)
-  // ---- block-start tables (decode side) ------------------------------------------------------------------------------
-  int32_t *bs_host = nullptr, *bs_dev = nullptr;   // [N_RING][S*8 + S*block_size]: ctrl rows, then log-softmax rows
-  size_t bs_cap = 0;
-  int bs_i = 0;
-  // ---- host input staging (sc_push / sc_submit with host pointers): one H2D copy + one scatter launch per group ----
-  float *stage_host = nullptr, *stage_dev = nullptr;
-  size_t stage_cap = 0;           // floats per slot
-  hipEvent_t ev_stage[N_STAGE] = {nullptr};
-  bool stage_busy[N_STAGE] = {false};
-  int stage_next = 0;
-  long long *cjobs_host = nullptr, *cjobs_dev = nullptr;   // [N_STAGE][S*3] scatter jobs of a staging slot
-  // ---- sample-rate conversion of the streams whose input rate is not 16000 (resample.hip; one launch per admission) ----
-  sc_rs_job *rsjobs_host = nullptr, *rsjobs_dev = nullptr;   // [N_STAGE][S] jobs of a staging slot
-  float *rs_hist = nullptr;       // [2][S][SC_RS_HIST] last K - 1 input samples of every stream, flipped per call
-  sc_rs_tabs rs_tabs{};           // coefficient tables of the rates set on this handle (designed when a rate is first set)
-  int rs_rate[SC_RS_MAX_TABS] = {0};
-  int n_rs_tabs = 0;
-  // ---- wire-format input (sc_stream_set_input_format; pcm.hip): everything below is allocated when a format is first set ----
-  uint8_t *stageb_host = nullptr, *stageb_dev = nullptr;   // [N_STAGE][stageb_cap] byte region of a staging slot
-  size_t stageb_cap = 0;          // bytes per slot = the float slot's bytes
-  sc_pcm_job *pcmjobs_host = nullptr, *pcmjobs_dev = nullptr;             // [N_STAGE][S] decode jobs of a staging slot
-  sc_input_level_t *lvl_state = nullptr;                                  // device [S]: the running level of every stream
-  sc_input_level_t *lvl_out_host = nullptr, *lvl_out_dev = nullptr;       // [N_STAGE][S] host-mapped: the jobs' levels-after
-  struct LvlSpan { int s; long epoch, ticket; };
-  std::vector<LvlSpan> stage_lvl[N_STAGE];   // the decode jobs of the slot's latest admission, until their levels are collected
-  handover::Track<LevelState> lvl;           // keyed by ticket: `pending` is the stream's latest job not collected yet
-  long lvl_ticket = 0;
-  // ---- batched hypothesis read-back (sc_get_hyps_batch): pack kernel -> one D2H into pinned memory -------------------
-  int32_t *pack_dev = nullptr, *pack_host = nullptr, *pjobs_host = nullptr, *pjobs_dev = nullptr;
-  size_t pack_cap = 0;            // int32 elements
-  // ---- stable partials (sc_get_hyps_delta): job table and packed outputs, one job per stream; allocated on the first call ----
-  sc_hyp_commit_job *cmjobs_host = nullptr, *cmjobs_dev = nullptr;   // [S]
-  int32_t *cm_dev = nullptr, *cm_host = nullptr;
-  size_t cm_cap = 0;              // int32 elements
-  // ---- CTC forced alignment (sc_align_hyps / sc_align_tokens): job table, labels, outputs, workspaces -----------------
-  char *al_dev = nullptr;         // allocated on the first call, grown geometrically
-  size_t al_cap = 0;
-  // ---- acoustic activity (sc_streams_set_activity): everything below is allocated when the option is first switched on ----
-  bool act_on = false;
-  double act_thr = 0.8;
-  int32_t *act_state = nullptr;   // device [S][6]: the running state of every stream (advanced group by group, encoder stream)
-  double *act_track = nullptr;    // device [S][TCAP]: p_blank per CTC row
-  sc_ctc_activity_job *act_jobs_host = nullptr, *act_jobs_dev = nullptr;   // [N_ARENA][S]: the job table of a group's launch
-  int32_t *act_out_host = nullptr, *act_out_dev = nullptr;                 // [N_ARENA][S][6] host-mapped: the jobs' states-after
-  handover::Track<ActState> act;  // keyed by encoder group: `known` is the state after the latest RETIRED group that scanned the stream
-  // ---- phrase spotting (sc_streams_set_phrases): everything below is allocated when a phrase set is first given ----------
-  bool spot_on = false;
-  int spot_P = 0;
-  int32_t *spot_labels = nullptr, *spot_lens = nullptr;   // device [64][32], [64]: the phrase set
-  double *spot_floors = nullptr;                          // device [64]
-  int32_t *spot_counters = nullptr;   // device [S][2]: n_frames, n_events of every stream (advanced group by group)
-  double *spot_values = nullptr;      // device [S][64][64]
-  int32_t *spot_starts = nullptr;     // device [S][64][64]
-  sc_spot_event *spot_events = nullptr;   // device [S][SC_SPOT_MAX_EVENTS]
-  sc_ctc_spot_job *spot_jobs_host = nullptr, *spot_jobs_dev = nullptr;   // [N_ARENA][S]: the job table of a group's launch
-  int32_t *spot_out_host = nullptr, *spot_out_dev = nullptr;             // [N_ARENA][S][2] host-mapped: the jobs' counters-after
-  handover::Track<SpotState> spot;             // keyed by encoder group, as act
-  std::vector<uint64_t> spot_mask;             // per stream: enabled phrases
-  // ---- draft transcript (sc_streams_set_draft): everything below is allocated when the option is first switched on --------
-  bool draft_on = false;
-  sc_draft_t *draft_state = nullptr;        // device [S]: the running state of every stream (advanced group by group)
-  sc_draft_token *draft_tokens = nullptr;   // device [S][TCAP]: a frame opens at most one token, so the store cannot overflow
-  sc_ctc_draft_job *draft_jobs_host = nullptr, *draft_jobs_dev = nullptr;   // [N_ARENA][S]: the job table of a group's launch
-  sc_draft_t *draft_out_host = nullptr, *draft_out_dev = nullptr;           // [N_ARENA][S] host-mapped: the jobs' states-after
-  handover::Track<DraftState> draft;              // keyed by encoder group, as act
-  // ---- CTC prefix beam search (sc_streams_set_ctc_beam): everything below is allocated when the option is first switched on ----
-  bool beam_on = false;
-  int beam_B = 0, beam_C = 0;
-  int beam_nodes_B = 0;                     // the B the node store was sized for
-  sc_beam_t *beam_state = nullptr;          // device [S]: the running state of every stream (advanced group by group)
-  sc_beam_node *beam_nodes = nullptr;       // device [S][1 + beam_nodes_B * TCAP]: a frame adds at most B nodes, so the store cannot overflow
-  sc_ctc_beam_job *beam_jobs_host = nullptr, *beam_jobs_dev = nullptr;   // [N_ARENA][S]: the job table of a group's launch
-  sc_beam_t *beam_out_host = nullptr, *beam_out_dev = nullptr;           // [N_ARENA][S] host-mapped: the jobs' states-after
-  handover::Track<BeamState> beam;          // keyed by encoder group, as act
-  // language model fused into the beam (sc_streams_set_ctc_beam_lm): allocated when a model is first attached
-  const sc_lm *beam_lm = nullptr;           // the caller's model (NULL: none - the group launches sc_ctc_beam as before)
-  const sc_lm_view *beam_lm_view = nullptr; // its device view
-  sc_lm_view beam_lm_info{};                // ... and a host copy of it
-  double beam_alpha = 0.0, beam_beta = 0.0;
-  sc_beam_lm_t *beam_lm_state = nullptr;    // device [S], beside beam_state
-  sc_ctc_beam_lm_job *beam_lm_jobs_host = nullptr, *beam_lm_jobs_dev = nullptr;   // [N_ARENA][S]
-  sc_beam_lm_t *beam_lm_out_host = nullptr, *beam_lm_out_dev = nullptr;           // [N_ARENA][S] host-mapped, beside beam_out
-  // grammars (sc_stream_set_grammar): a menu belongs to a stream.  Allocated when a grammar is first set on the handle.
-  std::vector<sc_grammar *> beam_gr;         // [S] the stream's grammar (NULL: none); the handle holds one use of each
-  int beam_gr_n = 0;                         // streams with a grammar
-  sc_beam_gr_t *beam_gr_state = nullptr;    // device [S], beside beam_state
-  sc_ctc_beam_gr_job *beam_gr_jobs_host = nullptr, *beam_gr_jobs_dev = nullptr;   // [N_ARENA][S]
-  sc_beam_gr_t *beam_gr_out_host = nullptr, *beam_gr_out_dev = nullptr;           // [N_ARENA][S] host-mapped, beside beam_out
-  char *bh_dev = nullptr, *bh_host = nullptr;   // sc_ctc_beam_hyps: states, pack jobs and packed outputs; grown geometrically
-  size_t bh_cap = 0;
-  char *rs_dev = nullptr, *rs_host = nullptr;   // sc_rescore_hyps / sc_lm_rescore_lists: job table, inputs, outputs; grown geometrically
-  size_t rs_cap = 0;
-  // ---- attention rescoring (sc_attention_rescore_beam / _lists): everything below is allocated by the first call ----
-  char *ar_dev = nullptr, *ar_host = nullptr;   // the lists' inputs and the outputs; grown geometrically
-  size_t ar_cap = 0;
-  char *ar_ws = nullptr;                        // workspace of sc_dec_rescore: what a call needs, at most ar_ws_limit bytes
-  size_t ar_ws_bytes = 0, ar_ws_limit = SC_ATT_WS_DEFAULT_BYTES;
-  void *ar_splitk = nullptr;                    // split-K workspace of the read-back stream (the fused feed-forward's partial sums)
-  size_t beam_ncap() const { return 1 + (size_t)beam_nodes_B * TCAP; }
-  // ---- tick engine -----------------------------------------------------------------------------------------------------
-  std::vector<St> st;
-  std::vector<Run> run;
-  std::vector<std::deque<Blk>> bq;
-  std::vector<Job> job;                    // the OLDEST outstanding chunk of a stream (reported next)
-  std::vector<std::deque<Job>> ahead;      // chunks queued behind it (queue_depth > 1)
-  std::vector<long> job_seq;               // sequence number of the stream's latest chunk
-  int queue_depth = 1;                     // outstanding chunks a stream may have (sc_streams_set_queue_depth)
-  std::vector<Snap> snap;
-  std::vector<long> done_at;               // sc_poll: order in which the streams' oldest chunks became complete (0: not yet)
-  long done_counter = 0;
-  int32_t *snap_yseq = nullptr, *snap_xpos = nullptr;   // [S*W][LCAP]
-  double *snap_score = nullptr;                         // [S*W][3]
-  hipEvent_t ev_snap = nullptr;
-  std::vector<std::string> fault_msg;
-  std::vector<long> enc_gen;       // group of the stream's latest encoder stage
-  std::deque<EncGroup *> groups;   // planned or in flight, oldest first
-  long gen_next = 1, gen_done = 0, gen_ordered = 0;   // groups: issued, known complete, main stream ordered behind
-  int n_open = 0;                  // outstanding chunks
-  long iter = 0;
-  bool inflight = false;           // a decode step has been enqueued and not collected yet (between two sc_poll calls)
-  std::vector<int> tick_active;    // ... for these streams
-  std::chrono::steady_clock::time_point tick_t0, tick_t1;
-  hipStream_t stream_rb = nullptr; // hypothesis read-back (sc_get_hyps_batch) beside an enqueued decode step
-  bool poisoned = false;           // a call failed half-way: device and host state may disagree
-  std::vector<int> rowmap_key;
-  int row_bucket = 1, n_rows_step = 0;
-  bool decode_prepared = false;
-  std::map<int, hipGraphExec_t> dec_graphs;
-  std::map<std::vector<long>, hipGraphExec_t> enc_graphs;
-  long dec_steps = 0, dec_blocks = 0, enc_calls = 0, xattn_rows[3] = {0, 0, 0};   // [0] flash kernels, [1] head-parallel layer kernels, [2] stream-resident layer kernel
-  long sattn_pos[3] = {0, 0, 0};           // token positions the self-attention covered (sum of L over steps, streams, layers)
-  unsigned long long *stat_rows = nullptr; // device [3]: distinct self-attention K|V rows read (sc_search.stat_rows)
-  double t_launch = 0, t_wait = 0;               // seconds in the step loop: issuing, waiting for the flags
-  double t_bucket[17] = {0};                     // ... by compaction bucket (n_rows_step / (row_bucket*W))
-  long n_bucket[17] = {0};
-  bool use_graphs = true;
-  long n_enc_captures = 0;        // encoder-layer graphs captured (one per group shape) and the host time that took
-  double t_enc_capture = 0;
-
-  ~sc_streams() {
-    for (auto &g : dec_graphs) (void)hipGraphExecDestroy(g.second);
-    for (auto &g : enc_graphs) (void)hipGraphExecDestroy(g.second);
-    if (stream) (void)sc_set_stream_workspace(stream, nullptr, 0);
-    if (stream_enc) {
-      (void)sc_set_stream_workspace(stream_enc, nullptr, 0);
-      (void)hipStreamDestroy(stream_enc);
-    }
-    for (int i = 0; i < 2; ++i)
-      if (ev_iter[i]) (void)hipEventDestroy(ev_iter[i]);
-    for (int i = 0; i < N_ARENA; ++i)
-      if (ev_group[i]) (void)hipEventDestroy(ev_group[i]);
-    for (int i = 0; i < N_STAGE; ++i)
-      if (ev_stage[i]) (void)hipEventDestroy(ev_stage[i]);
-    if (ev_snap) (void)hipEventDestroy(ev_snap);
-    for (EncGroup *g : groups) delete g;
-    for (void *p : owned) (void)hipFree(p);
-    for (void *p : owned_host) (void)hipHostFree(p);
-    if (stream_rb && ar_splitk) (void)sc_set_stream_workspace(stream_rb, nullptr, 0);
-    if (stream_rb) (void)hipStreamDestroy(stream_rb);
-    if (stream) (void)hipStreamDestroy(stream);
-    if (ar_dev) (void)hipFree(ar_dev);
-    if (ar_host) (void)hipHostFree(ar_host);
-    if (ar_ws) (void)hipFree(ar_ws);
-    if (ar_splitk) (void)hipFree(ar_splitk);
-    if (al_dev) (void)hipFree(al_dev);
-    if (beam_nodes) (void)hipFree(beam_nodes);
-    for (sc_grammar *g : beam_gr)   // (the streams are synchronised: nothing reads a grammar any more)
-      if (g) (void)sc_grammar_use(g, -1);
-    if (bh_dev) (void)hipFree(bh_dev);
-    if (bh_host) (void)hipHostFree(bh_host);
-    if (rs_dev) (void)hipFree(rs_dev);
-    if (rs_host) (void)hipHostFree(rs_host);
-  }
-
-  template <typename T>
-  int alloc(T **p, size_t n) {
-    RC_TRY(dalloc(p, n));
-    owned.push_back(*p);
-    return SC_OK;
-  }
-  template <typename T>
-  int halloc(T **p, size_t n) {   // pinned, device-visible
-    HIP_TRY(hipHostMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)));
-    owned_host.push_back(*p);
-    memset(*p, 0, std::max<size_t>(n, 1) * sizeof(T));
-    return SC_OK;
-  }
-  template <typename T>
-  int halloc_mapped(T **host, T **dev, size_t n, const char *who, const char *what) {   // ... and its device view
-    RC_TRY(halloc(host, n));
-    void *dv = nullptr;
-    if (hipHostGetDevicePointer(&dv, *host, 0) != hipSuccess || !dv) {
-      sc_set_error("%s: the pinned %s are not visible to the device", who, what);
-      return SC_ERR_LAUNCH;
-    }
-    *dev = (T *)dv;
-    return SC_OK;
-  }
-  int32_t *ctrl_host() { return ctrlmap_host; }              // [S][8]
-  int32_t *rowmap_host() { return rm_host[rm_idx]; }          // [S*W]
-
-  // host int table -> device (slot `cur_slot` of the pinned arena, async copy on the encoder-side stream; the launches
-  // that read it are ordered behind the copy; a slot is recycled when its group's event has completed)
-  int itensor(const std::vector<int32_t> &a, const int32_t **out) {
-    const size_t n = a.size();
-    if (arena_off + n > slot_cap) {
-      sc_set_error("job-table arena exhausted (%zu + %zu of %zu entries)", arena_off, n, slot_cap);
-      return SC_ERR_ARG;
-    }
-    const size_t off = (size_t)cur_slot * slot_cap + arena_off;
-    arena_off += (n + 63) & ~size_t(63);
-    if (n) {
-      memcpy(arena_host + off, a.data(), n * sizeof(int32_t));
-      HIP_TRY(hipMemcpyAsync(arena_dev + off, arena_host + off, n * sizeof(int32_t), hipMemcpyHostToDevice, es));
-    }
-    *out = arena_dev + off;
-    return SC_OK;
-  }
-};
 
 
 namespace {
@@ -1092,13 +563,15 @@ int retire_groups(sc_streams *b) {
 
 // host-blocking wait for the group `gen` (and, the stream being in order, every group before it)
 int launch_pending_groups(sc_streams *b, long upto = -1);
-int wait_group(sc_streams *b, long gen) {
+}  // namespace
+int sc_state::wait_group(sc_streams *b, long gen) {   // (shared with the read-back services: streams_state.h)
   if (gen <= b->gen_done) return SC_OK;
   RC_TRY(launch_pending_groups(b, gen));
   const int slot = (int)(gen % N_ARENA);
   HIP_TRY(hipEventSynchronize(b->ev_group[slot]));
   return retire_groups(b);
 }
+namespace {
 
 // what the jobs of every side-state option share: the stream's CTC table and the span of its rows
 template <typename J>
@@ -2031,18 +1504,6 @@ int poison(sc_streams *b, int rc) {
   return rc;
 }
 
-#define SC_API_BEGIN try {
-#define SC_API_END                                                            \
-  } catch (const std::bad_alloc &) {                                         \
-    sc_set_error("%s: out of host memory", __func__);                        \
-    return SC_ERR_ARG;                                                       \
-  } catch (const std::exception &ex) {                                       \
-    sc_set_error("%s: %s", __func__, ex.what());                             \
-    return SC_ERR_ARG;                                                       \
-  } catch (...) {                                                            \
-    sc_set_error("%s: unexpected exception", __func__);                      \
-    return SC_ERR_ARG;                                                       \
-  }
 
 // depth: outstanding chunks a stream may have INCLUDING the new one (sc_push, sc_push_features: 1)
 int check_chunks(sc_streams *b, const int *stream_ids, const int *counts, int n, const char *what, int depth = 1) {
@@ -3028,30 +2489,17 @@ extern "C" int sc_get_hyps_batch(sc_streams *b, const int *stream_ids, int n, in
   std::vector<char> listed(b->S, 0);
   for (int i = 0; i < n; ++i) {
     const int s = stream_ids[i];
-    SC_CHECK_ARG(s >= 0 && s < b->S, "stream out of range");
-    SC_CHECK_ARG(!listed[s], "a stream is listed twice");
-    listed[s] = 1;
-    const Snap &sn = b->snap[s];
-    if (sn.valid) {   // queue depth > 1: the copy taken when the stream's last reported chunk completed
-      const int nh = std::min(nbest, sn.nhyp);
-      n_hyps[i] = nh;
-      SC_CHECK_ARG(nh == 0 || (!ids && !xpos) || max_len >= sn.L, "max_len is smaller than the hypotheses");
-      for (int h = 0; h < nh; ++h) {
-        jobs.insert(jobs.end(), {(int32_t)((size_t)s * b->W + h), sn.L, (int32_t)off, 1});
-        off += (size_t)((2 * sn.L + 1) & ~1) + 6;
-      }
-      from_snapshot = true;
-      continue;
-    }
-    SC_CHECK_ARG(!b->run[s].inblk && b->bq[s].empty(), "stream is inside a decode block (its chunk has not been reported yet)");
-    const St &st = b->st[s];
-    const int nh = st.started ? std::min(nbest, st.nhyp) : 0;
+    RC_TRY(listed_once(b, s, listed));
+    HypSrc src;
+    RC_TRY(hyp_source(b, s, &src));
+    const int nh = std::min(nbest, src.nh);
     n_hyps[i] = nh;
-    SC_CHECK_ARG(nh == 0 || (!ids && !xpos) || max_len >= st.L, "max_len is smaller than the hypotheses");
+    SC_CHECK_ARG(nh == 0 || (!ids && !xpos) || max_len >= src.L, "max_len is smaller than the hypotheses");
     for (int h = 0; h < nh; ++h) {
-      jobs.insert(jobs.end(), {(int32_t)(((size_t)st.cur * b->S + s) * b->W + h), st.L, (int32_t)off, 0});
-      off += (size_t)((2 * st.L + 1) & ~1) + 6;
+      jobs.insert(jobs.end(), {(int32_t)(src.row + h), src.L, (int32_t)off, src.snap ? 1 : 0});
+      off += (size_t)((2 * src.L + 1) & ~1) + 6;
     }
+    from_snapshot = from_snapshot || (src.snap && nh > 0);
   }
   const int m = (int)jobs.size() / 4;
   if (m == 0) return SC_OK;
@@ -3082,546 +2530,6 @@ extern "C" int sc_get_hyps_batch(sc_streams *b, const int *stream_ids, int n, in
   SC_API_END
 }
 
-// ---- stable partials ----------------------------------------------------------------------------------
-// The committed prefix of the listed streams' live beams and the tails of their best hypotheses behind from[i]: ONE
-// job-table upload, ONE sc_hyp_commit launch, ONE copy back, all on the read-back stream as sc_get_hyps_batch does it.  A
-// job's outputs lie packed at an even int32 offset of cm_dev: [header: 4][agree: SC_COMMIT_MAX_HYPS][totals: 3 doubles]
-// [stability: t doubles][ids: t][positions: t] with t = L - from.  Reads the engine's state, changes none.
-extern "C" int sc_get_hyps_delta(sc_streams *b, const int *stream_ids, int n, const int *from, const int *final,
-                                 int max_tail, int32_t *L_out, int32_t *commit, int32_t *n_hyps, int32_t *ids,
-                                 int32_t *xpos, double *stability, double *scores, int32_t *status) {
-  SC_CHECK_ARG(b && stream_ids && from && n >= 0 && max_tail >= 0, "bad arguments");
-  SC_API_BEGIN
-  HIP_TRY(hipSetDevice(b->eng->device));
-  SC_CHECK_ARG(n <= b->S, "more streams listed than the batch has");
-  if (!b->cmjobs_host) {   // the first call (the last of the four allocations marks them done): a handle that never asks holds none
-    b->cm_cap = (size_t)b->S * (4 * (size_t)b->LCAP + CM_FIXED + 2);
-    RC_TRY(b->alloc(&b->cm_dev, b->cm_cap));
-    RC_TRY(b->alloc(&b->cmjobs_dev, (size_t)b->S));
-    RC_TRY(b->halloc(&b->cm_host, b->cm_cap));
-    RC_TRY(b->halloc(&b->cmjobs_host, (size_t)b->S));
-  }
-  std::vector<char> listed(b->S, 0);
-  std::vector<int> job_of(n, -1);
-  std::vector<size_t> offs;
-  size_t off = 0;
-  int m = 0;
-  bool from_snapshot = false;
-  for (int i = 0; i < n; ++i) {
-    const int s = stream_ids[i];
-    SC_CHECK_ARG(s >= 0 && s < b->S, "stream out of range");
-    SC_CHECK_ARG(!listed[s], "a stream is listed twice");
-    listed[s] = 1;
-    const Snap &sn = b->snap[s];
-    int nh, L;
-    size_t row;
-    if (sn.valid) {   // queue depth > 1: the copy taken when the stream's last reported chunk completed
-      nh = sn.nhyp; L = sn.L; row = (size_t)s * b->W;
-      from_snapshot = from_snapshot || nh > 0;
-    } else {
-      SC_CHECK_ARG(!b->run[s].inblk && b->bq[s].empty(), "stream is inside a decode block (its chunk has not been reported yet)");
-      const St &st = b->st[s];
-      nh = st.started ? st.nhyp : 0; L = st.L; row = ((size_t)st.cur * b->S + s) * b->W;
-    }
-    if (nh == 0) {
-      SC_CHECK_ARG(from[i] == 0, "from is beyond the hypotheses");
-      continue;
-    }
-    SC_CHECK_ARG(nh <= SC_COMMIT_MAX_HYPS, "more than SC_COMMIT_MAX_HYPS live hypotheses");
-    SC_CHECK_ARG(from[i] >= 0 && from[i] <= L, "from is beyond the hypotheses");
-    const int t = L - from[i];
-    SC_CHECK_ARG(t <= max_tail, "max_tail is smaller than the tail");
-    sc_hyp_commit_job &j = b->cmjobs_host[m];
-    int32_t *o = b->cm_dev + off;
-    if (sn.valid) {
-      j.yseq = b->snap_yseq + row * b->LCAP;
-      j.xpos = b->snap_xpos + row * b->LCAP;
-      j.score = b->snap_score + row * 3;
-      j.score_dec = j.score + 1;
-      j.score_ctc = j.score + 2;
-      j.score_stride = 3;
-    } else {
-      j.yseq = b->sb.yseq + row * b->LCAP;
-      j.xpos = b->sb.xpos + row * b->LCAP;
-      j.score = b->sb.score + row;
-      j.score_dec = b->sb.sc_dec + row;
-      j.score_ctc = b->sb.sc_ctc + row;
-      j.score_stride = 1;
-    }
-    j.header = o;
-    j.agree = o + 4;
-    j.totals = (double *)(o + 4 + SC_COMMIT_MAX_HYPS);
-    j.stability = j.totals + 3;
-    j.ids = o + CM_FIXED + 2 * (size_t)t;
-    j.pos = j.ids + t;
-    j.row_stride = b->LCAP;
-    j.n_hyp = nh; j.L = L; j.from = from[i];
-    j.flags = (final && final[i]) ? SC_COMMIT_FINAL : 0;
-    job_of[i] = m++;
-    offs.push_back(off);
-    off += ((size_t)CM_FIXED + 4 * (size_t)t + 1) & ~(size_t)1;
-  }
-  SC_CHECK_ARG(off <= b->cm_cap, "tails exceed the read-back buffer");
-  if (m > 0) {
-    // on the read-back stream: a decode step of OTHER streams may be in flight on the batch's stream (sc_poll); the
-    // listed streams' last steps have been collected (host-synchronised) by then
-    const int rc = [&]() -> int {
-      HIP_TRY(hipMemcpyAsync(b->cmjobs_dev, b->cmjobs_host, (size_t)m * sizeof(sc_hyp_commit_job), hipMemcpyHostToDevice, b->stream_rb));
-      if (from_snapshot) HIP_TRY(hipStreamWaitEvent(b->stream_rb, b->ev_snap, 0));   // the copies are written on the batch's stream
-      RC_TRY(sc_hyp_commit(b->cmjobs_dev, m, b->stream_rb));
-      HIP_TRY(hipMemcpyAsync(b->cm_host, b->cm_dev, off * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream_rb));
-      HIP_TRY(hipStreamSynchronize(b->stream_rb));
-      return SC_OK;
-    }();
-    if (rc != SC_OK) {   // nothing of this call may still read the pinned job table when the next call fills it
-      (void)hipStreamSynchronize(b->stream_rb);
-      return rc;
-    }
-  }
-  for (int i = 0; i < n; ++i) {
-    const int k = job_of[i];
-    if (k < 0) {
-      if (L_out) L_out[i] = 0;
-      if (commit) commit[i] = 0;
-      if (n_hyps) n_hyps[i] = 0;
-      if (status) status[i] = 0;
-      if (scores) scores[3 * i] = scores[3 * i + 1] = scores[3 * i + 2] = 0.0;
-      continue;
-    }
-    const int32_t *src = b->cm_host + offs[k];
-    const size_t t = (size_t)(b->cmjobs_host[k].L - from[i]);
-    if (L_out) L_out[i] = src[0];
-    if (commit) commit[i] = src[1];
-    if (n_hyps) n_hyps[i] = src[2];
-    if (status) status[i] = src[3];
-    const double *d = (const double *)(src + 4 + SC_COMMIT_MAX_HYPS);
-    if (scores) memcpy(scores + 3 * (size_t)i, d, 3 * sizeof(double));
-    if (stability) memcpy(stability + (size_t)i * max_tail, d + 3, t * sizeof(double));
-    if (ids) memcpy(ids + (size_t)i * max_tail, src + CM_FIXED + 2 * t, t * 4);
-    if (xpos) memcpy(xpos + (size_t)i * max_tail, src + CM_FIXED + 3 * t, t * 4);
-  }
-  return SC_OK;
-  SC_API_END
-}
-
-// ---- n-gram rescoring of n-best lists ---------------------------------------------------------------
-// rs_dev / rs_host hold [job table][inputs of caller-given lists][outputs]: what lies before the outputs goes up in ONE
-// copy, ONE sc_lm_rescore launch, the outputs come back in ONE copy, all on the read-back stream.  A job's outputs:
-// fused, lm, eos_lm [16] doubles, then end_state, order, status [16] int32.
-namespace {
-constexpr size_t RS_OUT = (size_t)SC_RESCORE_MAX_HYPS * (3 * sizeof(double) + 3 * sizeof(int32_t));
-
-int rs_reserve(sc_streams *b, size_t need) {
-  if (need <= b->rs_cap) return SC_OK;
-  HIP_TRY(hipStreamSynchronize(b->stream_rb));
-  if (b->rs_dev) (void)hipFree(b->rs_dev);
-  if (b->rs_host) (void)hipHostFree(b->rs_host);
-  const size_t cap = std::max(need, 2 * b->rs_cap);
-  b->rs_dev = b->rs_host = nullptr;
-  b->rs_cap = 0;
-  HIP_TRY(hipMalloc((void **)&b->rs_dev, cap));
-  HIP_TRY(hipHostMalloc((void **)&b->rs_host, cap));
-  b->rs_cap = cap;
-  return SC_OK;
-}
-
-void rs_outputs(sc_lm_rescore_job &j, char *out) {
-  j.fused = (double *)out;
-  j.lm = j.fused + SC_RESCORE_MAX_HYPS;
-  j.eos_lm = j.lm + SC_RESCORE_MAX_HYPS;
-  j.end_state = (int32_t *)(j.eos_lm + SC_RESCORE_MAX_HYPS);
-  j.order = j.end_state + SC_RESCORE_MAX_HYPS;
-  j.status = j.order + SC_RESCORE_MAX_HYPS;
-  j.tok_lm = nullptr;
-  j.tok_stride = 0;
-}
-
-// the m jobs at the head of rs_host, with whatever else lies before o_out, go up; the outputs [o_out, o_out + m RS_OUT) come back
-int rs_run(sc_streams *b, size_t o_out, int m, bool from_snapshot) {
-  const int rc = [&]() -> int {
-    HIP_TRY(hipMemcpyAsync(b->rs_dev, b->rs_host, o_out, hipMemcpyHostToDevice, b->stream_rb));
-    if (from_snapshot) HIP_TRY(hipStreamWaitEvent(b->stream_rb, b->ev_snap, 0));   // the copies are written on the batch's stream
-    RC_TRY(sc_lm_rescore((const sc_lm_rescore_job *)b->rs_dev, m, b->stream_rb));
-    HIP_TRY(hipMemcpyAsync(b->rs_host + o_out, b->rs_dev + o_out, (size_t)m * RS_OUT, hipMemcpyDeviceToHost, b->stream_rb));
-    HIP_TRY(hipStreamSynchronize(b->stream_rb));
-    return SC_OK;
-  }();
-  if (rc != SC_OK) (void)hipStreamSynchronize(b->stream_rb);   // nothing of this call may still read the pinned table
-  return rc;
-}
-
-// the outputs of job k -> row i of the caller's [n][nbest] arrays (nh entries each)
-void rs_copy_out(const char *out, size_t i, int nbest, int nh, int32_t *order, double *fused, double *lm_sum, double *eos_lm,
-                 int32_t *status, int32_t *end_state) {
-  const double *d = (const double *)out;
-  const int32_t *q = (const int32_t *)(d + 3 * SC_RESCORE_MAX_HYPS);
-  const size_t o = i * (size_t)nbest;
-  if (fused) memcpy(fused + o, d, nh * sizeof(double));
-  if (lm_sum) memcpy(lm_sum + o, d + SC_RESCORE_MAX_HYPS, nh * sizeof(double));
-  if (eos_lm) memcpy(eos_lm + o, d + 2 * SC_RESCORE_MAX_HYPS, nh * sizeof(double));
-  if (end_state) memcpy(end_state + o, q, nh * sizeof(int32_t));
-  if (order) memcpy(order + o, q + SC_RESCORE_MAX_HYPS, nh * sizeof(int32_t));
-  if (status) memcpy(status + o, q + 2 * SC_RESCORE_MAX_HYPS, nh * sizeof(int32_t));
-}
-
-int rs_model(const sc_lm *lm, double alpha, double beta, int lm_eos, const sc_lm_view **view, sc_lm_view *info) {
-  SC_CHECK_ARG(std::isfinite(alpha) && std::isfinite(beta), "alpha and beta must be finite");
-  RC_TRY(sc_lm_device_view(lm, view, info));
-  SC_CHECK_ARG(*view, "the model has no device view");
-  SC_CHECK_ARG(lm_eos >= -1 && lm_eos < info->V, "lm_eos is outside the model's vocabulary");
-  return SC_OK;
-}
-}  // namespace
-
-// The hypotheses sc_get_hyps_batch would return (same rules: the snapshot with a queue depth > 1, an error for a stream
-// inside a decode block or listed twice), rescored: labels without <sos> and without a trailing <eos>.  Reads the
-// engine's state, changes none, keeps none of its own; synchronised before it returns.
-extern "C" int sc_rescore_hyps(sc_streams *b, const int *stream_ids, int n, int nbest, const sc_lm *lm, double alpha,
-                               double beta, int lm_eos, const int *final, int32_t *order, double *fused, double *lm_sum,
-                               double *eos_lm, int32_t *status, int *n_hyps) {
-  SC_CHECK_ARG(b && stream_ids && lm && n_hyps && n >= 0 && nbest >= 0 && nbest <= SC_RESCORE_MAX_HYPS, "bad arguments");
-  SC_API_BEGIN
-  HIP_TRY(hipSetDevice(b->eng->device));
-  SC_CHECK_ARG(n <= b->S, "more streams listed than the batch has");
-  sc_lm_view info;
-  const sc_lm_view *view = nullptr;
-  RC_TRY(rs_model(lm, alpha, beta, lm_eos, &view, &info));
-  SC_CHECK_ARG(info.V == b->cfg.vocab_size, "the model's vocabulary size is not the batch's");
-  const size_t o_out = (size_t)std::max(n, 1) * sizeof(sc_lm_rescore_job);
-  RC_TRY(rs_reserve(b, o_out + (size_t)std::max(n, 1) * RS_OUT));
-  sc_lm_rescore_job *jobs = (sc_lm_rescore_job *)b->rs_host;
-  std::vector<char> listed(b->S, 0);
-  std::vector<int> job_of(n, -1);
-  int m = 0;
-  bool from_snapshot = false;
-  for (int i = 0; i < n; ++i) {
-    const int s = stream_ids[i];
-    SC_CHECK_ARG(s >= 0 && s < b->S, "stream out of range");
-    SC_CHECK_ARG(!listed[s], "a stream is listed twice");
-    listed[s] = 1;
-    const Snap &sn = b->snap[s];
-    int nh, L;
-    sc_lm_rescore_job j{};
-    if (sn.valid) {   // queue depth > 1: the copy taken when the stream's last reported chunk completed
-      const size_t row = (size_t)s * b->W;
-      nh = std::min(nbest, sn.nhyp); L = sn.L;
-      j.yseq = b->snap_yseq + row * b->LCAP;
-      j.score = b->snap_score + row * 3;
-      j.score_stride = 3;
-      from_snapshot = from_snapshot || nh > 0;
-    } else {
-      SC_CHECK_ARG(!b->run[s].inblk && b->bq[s].empty(), "stream is inside a decode block (its chunk has not been reported yet)");
-      const St &st = b->st[s];
-      const size_t row = ((size_t)st.cur * b->S + s) * b->W;
-      nh = st.started ? std::min(nbest, st.nhyp) : 0; L = st.L;
-      j.yseq = b->sb.yseq + row * b->LCAP;
-      j.score = b->sb.score + row;
-      j.score_stride = 1;
-    }
-    n_hyps[i] = nh;
-    if (nh == 0) continue;
-    j.model = view;
-    j.lens = nullptr;
-    rs_outputs(j, b->rs_dev + o_out + (size_t)m * RS_OUT);
-    j.row_stride = b->LCAP;
-    j.alpha = alpha; j.beta = beta;
-    j.n_hyp = nh; j.L = L; j.skip = 1; j.strip = b->cfg.eos_id; j.state0 = -1;
-    j.lm_eos = (final && final[i]) ? lm_eos : -1;
-    j.V = info.V; j.flags = 0;
-    jobs[m] = j;
-    job_of[i] = m++;
-  }
-  if (m > 0) RC_TRY(rs_run(b, o_out, m, from_snapshot));
-  for (int i = 0; i < n; ++i)
-    if (job_of[i] >= 0)
-      rs_copy_out(b->rs_host + o_out + (size_t)job_of[i] * RS_OUT, (size_t)i, nbest, n_hyps[i], order, fused, lm_sum, eos_lm,
-                  status, nullptr);
-  return SC_OK;
-  SC_API_END
-}
-
-// The same launch for caller-given lists: list i has list_sizes[i] <= nbest rows, row r its lens[i][r] LABELS
-// ids[i][r][0 .. lens) (nothing skipped, nothing stripped) and its total scores[i][r]; state0[i] is the automaton's state
-// before the first label (-1, or state0 == NULL: the model's start_state).  How a decoder-free stream's final gets its
-// </s> term (the ids and totals of sc_ctc_beam_hyps), and how any list from elsewhere is rescored.
-extern "C" int sc_lm_rescore_lists(sc_streams *b, const sc_lm *lm, const int32_t *ids, const int32_t *lens,
-                                   const double *scores, const int *list_sizes, int n, int nbest, int max_len,
-                                   const int32_t *state0, double alpha, double beta, int lm_eos, int32_t *order,
-                                   double *fused, double *lm_sum, double *eos_lm, int32_t *status, int32_t *end_state) {
-  SC_CHECK_ARG(b && lm && lens && scores && list_sizes && n >= 0 && n <= SC_RESCORE_MAX_JOBS && nbest >= 0 &&
-               nbest <= SC_RESCORE_MAX_HYPS && max_len >= 0 && (ids || max_len == 0), "bad arguments");
-  SC_API_BEGIN
-  HIP_TRY(hipSetDevice(b->eng->device));
-  sc_lm_view info;
-  const sc_lm_view *view = nullptr;
-  RC_TRY(rs_model(lm, alpha, beta, lm_eos, &view, &info));
-  const size_t rows = (size_t)n * nbest;
-  const size_t o_sc = (size_t)std::max(n, 1) * sizeof(sc_lm_rescore_job), o_len = o_sc + rows * sizeof(double),
-               o_ids = o_len + ((rows * sizeof(int32_t) + 7) & ~(size_t)7),
-               o_out = o_ids + ((rows * max_len * sizeof(int32_t) + 7) & ~(size_t)7);
-  for (int i = 0; i < n; ++i) {
-    SC_CHECK_ARG(list_sizes[i] >= 0 && list_sizes[i] <= nbest, "a list size outside [0, nbest]");
-    SC_CHECK_ARG(!state0 || (state0[i] >= -1 && state0[i] < info.n_states), "a state0 outside the model's states");
-  }
-  RC_TRY(rs_reserve(b, o_out + (size_t)std::max(n, 1) * RS_OUT));
-  sc_lm_rescore_job *jobs = (sc_lm_rescore_job *)b->rs_host;
-  memcpy(b->rs_host + o_sc, scores, rows * sizeof(double));
-  memcpy(b->rs_host + o_len, lens, rows * sizeof(int32_t));
-  if (rows * max_len) memcpy(b->rs_host + o_ids, ids, rows * max_len * sizeof(int32_t));
-  std::vector<int> job_of(n, -1);
-  int m = 0;
-  for (int i = 0; i < n; ++i) {
-    if (list_sizes[i] == 0) continue;
-    sc_lm_rescore_job j{};
-    j.model = view;
-    j.yseq = (const int32_t *)(b->rs_dev + o_ids) + (size_t)i * nbest * max_len;
-    j.score = (const double *)(b->rs_dev + o_sc) + (size_t)i * nbest;
-    j.lens = (const int32_t *)(b->rs_dev + o_len) + (size_t)i * nbest;
-    rs_outputs(j, b->rs_dev + o_out + (size_t)m * RS_OUT);
-    j.row_stride = max_len; j.score_stride = 1;
-    j.alpha = alpha; j.beta = beta;
-    j.n_hyp = list_sizes[i]; j.L = max_len; j.skip = 0; j.strip = -1; j.state0 = state0 ? state0[i] : -1;
-    j.lm_eos = lm_eos; j.V = info.V; j.flags = 0;
-    jobs[m] = j;
-    job_of[i] = m++;
-  }
-  if (m > 0) RC_TRY(rs_run(b, o_out, m, false));
-  for (int i = 0; i < n; ++i)
-    if (job_of[i] >= 0)
-      rs_copy_out(b->rs_host + o_out + (size_t)job_of[i] * RS_OUT, (size_t)i, nbest, list_sizes[i], order, fused, lm_sum,
-                  eos_lm, status, end_state);
-  return SC_OK;
-  SC_API_END
-}
-
-// ---- CTC forced alignment ------------------------------------------------------------------------------------------
-// One sc_ctc_align launch pair on the read-back stream for a list of (stream, frames, labels) requests; outputs back to
-// the host.  The device area holds [job table][labels][outputs: start, end | logp_mean | path_score, status][workspaces].
-struct AlignReq { int s, T; std::vector<int32_t> y; };
-struct AlignOut {
-  std::vector<int32_t> start, end;
-  std::vector<float> lp;
-  float score;
-  int32_t status;
-  // alt_K > 0 (sc_alternates_hyps): [L][K] ids and logp, [L] own_rank and span status
-  std::vector<int32_t> alt_ids, own_rank, span_status;
-  std::vector<double> alt_logp;
-};
-
-static size_t al_round(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// alt_K > 0: ONE sc_ctc_alternates launch behind them reads start / end where the alignment left them on the device; its
-// job table travels in the same upload (behind the labels), its outputs come back in the same copy (behind the
-// alignment's: [alt_logp: doubles][alt_ids | own_rank | span status]).  The alignment's launches, areas and bits are the
-// same with and without it.
-static int run_align(sc_streams *b, const std::vector<AlignReq> &reqs, bool after_snap, std::vector<AlignOut> &out,
-                     int alt_K = 0) {
-  const int n = (int)reqs.size();
-  out.assign(n, AlignOut());
-  if (n == 0) return SC_OK;
-  int max_T = 0, max_L = 0;
-  size_t n_lab = 0;
-  for (const AlignReq &r : reqs) {
-    max_T = std::max(max_T, r.T);
-    max_L = std::max(max_L, (int)r.y.size());
-    n_lab += r.y.size();
-  }
-  SC_CHECK_ARG(max_L <= SC_ALIGN_MAX_L, "a label sequence is longer than SC_ALIGN_MAX_L");
-  const size_t o_lab = al_round((size_t)n * sizeof(sc_ctc_align_job));
-  const size_t K = (size_t)alt_K;
-  const size_t o_alt = o_lab + al_round(n_lab * 4);   // the alternates' job table (empty without them)
-  const size_t o_out = o_alt + (alt_K ? al_round((size_t)n * sizeof(sc_ctc_alt_job)) : 0);
-  const size_t n_alw = 3 * n_lab + 2 * (size_t)n;   // start, end, logp_mean per label; path_score, status per job
-  const size_t o_altout = (n_alw * 4 + 7) & ~(size_t)7;   // (bytes behind o_out; doubles first)
-  const size_t n_outb = alt_K ? o_altout + n_lab * K * 8 + (n_lab * K + 2 * n_lab) * 4 : n_alw * 4;
-  size_t o_ws = o_out + al_round(n_outb), total = o_ws;
-  for (const AlignReq &r : reqs) total += al_round(sc_ctc_align_ws_bytes(r.T));
-  if (total > b->al_cap) {
-    const size_t cap = std::max(total, 2 * b->al_cap);   // geometric: few reallocations (a hipFree may stall the device)
-    if (b->al_dev) {
-      HIP_TRY(hipStreamSynchronize(b->stream_rb));
-      HIP_TRY(hipFree(b->al_dev));
-      b->al_dev = nullptr;
-      b->al_cap = 0;
-    }
-    HIP_TRY(hipMalloc((void **)&b->al_dev, cap));
-    b->al_cap = cap;
-  }
-  char *D = b->al_dev;
-  std::vector<char> host(o_out, 0);
-  sc_ctc_align_job *J = (sc_ctc_align_job *)host.data();
-  int32_t *lab = (int32_t *)(host.data() + o_lab);
-  int32_t *od = (int32_t *)(D + o_out);
-  const int V = b->cfg.vocab_size;
-  size_t li = 0, wo = o_ws;
-  for (int k = 0; k < n; ++k) {
-    const AlignReq &r = reqs[k];
-    const int L = (int)r.y.size();
-    if (L) memcpy(lab + li, r.y.data(), (size_t)L * 4);
-    sc_ctc_align_job &j = J[k];
-    j.emis = b->sb.ctcx + (size_t)r.s * b->TCAP * V;
-    j.labels = (const int32_t *)(D + o_lab) + li;
-    j.ws = D + wo;
-    j.start = od + 3 * li;
-    j.end = od + 3 * li + L;
-    j.logp_mean = (float *)(od + 3 * li + 2 * L);
-    j.path_score = (float *)(od + 3 * n_lab + 2 * k);
-    j.status = od + 3 * n_lab + 2 * k + 1;
-    j.stride = V;
-    j.T = r.T; j.L = L; j.V = V; j.blank = b->cfg.blank_id;
-    if (alt_K) {
-      sc_ctc_alt_job &a = ((sc_ctc_alt_job *)(host.data() + o_alt))[k];
-      char *ao = D + o_out + o_altout;
-      a.emis = j.emis;
-      a.labels = j.labels;
-      a.start = j.start;
-      a.end = j.end;
-      a.alt_logp = (double *)ao + li * K;
-      int32_t *ai = (int32_t *)(ao + n_lab * K * 8);
-      a.alt_ids = ai + li * K;
-      a.own_rank = ai + n_lab * K + li;
-      a.status = ai + n_lab * K + n_lab + li;
-      a.stride = V;
-      a.T = r.T; a.V = V; a.blank = b->cfg.blank_id; a.L = L;
-    }
-    li += L;
-    wo += al_round(sc_ctc_align_ws_bytes(r.T));
-  }
-  HIP_TRY(hipMemcpyAsync(D, host.data(), o_out, hipMemcpyHostToDevice, b->stream_rb));
-  if (after_snap) HIP_TRY(hipStreamWaitEvent(b->stream_rb, b->ev_snap, 0));
-  RC_TRY(sc_ctc_align((const sc_ctc_align_job *)D, n, max_T, max_L, b->stream_rb));
-  if (alt_K) RC_TRY(sc_ctc_alternates((const sc_ctc_alt_job *)(D + o_alt), n, max_L, alt_K, b->stream_rb));
-  std::vector<int32_t> res((n_outb + 3) / 4 + 2);
-  HIP_TRY(hipMemcpyAsync(res.data(), D + o_out, n_outb, hipMemcpyDeviceToHost, b->stream_rb));
-  HIP_TRY(hipStreamSynchronize(b->stream_rb));
-  const char *ro = (const char *)res.data() + o_altout;
-  const int32_t *ri = (const int32_t *)(ro + n_lab * K * 8);
-  li = 0;
-  for (int k = 0; k < n; ++k) {
-    const int L = (int)reqs[k].y.size();
-    AlignOut &o = out[k];
-    o.start.assign(res.begin() + 3 * li, res.begin() + 3 * li + L);
-    o.end.assign(res.begin() + 3 * li + L, res.begin() + 3 * li + 2 * L);
-    o.lp.resize(L);
-    if (L) memcpy(o.lp.data(), res.data() + 3 * li + 2 * L, (size_t)L * 4);
-    memcpy(&o.score, res.data() + 3 * n_lab + 2 * k, 4);
-    o.status = res[3 * n_lab + 2 * k + 1];
-    if (alt_K) {
-      o.alt_logp.resize((size_t)L * K);
-      if (L) memcpy(o.alt_logp.data(), ro + li * K * 8, (size_t)L * K * 8);
-      o.alt_ids.assign(ri + li * K, ri + (li + L) * K);
-      o.own_rank.assign(ri + n_lab * K + li, ri + n_lab * K + li + L);
-      o.span_status.assign(ri + n_lab * K + n_lab + li, ri + n_lab * K + n_lab + li + L);
-    }
-    li += L;
-  }
-  return SC_OK;
-}
-
-// frames of the hypotheses sc_get_hyps_batch reports for stream s (the snapshot's with a queue depth > 1)
-static int hyp_frames(const sc_streams *b, int s, int *T, bool *snap) {
-  const Snap &sn = b->snap[s];
-  *snap = sn.valid;
-  if (sn.valid) {
-    *T = sn.T;
-    return SC_OK;
-  }
-  SC_CHECK_ARG(!b->run[s].inblk && b->bq[s].empty(), "stream is inside a decode block (its chunk has not been reported yet)");
-  *T = b->st[s].T_hyp;
-  return SC_OK;
-}
-
-// sc_align_hyps (K == 0) and sc_alternates_hyps (K > 0): the same requests, the same alignment
-static int align_hyps(sc_streams *b, const int *stream_ids, int n, int nbest, int max_len, int K, int32_t *start,
-                      int32_t *end, float *logp_mean, double *path_score, int *status, int32_t *alt_ids, double *alt_logp,
-                      int32_t *own_rank, int32_t *span_status, int *n_hyps) {
-  SC_CHECK_ARG(b && stream_ids && n_hyps && n >= 0 && nbest >= 0 && max_len >= 0, "bad arguments");
-  SC_API_BEGIN
-  HIP_TRY(hipSetDevice(b->eng->device));
-  if (n == 0 || nbest == 0) {
-    for (int i = 0; i < n; ++i) n_hyps[i] = 0;
-    return SC_OK;
-  }
-  const int LC = b->LCAP;
-  std::vector<int32_t> ids((size_t)n * nbest * LC);
-  std::vector<int> lens((size_t)n * nbest);
-  RC_TRY(sc_get_hyps_batch(b, stream_ids, n, nbest, LC, ids.data(), nullptr, lens.data(), n_hyps, nullptr, nullptr, nullptr));
-  std::vector<AlignReq> reqs;
-  bool any_snap = false;
-  for (int i = 0; i < n; ++i) {
-    int T = 0;
-    bool snap = false;
-    RC_TRY(hyp_frames(b, stream_ids[i], &T, &snap));
-    any_snap |= snap && n_hyps[i] > 0;
-    for (int h = 0; h < n_hyps[i]; ++h) {
-      const size_t o = (size_t)i * nbest + h;
-      const int32_t *y = ids.data() + o * LC;
-      int a = 1, e = lens[o];                                  // without <sos> ...
-      if (e > a && y[e - 1] == b->cfg.eos_id) --e;             // ... and without a trailing <eos>
-      AlignReq r{stream_ids[i], T, std::vector<int32_t>(y + a, y + std::max(a, e))};
-      SC_CHECK_ARG((int)r.y.size() <= max_len || (!start && !end && !logp_mean && !alt_ids && !alt_logp && !own_rank && !span_status),
-                   "max_len is smaller than the hypotheses");
-      reqs.push_back(std::move(r));
-    }
-  }
-  std::vector<AlignOut> out;
-  RC_TRY(run_align(b, reqs, any_snap, out, K));
-  int k = 0;
-  for (int i = 0; i < n; ++i)
-    for (int h = 0; h < n_hyps[i]; ++h, ++k) {
-      const size_t o = (size_t)i * nbest + h;
-      const AlignOut &a = out[k];
-      const size_t L = a.start.size();
-      if (start) memcpy(start + o * max_len, a.start.data(), L * 4);
-      if (end) memcpy(end + o * max_len, a.end.data(), L * 4);
-      if (logp_mean) memcpy(logp_mean + o * max_len, a.lp.data(), L * 4);
-      if (path_score) path_score[o] = a.score;
-      if (status) status[o] = a.status;
-      if (K) {
-        if (alt_ids) memcpy(alt_ids + o * max_len * K, a.alt_ids.data(), L * K * 4);
-        if (alt_logp) memcpy(alt_logp + o * max_len * K, a.alt_logp.data(), L * K * 8);
-        if (own_rank) memcpy(own_rank + o * max_len, a.own_rank.data(), L * 4);
-        if (span_status) memcpy(span_status + o * max_len, a.span_status.data(), L * 4);
-      }
-    }
-  return SC_OK;
-  SC_API_END
-}
-
-extern "C" int sc_align_hyps(sc_streams *b, const int *stream_ids, int n, int nbest, int max_len, int32_t *start,
-                             int32_t *end, float *logp_mean, double *path_score, int *status, int *n_hyps) {
-  return align_hyps(b, stream_ids, n, nbest, max_len, 0, start, end, logp_mean, path_score, status, nullptr, nullptr,
-                    nullptr, nullptr, n_hyps);
-}
-
-extern "C" int sc_alternates_hyps(sc_streams *b, const int *stream_ids, int n, int nbest, int max_len, int K,
-                                  int32_t *start, int32_t *end, float *logp_mean, double *path_score, int *status,
-                                  int32_t *alt_ids, double *alt_logp, int32_t *own_rank, int32_t *span_status, int *n_hyps) {
-  SC_CHECK_ARG(K >= 1 && K <= SC_ALT_MAX_K, "K outside [1, SC_ALT_MAX_K]");
-  return align_hyps(b, stream_ids, n, nbest, max_len, K, start, end, logp_mean, path_score, status, alt_ids, alt_logp,
-                    own_rank, span_status, n_hyps);
-}
-
-extern "C" int sc_align_tokens(sc_streams *b, int stream, const int32_t *ids, int L, int32_t *start, int32_t *end,
-                               float *logp_mean, double *path_score, int *status) {
-  SC_CHECK_ARG(b && stream >= 0 && stream < b->S && L >= 0 && (L == 0 || ids), "bad arguments");
-  SC_API_BEGIN
-  HIP_TRY(hipSetDevice(b->eng->device));
-  int T = 0;
-  bool snap = false;
-  RC_TRY(hyp_frames(b, stream, &T, &snap));
-  std::vector<AlignReq> reqs{AlignReq{stream, T, std::vector<int32_t>(ids, ids + L)}};
-  std::vector<AlignOut> out;
-  RC_TRY(run_align(b, reqs, snap, out));
-  const AlignOut &a = out[0];
-  if (start) memcpy(start, a.start.data(), (size_t)L * 4);
-  if (end) memcpy(end, a.end.data(), (size_t)L * 4);
-  if (logp_mean) memcpy(logp_mean, a.lp.data(), (size_t)L * 4);
-  if (path_score) *path_score = a.score;
-  if (status) *status = a.status;
-  return SC_OK;
-  SC_API_END
-}
 
 // host <-> device copies of a stream's PCM ring and encoder output (tests, bench preload, the drop-in class's
 // frontend_states / encoder_buffer views)
@@ -3663,10 +2571,9 @@ extern "C" int sc_streams_read_ctc(sc_streams *b, int stream, float *host, int m
   SC_CHECK_ARG(b && stream >= 0 && stream < b->S && max_rows >= 0, "bad arguments");
   SC_API_BEGIN
   HIP_TRY(hipSetDevice(b->eng->device));
-  int T = 0;
-  bool snap = false;
-  RC_TRY(hyp_frames(b, stream, &T, &snap));
-  T = std::min(T, max_rows);
+  HypSrc src;   // the frames of the hypotheses sc_get_hyps_batch reports for the stream
+  RC_TRY(hyp_source(b, stream, &src));
+  const int T = std::min(src.T, max_rows);
   const size_t V = (size_t)b->cfg.vocab_size;
   if (host && T > 0) {
     HIP_TRY(hipMemcpyAsync(host, b->sb.ctcx + (size_t)stream * b->TCAP * V, (size_t)T * V * sizeof(float),
@@ -3735,7 +2642,7 @@ static int side_ready(sc_streams *b, const handover::Pending<V> &r, int s, const
 static int activity_ready(sc_streams *b, int s) { return side_ready(b, b->act.rep[s], s, "activity state", "its"); }
 static int spot_ready(sc_streams *b, int s) { return side_ready(b, b->spot.rep[s], s, "spotting counters", "their"); }
 static int draft_ready(sc_streams *b, int s) { return side_ready(b, b->draft.rep[s], s, "draft state", "its"); }
-static int beam_ready(sc_streams *b, int s) { return side_ready(b, b->beam.rep[s], s, "beam state", "its"); }
+int sc_state::beam_ready(sc_streams *b, int s) { return side_ready(b, b->beam.rep[s], s, "beam state", "its"); }
 
 extern "C" int sc_stream_activity(sc_streams *b, int stream, sc_activity_t *out) {
   SC_CHECK_ARG(b && out && stream >= 0 && stream < b->S, "bad arguments");
@@ -4035,38 +2942,6 @@ extern "C" int sc_stream_ctc_beam_lm(sc_streams *b, int stream, sc_beam_lm_t *ou
   SC_API_END
 }
 
-// beside sc_ctc_beam_hyps' scores: lm [n][nbest] and fused [n][nbest] = lae(pb, pnb) + (alpha * lm + beta * len) of the
-// same entries (NaN where the state has no such entry); host arithmetic on the reported states, no launch.  Either may
-// be NULL.
-extern "C" int sc_ctc_beam_hyps_lm(sc_streams *b, const int *stream_ids, int n, int nbest, double *lm, double *fused) {
-  SC_CHECK_ARG(b && stream_ids && n >= 0 && nbest >= 0 && nbest <= SC_BEAM_MAX, "bad arguments");
-  SC_API_BEGIN
-  SC_CHECK_ARG(b->beam_on && b->beam_lm, "no language model is attached (sc_streams_set_ctc_beam_lm)");
-  SC_CHECK_ARG(n <= b->S, "more streams listed than the batch has");
-  HIP_TRY(hipSetDevice(b->eng->device));
-  for (int i = 0; i < n; ++i) {
-    const int s = stream_ids[i];
-    SC_CHECK_ARG(s >= 0 && s < b->S, "stream out of range");
-    RC_TRY(beam_ready(b, s));
-    const BeamState &v = b->beam.rep[s].v;
-    for (int r = 0; r < nbest; ++r) {
-      const size_t k = (size_t)i * nbest + r;
-      double l = NAN, f = NAN;
-      if (r < v.d.n_entries) {
-        const sc_beam_entry &e = v.d.e[r];
-        const double hi = std::max(e.pb, e.pnb), lo = std::min(e.pb, e.pnb);
-        const double total = lo == -INFINITY ? hi : hi + log1p(exp(lo - hi));
-        l = v.lm.lm[r];
-        const double wa = b->beam_alpha * l, wb = b->beam_beta * (double)e.len;
-        f = total + (wa + wb);
-      }
-      if (lm) lm[k] = l;
-      if (fused) fused[k] = f;
-    }
-  }
-  return SC_OK;
-  SC_API_END
-}
 
 // ---- grammars: a menu per stream ------------------------------------------------------------------------------------------
 // The rule of sc_stream_set_decoder: only while the stream is idle and has taken nothing of its utterance.  The handle
@@ -4132,34 +3007,6 @@ extern "C" int sc_stream_ctc_beam_grammar(sc_streams *b, int stream, sc_beam_gr_
   SC_API_END
 }
 
-// beside sc_ctc_beam_hyps: g [n][nbest], the grammar's state after each entry's prefix, and accept [n][nbest], its accept
-// flag; -1 where the state has no such entry or the stream has no grammar.  Host arithmetic on the reported states and the
-// grammars' host copies, no launch.  Either may be NULL.
-extern "C" int sc_ctc_beam_hyps_grammar(sc_streams *b, const int *stream_ids, int n, int nbest, int32_t *g, int32_t *accept) {
-  SC_CHECK_ARG(b && stream_ids && n >= 0 && nbest >= 0 && nbest <= SC_BEAM_MAX, "bad arguments");
-  SC_API_BEGIN
-  SC_CHECK_ARG(b->beam_on, "the beam option is off (sc_streams_set_ctc_beam)");
-  SC_CHECK_ARG(n <= b->S, "more streams listed than the batch has");
-  HIP_TRY(hipSetDevice(b->eng->device));
-  for (int i = 0; i < n; ++i) {
-    const int s = stream_ids[i];
-    SC_CHECK_ARG(s >= 0 && s < b->S, "stream out of range");
-    RC_TRY(beam_ready(b, s));
-    const BeamState &v = b->beam.rep[s].v;
-    const sc_grammar *gr = b->beam_gr_n ? b->beam_gr[s] : nullptr;
-    sc_grammar_view info{};
-    if (gr) RC_TRY(sc_grammar_device_view(gr, nullptr, &info));
-    for (int r = 0; r < nbest; ++r) {
-      const size_t k = (size_t)i * nbest + r;
-      int32_t st = -1;
-      if (gr && r < v.d.n_entries) st = v.d.n_frames == 0 ? info.start_state : v.gr.g[r];
-      if (g) g[k] = st;
-      if (accept) accept[k] = st < 0 ? -1 : sc_grammar_accepts(gr, st);
-    }
-  }
-  return SC_OK;
-  SC_API_END
-}
 
 extern "C" int sc_stream_ctc_beam(sc_streams *b, int stream, sc_beam_t *out) {
   SC_CHECK_ARG(b && out && stream >= 0 && stream < b->S, "bad arguments");
@@ -4172,345 +3019,6 @@ extern "C" int sc_stream_ctc_beam(sc_streams *b, int stream, sc_beam_t *out) {
   SC_API_END
 }
 
-// The first nbest entries of the listed streams' reported beams as token sequences: the states and ONE job table go up,
-// ONE sc_ctc_beam_pack launch walks the chains, ONE copy comes back, all on the read-back stream as sc_get_hyps_batch
-// does it.  header [n][nbest][4] (len, SC_BEAM_PACK_* status, node, last), ids / frames [n][nbest][max_len], scores
-// [n][nbest][2] (pb, pnb); any of ids / frames / scores may be NULL.
-extern "C" int sc_ctc_beam_hyps(sc_streams *b, const int *stream_ids, int n, int nbest, int max_len, int32_t *header,
-                                int32_t *ids, int32_t *frames, double *scores) {
-  SC_CHECK_ARG(b && stream_ids && header && n >= 0 && nbest >= 0 && nbest <= SC_BEAM_MAX && max_len >= 0, "bad arguments");
-  SC_API_BEGIN
-  SC_CHECK_ARG(b->beam_on, "the beam option is off (sc_streams_set_ctc_beam)");
-  SC_CHECK_ARG(n <= b->S, "more streams listed than the batch has");
-  HIP_TRY(hipSetDevice(b->eng->device));
-  const size_t m = (size_t)n * nbest;
-  if (m == 0) return SC_OK;
-  SC_CHECK_ARG(m <= SC_BEAM_MAX_JOBS, "more than SC_BEAM_MAX_JOBS entries asked for");
-  std::vector<char> listed(b->S, 0);
-  for (int i = 0; i < n; ++i) {
-    const int s = stream_ids[i];
-    SC_CHECK_ARG(s >= 0 && s < b->S, "stream out of range");
-    SC_CHECK_ARG(!listed[s], "a stream is listed twice");
-    listed[s] = 1;
-    RC_TRY(beam_ready(b, s));
-  }
-  // [states: n][jobs: m] go up; [scores: m][2] doubles, [header: m][4], [ids: m][max_len], [frames: m][max_len] come back
-  const size_t o_jobs = (size_t)n * sizeof(sc_beam_t), o_sc = o_jobs + m * sizeof(sc_ctc_beam_pack_job),
-               o_head = o_sc + m * 2 * sizeof(double), o_ids = o_head + m * 4 * sizeof(int32_t),
-               o_frames = o_ids + m * max_len * sizeof(int32_t), need = o_frames + m * max_len * sizeof(int32_t);
-  if (need > b->bh_cap) {
-    HIP_TRY(hipStreamSynchronize(b->stream_rb));
-    if (b->bh_dev) (void)hipFree(b->bh_dev);
-    if (b->bh_host) (void)hipHostFree(b->bh_host);
-    const size_t cap = std::max(need, 2 * b->bh_cap);
-    b->bh_dev = b->bh_host = nullptr;
-    b->bh_cap = 0;
-    HIP_TRY(hipMalloc((void **)&b->bh_dev, cap));
-    HIP_TRY(hipHostMalloc((void **)&b->bh_host, cap));
-    b->bh_cap = cap;
-  }
-  sc_beam_t *st_host = (sc_beam_t *)b->bh_host;
-  sc_ctc_beam_pack_job *jobs = (sc_ctc_beam_pack_job *)(b->bh_host + o_jobs);
-  for (int i = 0; i < n; ++i) {
-    const int s = stream_ids[i];
-    st_host[i] = b->beam.rep[s].v.d;
-    for (int r = 0; r < nbest; ++r) {
-      const size_t k = (size_t)i * nbest + r;
-      sc_ctc_beam_pack_job &j = jobs[k];
-      j.state = (const sc_beam_t *)b->bh_dev + i;
-      j.nodes = b->beam_nodes + (size_t)s * b->beam_ncap();
-      j.ids = (int32_t *)(b->bh_dev + o_ids) + k * max_len;
-      j.frames = (int32_t *)(b->bh_dev + o_frames) + k * max_len;
-      j.header = (int32_t *)(b->bh_dev + o_head) + k * 4;
-      j.scores = (double *)(b->bh_dev + o_sc) + k * 2;
-      j.capacity = (int32_t)b->beam_ncap(); j.rank = r; j.max_len = max_len; j.reserved = 0;
-    }
-  }
-  // (the groups that stored the nodes of these states have been retired; later groups write behind them)
-  HIP_TRY(hipMemcpyAsync(b->bh_dev, b->bh_host, o_sc, hipMemcpyHostToDevice, b->stream_rb));
-  RC_TRY(sc_ctc_beam_pack((const sc_ctc_beam_pack_job *)(b->bh_dev + o_jobs), (int)m, b->stream_rb));
-  HIP_TRY(hipMemcpyAsync(b->bh_host + o_sc, b->bh_dev + o_sc, need - o_sc, hipMemcpyDeviceToHost, b->stream_rb));
-  HIP_TRY(hipStreamSynchronize(b->stream_rb));
-  memcpy(header, b->bh_host + o_head, m * 4 * sizeof(int32_t));
-  if (scores) memcpy(scores, b->bh_host + o_sc, m * 2 * sizeof(double));
-  // (only [0, min(len, max_len)) of a row is written by the launch: the rest of the caller's rows is left as it is)
-  for (size_t k = 0; k < m; ++k) {
-    const int32_t *h = (const int32_t *)(b->bh_host + o_head) + k * 4;
-    const size_t L = (size_t)std::max(0, std::min(h[0], max_len));
-    if (ids) memcpy(ids + k * max_len, (const int32_t *)(b->bh_host + o_ids) + k * max_len, L * sizeof(int32_t));
-    if (frames) memcpy(frames + k * max_len, (const int32_t *)(b->bh_host + o_frames) + k * max_len, L * sizeof(int32_t));
-  }
-  return SC_OK;
-  SC_API_END
-}
-
-// ---- attention rescoring of n-best lists at finals (dec_rescore.hip) ------------------------------------
-// The lists' rows are scored by ONE sc_dec_rescore call against the listed streams' encoder rows enc[s][0 .. T_enc), on
-// the read-back stream, with ONE copy back; nothing of the engine is written.  ar_dev / ar_host hold [inputs][outputs]; a
-// job's outputs: att, fused [16] doubles, then order, status [16] int32.  The workspace is allocated by the first call, as
-// large as the call needs and never beyond ar_ws_limit (sc_streams_set_attention_rescore_ws): a call that needs more
-// runs in slabs of whole streams, with the same bits.
-namespace {
-constexpr size_t AR_OUT = (size_t)SC_ATT_MAX_HYPS * (2 * sizeof(double) + 2 * sizeof(int32_t));
-constexpr size_t AR_SPLITK = (size_t)32 << 20;
-
-size_t ar_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
-int ar_reserve(sc_streams *b, size_t need) {
-  if (need <= b->ar_cap) return SC_OK;
-  HIP_TRY(hipStreamSynchronize(b->stream_rb));
-  if (b->ar_dev) (void)hipFree(b->ar_dev);
-  if (b->ar_host) (void)hipHostFree(b->ar_host);
-  const size_t cap = std::max(need, 2 * b->ar_cap);
-  b->ar_dev = b->ar_host = nullptr;
-  b->ar_cap = 0;
-  HIP_TRY(hipMalloc((void **)&b->ar_dev, cap));
-  HIP_TRY(hipHostMalloc((void **)&b->ar_host, cap));
-  b->ar_cap = cap;
-  return SC_OK;
-}
-
-int ar_workspace(sc_streams *b, size_t need) {
-  if (!b->ar_splitk) {   // the read-back stream gets split-K storage of its own: the dense launchers never share partial sums
-    HIP_TRY(hipMalloc(&b->ar_splitk, AR_SPLITK));
-    RC_TRY(sc_set_stream_workspace(b->stream_rb, b->ar_splitk, AR_SPLITK));
-  }
-  const size_t want = std::min(ar_up(need), b->ar_ws_limit & ~(size_t)255);
-  if (want <= b->ar_ws_bytes) return SC_OK;
-  HIP_TRY(hipStreamSynchronize(b->stream_rb));
-  if (b->ar_ws) (void)hipFree(b->ar_ws);
-  b->ar_ws = nullptr;
-  b->ar_ws_bytes = 0;
-  HIP_TRY(hipMalloc((void **)&b->ar_ws, want));
-  b->ar_ws_bytes = want;
-  return SC_OK;
-}
-
-// the layers' cross-attention K|V weights one behind the other, as sc_dec_rescore takes them
-int ar_weights(const sc_streams *b, const float **wkv, const float **bkv) {
-  const sc_engine *e = b->eng;
-  if (e->wkv_all && e->bkv_all) { *wkv = e->wkv_all; *bkv = e->bkv_all; return SC_OK; }
-  if (b->cfg.dec_layers == 1) { *wkv = e->wkv[0]; *bkv = e->bkv[0]; return SC_OK; }
-  sc_set_error("attention rescoring: the engine holds no contiguous copy of the cross-attention K|V weights");
-  return SC_ERR_UNSUPPORTED;
-}
-
-// a listed stream: idle (its chunks reported), its encoder rows complete
-int ar_stream(sc_streams *b, int s) {
-  SC_CHECK_ARG(s >= 0 && s < b->S, "stream out of range");
-  SC_CHECK_ARG(!b->job[s].open && b->ahead[s].empty(), "the stream has a chunk outstanding (sc_poll reports it first)");
-  return wait_group(b, b->enc_gen[s]);
-}
-
-void ar_job(const sc_streams *b, sc_dec_rescore_job &j, int s, const float *wkv, const float *bkv, double w_att, double w_ctc,
-            double beta, char *out) {
-  j.E = b->enc + (size_t)s * b->TCAP * b->cfg.d_model;
-  j.e_stride = b->cfg.d_model;
-  j.T = b->st[s].T_enc;
-  j.wkv = wkv; j.bkv = bkv;
-  j.att = (double *)out;
-  j.fused = j.att + SC_ATT_MAX_HYPS;
-  j.order = (int32_t *)(j.fused + SC_ATT_MAX_HYPS);
-  j.status = j.order + SC_ATT_MAX_HYPS;
-  j.tok_att = nullptr; j.tok_stride = 0;
-  j.score_stride = 1;
-  j.w_att = w_att; j.w_ctc = w_ctc; j.beta = beta;
-  j.pe_rows = b->cfg.pe_max_len;
-}
-
-// what lies before `up` of ar_host goes up, `before` (NULL: nothing) is launched, the jobs run, their outputs come back
-template <typename Before>
-int ar_run(sc_streams *b, const std::vector<sc_dec_rescore_job> &jobs, size_t up, size_t o_out, Before before) {
-  long rows = 0, enc_rows = 0;
-  int seqs = 0;
-  for (const sc_dec_rescore_job &j : jobs) { rows += (long)j.n_hyp * (j.L + 1); enc_rows += j.T; seqs += j.n_hyp; }
-  RC_TRY(ar_workspace(b, sc_dec_rescore_ws_bytes(&b->sb, rows, enc_rows, seqs, (int)jobs.size())));
-  const int rc = [&]() -> int {
-    HIP_TRY(hipMemcpyAsync(b->ar_dev, b->ar_host, up, hipMemcpyHostToDevice, b->stream_rb));
-    RC_TRY(before());
-    RC_TRY(sc_dec_rescore(jobs.data(), (int)jobs.size(), &b->sb, b->ar_ws, b->ar_ws_bytes, b->stream_rb));
-    HIP_TRY(hipMemcpyAsync(b->ar_host + o_out, b->ar_dev + o_out, jobs.size() * AR_OUT, hipMemcpyDeviceToHost, b->stream_rb));
-    HIP_TRY(hipStreamSynchronize(b->stream_rb));
-    return SC_OK;
-  }();
-  if (rc != SC_OK) (void)hipStreamSynchronize(b->stream_rb);   // nothing of this call may still read the pinned area
-  return rc;
-}
-
-void ar_copy_out(const char *out, size_t i, int nbest, int nh, int32_t *order, double *fused, double *att, int32_t *status) {
-  const double *d = (const double *)out;
-  const int32_t *q = (const int32_t *)(d + 2 * SC_ATT_MAX_HYPS);
-  const size_t o = i * (size_t)nbest;
-  if (att) memcpy(att + o, d, nh * sizeof(double));
-  if (fused) memcpy(fused + o, d + SC_ATT_MAX_HYPS, nh * sizeof(double));
-  if (order) memcpy(order + o, q, nh * sizeof(int32_t));
-  if (status) memcpy(status + o, q + SC_ATT_MAX_HYPS, nh * sizeof(int32_t));
-}
-
-int ar_weights_ok(double w_att, double w_ctc, double beta) {
-  SC_CHECK_ARG(std::isfinite(w_att) && std::isfinite(w_ctc) && std::isfinite(beta), "w_att, w_ctc and beta must be finite");
-  return SC_OK;
-}
-}  // namespace
-
-extern "C" int sc_streams_set_attention_rescore_ws(sc_streams *b, size_t max_bytes) {
-  SC_CHECK_ARG(b && max_bytes >= ((size_t)1 << 20), "a workspace limit of at least 1 MiB");
-  SC_API_BEGIN
-  HIP_TRY(hipSetDevice(b->eng->device));
-  b->ar_ws_limit = max_bytes;
-  if (b->ar_ws_bytes > max_bytes) {   // the next call allocates within the new limit
-    HIP_TRY(hipStreamSynchronize(b->stream_rb));
-    (void)hipFree(b->ar_ws);
-    b->ar_ws = nullptr;
-    b->ar_ws_bytes = 0;
-  }
-  return SC_OK;
-  SC_API_END
-}
-
-extern "C" int sc_streams_attention_rescore_ws(const sc_streams *b, size_t *limit, size_t *allocated) {
-  SC_CHECK_ARG(b, "null");
-  if (limit) *limit = b->ar_ws_limit;
-  if (allocated) *allocated = b->ar_ws_bytes;
-  return SC_OK;
-}
-
-extern "C" int sc_attention_rescore_lists(sc_streams *b, const int *stream_ids, int n, const int32_t *ids, const int32_t *lens,
-                                          const double *scores, const int *list_sizes, int nbest, int max_len, double w_att,
-                                          double w_ctc, double beta, int32_t *order, double *fused, double *att,
-                                          int32_t *status) {
-  SC_CHECK_ARG(b && stream_ids && lens && scores && list_sizes && n >= 0 && n <= SC_ATT_MAX_JOBS && nbest >= 0 &&
-               nbest <= SC_ATT_MAX_HYPS && max_len >= 0 && max_len < 65535 && (ids || max_len == 0), "bad arguments");
-  SC_API_BEGIN
-  HIP_TRY(hipSetDevice(b->eng->device));
-  RC_TRY(ar_weights_ok(w_att, w_ctc, beta));
-  const float *wkv = nullptr, *bkv = nullptr;
-  RC_TRY(ar_weights(b, &wkv, &bkv));
-  for (int i = 0; i < n; ++i) {
-    SC_CHECK_ARG(list_sizes[i] >= 0 && list_sizes[i] <= nbest, "a list size outside [0, nbest]");
-    RC_TRY(ar_stream(b, stream_ids[i]));
-  }
-  const size_t rows = (size_t)n * nbest;
-  const size_t o_len = ar_up(rows * sizeof(double)), o_ids = o_len + ar_up(rows * sizeof(int32_t)),
-               o_out = o_ids + ar_up(rows * max_len * sizeof(int32_t));
-  RC_TRY(ar_reserve(b, o_out + (size_t)std::max(n, 1) * AR_OUT));
-  memcpy(b->ar_host, scores, rows * sizeof(double));
-  memcpy(b->ar_host + o_len, lens, rows * sizeof(int32_t));
-  if (rows * max_len) memcpy(b->ar_host + o_ids, ids, rows * max_len * sizeof(int32_t));
-  std::vector<sc_dec_rescore_job> jobs;
-  std::vector<int> job_of(n, -1);
-  for (int i = 0; i < n; ++i) {
-    if (list_sizes[i] == 0) continue;
-    sc_dec_rescore_job j{};
-    ar_job(b, j, stream_ids[i], wkv, bkv, w_att, w_ctc, beta, b->ar_dev + o_out + jobs.size() * AR_OUT);
-    j.yseq = (const int32_t *)(b->ar_dev + o_ids) + (size_t)i * nbest * max_len;
-    j.score = (const double *)b->ar_dev + (size_t)i * nbest;
-    j.lens = (const int32_t *)(b->ar_dev + o_len) + (size_t)i * nbest;
-    j.row_stride = max_len;
-    j.n_hyp = list_sizes[i]; j.L = max_len;
-    job_of[i] = (int)jobs.size();
-    jobs.push_back(j);
-  }
-  if (!jobs.empty()) RC_TRY(ar_run(b, jobs, o_out, o_out, []() { return SC_OK; }));
-  for (int i = 0; i < n; ++i)
-    if (job_of[i] >= 0)
-      ar_copy_out(b->ar_host + o_out + (size_t)job_of[i] * AR_OUT, (size_t)i, nbest, list_sizes[i], order, fused, att, status);
-  return SC_OK;
-  SC_API_END
-}
-
-// The first nbest entries of the listed streams' REPORTED beam states - the entries sc_ctc_beam_hyps returns -, packed on
-// the device by sc_ctc_beam_pack; their first-pass scores are the entries' totals lae(pb, pnb), with a language model
-// attached the fused totals sc_ctc_beam_hyps_lm reports.  ctc_score [n][nbest] receives them.
-extern "C" int sc_attention_rescore_beam(sc_streams *b, const int *stream_ids, int n, int nbest, double w_att, double w_ctc,
-                                         double beta, int32_t *order, double *fused, double *att, double *ctc_score,
-                                         int32_t *status, int *n_hyps) {
-  SC_CHECK_ARG(b && stream_ids && n_hyps && n >= 0 && nbest >= 0 && nbest <= SC_ATT_MAX_HYPS, "bad arguments");
-  SC_API_BEGIN
-  SC_CHECK_ARG(b->beam_on, "the beam option is off (sc_streams_set_ctc_beam)");
-  SC_CHECK_ARG(n <= b->S, "more streams listed than the batch has");
-  HIP_TRY(hipSetDevice(b->eng->device));
-  RC_TRY(ar_weights_ok(w_att, w_ctc, beta));
-  const float *wkv = nullptr, *bkv = nullptr;
-  RC_TRY(ar_weights(b, &wkv, &bkv));
-  std::vector<char> listed(b->S, 0);
-  int max_len = 0;
-  for (int i = 0; i < n; ++i) {
-    const int s = stream_ids[i];
-    RC_TRY(ar_stream(b, s));
-    SC_CHECK_ARG(!listed[s], "a stream is listed twice");
-    listed[s] = 1;
-    RC_TRY(beam_ready(b, s));
-    const sc_beam_t &d = b->beam.rep[s].v.d;
-    n_hyps[i] = std::max(0, std::min(nbest, d.n_entries));
-    for (int r = 0; r < n_hyps[i]; ++r) max_len = std::max(max_len, d.e[r].len);
-  }
-  SC_CHECK_ARG(max_len < 65535, "an entry too long");
-  const size_t m = (size_t)n * nbest;
-  if (m == 0) return SC_OK;
-  // [states: n][pack jobs: m][scores: m][lens: m] go up; [ids, frames: m][max_len], [pack header: m][4], [pack scores: m][2] stay on
-  // the device; [outputs] come back
-  const size_t o_pj = ar_up((size_t)n * sizeof(sc_beam_t)), o_sc = o_pj + ar_up(m * sizeof(sc_ctc_beam_pack_job)),
-               o_len = o_sc + ar_up(m * sizeof(double)), o_ids = o_len + ar_up(m * sizeof(int32_t)),
-               o_frames = o_ids + ar_up(m * max_len * sizeof(int32_t)), o_head = o_frames + ar_up(m * max_len * sizeof(int32_t)),
-               o_psc = o_head + ar_up(m * 4 * sizeof(int32_t)),
-               o_out = o_psc + ar_up(m * 2 * sizeof(double));
-  RC_TRY(ar_reserve(b, o_out + (size_t)n * AR_OUT));
-  sc_beam_t *st_host = (sc_beam_t *)b->ar_host;
-  sc_ctc_beam_pack_job *pj = (sc_ctc_beam_pack_job *)(b->ar_host + o_pj);
-  double *sc_host = (double *)(b->ar_host + o_sc);
-  int32_t *len_host = (int32_t *)(b->ar_host + o_len);
-  std::vector<sc_dec_rescore_job> jobs;
-  std::vector<int> job_of(n, -1);
-  for (int i = 0; i < n; ++i) {
-    const int s = stream_ids[i];
-    const BeamState &v = b->beam.rep[s].v;
-    st_host[i] = v.d;
-    for (int r = 0; r < nbest; ++r) {
-      const size_t k = (size_t)i * nbest + r;
-      sc_ctc_beam_pack_job &j = pj[k];
-      j.state = (const sc_beam_t *)b->ar_dev + i;
-      j.nodes = b->beam_nodes + (size_t)s * b->beam_ncap();
-      j.ids = (int32_t *)(b->ar_dev + o_ids) + k * max_len;
-      j.frames = (int32_t *)(b->ar_dev + o_frames) + k * max_len;
-      j.header = (int32_t *)(b->ar_dev + o_head) + k * 4;
-      j.scores = (double *)(b->ar_dev + o_psc) + k * 2;
-      j.capacity = (int32_t)b->beam_ncap(); j.rank = r; j.max_len = max_len; j.reserved = 0;
-      double total = NAN;
-      int len = 0;
-      if (r < n_hyps[i]) {
-        const sc_beam_entry &e = v.d.e[r];
-        const double hi = std::max(e.pb, e.pnb), lo = std::min(e.pb, e.pnb);
-        total = lo == -INFINITY ? hi : hi + log1p(exp(lo - hi));
-        if (b->beam_lm) total = total + (b->beam_alpha * v.lm.lm[r] + b->beam_beta * (double)e.len);   // (sc_ctc_beam_hyps_lm)
-        len = e.len;
-      }
-      sc_host[k] = total;
-      len_host[k] = len;
-      if (ctc_score) ctc_score[k] = total;
-    }
-    if (n_hyps[i] == 0) continue;
-    sc_dec_rescore_job j{};
-    ar_job(b, j, s, wkv, bkv, w_att, w_ctc, beta, b->ar_dev + o_out + jobs.size() * AR_OUT);
-    j.yseq = (const int32_t *)(b->ar_dev + o_ids) + (size_t)i * nbest * max_len;
-    j.score = (const double *)(b->ar_dev + o_sc) + (size_t)i * nbest;
-    j.lens = (const int32_t *)(b->ar_dev + o_len) + (size_t)i * nbest;
-    j.row_stride = max_len;
-    j.n_hyp = n_hyps[i]; j.L = max_len;
-    job_of[i] = (int)jobs.size();
-    jobs.push_back(j);
-  }
-  if (!jobs.empty())
-    RC_TRY(ar_run(b, jobs, o_ids, o_out, [&]() -> int {
-      if (max_len == 0) return SC_OK;   // every entry is the empty prefix: there is nothing to pack
-      return sc_ctc_beam_pack((const sc_ctc_beam_pack_job *)(b->ar_dev + o_pj), (int)m, b->stream_rb);
-    }));
-  for (int i = 0; i < n; ++i)
-    if (job_of[i] >= 0)
-      ar_copy_out(b->ar_host + o_out + (size_t)job_of[i] * AR_OUT, (size_t)i, nbest, n_hyps[i], order, fused, att, status);
-  return SC_OK;
-  SC_API_END
-}
 
 extern "C" int sc_stream_info(const sc_streams *b, int stream, sc_stream_info_t *out) {
   SC_CHECK_ARG(b && out && stream >= 0 && stream < b->S, "bad arguments");

@@ -1,4 +1,4 @@
-"""CTC token alternates on the GPU (csrc/alternates.hip: sc_ctc_alternates; csrc/streams.hip: sc_alternates_hyps) against
+"""CTC token alternates on the GPU (csrc/alternates.hip: sc_ctc_alternates; csrc/stream_readback.hip: sc_alternates_hyps) against
 the float64 contract of tests/ctc_alt_ref.py: the kernel on constructed tables - every int32 (alt_ids, own_rank, status)
 equal with no case excluded, alt_logp within 1e-11 on the tables with |x| <= 50 -, the stream level on the tiny and the XL
 synthetic model (lock-step and served at queue depth 2), the scheduler / ServerLoop / CLI round trips.

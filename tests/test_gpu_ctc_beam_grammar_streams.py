@@ -1,5 +1,5 @@
-"""A grammar per stream at stream level (csrc/streams.hip: sc_stream_set_grammar / sc_stream_ctc_beam_grammar /
-sc_ctc_beam_hyps_grammar) on the tiny synthetic model, (B, C) = (8, 8).
+"""A grammar per stream at stream level (csrc/streams.hip: sc_stream_set_grammar / sc_stream_ctc_beam_grammar;
+csrc/stream_readback.hip: sc_ctc_beam_hyps_grammar) on the tiny synthetic model, (B, C) = (8, 8).
 
 As in tests/test_gpu_ctc_beam_streams.py the contract (tests/ctc_beam_grammar_ref.py) is run on the RAW CTC rows of a
 handle whose streams are all decoder-free (sc_streams_read_ctc_projected): stream 0 carries grammar A (a looped menu),

@@ -1,5 +1,5 @@
 """The n-gram model fused into the CTC beam at stream level (csrc/streams.hip: sc_streams_set_ctc_beam_lm /
-sc_stream_ctc_beam_lm / sc_ctc_beam_hyps_lm) on the tiny synthetic model.
+sc_stream_ctc_beam_lm; csrc/stream_readback.hip: sc_ctc_beam_hyps_lm) on the tiny synthetic model.
 
 As in tests/test_gpu_ctc_beam_streams.py the contract (tests/ctc_beam_lm_ref.py) is run on the RAW CTC rows of a handle
 whose streams are all decoder-free (sc_streams_read_ctc_projected; DESIGN.md 8j says why that handle): every int32 and

@@ -1,5 +1,5 @@
-"""CTC prefix beam search at stream level (csrc/streams.hip: sc_streams_set_ctc_beam / sc_stream_ctc_beam /
-sc_ctc_beam_hyps) and decoder-free streams (sc_stream_set_decoder) on the tiny and the XL synthetic model.
+"""CTC prefix beam search at stream level (csrc/streams.hip: sc_streams_set_ctc_beam / sc_stream_ctc_beam;
+csrc/stream_readback.hip: sc_ctc_beam_hyps) and decoder-free streams (sc_stream_set_decoder) on the tiny and the XL synthetic model.
 
 The contract (tests/ctc_beam_ref.py) is run on the RAW CTC rows: a handle whose streams are all SC_DECODER_NONE never
 runs a decode block, so the rows it holds are the logits its beam launches read (the first decode block of a FULL

@@ -1,4 +1,4 @@
-"""Attention rescoring at stream level (csrc/streams.hip: sc_attention_rescore_beam, sc_attention_rescore_lists; DESIGN.md
+"""Attention rescoring at stream level (csrc/stream_readback.hip: sc_attention_rescore_beam, sc_attention_rescore_lists; DESIGN.md
 8n) on the tiny synthetic model.
 
 On a handle whose streams are all decoder-free, attention_rescore_beam equals the contract (tests/dec_rescore_ref.py) run

@@ -1,4 +1,4 @@
-"""Stable partials on the GPU (csrc/commit.hip: sc_hyp_commit; csrc/streams.hip: sc_get_hyps_delta) against the float64
+"""Stable partials on the GPU (csrc/commit.hip: sc_hyp_commit; csrc/stream_readback.hip: sc_get_hyps_delta) against the float64
 contract of tests/hyp_commit_ref.py: the kernel on constructed beams - every int32 equal, stability within 1e-12, the two
 exact properties on the device output itself -, the stream level on the tiny and the XL synthetic model (lock-step,
 continuous batching at queue depth 2), the call's effect on decoding (none) and its refusals.

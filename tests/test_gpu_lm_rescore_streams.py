@@ -1,4 +1,4 @@
-"""N-gram rescoring at stream level (csrc/streams.hip: sc_rescore_hyps, sc_lm_rescore_lists) on the tiny
+"""N-gram rescoring at stream level (csrc/stream_readback.hip: sc_rescore_hyps, sc_lm_rescore_lists) on the tiny
 synthetic model, with an order-3 model estimated from the streams' own hypotheses.
 
 sc_rescore_hyps on FULL streams equals the contract (tests/lm_rescore_ref.py) run on what sc_get_hyps_batch returned,
