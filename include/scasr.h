@@ -792,6 +792,81 @@ typedef struct sc_lm_rescore_job {
  * unknown flags) writes nothing.  Two jobs of one call must not share outputs. */
 int sc_lm_rescore(const sc_lm_rescore_job *jobs, int n_jobs, void *stream);
 
+/* ---- consensus of n-best lists: minimum-Bayes-risk row and slot confidences (mbr.hip) ----------------
+ * A job is one list in sc_lm_rescore_job's layout: n_hyp <= SC_MBR_MAX_HYPS rows, row h at yseq + h * row_stride with
+ * lens[h] tokens (lens == NULL: L each), its LABELS y_h[0 .. m_h) the tokens without the first `skip` and without ONE
+ * trailing token equal to `strip` (-1: none).  Per row EITHER weight[h] (score == NULL) OR score[h * score_stride]
+ * (weight == NULL).
+ *   status[h]     SC_MBR_BAD_TOKEN: a label outside [0, V) or a lens[h] outside [0, L].  SC_MBR_TOO_LONG: m_h >
+ *                 SC_MBR_MAX_LEN.  SC_MBR_NONFINITE: a weight that is NaN, infinite or negative; a score that is NaN or
+ *                 +inf, or whose z_h (below) is (-inf is a legal score: weight 0).  A row with any of these is OUT: -1 in
+ *                 its row and column of dist, risk the quiet NaN 0x7FF8000000000000, weight 0.0; it ranks behind all
+ *                 others, in row order.  SC_MBR_NO_PIVOT: on every row of a list without a pivot (below).
+ *   weight_out[h] w_h.  With `weight`: the value itself.  With `score`, over the rows that are in: z_h = scale * score[h]
+ *                 (-inf for a score of -inf whatever the scale), M = max z, e_h = exp(z_h - M), Z = ((0 + e_0) + e_1) +
+ *                 ... ascending, w_h = e_h / Z; when every z is -inf, w_h = 1 / n_in.
+ *   dist[h][j]    [16][16] row-major: Levenshtein distance of y_h and y_j, unit costs; entries of rows or columns at or
+ *                 beyond n_hyp are not written
+ *   risk[h]       ((0.0 + w_0 dist[h][0]) + w_1 dist[h][1]) + ..., ascending j over the rows that are in, every product and
+ *                 sum rounded on its own
+ *   order[r]      the row at rank r: risk ascending, ties to the lower row, rows that are out last
+ *   header        {P, m_P, n_in, 0}: the pivot P = order[0] when the job's pivot is -1, else the named row; P = -1 and
+ *                 m_P = 0 when no row is in or the named row is out
+ *   slots[j * slot_stride + t], t in [0, m_P) (wanted only with a non-null pointer): row j, when it is in, aligned
+ *                 against the pivot.  D is the full table of (y_P, y_j); from (m_P, m_j): DIAGONAL if i > 0, j > 0 and
+ *                 D[i][j] == D[i-1][j-1] + (y_P[i-1] != y_j[j-1]) - slot i-1 gets y_j[j-1]; otherwise UP if i > 0 and
+ *                 D[i][j] == D[i-1][j] + 1 - slot i-1 gets -1 (epsilon); otherwise LEFT - row j has an insertion in gap
+ *                 i (before the pivot's position i; gap m_P is the end).  A row that is out has -2 in every slot.
+ *   conf[t]       t in [0, m_P): the sum over j ascending (rows in) of w_j where slot t of row j equals y_P[t]
+ *   alt_tok[t], alt_mass[t]  among the symbols other than y_P[t] in column t (a token id or -1) the one with the largest
+ *                 mass (the same kind of sum), ties to the lower symbol; -2 and 0.0 when there is none
+ *   gap_mass[g]   g in [0, m_P] (nothing without a pivot): the mass of the rows with at least one insertion in gap g
+ * tests/mbr_ref.py is the contract.  With `weight` every output is the contract's bit for bit; with `score` the
+ * library's exp() stands in for the host's, and the doubles agree within 64 ulp of max(1, |value|). */
+#define SC_MBR_MAX_HYPS 16
+#define SC_MBR_MAX_LEN 1024 /* labels per row; a longer row is SC_MBR_TOO_LONG */
+#define SC_MBR_NONFINITE 1  /* status bits */
+#define SC_MBR_BAD_TOKEN 2
+#define SC_MBR_TOO_LONG 4
+#define SC_MBR_NO_PIVOT 8
+typedef struct sc_mbr_job {
+  const int32_t *yseq;   /* row h at yseq + h * row_stride (device) */
+  const double *score;   /* total of row h at score[h * score_stride], or NULL (device) */
+  const double *weight;  /* [n_hyp] weights, or NULL; exactly one of score and weight is given (device) */
+  const int32_t *lens;   /* [n_hyp] tokens per row, or NULL: L each (device) */
+  double *weight_out;    /* [n_hyp] (device) */
+  double *risk;          /* [n_hyp] (device) */
+  int32_t *dist;         /* [16][16] (device) */
+  int32_t *order;        /* [n_hyp] (device) */
+  int32_t *status;       /* [n_hyp] SC_MBR_* (device) */
+  int32_t *header;       /* [4] (device) */
+  double *conf;          /* [m_P]; room for min(max(0, L - skip), SC_MBR_MAX_LEN) values (device) */
+  double *alt_mass;      /* as conf (device) */
+  double *gap_mass;      /* [m_P + 1]; room for one value more than conf (device) */
+  int32_t *alt_tok;      /* as conf (device) */
+  int32_t *slots;        /* row j at slots + j * slot_stride, m_P values; NULL: not wanted (device) */
+  int64_t row_stride;    /* int32 elements between two rows, >= L */
+  int64_t score_stride;  /* doubles between two rows' scores, >= 1 when score is given */
+  int64_t slot_stride;   /* int32 elements between two rows of slots, >= min(max(0, L - skip), SC_MBR_MAX_LEN) with slots */
+  double scale;          /* of the scores; finite, >= 0 */
+  int32_t n_hyp, L, skip, strip, V, pivot, flags, reserved;   /* pivot: -1 the minimum-risk row, else the row; flags: 0 */
+} sc_mbr_job;
+#define SC_MBR_MAX_JOBS 65535
+/* Bytes of workspace (direction bits of the backtraces, slots, gap marks) for n_jobs lists of at most max_len labels a
+ * row; 0 for arguments out of range. */
+size_t sc_mbr_ws_bytes(int n_jobs, int max_len);
+/* jobs: device table of n_jobs entries; ws: device workspace of ws_bytes, of which every job gets an equal share.
+ * THREE launches on `stream`, no host synchronisation between them: validation, weights and the pair distances (one
+ * wave per job and one per pair); risk, order and pivot (one workgroup per job); the backtraces against the pivot (one
+ * wave per row) and the column pass.  No atomics, one writer per output, plain stores; the inputs are only read.
+ * SC_ERR_ARG before anything is launched for n_jobs outside [0, SC_MBR_MAX_JOBS], a null table or a null workspace with
+ * n_jobs > 0.  A job whose own fields are malformed (a null pointer other than lens / slots, both or neither of score
+ * and weight, n_hyp outside [1, SC_MBR_MAX_HYPS], L < 0, row_stride < L, score_stride < 1 with score, a slot_stride too
+ * small with slots, skip < 0, strip < -1, V < 1, a scale that is not finite or negative, pivot outside [-1, n_hyp),
+ * flags or reserved other than 0, a share of the workspace below what sc_mbr_ws_bytes gives for one list of the job's
+ * max(0, L - skip) labels) writes nothing.  Two jobs of one call must not share outputs. */
+int sc_mbr(const sc_mbr_job *jobs, int n_jobs, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- attention rescoring of n-best lists (dec_rescore.hip) --------------------------------------------
  * Attention of whole sequences (sc_seq_attention).  A job is ONE sequence: Lq query rows against Lk key / value rows, H
  * heads of dk columns each (head h at columns [h * dk, (h + 1) * dk) of a row of q, k, v and o), every buffer with its
@@ -1397,6 +1472,38 @@ int sc_attention_rescore_lists(sc_streams *streams, const int *stream_ids, int n
                                double w_ctc, double beta, int32_t *order, double *fused, double *att, int32_t *status);
 int sc_streams_set_attention_rescore_ws(sc_streams *streams, size_t max_bytes);
 int sc_streams_attention_rescore_ws(const sc_streams *streams, size_t *limit, size_t *allocated);
+/* Consensus of n-best lists at finals (sc_mbr above): the minimum-Bayes-risk row and the slot statistics
+ * of the pivot.  The scratch area of the read-back services holds the job table, the inputs and the outputs; ONE
+ * upload, the launches of sc_mbr on the read-back stream, ONE copy back; nothing of the engine is written, and a handle
+ * that never calls these allocates nothing for them and issues the launches it issued before.  The direction workspace
+ * is an allocation of its own, made by the first call as large as that call needs, grow-only and never beyond the limit
+ * (default SC_MBR_WS_DEFAULT_BYTES; sc_streams_set_mbr_ws, at least SC_MBR_WS_MIN_BYTES - what one list of
+ * SC_MBR_MAX_LEN labels needs); a call that needs more runs in slabs of whole lists, with the same bits.
+ * sc_streams_mbr_ws reports the limit and what is allocated.
+ * sc_mbr_hyps: the hypotheses sc_get_hyps_batch would return (same rules: the snapshot with a queue depth > 1, an error
+ * for a stream inside a decode block or listed twice), per stream its first n_hyps[i] = min(nbest, live hypotheses) rows,
+ * labels without <sos> and without a trailing <eos>, scores the hypotheses' totals times `scale` (finite, >= 0).
+ * pivot_best != 0 pins the pivot to row 0: the reported transcript stays the search's, only the slot statistics are
+ * added.  nbest <= SC_MBR_MAX_HYPS; SC_ERR_ARG when a stream's rows have more than max_len labels (at most
+ * SC_MBR_MAX_LEN are ever needed).
+ * sc_mbr_lists: the same for caller-given lists (all arrays HOST): list i has list_sizes[i] <= nbest rows, row r the
+ * LABELS ids[i][r][0 .. lens[i][r]) - nothing skipped, nothing stripped -, values[i][r] its total (are_weights == 0) or
+ * its weight (are_weights != 0), pivot[i] the job's pivot (NULL: -1 everywhere); V is the handle's vocabulary size.
+ * The way in for the n-best of decoder-free streams and for lists whose totals were fused by 8l or 8n.
+ * Outputs (any may be NULL; what lies behind n_hyps[i] / list_sizes[i] entries, or behind m_P positions, is left as it
+ * is): order / risk / weight / status [n][nbest], header [n][4], dist [n][16][16], conf / alt_tok / alt_mass [n][max_len],
+ * gap_mass [n][max_len + 1]; a stream without hypotheses or an empty list gets header {-1, 0, 0, 0}. */
+#define SC_MBR_WS_DEFAULT_BYTES ((size_t)256 << 20)
+#define SC_MBR_WS_MIN_BYTES ((size_t)8 << 20)
+int sc_mbr_hyps(sc_streams *streams, const int *stream_ids, int n, int nbest, double scale, int pivot_best, int max_len,
+                int32_t *order, double *risk, double *weight, int32_t *status, int32_t *header, int32_t *dist,
+                double *conf, int32_t *alt_tok, double *alt_mass, double *gap_mass, int *n_hyps);
+int sc_mbr_lists(sc_streams *streams, const int32_t *ids, const int32_t *lens, const double *values, int are_weights,
+                 const int *list_sizes, const int32_t *pivot, int n, int nbest, int max_len, double scale,
+                 int32_t *order, double *risk, double *weight, int32_t *status, int32_t *header, int32_t *dist,
+                 double *conf, int32_t *alt_tok, double *alt_mass, double *gap_mass);
+int sc_streams_set_mbr_ws(sc_streams *streams, size_t max_bytes);
+int sc_streams_mbr_ws(const sc_streams *streams, size_t *limit, size_t *allocated);
 
 /* CTC forced alignment of the hypotheses sc_get_hyps_batch would return (same rules: the snapshot with a queue depth
  * > 1, an error for a stream inside a decode block), best first, against the stream's own CTC rows: the T frames of

@@ -74,7 +74,7 @@ def to_16k(raw, rate, device="cuda:0"):
 def recognize_file(speech2text, media_path, output_file="", quiet=True, progress=True, num_slots=1, chunk_length=8192,
                    token_alignment=False, segmentation="host", channel=None, token_alternates=0, ctc_beam=0,
                    ctc_only=False, ctc_lm=None, lm_weight=0.5, word_bonus=0.0, rescore_lm=None, rescore_weight=0.5,
-                   rescore_bonus=0.0, ctc_grammar=None, attention_rescore=None):
+                   rescore_bonus=0.0, ctc_grammar=None, attention_rescore=None, consensus=None):
     """speechcatcher.py:358-400: recording -> text + paragraphs JSON next to the input.  ``token_alignment``: the
     paragraphs also get token_start / token_end (seconds) and token_conf from a CTC forced alignment of each segment.
     ``segmentation``: "host" or "gpu" - where the energy curve for the cut points of a recording over 60 s is computed.
@@ -87,13 +87,18 @@ def recognize_file(speech2text, media_path, output_file="", quiet=True, progress
     ``word_bonus`` (needs ``ctc_beam`` or ``ctc_only``).  ``rescore_lm``: the path of a packed n-gram model the final
     n-best list of every segment is rescored with and re-ranked by, at ``rescore_weight`` / ``rescore_bonus`` (not with
     ``ctc_only``).  ``ctc_grammar``: the path of a compiled grammar (python -m speechcatcher_amd.grammar) or of a text file
-    with one phrase per line - the CTC beam answers only from it (needs ``ctc_beam`` or ``ctc_only``; not with ``ctc_lm``)."""
+    with one phrase per line - the CTC beam answers only from it (needs ``ctc_beam`` or ``ctc_only``; not with ``ctc_lm``).
+    ``consensus``: True - every segment's text is the minimum-Bayes-risk row of its final n-best list - or "confidence" -
+    the text stays the search's; both: the paragraphs get token_consensus / token_rival per token and mbr per segment
+    (needs a beam of at least 2)."""
     if ctc_grammar and not (ctc_only or int(ctc_beam)):
         raise SystemExit("Error: --ctc-grammar constrains the CTC prefix beam search: it needs --ctc-beam or --ctc-only")
     if ctc_grammar and ctc_lm:
         raise SystemExit("Error: --ctc-grammar and --ctc-lm together are not served")
     if ctc_grammar and not os.path.isfile(ctc_grammar):
         raise SystemExit(f"Error: --ctc-grammar: '{ctc_grammar}' does not exist or is not a file")
+    if consensus and max(int(getattr(speech2text, "beam_size", 0) or 0), int(ctc_beam), 8 if ctc_only else 0) < 2:
+        raise SystemExit("Error: --consensus compares the rows of an n-best list: it needs --beamsize of at least 2")
     if attention_rescore is not None and not ctc_only:
         raise SystemExit("Error: --attention-rescore re-ranks the n-best list of a decoder-free segment: it needs --ctc-only")
     if rescore_lm and ctc_only:
@@ -131,7 +136,8 @@ def recognize_file(speech2text, media_path, output_file="", quiet=True, progress
                                      rescore_lm=rescore_lm or None, rescore_weight=float(rescore_weight),
                                      rescore_bonus=float(rescore_bonus),
                                      **({"ctc_grammar": ctc_grammar} if ctc_grammar else {}),
-                                     **({} if attention_rescore is None else {"attention_rescore": (float(attention_rescore), 0.5)}))
+                                     **({} if attention_rescore is None else {"attention_rescore": (float(attention_rescore), 0.5)}),
+                                     **({"consensus": consensus} if consensus else {}))
     out_txt, out_json = (output_file or media_path) + ".txt", (output_file or media_path) + ".json"
     with open(out_txt, "w") as f:
         f.write(text)
@@ -203,6 +209,12 @@ def make_parser():
                    help="with --ctc-only: re-rank every segment's final n-best list by one teacher-forced pass of the attention "
                         "decoder over the segment's encoder output, fused = 0.5 * ctc + W_ATT * att (default 1.0; parameters, not "
                         "tuned); the segment .json carries the re-ranked ctc_nbest")
+    p.add_argument("--consensus", dest="consensus", action="store_const", const=True, default=None,
+                   help="report the minimum-Bayes-risk row of every segment's final n-best list under the edit distance "
+                        "instead of the best-scored one, and add token_consensus / token_rival / mbr to the .json: per token "
+                        "the share of the list's mass that agrees on it and its strongest rival (needs --beamsize >= 2)")
+    p.add_argument("--consensus-confidence", dest="consensus", action="store_const", const="confidence",
+                   help="as --consensus, but the transcript stays the best-scored row: only the statistics are added")
     p.add_argument("--segmentation", dest="segmentation", choices=["host", "gpu"], default="host",
                    help="where the energy curve for the cut points of a recording over 60 s is computed: 'host' (numpy, the "
                         "default) or 'gpu' (float64 kernels; the same cuts, without the host pass over the whole recording)")
@@ -241,7 +253,8 @@ def main(argv=None):
                    ctc_only=args.ctc_only, ctc_lm=args.ctc_lm or None, lm_weight=args.lm_weight, word_bonus=args.word_bonus,
                    rescore_lm=args.rescore_lm or None, rescore_weight=args.rescore_weight, rescore_bonus=args.rescore_bonus,
                    **({"ctc_grammar": args.ctc_grammar} if args.ctc_grammar else {}),
-                   **({} if args.attention_rescore is None else {"attention_rescore": args.attention_rescore}))
+                   **({} if args.attention_rescore is None else {"attention_rescore": args.attention_rescore}),
+                   **({"consensus": args.consensus} if args.consensus else {}))
     return 0
 
 

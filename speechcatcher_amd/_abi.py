@@ -232,6 +232,20 @@ RESCORE_MAX_HYPS, RESCORE_MAX_JOBS, RESCORE_FORCE_SERIAL = 16, 65535, 1
 RESCORE_NONFINITE, RESCORE_BAD_TOKEN, RESCORE_SERIAL = 1, 2, 4
 
 
+class MbrJob(C.Structure):
+    """sc_mbr_job (include/scasr.h): one n-best list whose consensus sc_mbr computes"""
+    _fields_ = ([(n, vp) for n in ("yseq", "score", "weight", "lens", "weight_out", "risk", "dist", "order", "status",
+                                   "header", "conf", "alt_mass", "gap_mass", "alt_tok", "slots")]
+                + [(n, C.c_int64) for n in ("row_stride", "score_stride", "slot_stride")]
+                + [("scale", C.c_double)]
+                + [(n, C.c_int32) for n in ("n_hyp", "L", "skip", "strip", "V", "pivot", "flags", "reserved")])
+
+
+# SC_MBR_* of include/scasr.h
+MBR_MAX_HYPS, MBR_MAX_LEN, MBR_MAX_JOBS = 16, 1024, 65535
+MBR_NONFINITE, MBR_BAD_TOKEN, MBR_TOO_LONG, MBR_NO_PIVOT = 1, 2, 4, 8
+
+
 class SeqAttnJob(C.Structure):
     """sc_seq_attn_job (include/scasr.h): the attention of one sequence in sc_seq_attention"""
     _fields_ = ([(n, vp) for n in ("q", "k", "v", "o")]
@@ -488,6 +502,15 @@ _SIGS = {
                                   vp, vp, vp, c_int_p]),
     "sc_lm_rescore_lists": (C.c_int, [vp, vp, vp, vp, vp, c_int_p, C.c_int, C.c_int, C.c_int, vp, C.c_double,
                                       C.c_double, C.c_int, vp, vp, vp, vp, vp, vp]),
+    # consensus of n-best lists (mbr.hip, stream_readback.hip)
+    "sc_mbr_ws_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "sc_mbr": (C.c_int, [vp, C.c_int, vp, C.c_size_t, vp]),
+    "sc_mbr_hyps": (C.c_int, [vp, c_int_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                              vp, c_int_p]),
+    "sc_mbr_lists": (C.c_int, [vp, vp, vp, vp, C.c_int, c_int_p, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp,
+                               vp, vp, vp, vp, vp, vp]),
+    "sc_streams_set_mbr_ws": (C.c_int, [vp, C.c_size_t]),
+    "sc_streams_mbr_ws": (C.c_int, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     # attention rescoring of n-best lists (dec_rescore.hip)
     "sc_seq_attention": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "sc_dec_rescore_ws_bytes": (C.c_size_t, [vp, C.c_long, C.c_long, C.c_int, C.c_int]),

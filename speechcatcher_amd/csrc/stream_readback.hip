@@ -330,6 +330,219 @@ extern "C" int sc_lm_rescore_lists(sc_streams *b, const sc_lm *lm, const int32_t
   SC_API_END
 }
 
+// ---- consensus of n-best lists ------------------------------------------------------------------------
+// The scratch area holds [job table][inputs of caller-given lists][outputs]: what lies before the outputs goes up in ONE
+// copy, the launches of sc_mbr, the outputs come back in ONE copy, all on the read-back stream.  A job's outputs, for a
+// call whose rows have at most `cap` labels: weight, risk [16], conf, alt_mass [cap], gap_mass [cap + 1] doubles, then
+// order, status [16], header [4], dist [256], alt_tok [cap] int32.  The direction workspace is the handle's own
+// allocation (mbr_ws): as large as a call needs, never beyond mbr_ws_limit; beyond it the jobs run in slabs of whole
+// lists, one sc_mbr call each, in stream order on the one workspace.
+namespace {
+constexpr int MB_H = SC_MBR_MAX_HYPS;
+
+struct MbrLayout {
+  int cap;   // labels a row of the call has at most, clamped to SC_MBR_MAX_LEN
+  size_t doubles() const { return 2 * MB_H + 3 * (size_t)cap + 1; }
+  size_t ints() const { return 2 * MB_H + 4 + MB_H * MB_H + (size_t)cap; }
+  size_t bytes() const { return (doubles() * sizeof(double) + ints() * sizeof(int32_t) + 7) & ~(size_t)7; }
+};
+
+void mb_outputs(sc_mbr_job &j, const MbrLayout &lay, char *out) {
+  j.weight_out = (double *)out;
+  j.risk = j.weight_out + MB_H;
+  j.conf = j.risk + MB_H;
+  j.alt_mass = j.conf + lay.cap;
+  j.gap_mass = j.alt_mass + lay.cap;
+  j.order = (int32_t *)(j.gap_mass + lay.cap + 1);
+  j.status = j.order + MB_H;
+  j.header = j.status + MB_H;
+  j.dist = j.header + 4;
+  j.alt_tok = j.dist + MB_H * MB_H;
+  j.slots = nullptr;
+  j.slot_stride = 0;
+}
+
+int mb_workspace(sc_streams *b, size_t need) {
+  const size_t want = std::min((need + 255) & ~(size_t)255, b->mbr_ws_limit & ~(size_t)255);
+  if (want <= b->mbr_ws_bytes) return SC_OK;
+  HIP_TRY(hipStreamSynchronize(b->stream_rb));
+  if (b->mbr_ws) (void)hipFree(b->mbr_ws);
+  b->mbr_ws = nullptr;
+  b->mbr_ws_bytes = 0;
+  HIP_TRY(hipMalloc((void **)&b->mbr_ws, want));
+  b->mbr_ws_bytes = want;
+  return SC_OK;
+}
+
+// the m jobs at the head of the area (job k's rows have at most caps[k] labels), with whatever else lies before o_out, go
+// up; the jobs run in slabs that fit the workspace; the outputs [o_out, o_out + m lay.bytes()) come back
+int mb_run(sc_streams *b, size_t o_out, const MbrLayout &lay, const std::vector<int> &caps, bool from_snapshot) {
+  const int m = (int)caps.size();
+  std::vector<std::pair<int, int>> slabs;   // [first, count)
+  size_t need = 0;
+  for (int a = 0; a < m;) {
+    int cnt = 1, cap = caps[a];
+    while (a + cnt < m && sc_mbr_ws_bytes(cnt + 1, std::max(cap, caps[a + cnt])) <= (b->mbr_ws_limit & ~(size_t)255)) {
+      cap = std::max(cap, caps[a + cnt]);
+      ++cnt;
+    }
+    need = std::max(need, sc_mbr_ws_bytes(cnt, cap));
+    slabs.emplace_back(a, cnt);
+    a += cnt;
+  }
+  RC_TRY(mb_workspace(b, need));
+  return area_run(b, o_out, from_snapshot, [&]() -> int {
+    for (const auto &sl : slabs)
+      RC_TRY(sc_mbr((const sc_mbr_job *)b->rb.dev + sl.first, sl.second, b->mbr_ws, b->mbr_ws_bytes, b->stream_rb));
+    return SC_OK;
+  }, o_out, (size_t)m * lay.bytes());
+}
+
+struct MbrOut {
+  int32_t *order; double *risk, *weight; int32_t *status, *header, *dist; double *conf; int32_t *alt_tok; double *alt_mass, *gap_mass;
+};
+
+// the outputs of job k (nh rows) -> entry i of the caller's arrays; k < 0: the list was empty
+void mb_copy_out(const sc_streams *b, size_t o_out, const MbrLayout &lay, int k, size_t i, int nbest, int max_len, int nh,
+                 const MbrOut &o) {
+  if (k < 0) {
+    if (o.header) { int32_t *h = o.header + 4 * i; h[0] = -1; h[1] = h[2] = h[3] = 0; }
+    return;
+  }
+  const char *src = b->rb.host + o_out + (size_t)k * lay.bytes();
+  const double *d = (const double *)src;
+  const int32_t *q = (const int32_t *)(d + lay.doubles());
+  const int mp = std::max(0, std::min(q[2 * MB_H + 1], lay.cap));
+  const bool has_pivot = q[2 * MB_H] >= 0;
+  if (o.weight) memcpy(o.weight + i * nbest, d, nh * sizeof(double));
+  if (o.risk) memcpy(o.risk + i * nbest, d + MB_H, nh * sizeof(double));
+  if (o.conf) memcpy(o.conf + i * max_len, d + 2 * MB_H, mp * sizeof(double));
+  if (o.alt_mass) memcpy(o.alt_mass + i * max_len, d + 2 * MB_H + lay.cap, mp * sizeof(double));
+  if (o.gap_mass && has_pivot) memcpy(o.gap_mass + i * ((size_t)max_len + 1), d + 2 * MB_H + 2 * (size_t)lay.cap, (mp + 1) * sizeof(double));
+  if (o.order) memcpy(o.order + i * nbest, q, nh * sizeof(int32_t));
+  if (o.status) memcpy(o.status + i * nbest, q + MB_H, nh * sizeof(int32_t));
+  if (o.header) memcpy(o.header + 4 * i, q + 2 * MB_H, 4 * sizeof(int32_t));
+  if (o.dist) memcpy(o.dist + i * MB_H * MB_H, q + 2 * MB_H + 4, MB_H * MB_H * sizeof(int32_t));
+  if (o.alt_tok) memcpy(o.alt_tok + i * max_len, q + 2 * MB_H + 4 + MB_H * MB_H, mp * sizeof(int32_t));
+}
+}  // namespace
+
+extern "C" int sc_streams_set_mbr_ws(sc_streams *b, size_t max_bytes) {
+  SC_CHECK_ARG(b && max_bytes >= SC_MBR_WS_MIN_BYTES, "a workspace limit of at least SC_MBR_WS_MIN_BYTES");
+  SC_API_BEGIN
+  HIP_TRY(hipSetDevice(b->eng->device));
+  b->mbr_ws_limit = max_bytes;
+  if (b->mbr_ws_bytes > max_bytes) {   // the next call allocates within the new limit
+    HIP_TRY(hipStreamSynchronize(b->stream_rb));
+    (void)hipFree(b->mbr_ws);
+    b->mbr_ws = nullptr;
+    b->mbr_ws_bytes = 0;
+  }
+  return SC_OK;
+  SC_API_END
+}
+
+extern "C" int sc_streams_mbr_ws(const sc_streams *b, size_t *limit, size_t *allocated) {
+  SC_CHECK_ARG(b, "null");
+  if (limit) *limit = b->mbr_ws_limit;
+  if (allocated) *allocated = b->mbr_ws_bytes;
+  return SC_OK;
+}
+
+extern "C" int sc_mbr_hyps(sc_streams *b, const int *stream_ids, int n, int nbest, double scale, int pivot_best, int max_len,
+                           int32_t *order, double *risk, double *weight, int32_t *status, int32_t *header, int32_t *dist,
+                           double *conf, int32_t *alt_tok, double *alt_mass, double *gap_mass, int *n_hyps) {
+  SC_CHECK_ARG(b && stream_ids && n_hyps && n >= 0 && nbest >= 0 && nbest <= SC_MBR_MAX_HYPS && max_len >= 0, "bad arguments");
+  SC_CHECK_ARG(std::isfinite(scale) && scale >= 0.0, "scale must be finite and not negative");
+  SC_API_BEGIN
+  HIP_TRY(hipSetDevice(b->eng->device));
+  SC_CHECK_ARG(n <= b->S, "more streams listed than the batch has");
+  const MbrLayout lay{std::min(max_len, SC_MBR_MAX_LEN)};
+  const size_t o_out = (size_t)std::max(n, 1) * sizeof(sc_mbr_job);
+  RC_TRY(b->rb.reserve(o_out + (size_t)std::max(n, 1) * lay.bytes(), b->stream_rb));
+  sc_mbr_job *jobs = (sc_mbr_job *)b->rb.host;
+  std::vector<char> listed(b->S, 0);
+  std::vector<int> job_of(n, -1), caps;
+  bool from_snapshot = false;
+  for (int i = 0; i < n; ++i) {
+    const int s = stream_ids[i];
+    RC_TRY(listed_once(b, s, listed));
+    HypSrc h;
+    RC_TRY(hyp_source(b, s, &h));
+    const int nh = std::min(nbest, h.nh);
+    from_snapshot = from_snapshot || (h.snap && nh > 0);
+    n_hyps[i] = nh;
+    if (nh == 0) continue;
+    const int cap = std::min(std::max(0, h.L - 1), SC_MBR_MAX_LEN);
+    SC_CHECK_ARG(cap <= max_len, "max_len is smaller than the hypotheses");
+    sc_mbr_job j{};
+    j.yseq = h.yseq;
+    j.score = h.score;
+    j.score_stride = h.score_stride;
+    mb_outputs(j, lay, b->rb.dev + o_out + caps.size() * lay.bytes());
+    j.row_stride = b->LCAP;
+    j.scale = scale;
+    j.n_hyp = nh; j.L = h.L; j.skip = 1; j.strip = b->cfg.eos_id; j.V = b->cfg.vocab_size;
+    j.pivot = pivot_best ? 0 : -1;
+    jobs[caps.size()] = j;
+    job_of[i] = (int)caps.size();
+    caps.push_back(cap);
+  }
+  if (!caps.empty()) RC_TRY(mb_run(b, o_out, lay, caps, from_snapshot));
+  const MbrOut o{order, risk, weight, status, header, dist, conf, alt_tok, alt_mass, gap_mass};
+  for (int i = 0; i < n; ++i) mb_copy_out(b, o_out, lay, job_of[i], (size_t)i, nbest, max_len, n_hyps[i], o);
+  return SC_OK;
+  SC_API_END
+}
+
+extern "C" int sc_mbr_lists(sc_streams *b, const int32_t *ids, const int32_t *lens, const double *values, int are_weights,
+                            const int *list_sizes, const int32_t *pivot, int n, int nbest, int max_len, double scale,
+                            int32_t *order, double *risk, double *weight, int32_t *status, int32_t *header, int32_t *dist,
+                            double *conf, int32_t *alt_tok, double *alt_mass, double *gap_mass) {
+  SC_CHECK_ARG(b && lens && values && list_sizes && n >= 0 && n <= SC_MBR_MAX_JOBS && nbest >= 0 && nbest <= SC_MBR_MAX_HYPS &&
+               max_len >= 0 && (ids || max_len == 0), "bad arguments");
+  SC_CHECK_ARG(std::isfinite(scale) && scale >= 0.0, "scale must be finite and not negative");
+  SC_API_BEGIN
+  HIP_TRY(hipSetDevice(b->eng->device));
+  for (int i = 0; i < n; ++i) {
+    SC_CHECK_ARG(list_sizes[i] >= 0 && list_sizes[i] <= nbest, "a list size outside [0, nbest]");
+    SC_CHECK_ARG(!pivot || (pivot[i] >= -1 && pivot[i] < std::max(list_sizes[i], 1)), "a pivot outside [-1, list size)");
+  }
+  const MbrLayout lay{std::min(max_len, SC_MBR_MAX_LEN)};
+  const size_t rows = (size_t)n * nbest;
+  const size_t o_val = (size_t)std::max(n, 1) * sizeof(sc_mbr_job), o_len = o_val + rows * sizeof(double),
+               o_ids = o_len + ((rows * sizeof(int32_t) + 7) & ~(size_t)7),
+               o_out = o_ids + ((rows * max_len * sizeof(int32_t) + 7) & ~(size_t)7);
+  RC_TRY(b->rb.reserve(o_out + (size_t)std::max(n, 1) * lay.bytes(), b->stream_rb));
+  sc_mbr_job *jobs = (sc_mbr_job *)b->rb.host;
+  memcpy(b->rb.host + o_val, values, rows * sizeof(double));
+  memcpy(b->rb.host + o_len, lens, rows * sizeof(int32_t));
+  if (rows * max_len) memcpy(b->rb.host + o_ids, ids, rows * max_len * sizeof(int32_t));
+  std::vector<int> job_of(n, -1), caps;
+  for (int i = 0; i < n; ++i) {
+    if (list_sizes[i] == 0) continue;
+    sc_mbr_job j{};
+    j.yseq = (const int32_t *)(b->rb.dev + o_ids) + (size_t)i * nbest * max_len;
+    const double *v = (const double *)(b->rb.dev + o_val) + (size_t)i * nbest;
+    if (are_weights) j.weight = v; else j.score = v;
+    j.score_stride = 1;
+    j.lens = (const int32_t *)(b->rb.dev + o_len) + (size_t)i * nbest;
+    mb_outputs(j, lay, b->rb.dev + o_out + caps.size() * lay.bytes());
+    j.row_stride = max_len;
+    j.scale = scale;
+    j.n_hyp = list_sizes[i]; j.L = max_len; j.skip = 0; j.strip = -1; j.V = b->cfg.vocab_size;
+    j.pivot = pivot ? pivot[i] : -1;
+    jobs[caps.size()] = j;
+    job_of[i] = (int)caps.size();
+    caps.push_back(lay.cap);
+  }
+  if (!caps.empty()) RC_TRY(mb_run(b, o_out, lay, caps, false));
+  const MbrOut o{order, risk, weight, status, header, dist, conf, alt_tok, alt_mass, gap_mass};
+  for (int i = 0; i < n; ++i) mb_copy_out(b, o_out, lay, job_of[i], (size_t)i, nbest, max_len, list_sizes[i], o);
+  return SC_OK;
+  SC_API_END
+}
+
 // ---- CTC forced alignment ------------------------------------------------------------------------------------------
 // One sc_ctc_align launch pair on the read-back stream for a list of (stream, frames, labels) requests; outputs back to
 // the host.  The scratch area holds [job table][labels][outputs: start, end | logp_mean | path_score, status][workspaces]

@@ -394,7 +394,7 @@ struct sc_streams {
   size_t cm_cap = 0;              // int32 elements
   // ---- scratch area of the read-back services (stream_readback.hip): job tables, inputs, outputs, workspaces ---------------
   // ONE area serves sc_rescore_hyps / sc_lm_rescore_lists, sc_align_hyps / sc_alternates_hyps / sc_align_tokens,
-  // sc_ctc_beam_hyps and sc_attention_rescore_beam / _lists, each with a layout of its own from offset 0.  That is sound
+  // sc_ctc_beam_hyps, sc_attention_rescore_beam / _lists and sc_mbr_hyps / _lists, each with a layout of its own from offset 0.  That is sound
   // because every one of them reserves what it needs, fills the pinned half, makes its round trip on stream_rb, ends in a
   // host synchronise (on failure too) and copies its results to the caller's arrays before it returns: nothing is kept in
   // the area between two calls, and the handle serves one call at a time.  Allocated by the first such call.
@@ -456,6 +456,9 @@ struct sc_streams {
   char *ar_ws = nullptr;                        // workspace of sc_dec_rescore: what a call needs, at most ar_ws_limit bytes
   size_t ar_ws_bytes = 0, ar_ws_limit = SC_ATT_WS_DEFAULT_BYTES;
   void *ar_splitk = nullptr;                    // split-K workspace of the read-back stream (the fused feed-forward's partial sums)
+  // ---- consensus of n-best lists (sc_mbr_hyps / sc_mbr_lists): allocated by the first call ---------------------------
+  char *mbr_ws = nullptr;                       // direction workspace of sc_mbr: what a call needs, at most mbr_ws_limit bytes
+  size_t mbr_ws_bytes = 0, mbr_ws_limit = SC_MBR_WS_DEFAULT_BYTES;
   size_t beam_ncap() const { return 1 + (size_t)beam_nodes_B * TCAP; }
   // ---- tick engine -----------------------------------------------------------------------------------------------------
   std::vector<St> st;
@@ -519,6 +522,7 @@ struct sc_streams {
     if (stream_rb) (void)hipStreamDestroy(stream_rb);
     if (stream) (void)hipStreamDestroy(stream);
     if (ar_ws) (void)hipFree(ar_ws);
+    if (mbr_ws) (void)hipFree(mbr_ws);
     if (ar_splitk) (void)hipFree(ar_splitk);
     if (beam_nodes) (void)hipFree(beam_nodes);
     for (sc_grammar *g : beam_gr)   // (the streams are synchronised: nothing reads a grammar any more)

@@ -918,6 +918,103 @@ class HipBackend:
                         "raw": {"f64": f64[k].copy(), "i32": i32[k].copy(), "tok": tok[a:b].copy()}})
         return out
 
+    # ---- consensus of n-best lists (csrc/mbr.hip) ---------------------------------------------------------
+    def mbr(self, jobs, tweak=None, guard: int = 2, ws_limit=None, ws_bytes=None):
+        """Minimum-Bayes-risk row and slot confidences of n-best lists (sc_mbr) on the caller's device
+        arrays.  jobs: list of dicts - "rows": int32 device tensor [n, >= L], rows may be strided; "weights" OR "scores":
+        float64 device tensor [n] (scores may be strided); "L"; "V"; optional "lens" (n ints; default: L each), "skip"
+        (0), "strip" (-1), "scale" (1.0), "pivot" (-1), "slots" (True: wanted).  ``ws_limit``: bytes of workspace a call
+        may use - beyond it the jobs go in slabs of whole lists, one sc_mbr call each; ``ws_bytes``: the size handed to
+        the one call instead of what sc_mbr_ws_bytes asks for (test aid).  Returns one dict per job: "weight", "risk"
+        (float64 [n]), "dist" (int32 [16, 16]), "order", "status" (int32 [n]), "header" (int32 [4]), "conf", "alt_mass"
+        (float64 [m_P]), "alt_tok" (int32 [m_P]), "gap_mass" (float64 [m_P + 1] or empty), "slots" (int32 [n, m_P] or
+        None) and "raw": the output buffers whole, every one handed over filled with -7 and ``guard`` words longer than
+        the kernel may write.  ``tweak(k, job)``: test aid, edits the sc_mbr_job of job k before the launch."""
+        import numpy as np
+        n = len(jobs)
+        dev = self.device
+        H = _abi.MBR_MAX_HYPS
+        caps = [min(max(0, int(j["L"]) - int(j.get("skip", 0))), _abi.MBR_MAX_LEN) for j in jobs]
+        f64 = torch.full((max(n, 1), 2, H + guard), -7.0, dtype=torch.float64, device=dev)
+        i32 = torch.full((max(n, 1), 2, H + guard), -7, dtype=torch.int32, device=dev)
+        dist = torch.full((max(n, 1), H * H + guard), -7, dtype=torch.int32, device=dev)
+        head = torch.full((max(n, 1), 4 + guard), -7, dtype=torch.int32, device=dev)
+        pi = np.concatenate([[0], np.cumsum([c + 1 + guard for c in caps])]).astype(np.int64)
+        pos = torch.full((3, max(int(pi[-1]), 1)), -7.0, dtype=torch.float64, device=dev)     # conf, alt_mass, gap_mass
+        atok = torch.full((max(int(pi[-1]), 1),), -7, dtype=torch.int32, device=dev)
+        si = np.concatenate([[0], np.cumsum([int(j["rows"].shape[0]) * c + guard if j.get("slots", True) else 0
+                                             for j, c in zip(jobs, caps)])]).astype(np.int64)
+        slots = torch.full((max(int(si[-1]), 1),), -7, dtype=torch.int32, device=dev)
+        keep = []
+        tab = (_abi.MbrJob * max(1, n))()
+        for k, job in enumerate(jobs):
+            rows = job["rows"]
+            assert rows.dtype == torch.int32 and rows.dim() == 2 and (rows.shape[1] == 0 or rows.stride(1) == 1)
+            assert int(job["L"]) <= rows.shape[1] and ("weights" in job) != ("scores" in job)
+            j = tab[k]
+            j.yseq, j.row_stride = rows.data_ptr(), rows.stride(0) if rows.shape[0] > 1 else max(rows.shape[1], 1)
+            v = job["weights"] if "weights" in job else job["scores"]
+            assert v.dtype == torch.float64 and v.dim() == 1 and v.shape[0] == rows.shape[0]
+            if "weights" in job:
+                assert v.shape[0] <= 1 or v.stride(0) == 1
+                j.weight = v.data_ptr()
+            else:
+                j.score, j.score_stride = v.data_ptr(), v.stride(0) if v.shape[0] > 1 else 1
+            if job.get("lens") is not None:
+                lens = torch.tensor([int(x) for x in job["lens"]], dtype=torch.int32, device=dev)
+                keep.append(lens)
+                j.lens = lens.data_ptr()
+            j.weight_out, j.risk = f64[k, 0].data_ptr(), f64[k, 1].data_ptr()
+            j.order, j.status = i32[k, 0].data_ptr(), i32[k, 1].data_ptr()
+            j.dist, j.header = dist[k].data_ptr(), head[k].data_ptr()
+            j.conf, j.alt_mass, j.gap_mass = (pos[c].data_ptr() + 8 * int(pi[k]) for c in range(3))
+            j.alt_tok = atok.data_ptr() + 4 * int(pi[k])
+            if job.get("slots", True):
+                j.slots, j.slot_stride = slots.data_ptr() + 4 * int(si[k]), caps[k]
+            j.scale = float(job.get("scale", 1.0))
+            j.n_hyp, j.L, j.skip, j.strip = rows.shape[0], int(job["L"]), int(job.get("skip", 0)), int(job.get("strip", -1))
+            j.V, j.pivot, j.flags, j.reserved = int(job["V"]), int(job.get("pivot", -1)), 0, 0
+            if tweak is not None:
+                tweak(k, j)
+        tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+        need = lambda a, b: int(self.lib.sc_mbr_ws_bytes(b - a, max(caps[a:b], default=0)))   # noqa: E731
+        slabs, a = [], 0
+        while a < n:
+            b = a + 1
+            while ws_limit is not None and b < n and need(a, b + 1) <= ws_limit:
+                b += 1
+            if ws_limit is None:
+                b = n
+            slabs.append((a, b))
+            a = b
+        self.mbr_slabs = len(slabs)
+        ws_size = max([need(a, b) for a, b in slabs] + [int(ws_bytes or 0), 256])
+        ws = torch.empty((ws_size,), dtype=torch.uint8, device=dev)
+        for a, b in slabs:
+            size = need(a, b) if ws_bytes is None else int(ws_bytes)
+            self._chk(self.lib.sc_mbr(tab_dev.data_ptr() + a * C.sizeof(_abi.MbrJob), b - a, ws.data_ptr(), size,
+                                      self._stream()), "sc_mbr")
+        torch.cuda.synchronize(dev)
+        f64, i32, dist, head, pos, atok, slots = (t.cpu().numpy() for t in (f64, i32, dist, head, pos, atok, slots))
+        out = []
+        for k, job in enumerate(jobs):
+            nh, c = int(job["rows"].shape[0]), caps[k]
+            mp = max(0, min(int(head[k, 1]), c))
+            a, b = int(pi[k]), int(pi[k + 1])
+            sa, sb = int(si[k]), int(si[k + 1])
+            has_pivot = int(head[k, 0]) >= 0
+            want_slots = bool(job.get("slots", True))
+            out.append({"weight": f64[k, 0, :nh].copy(), "risk": f64[k, 1, :nh].copy(),
+                        "dist": dist[k, :H * H].reshape(H, H).copy(), "order": i32[k, 0, :nh].copy(),
+                        "status": i32[k, 1, :nh].copy(), "header": head[k, :4].copy(),
+                        "conf": pos[0, a:a + mp].copy(), "alt_mass": pos[1, a:a + mp].copy(),
+                        "gap_mass": pos[2, a:a + mp + 1].copy() if has_pivot else np.zeros(0, np.float64),
+                        "alt_tok": atok[a:a + mp].copy(),
+                        "slots": (slots[sa:sa + nh * c].reshape(nh, c)[:, :mp].copy() if want_slots else None),
+                        "raw": {"f64": f64[k].copy(), "i32": i32[k].copy(), "dist": dist[k].copy(), "header": head[k].copy(),
+                                "pos": pos[:3, a:b].copy(), "alt_tok": atok[a:b].copy(), "slots": slots[sa:sb].copy()}})
+        return out
+
     # ---- attention rescoring of n-best lists (csrc/dec_rescore.hip; DESIGN.md 8n) -------------------------------------
     def seq_attention(self, jobs, dk: int, max_Lq=None, tweak=None):
         """Attention of whole sequences (sc_seq_attention), one call for all jobs.  jobs: list of dicts - "q" [>= Lq,

@@ -960,6 +960,91 @@ class NativeStreamBatch:
         _abi.check(self.lib.sc_streams_attention_rescore_ws(self.handle, C.byref(lim), C.byref(got)), "sc_streams_attention_rescore_ws")
         return int(lim.value), int(got.value)
 
+    # ---- consensus of final n-best lists (sc_mbr_hyps / sc_mbr_lists) ------------------------------------
+    @staticmethod
+    def _mbr_arrays(n: int, nb: int, ml: int):
+        i32 = lambda *shape: np.zeros(shape, np.int32)     # noqa: E731
+        return {"order": i32(n, nb), "risk": np.zeros((n, nb)), "weight": np.zeros((n, nb)), "status": i32(n, nb),
+                "header": i32(n, 4), "dist": i32(n, 16, 16), "conf": np.zeros((n, ml)), "alt_tok": i32(n, ml),
+                "alt_mass": np.zeros((n, ml)), "gap_mass": np.zeros((n, ml + 1))}
+
+    @staticmethod
+    def _mbr_entry(a, i: int, k: int):
+        P, mp = int(a["header"][i, 0]), int(a["header"][i, 1])
+        return {"order": a["order"][i, :k], "risk": a["risk"][i, :k], "weight": a["weight"][i, :k],
+                "status": a["status"][i, :k], "pivot": P, "n_in": int(a["header"][i, 2]), "dist": a["dist"][i, :k, :k],
+                "conf": a["conf"][i, :mp], "alt_tok": a["alt_tok"][i, :mp], "alt_mass": a["alt_mass"][i, :mp],
+                "gap_mass": a["gap_mass"][i, :mp + 1] if P >= 0 else a["gap_mass"][i, :0]}
+
+    def mbr_hyps(self, streams: Sequence[int], scale: float = 1.0, pivot_best: bool = False, nbest: Optional[int] = None):
+        """{stream: consensus} for the hypotheses ``hypotheses_batch`` would return: the minimum-Bayes-risk row under
+        the edit distance with weights softmax(scale * total), and the list's mass per slot of the pivot - "order"
+        (rows by ascending risk), "risk", "weight", "status" (numpy arrays over those rows), "pivot" (the row; -1: none),
+        "n_in", "dist", and per label of the pivot "conf", "alt_tok" (-1: nothing here; -2: no rival), "alt_mass", per gap
+        "gap_mass".  ``pivot_best``: the pivot is row 0, the search's best.  One call and one copy back for all listed
+        streams; nothing of the engine changes."""
+        sid = np.ascontiguousarray(streams, dtype=np.int32)
+        n = len(sid)
+        nb = min(int(self.W if nbest is None else nbest), _abi.MBR_MAX_HYPS)
+        ml = min(int(self.LCAP), _abi.MBR_MAX_LEN)
+        a = self._mbr_arrays(n, nb, ml)
+        nh = np.zeros(n, np.int32)
+        try:
+            _abi.check(self.lib.sc_mbr_hyps(self.handle, sid.ctypes.data_as(_abi.c_int_p), n, nb, float(scale),
+                                            int(bool(pivot_best)), ml, a["order"].ctypes.data, a["risk"].ctypes.data,
+                                            a["weight"].ctypes.data, a["status"].ctypes.data, a["header"].ctypes.data,
+                                            a["dist"].ctypes.data, a["conf"].ctypes.data, a["alt_tok"].ctypes.data,
+                                            a["alt_mass"].ctypes.data, a["gap_mass"].ctypes.data,
+                                            nh.ctypes.data_as(_abi.c_int_p)), "sc_mbr_hyps")
+        except _abi.ScasrError as e:
+            raise EngineError(str(e)) from e
+        return {int(s): self._mbr_entry(a, i, int(nh[i])) for i, s in enumerate(sid)}
+
+    def mbr_lists(self, lists, values, weights: bool = False, scale: float = 1.0, pivots=None):
+        """The same for caller-given lists: ``lists[i]`` is a list of label sequences (at most 16, no <sos> / <eos>),
+        ``values[i]`` their totals - or, with ``weights``, their weights -, ``pivots[i]`` a row that is to be the pivot
+        (default -1: the minimum-risk row).  Returns one dict per list, as mbr_hyps."""
+        n = len(lists)
+        if len(values) != n:
+            raise ValueError("one value list per list")
+        nb = max([len(li) for li in lists] + [1])
+        if nb > _abi.MBR_MAX_HYPS:
+            raise ValueError(f"a list holds more than {_abi.MBR_MAX_HYPS} rows")
+        ml = max([len(y) for li in lists for y in li] + [1])
+        ids, lens = np.zeros((n, nb, ml), np.int32), np.zeros((n, nb), np.int32)
+        val, sizes = np.zeros((n, nb)), np.zeros(n, np.int32)
+        for i, (li, vs) in enumerate(zip(lists, values)):
+            if len(li) != len(vs):
+                raise ValueError("one value per row")
+            sizes[i] = len(li)
+            for r, y in enumerate(li):
+                ids[i, r, :len(y)], lens[i, r], val[i, r] = y, len(y), vs[r]
+        pv = None if pivots is None else np.ascontiguousarray(pivots, dtype=np.int32)
+        if pv is not None and pv.shape != (n,):
+            raise ValueError("one pivot per list")
+        a = self._mbr_arrays(n, nb, ml)
+        try:
+            _abi.check(self.lib.sc_mbr_lists(self.handle, ids.ctypes.data, lens.ctypes.data, val.ctypes.data, int(bool(weights)),
+                                             sizes.ctypes.data_as(_abi.c_int_p), None if pv is None else pv.ctypes.data, n,
+                                             nb, ml, float(scale), a["order"].ctypes.data, a["risk"].ctypes.data,
+                                             a["weight"].ctypes.data, a["status"].ctypes.data, a["header"].ctypes.data,
+                                             a["dist"].ctypes.data, a["conf"].ctypes.data, a["alt_tok"].ctypes.data,
+                                             a["alt_mass"].ctypes.data, a["gap_mass"].ctypes.data), "sc_mbr_lists")
+        except _abi.ScasrError as e:
+            raise EngineError(str(e)) from e
+        return [self._mbr_entry(a, i, int(k)) for i, k in enumerate(sizes)]
+
+    def set_mbr_workspace(self, max_bytes: int):
+        """Upper bound of the direction workspace the two calls above allocate (default 256 MiB, at least 8 MiB;
+        include/scasr.h): a call that needs more runs in slabs of whole lists, with the same bits."""
+        _abi.check(self.lib.sc_streams_set_mbr_ws(self.handle, int(max_bytes)), "sc_streams_set_mbr_ws")
+
+    def mbr_workspace(self):
+        """(limit, allocated) bytes of that workspace; allocated is 0 until the first call"""
+        lim, got = C.c_size_t(0), C.c_size_t(0)
+        _abi.check(self.lib.sc_streams_mbr_ws(self.handle, C.byref(lim), C.byref(got)), "sc_streams_mbr_ws")
+        return int(lim.value), int(got.value)
+
     def hypotheses(self, s: int):
         """Live hypotheses of stream s: list of dicts (yseq, score, score_dec, score_ctc, xpos), best first."""
         return self.hypotheses_batch([int(s)])[int(s)]

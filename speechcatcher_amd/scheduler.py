@@ -30,6 +30,7 @@ from . import ctc_beam as beam_mod
 from . import alternates as alternates_mod
 from . import commit as commit_mod
 from . import rescore as rescore_mod
+from . import mbr as mbr_mod
 from .activity import of_stream as activity_of_stream
 from .align import FeatureClock
 from . import pcm as pcm_mod
@@ -55,6 +56,9 @@ class AlignedResults(list):
     alignment: Optional[dict] = None
     # StreamScheduler(final_lm=...): per result of a re-ranked final {"score", "lm", "fused", "am_rank"}
     rescored: Optional[list] = None
+    # StreamScheduler(consensus=...): of a final {"mbr": {"pivot", "risk", "am_rank"}, "tokens": a record per token of
+    # the first result {"id", "token", "consensus", "rival"?} (speechcatcher_amd.mbr)}
+    consensus: Optional[dict] = None
 
 
 class ActivityResults(AlignedResults):
@@ -124,7 +128,8 @@ class StreamScheduler:
                  phrases=None, min_scores=None, draft: bool = False, input_level: bool = False, alternates: int = 0,
                  align_nbest: int = 1, stable_partials: bool = False, ctc_beam=None, ctc_lm=None,
                  lm_weight: float = 0.5, word_bonus: float = 0.0, final_lm=None, final_lm_weight: float = 0.5,
-                 final_word_bonus: float = 0.0, final_lm_eos: bool = False, attention_rescore=None):
+                 final_word_bonus: float = 0.0, final_lm_eos: bool = False, attention_rescore=None, consensus=None,
+                 consensus_scale: float = 1.0):
         """``queue_depth`` > 1 (C++ engine, ``pump``): up to that many queued chunks of a session are handed to the engine
         at a time (sc_streams_set_queue_depth) - for sessions whose audio is already there (files): the encoder stage of
         the next chunk runs beside the decoding of the current one.  Replies and their order per session do not change.
@@ -181,6 +186,17 @@ class StreamScheduler:
         # parameters, not tuned.
         self.attention_rescore = None
         self._rescore_sessions = set()
+        # ``consensus`` (C++ engine): True or "confidence" - at a final the rows of the n-best list are
+        # compared on the GPU (NativeStreamBatch.mbr_hyps; mbr_lists for a list that ``final_lm`` / ``attention_rescore``
+        # re-ranked and for the ``ctc_nbest`` of a decoder-free session - the totals are then the fused ones), ONE call for
+        # all such finals of a reply round, with weights softmax(consensus_scale * total).  True: the reply's first
+        # result is the minimum-Bayes-risk row under the edit distance.  "confidence": the first-ranked row stays first.
+        # Both: the reply's ``consensus`` holds "mbr": {"pivot", "risk", "am_rank"} and "tokens", per token of the first
+        # result its "consensus" - the share of the list's mass with that token in that slot - and the strongest "rival".
+        # A grammar's "complete entries first" stays the outermost order.  Partials are untouched; the scale is a
+        # parameter, not tuned.
+        self.consensus = None
+        self.consensus_scale = 1.0
         self._slot_dec: Dict[int, str] = {}
         # grammars (``open(grammar=...)``, ``set_grammar``; needs ``ctc_beam``; C++ engine): compiled grammars by the
         # SHA-256 of their blob, {"handle": the device copy, "uses": the slots that name it, "walk": its host walk} - a
@@ -239,6 +255,8 @@ class StreamScheduler:
             self.enable_alternates(alternates)
         if stable_partials:
             self.enable_stable_partials()
+        if consensus is not None and consensus is not False:
+            self.enable_consensus(consensus, consensus_scale)
 
     def enable_activity(self, blank_threshold: float = 0.8):
         """switch the ``activity`` option on (only while no chunk is at the engine; every stream's state starts over)"""
@@ -298,6 +316,89 @@ class StreamScheduler:
         self._final_dev = self.batch.language_model(ngram.load(source))
         self.final_lm = (float(lm_weight), float(word_bonus), bool(eos))
         self.final_lm_eos = bool(eos)
+
+    def enable_consensus(self, mode=True, scale: float = 1.0):
+        """switch the ``consensus`` option on: True or "confidence"; None / False switches it off"""
+        mode = mbr_mod.check_mode(mode)
+        if mode is None:
+            self.consensus = None
+            return
+        wide = max(int(getattr(self.batch, "W", 0) or 0), self.ctc_beam[0] if self.ctc_beam is not None else 0)
+        if wide < 2:
+            raise ValueError("consensus compares the rows of an n-best list: it needs a beam_size of at least 2 "
+                             "(or ctc_beam=B with B >= 2 for decoder-free sessions)")
+        if not hasattr(self.batch, "mbr_hyps"):
+            raise NotImplementedError("consensus finals run in the C++ engine (NativeStreamBatch.mbr_hyps / mbr_lists, "
+                                      "sc_mbr_hyps / sc_mbr_lists); the Python lock-step engine has none")
+        if not (math.isfinite(scale) and scale >= 0):
+            raise ValueError("consensus_scale must be finite and not negative")
+        self.consensus, self.consensus_scale = mode, float(scale)
+
+    def _consensus_full(self, arrays: dict, row: dict, fins: list, perm: dict) -> Tuple[dict, dict]:
+        """ONE call for the round's finals of FULL sessions -> ({slot: the reply's ``consensus``}, {slot: order}): with
+        ``consensus=True`` the pivot's row of ``arrays`` is moved to the front (row q is then the engine's row order[q])"""
+        pinned = self.consensus == "confidence"
+        eos = self._eos_id
+        if perm:   # re-ranked finals: the lists as they stand now, each with its fused totals (a slot that was not
+            # re-ranked goes with the search's totals, in the same call)
+            lists, vals = [], []
+            for slot in fins:
+                i = row[slot]
+                nh = int(arrays["n_hyps"][i])
+                lists.append([mbr_mod.labels(arrays["ids"][i, j], arrays["lens"][i, j], eos) for j in range(nh)])
+                vals.append([float(v) for v in arrays["fused" if slot in perm else "score"][i, :nh]])
+            got = dict(zip(fins, self.batch.mbr_lists(lists, vals, scale=self.consensus_scale,
+                                                      pivots=[0 if li else -1 for li in lists] if pinned else None)))
+        else:
+            got = self.batch.mbr_hyps(fins, scale=self.consensus_scale, pivot_best=pinned, nbest=arrays["ids"].shape[1])
+        out, orders = {}, {}
+        for slot in fins:
+            e, i = got[slot], row[slot]
+            P, nh = int(e["pivot"]), len(e["order"])
+            if P < 0:
+                continue
+            base = perm.get(slot)
+            am = int(base[P]) if base is not None else P
+            piv = mbr_mod.labels(arrays["ids"][i, P], arrays["lens"][i, P], eos)
+            order = mbr_mod.pivot_first(arrays, i, P, nh)
+            orders[slot] = order if base is None else np.asarray(base)[order]
+            out[slot] = {"mbr": mbr_mod.summary(e, am), "tokens": mbr_mod.token_records(e, piv, self.token_list)}
+        return out, orders
+
+    def _consensus_ctc(self, out: dict, pending: list):
+        """ONE call for the round's finals of decoder-free sessions, over their ``ctc_nbest`` as it stands (re-ranked or
+        not; with a grammar over the group that leads the list, so "complete entries first" stays outermost); with
+        ``consensus=True`` the pivot moves to the front of its group and the reply's results follow"""
+        groups = []
+        for sid, has_gr in pending:
+            nb = out[sid].ctc_nbest
+            g = len(nb)
+            if has_gr:
+                g = next((k for k, e in enumerate(nb) if e.get("complete") != nb[0].get("complete")), len(nb))
+            groups.append(min(g, mbr_mod.MAX_HYPS))
+        pinned = self.consensus == "confidence"
+        got = self.batch.mbr_lists([[list(e["ids"]) for e in out[sid].ctc_nbest[:g]] for (sid, _), g in zip(pending, groups)],
+                                   [[float(e["score"]) for e in out[sid].ctc_nbest[:g]] for (sid, _), g in zip(pending, groups)],
+                                   scale=self.consensus_scale, pivots=[0] * len(pending) if pinned else None)
+        for (sid, _), g, e in zip(pending, groups, got):
+            old, P = out[sid], int(e["pivot"])
+            if P < 0:
+                continue
+            nb = list(old.ctc_nbest)
+            piv = nb[P]
+            am = int(piv.get("am_rank", P))
+            if P > 0:
+                nb = [piv] + nb[:P] + nb[P + 1:]
+                res = CtcBeamResults(self._ctc_results(nb))
+                for k in ("alignment", "activity", "detections", "draft", "ahead", "level", "stable", "rescored",
+                          "grammar_complete"):
+                    setattr(res, k, getattr(old, k, None))
+                res.ctc_nbest = nb
+                if old.alignment is not None and len(res):
+                    res.alignment = self._ctc_alignment(res)
+                out[sid] = res
+            names = None if self.token_list is None else self.token_list
+            out[sid].consensus = {"mbr": mbr_mod.summary(e, am), "tokens": mbr_mod.token_records(e, piv["ids"], names)}
 
     def enable_attention_rescore(self, spec=True):
         """switch the ``attention_rescore`` option on: True, or (w_att, w_ctc[, beta]); None / False switches it off"""
@@ -677,6 +778,12 @@ class StreamScheduler:
                                               nbest=arrays["ids"].shape[1])
                 for slot in fins:
                     perm[slot] = rescore_mod.rerank_arrays(arrays, row[slot], got[slot])
+        cons, cperm, cons_ctc = {}, {}, []
+        if self.consensus is not None and arrays is not None:   # ONE call and one copy back for the round's finals
+            fins = [slot for sid, (slot, fin, _) in meta.items()
+                    if fin and has[slot] is True and sid not in self._ctc_sessions]
+            if fins:
+                cons, cperm = self._consensus_full(arrays, row, fins, perm)
         act = act_row = None
         if self.activity:
             act_slots = [slot for (slot, _, _) in meta.values() if not isinstance(has[slot], Exception)]
@@ -724,7 +831,7 @@ class StreamScheduler:
                 out[sid] = hyps_to_results(hyps[slot], fin, fa, self.token_list, self.result_format)
             if fin and self.align_final and not isinstance(out[sid], Exception) and sid not in self._ctc_sessions:
                 out[sid] = self._aligned(out[sid], arrays, row[slot] if arrays is not None and has[slot] is True else None,
-                                         slot, fin, fa, self._clock.get(sid), perm.get(slot))
+                                         slot, fin, fa, self._clock.get(sid), cperm.get(slot, perm.get(slot)))
             if rescored is not None:
                 if not isinstance(out[sid], AlignedResults):
                     out[sid] = AlignedResults(out[sid])
@@ -786,10 +893,18 @@ class StreamScheduler:
                 if free and fin and self.align_final and len(res):
                     res.alignment = self._ctc_alignment(res)
                 out[sid] = res
+                if free and fin and self.consensus is not None and has[slot] and nbest and hasattr(self.batch, "mbr_lists"):
+                    cons_ctc.append((sid, gr_key is not None))
+            if slot in cons:
+                if not isinstance(out[sid], AlignedResults):
+                    out[sid] = AlignedResults(out[sid])
+                out[sid].consensus = cons[slot]
             if fin and self.reset_after_final:
                 self.batch.reset(slot)
                 self._clock.pop(sid, None)
                 self._spot_seen.pop(sid, None)
+        if cons_ctc:
+            self._consensus_ctc(out, cons_ctc)
         return out
 
     def _ctc_nbest(self, sid: int, hyps: list, side: Optional[dict] = None) -> list:
@@ -1041,7 +1156,7 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
                        queue_depth: int = 1, token_alignment: bool = False, token_alternates: int = 0,
                        ctc_beam=None, ctc_only: bool = False, ctc_lm=None, lm_weight: float = 0.5,
                        word_bonus: float = 0.0, rescore_lm=None, rescore_weight: float = 0.5,
-                       rescore_bonus: float = 0.0, ctc_grammar=None, attention_rescore=None) -> List[dict]:
+                       rescore_bonus: float = 0.0, ctc_grammar=None, attention_rescore=None, consensus=None) -> List[dict]:
     """Decode the (start, end) sample ranges of one recording as PARALLEL streams
     of one batch instead of the reference's process pool over segments
     (speechcatcher/speechcatcher.py:474-497, chunk loop :574-592; SURVEY 8(f)
@@ -1062,7 +1177,11 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
     (the scheduler's ``final_lm`` option): the segment's text is the fused best, "score" stays its search
     score, "lm_score" / "fused_score" / "am_rank" say what the model added and which row of the search's list it was.
     ``ctc_grammar`` (needs ``ctc_beam`` or ``ctc_only``; not with ``ctc_lm``): every segment's CTC beam answers only from
-    this grammar (``StreamScheduler.open(grammar=...)``); the entries of ``ctc_nbest`` carry "complete"."""
+    this grammar (``StreamScheduler.open(grammar=...)``); the entries of ``ctc_nbest`` carry "complete".
+    ``consensus`` (C++ engine): True or "confidence" - the scheduler's option of that name: with True a
+    segment's text is the minimum-Bayes-risk row of its final n-best list; with both a segment gets ``token_consensus``
+    (per token the share of the list's mass behind it), ``token_rival`` (per token {"id", "token", "mass"} or None) and
+    ``mbr`` ([{"pivot", "risk", "am_rank"}])."""
     token_alignment = token_alignment or token_alternates > 0
     if rescore_lm is not None and ctc_only:
         raise ValueError("rescore_lm re-ranks the n-best list of the attention decoder's search: not with ctc_only "
@@ -1089,7 +1208,7 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
                           alternates=token_alternates, ctc_beam=ctc_beam, ctc_lm=ctc_lm, lm_weight=lm_weight,
                           word_bonus=word_bonus, final_lm=rescore_lm, final_lm_weight=rescore_weight,
                           final_word_bonus=rescore_bonus, final_lm_eos=rescore_lm is not None,
-                          attention_rescore=attention_rescore)
+                          attention_rescore=attention_rescore, consensus=consensus)
     free = "rescore" if sch.attention_rescore is not None else "ctc"
     out: List[Optional[dict]] = [None] * len(segments)
     todo = list(enumerate(segments))
@@ -1128,6 +1247,13 @@ def recognize_segments(batch: StreamBatch, speech: np.ndarray, segments: List[Tu
                 if sch.ctc_beam is not None:   # (a list of one n-best per segment: paragraphs append them)
                     out[idx]["ctc_nbest"] = [[{k: e[k] for k in ("text", "score", "conf", "lm", "ctc_score", "complete") if k in e}
                                               for e in (getattr(res, "ctc_nbest", None) or [])]]
+                cons = getattr(res, "consensus", None)
+                if sch.consensus is not None:   # (a list of one record per segment: paragraphs append them)
+                    n = len(out[idx]["tokens"])
+                    recs = cons["tokens"] if cons is not None and len(cons["tokens"]) == n else None
+                    out[idx]["token_consensus"] = [None] * n if recs is None else [r["consensus"] for r in recs]
+                    out[idx]["token_rival"] = [None] * n if recs is None else [r.get("rival") for r in recs]
+                    out[idx]["mbr"] = [cons["mbr"]] if cons is not None else [None]
                 if token_alignment:
                     al = getattr(res, "alignment", None) if res else None
                     n = len(out[idx]["tokens"])

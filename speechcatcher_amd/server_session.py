@@ -34,6 +34,7 @@ import numpy as np
 
 from .activity import FRAME_SECONDS
 from .align import merge_words
+from . import mbr as mbr_mod
 from . import alternates as alternates_mod
 from . import pcm as pcm_mod
 from .scheduler import ServerBusy, StreamScheduler
@@ -228,7 +229,7 @@ class ServerLoop:
                  input_level: bool = False, vosk_alternatives: int = 0, token_alternates: int = 0,
                  stable_partials: bool = False, ctc_beam=None, ctc_lm=None, lm_weight: float = 0.5,
                  word_bonus: float = 0.0, rescore_lm=None, rescore_weight: float = 0.5, rescore_bonus: float = 0.0,
-                 attention_rescore=None):
+                 attention_rescore=None, consensus=None, consensus_scale: float = 1.0):
         """``strict_reference``: no stream reset after a finalised utterance nor between clients, exactly like
         ``recognize_ws`` / ``process_audio_chunk`` (speechcatcher_server.py:270,359-397); the default resets.
         ``continuous`` (default: on whenever the batch has the C++ engine's submit / poll - round 4; False forces one
@@ -312,6 +313,15 @@ class ServerLoop:
         # the re-ranked list
         if attention_rescore is not None and attention_rescore is not False:
             scheduler.enable_attention_rescore(attention_rescore)
+        # ``consensus`` = True or "confidence" (C++ engine): the scheduler's option of that name.  In the Vosk
+        # format the entries of a final's "result" (of its first alternative) carry the consensus mass as "conf" - the
+        # share of the n-best list's mass that agrees on the word, the minimum over its tokens -, the acoustic value as
+        # "am_conf", and "rival" {"word", "mass"} where the list has a strongest other reading; with True the final also
+        # carries "mbr" {"pivot", "risk", "am_rank"}.  Off by default: nothing changes.
+        self.consensus = None
+        if consensus is not None and consensus is not False:
+            scheduler.enable_consensus(consensus, consensus_scale)
+            self.consensus = scheduler.consensus
         self.stable_partials = bool(stable_partials) and vosk_output_format
         if self.stable_partials and not scheduler.stable_partials:
             scheduler.enable_stable_partials()
@@ -561,7 +571,7 @@ class ServerLoop:
         A session with a ``phrase_list``: the text is the best COMPLETE entry's (the scheduler lists those first); when
         none is complete the text is empty and the best entry's goes out under "incomplete"; alternatives carry
         "complete"."""
-        msg = self._final_message_plain(ses, results)
+        msg = self._with_consensus(self._final_message_plain(ses, results), results)
         complete = getattr(results, "grammar_complete", None)
         if complete is None:
             return msg
@@ -570,6 +580,26 @@ class ServerLoop:
                 a["complete"] = bool(r[4].get("complete")) if len(r) > 4 and isinstance(r[4], dict) else bool(complete)
             return msg
         return msg if complete else {"result": [], "text": "", "incomplete": msg["text"]}
+
+    def _with_consensus(self, msg: dict, results: list) -> dict:
+        """``msg`` with the consensus mass in the word entries of the first result (ServerLoop(consensus=...))"""
+        cons = getattr(results, "consensus", None)
+        if self.consensus is None or cons is None:
+            return msg
+        tokens = results[0][1]
+        recs = cons["tokens"]
+        if len(recs) == len(tokens):
+            first = msg["alternatives"][0] if "alternatives" in msg else msg
+            words = first.get("result", [])
+            slots = mbr_mod.word_slots(tokens, recs)
+            if len(slots) != len(words) and len(words) == len(recs):   # an entry per token (no forced alignment)
+                slots = [dict({"consensus": r["consensus"]}, **({"rival": {"word": r["rival"]["token"].replace("▁", ""),
+                                                                          "mass": r["rival"]["mass"]}} if "rival" in r else {}))
+                         for r in recs]
+            first["result"] = mbr_mod.vosk_words(words, slots)
+        if self.consensus is True:
+            msg["mbr"] = dict(cons["mbr"])
+        return msg
 
     def _final_message_plain(self, ses: _Session, results: list) -> dict:
         _text, tokens, _ids, pos, _hyp = results[0]
